@@ -1,12 +1,13 @@
 #!/usr/bin/env python
 """Contract bench: walker-updates/sec of the fused red/blue half-step path on MI355X.
 
-`python bench.py --gpus N --steps K --warmup W`  (N>1: launched by torch.distributed.run, one rank per GPU).
+`python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]`  (N>1: launched by torch.distributed.run, one rank per GPU).
 
 A "step" is one full ensemble step (every half-step of the move chosen for it) over an ensemble of synthetic
 walkers resident in HBM.  The HEADLINE (`metric`, `value`, `ms_per_step`, `roofline`) is BASELINE.json configs[1]:
 nwalkers=65536 per GPU, ndim=64, correlated Gaussian with a dense precision matrix, StretchMove a=2.0, counter-based
-RNG, float64 -- weak-scaled over the GPUs.  The same JSON line also carries (rank 0, N=1):
+RNG, float64 -- weak-scaled over the GPUs.  A plain run measures that and nothing else.  With `--full` the same JSON line also
+carries (rank 0, N=1):
 
   configs     C3 262144x32 Rosenbrock, C4 65536x64 DE+snooker mixture, C5 16384x1024 diagonal Gaussian and C2 with
               the chain stored every step: ms_per_step, wu_per_s, roofline fraction (SURVEY.md 8d bytes formulas)
@@ -17,11 +18,13 @@ RNG, float64 -- weak-scaled over the GPUs.  The same JSON line also carries (ran
               port (oracle/) timed here + the committed reference timings (profiles/r02/cpu_reference.json)
 
 and at N>1 `multi_gpu`: C2 weak, C3 (262144 walkers sharded) and C5 (16384x1024, strong scaling), each under every
-exchange protocol (emcee_amd/parallel.py), the fastest valid one reported per config.
+exchange protocol (emcee_amd/parallel.py), the fastest valid one reported per config (a plain run: C2 alone).
 
-Timing: after W warm-up steps, blocks of EXACTLY K steps are timed, each bracketed by barrier + synchronize, until
->= 1 s has been measured; the MEDIAN block is reported (max over ranks per block).  `--single-block` restores the
-one-block protocol.
+Timing: after W warm-up steps, ONE block of exactly K steps is timed, bracketed by barrier + synchronize: `ms_per_step` is
+that block's wall clock / K.  A plain run at N=1 puts the seeded inputs back after its spin-up, so the W + K steps start from
+them and `--dump-outputs DIR` writes the state after the K-th timed step (coords.npy, log_prob.npy, accepted.npy).  `--full`:
+blocks of EXACTLY K steps are timed until >= 1 s has been measured and the MEDIAN block is reported (max over ranks per block);
+`--single-block` restores the one-block protocol there.
 
 stdout carries exactly one JSON line, and a COMPACT one (< 6 KB: tools/benchkit/emit.py -- the contract keys, `roofline` and
 `cpu_baseline` as objects of numbers, one small object per further configuration); the full record with every audit field and
@@ -50,7 +53,7 @@ from tools.benchkit import sharded as _sharded  # noqa: E402
 from tools.benchkit.sharded import (ALL_EXCHANGES, EXCHANGES, HEAVY_EXCHANGES, _DEADLINE, agreed_remaining, child_main, measure_sharded,  # noqa: E402,F401
                                     preflight_child, run_preflight, sharded_config, sharded_workload, torch_all_ok, worst_case_seconds)
 from tools.benchkit.launcher import emit_line, error_line, self_launch  # noqa: E402,F401
-from tools.benchkit.emit import LINE_LIMIT, compact, emit_record  # noqa: E402,F401
+from tools.benchkit.emit import LINE_LIMIT, compact, emit_record, write_outputs  # noqa: E402,F401
 
 
 def run_child(*a, **k):          # (tests replace bench.run_child through EMX_BENCH_STUB: keep the name here and forward)
@@ -76,7 +79,14 @@ def main(argv=None):
     ap.add_argument("--pmc", action="store_true",
                     help="N=1: re-measure roofline.traffic (HBM bytes per launch) with two rocprofv3 --pmc passes of this command "
                          "instead of reading profiles/pmc_traffic.json")
-    ap.add_argument("--single-block", action="store_true", help="time one K-step block instead of the median of >= 1 s of blocks")
+    ap.add_argument("--single-block", action="store_true", help="--full: time one K-step block instead of the median of >= 1 s of blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the other configurations, exact mode, sampling quality, the CPU baseline "
+                         "(N > 1: C3, C5 and w512 beside C2), the per-launch kernel pass, and the median of >= 1 s of K-step blocks as "
+                         "the timing.  Without it a run times exactly K steps of the headline (one block) and measures nothing else")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="N = 1: write what the headline path computed in its last step (coordinates, log-probs, accept decisions: "
+                         "34 MB of float64) as DIR/<name>.npy; the inputs are seeded, so equal arguments give comparable files")
     ap.add_argument("--force-dist", action="store_true", help="use the sharded RCCL path even at world size 1 (testing)")
     ap.add_argument("--comm", default="rccl", choices=["rccl", "torch"],
                     help="sharded runs: collectives enqueued by libemx itself (default) or torch.distributed")
@@ -99,6 +109,8 @@ def main(argv=None):
     ap.add_argument("--child-port", type=int, default=0, help=argparse.SUPPRESS)
     argv = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(argv)
+    if not args.full:
+        args.single_block = True          # a plain run times exactly K steps: one block (the children at N > 1 are told so too)
 
     stub = os.environ.get("EMX_BENCH_STUB")       # tests only: a module whose install(bench) replaces the GPU legs
     if stub:
@@ -121,6 +133,10 @@ def main(argv=None):
                                        "--nproc-per-node %d) or run bench.py without a launcher" % (args.gpus, world, args.gpus)))
         return 2
     K, W = args.steps, args.warmup
+    if args.dump_outputs and (world > 1 or args.force_dist):
+        if rank == 0:
+            emit_line(error_line(args, "--dump-outputs is implemented for the one-GPU headline (--gpus 1) only"))
+        return 2
     if args.child:
         return child_main(args, rank, world, local_rank)
 
@@ -214,12 +230,16 @@ def main(argv=None):
 
     if not sharded:
         wl = Workload("c2", 65536)
-        res = measure_single(wl, K, W, device=local_rank, rng=args.rng, store=args.store, single_block=args.single_block)
+        # a plain run: spin-up, then the seeded inputs again, W warm-up steps and exactly K timed ones; --full: today's protocol
+        res = measure_single(wl, K, W, device=local_rank, rng=args.rng, store=args.store, single_block=args.single_block,
+                             want_kernel=args.full, restart=not args.full, outputs=bool(args.dump_outputs))
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, res.pop("outputs"))
         extra = {"timed_blocks": res["blocks"], "timed_ms": float(np.sum(res["walls_s"]) * 1e3), "best_block_ms_per_step": res["wall_min_s"] * 1e3 / K}
         line = headline(wl, res["wall_s"], res["gpu_ms"], res["per_launch_us"], res["accept_frac"], res["status"], "", extra,
                         hpl=res.get("halfsteps_per_launch", 1.0), event_hpl=res.get("per_launch_halfsteps"),
                         persist_total=res.get("persist_total"))
-        if not args.no_extras:
+        if not args.no_extras and (args.full or args.config != "all"):
             cfgs = {}
             plan = [("c3", 262144, False), ("c4", 65536, False), ("c5", 16384, False), ("c2", 65536, True),
                     # beyond the BASELINE list: two ensembles no cache can hold (the HBM roofline taken literally) and the
@@ -273,7 +293,7 @@ def main(argv=None):
                     line["quality"] = quality_entry(local_rank)
                 except Exception as e:  # noqa: BLE001
                     line["quality"] = {"error": repr(e)}
-        line["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(wl)
+        line["cpu_baseline"] = cpu_baseline(wl) if args.full and not args.no_cpu_baseline else None
         emit(line)
         return
 
@@ -287,7 +307,7 @@ def main(argv=None):
     dist.init_process_group("gloo")
     port_base = int(os.environ["MASTER_PORT"]) + 17
 
-    keys = ["c2", "c3", "c5", "w512"] if args.config == "all" else [args.config if args.config in ("c2", "c3", "c5", "w512") else "c2"]
+    keys = (["c2", "c3", "c5", "w512"] if args.full else ["c2"]) if args.config == "all" else [args.config if args.config in ("c2", "c3", "c5", "w512") else "c2"]
     if "c2" not in keys:
         keys = ["c2"] + keys                 # the headline is always C2
     multi = {}

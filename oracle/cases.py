@@ -137,3 +137,18 @@ def build(name):
                 thin_by=spec.get("thin_by", 1), per_walker=spec.get("per_walker", False),
                 rng_seed=seed + 5000)
     return spec
+
+
+def autocorr_series(name):
+    """The chains the autocorrelation tests hand to integrated_time (tests/golden/autocorr_ref.npz holds the reference's answers):
+    "walk" a random walk plus noise, 3000 steps x 5 walkers x 2 dims; "ar1" an AR(1) process, 2000 steps x 6 walkers x 2 dims."""
+    rs = np.random.RandomState(3)
+    if name == "walk":
+        return np.cumsum(rs.randn(3000, 5, 2), axis=0) * 0.01 + rs.randn(3000, 5, 2)
+    if name == "ar1":
+        x = np.empty((2000, 6, 2))
+        x[0] = rs.randn(6, 2)
+        for t in range(1, 2000):
+            x[t] = 0.9 * x[t - 1] + rs.randn(6, 2)
+        return x
+    raise ValueError(name)

@@ -1,6 +1,6 @@
 """Generate tests/golden/*.npz by running REFERENCE emcee (build container only).
 
-TEST INFRASTRUCTURE.  Usage:  python -m oracle.gen_golden [case ...]
+TEST INFRASTRUCTURE.  Usage:  python -m oracle.gen_golden [case ...]   (or `autocorr`: tests/golden/autocorr_ref.npz)
 
 For every case in oracle/cases.py the live reference (imported from
 /root/reference/src through oracle/ref_shim.py) is run from a recorded
@@ -108,8 +108,24 @@ def digest(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
+def autocorr_fixture():
+    """tests/golden/autocorr_ref.npz: the reference's integrated_time of cases.autocorr_series (and its function_1d of the first
+    walker's first dimension of "walk"), beside the SHA-256 of each series so that a test can tell that it rebuilt the same input."""
+    emcee = ref_shim.import_reference()
+    out = {}
+    for name in ("walk", "ar1"):
+        x = cases.autocorr_series(name)
+        out[name + "_sha256"] = np.array(digest(x))
+        out[name + "_tau"] = emcee.autocorr.integrated_time(x, quiet=True)
+    out["walk_acf"] = emcee.autocorr.function_1d(cases.autocorr_series("walk")[:, 0, 0])
+    np.savez_compressed(os.path.join(GOLDEN, "autocorr_ref.npz"), **out)
+    print("wrote autocorr_ref", out["walk_tau"], out["ar1_tau"])
+
+
 def main(argv):
     os.makedirs(GOLDEN, exist_ok=True)
+    if argv == ["autocorr"]:
+        return autocorr_fixture()
     names = argv or (list(cases.CASES) + list(cases.HOST_MOVE_CASES) + list(cases.DIGEST_CASES))
     digests = {}
     dpath = os.path.join(GOLDEN, "digests.json")

@@ -45,12 +45,20 @@ def install(bench):
         def cheap_workload(key, n, make_p0=True):
             return real_wl(key, n, make_p0=False)          # the description only: no gigabytes of start state
 
-        def measure_single(wl, K, W, device=0, rng="philox", store=False, single_block=False, want_kernel=True, spin_s=0.15, tuning=None):
+        def measure_single(wl, K, W, device=0, rng="philox", store=False, single_block=False, want_kernel=True, spin_s=0.15, tuning=None,
+                           restart=False, outputs=False):
+            if outdir:
+                with open(os.path.join(outdir, "single.log"), "a") as f:
+                    f.write(json.dumps({"key": wl.key, "N": wl.N, "K": K, "W": W, "single_block": single_block, "want_kernel": want_kernel,
+                                        "restart": restart, "outputs": outputs}) + "\n")
             wall = 21.0e-6 * K * (wl.N * wl.D / (65536.0 * 64.0)) * (2.2 if rng == "mt19937" else 1.0)
             hpl = 32.0 if (wl.key in ("c2", "c4") and wl.N <= 65536 and rng == "philox") else 1.0
             res = {"wall_s": wall, "gpu_ms": wall * 1e3 * 0.977, "blocks": 123, "wall_min_s": wall * 0.99, "accept_frac": 0.3456789012,
                    "status": 0, "per_launch_us": 190.8 if want_kernel else None, "walls_s": [wall] * 123, "halfsteps_per_launch": hpl,
                    "per_launch_halfsteps": 32.0, "persist_total": {"launches": 900, "halfsteps": 18000, "gaveup": 0, "p2p": 0}}
+            if outputs:          # what the device would hand back: a function of the arguments alone
+                x = np.random.RandomState(K + 1000 * W).standard_normal((wl.N, wl.D))
+                res["outputs"] = {"coords": x, "log_prob": -0.5 * np.sum(x * x, axis=1), "accepted": (x[:, 0] > 0.9).astype(np.float64)}
             if rng == "mt19937":
                 res["pipeline"] = {("stage%d_us_per_step" % i): 40.123456 + i for i in range(24)}
                 res["mtdev"] = {"steps": 50, "tokenizer": {"windows": 100, "rounds": 230, "kernel_us": 9000.0}}

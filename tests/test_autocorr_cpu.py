@@ -1,10 +1,12 @@
 """autocorr on the host: known answer (reference unit/test_autocorr.py:19-54) and equality with
-the reference implementation when it is importable (build container only)."""
+the reference implementation (its stored answers, tests/golden/autocorr_ref.npz, and the reference itself when importable)."""
 import numpy as np
 import pytest
 
 from emcee_amd import autocorr
-from oracle import ref_shim
+from oracle import cases, ref_shim
+
+from helpers import digest, load_golden
 
 
 def ar1(seed=1234, ndim=3, N=100000, a=0.9):
@@ -34,14 +36,19 @@ def test_too_short_raises_and_quiet():
         autocorr.function_1d(np.zeros((3, 3)))
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="reference tree not present")
 def test_equals_reference():
-    emcee = ref_shim.import_reference()
-    rs = np.random.RandomState(3)
-    x = np.cumsum(rs.randn(3000, 5, 2), axis=0) * 0.01 + rs.randn(3000, 5, 2)
-    np.testing.assert_allclose(autocorr.integrated_time(x, quiet=True),
-                               emcee.autocorr.integrated_time(x, quiet=True), rtol=1e-9)
-    np.testing.assert_allclose(autocorr.function_1d(x[:, 0, 0]), emcee.autocorr.function_1d(x[:, 0, 0]), atol=1e-12)
+    """against the reference's answers stored in tests/golden/autocorr_ref.npz (`python -m oracle.gen_golden autocorr`), and
+    against the reference itself as well when it is importable"""
+    g = load_golden("autocorr_ref")
+    x = cases.autocorr_series("walk")
+    assert digest(x) == str(g["walk_sha256"]), "the series is not the one the fixture was made from"
+    tau, acf = autocorr.integrated_time(x, quiet=True), autocorr.function_1d(x[:, 0, 0])
+    np.testing.assert_allclose(tau, g["walk_tau"], rtol=1e-9)
+    np.testing.assert_allclose(acf, g["walk_acf"], atol=1e-12)
+    if ref_shim.available():
+        emcee = ref_shim.import_reference()
+        np.testing.assert_allclose(tau, emcee.autocorr.integrated_time(x, quiet=True), rtol=1e-9)
+        np.testing.assert_allclose(acf, emcee.autocorr.function_1d(x[:, 0, 0]), atol=1e-12)
 
 
 def test_nd_layouts_agree():

@@ -45,7 +45,7 @@ def _ranks_seen(tmp_path):
 
 
 def test_self_launch_runs_n_ranks_and_prints_one_line(tmp_path):
-    r, lines = _run([sys.executable, "bench.py", "--gpus", "4", "--steps", "5", "--warmup", "1"], tmp_path)
+    r, lines = _run([sys.executable, "bench.py", "--gpus", "4", "--steps", "5", "--warmup", "1", "--full"], tmp_path)
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1, r.stdout                     # the contract: exactly one JSON line on stdout
     line = json.loads(lines[0])
@@ -82,7 +82,7 @@ def test_self_launch_runs_n_ranks_and_prints_one_line(tmp_path):
 def test_a_spent_time_budget_skips_the_rest_and_says_so(tmp_path):
     """--time-budget: with (almost) nothing left the orchestrator starts no further children; the headline configuration's first
     protocols are measured, what was skipped is named -- on every rank alike (the ranks agree on the remaining time)"""
-    r, lines = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "1", "--time-budget", "40", "--no-preflight"], tmp_path,
+    r, lines = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "1", "--time-budget", "40", "--no-preflight", "--full"], tmp_path,
                     extra_env={"EMX_BENCH_STUB_SLEEP": "2.0"})          # 2 s per measurement: the budget's last 30 s are reached after ~5 of 18
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(lines[-1])

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -38,7 +39,7 @@ def _check_line(text):
 
 
 def test_n1_line_is_compact_and_roofline_follows_from_value(tmp_path):
-    r, lines = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"], tmp_path, {"EMX_BENCH_STUB_SINGLE": "1"})
+    r, lines = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], tmp_path, {"EMX_BENCH_STUB_SINGLE": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     assert len(lines) == 1, r.stdout[:2000]
     line = _check_line(lines[0])
@@ -77,6 +78,66 @@ def test_n1_line_is_compact_and_roofline_follows_from_value(tmp_path):
     assert "[bench-detail] {" in r.stderr
 
 
+def _single_calls(tmp_path):
+    with open(os.path.join(str(tmp_path), "single.log")) as f:
+        return [json.loads(ln) for ln in f]
+
+
+def test_n1_plain_run_times_exactly_k_steps_of_the_headline_and_nothing_else(tmp_path):
+    r, lines = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"], tmp_path, {"EMX_BENCH_STUB_SINGLE": "1"})
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len(lines) == 1, r.stdout[:2000]
+    line = _check_line(lines[0])
+    assert line["steps"] == 20 and line["warmup"] == 5 and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert line["unit"] == "walker-updates/s" and line["metric"].startswith("walker-updates/sec")
+    assert line["value"] == pytest.approx(65536 / (line["ms_per_step"] * 1e-3), rel=1e-3)
+    assert line["roofline"]["frac"] == pytest.approx(line["value"] * 1553 / 8e12, rel=1e-3)
+    # one measurement: the headline, one block of exactly K steps after W, from the seeded inputs, no kernel pass
+    calls = _single_calls(tmp_path)
+    assert calls == [{"key": "c2", "N": 65536, "K": 20, "W": 5, "single_block": True, "want_kernel": False, "restart": True, "outputs": False}]
+    assert line["timing"] == "one K-step block"
+    for k in ("configs", "exact_mode", "quality"):
+        assert k not in line, k
+    assert line["cpu_baseline"] is None
+
+
+def test_n1_dump_outputs_writes_the_last_step_and_repeats(tmp_path):
+    got = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        r, lines = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(d)], tmp_path,
+                        {"EMX_BENCH_STUB_SINGLE": "1"})
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert len(lines) == 1 and _check_line(lines[0])["steps"] == 7
+        names = sorted(os.listdir(str(d)))
+        assert names == ["accepted.npy", "coords.npy", "log_prob.npy"]
+        arrs = {n: np.load(os.path.join(str(d), n)) for n in names}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(os.path.getsize(os.path.join(str(d), n)) for n in names) <= 64 << 20
+        assert arrs["coords.npy"].shape == (65536, 64) and arrs["log_prob.npy"].shape == (65536,)
+        got.append(arrs)
+    assert all(np.array_equal(got[0][n], got[1][n]) for n in got[0])
+    assert _single_calls(tmp_path)[0]["outputs"] is True
+
+
+def test_dump_outputs_is_refused_beyond_one_gpu(tmp_path):
+    r, lines = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "c2",
+                     "--dump-outputs", str(tmp_path / "out")], tmp_path)
+    assert r.returncode != 0
+    line = json.loads(lines[-1])
+    assert line["value"] is None and "--dump-outputs" in line["error"]
+    assert not os.path.exists(str(tmp_path / "out"))
+
+
+def test_multi_gpu_plain_run_measures_the_headline_configuration_alone(tmp_path):
+    r, lines = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "1"], tmp_path)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len(lines) == 1
+    line = _check_line(lines[0])
+    assert line["n_gpus"] == 2 and line["value"] > 0
+    assert set(line["multi_gpu"]) == {"c2_weak_65536_per_gpu"}
+
+
 def _strings(o):
     if isinstance(o, str):
         yield o
@@ -90,7 +151,7 @@ def _strings(o):
 
 @pytest.mark.parametrize("world", [2, 8])
 def test_multi_gpu_line_is_compact(tmp_path, world):
-    r, lines = _run([sys.executable, "bench.py", "--gpus", str(world), "--steps", "5", "--warmup", "1"], tmp_path)
+    r, lines = _run([sys.executable, "bench.py", "--gpus", str(world), "--steps", "5", "--warmup", "1", "--full"], tmp_path)
     assert r.returncode == 0, r.stderr[-3000:]
     assert len(lines) == 1
     line = _check_line(lines[0])

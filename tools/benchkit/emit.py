@@ -190,6 +190,24 @@ def detail_paths():
     return paths
 
 
+OUTPUTS_LIMIT = 64 << 20    # bytes of --dump-outputs in all
+
+
+def write_outputs(out_dir, outputs):
+    """`--dump-outputs DIR`: every array of `outputs` as DIR/<name>.npy, float64 (float32 kept); -> the names written"""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64)
+              for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > OUTPUTS_LIMIT:
+        raise ValueError("--dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, OUTPUTS_LIMIT))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    log("outputs of the last timed step: %s (%.1f MB) -> %s" % (", ".join(sorted(arrays)), total / 1e6, out_dir))
+    return sorted(arrays)
+
+
 def emit_record(rec):
     """full record -> bench_detail.json + stderr; compact line -> stdout (exactly one line)"""
     text = json.dumps(rec)

@@ -139,11 +139,15 @@ class Workload(object):
         return float(sum(wi * d.nsplits for wi, (_, d) in zip(w, self.moves)))
 
     def install(self, ens, rng, seed=20260923):
-        from emcee_amd import _lib
         kind, p0, p1, scale = self.target
         ens.set_target(kind, p0, p1, scale)
         cdf = np.cumsum(self.weights) / np.sum(self.weights)
         ens.set_moves([d for _, d in self.moves], cdf)
+        self.restart(ens, rng, seed)
+
+    def restart(self, ens, rng, seed=20260923):
+        """Back to the inputs install() gave: the RNG at its first draw, the start state and its log-probs (target and moves stay)."""
+        from emcee_amd import _lib
         if rng == "philox":
             ens.set_rng_mode(_lib.RNG_PHILOX)
             ens.set_philox(seed, 0)

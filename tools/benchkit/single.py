@@ -16,9 +16,14 @@ from tools.benchkit.out import log
 
 
 # ------------------------------------------------------------------------------------------------ single-GPU measurement
-def measure_single(wl, K, W, device=0, rng="philox", store=False, single_block=False, want_kernel=True, spin_s=0.15, tuning=None):
+def measure_single(wl, K, W, device=0, rng="philox", store=False, single_block=False, want_kernel=True, spin_s=0.15, tuning=None,
+                   restart=False, outputs=False):
     """W warm-up steps, then K-step blocks (each: sync, hipEvent + wall clock around emx_run(K), sync) until >= MIN_TIMED_MS (1 s);
-    median block.  Returns per-step times, per-launch event duration of the half-step kernel, accept fraction."""
+    median block.  Returns per-step times, per-launch event duration of the half-step kernel, accept fraction.
+    restart: after the spin-up the inputs are put back (wl.restart), so that the W + K steps start from the seeded inputs.
+    outputs: res["outputs"] = what a caller of the timed path receives after its last step (coordinates, log-probs, that step's
+    accept decisions).  With one timed block and restart these are the timed steps' own; otherwise (the number of blocks follows the
+    clock) W + K steps are replayed from the inputs before the kernel pass, so that the outputs depend on the arguments alone."""
     from emcee_amd.device import DeviceEnsemble
     ens = DeviceEnsemble(wl.N, wl.D, device=device)
     wl.install(ens, rng)
@@ -32,6 +37,8 @@ def measure_single(wl, K, W, device=0, rng="philox", store=False, single_block=F
     while time.perf_counter() - t_spin < spin_s:
         ens.run(min(50, max(1, K)), 1, False)
         ens.sync()
+    if restart:
+        wl.restart(ens, rng)
     if store:
         ens.chain_reset()
     ens.run(W, 1, store)
@@ -72,6 +79,16 @@ def measure_single(wl, K, W, device=0, rng="philox", store=False, single_block=F
             res["mtdev"] = dict(ens.mtdev_info(), tokenizer=ens.mtdev_tok_stats())
         except Exception as e:  # noqa: BLE001
             log("device producer stats unavailable:", e)
+    if outputs:
+        if not (single_block and restart):
+            wl.restart(ens, rng)
+            for n in (W, K):
+                if store:
+                    ens.chain_reset()
+                ens.run(n, 1, store)
+            ens.sync()
+        x, lp = ens.get_state()
+        res["outputs"] = {"coords": x, "log_prob": lp, "accepted": ens.accepted_mask().astype(np.float64)}
     if want_kernel:
         # per-launch hipEvent durations of the half-step kernel (separate pass: event records perturb)
         if persistent and rng == "philox":
@@ -391,7 +408,7 @@ def refresh_pmc_traffic(args):
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="emx_pmc_")
         cmd = [prof, "--pmc", ctr, "-d", d, "-o", "p", "-f", "csv", "--", sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10",
-               "--warmup", "2", "--no-cpu-baseline", "--no-extras"]
+               "--warmup", "2", "--full", "--no-cpu-baseline", "--no-extras"]
         env = dict(os.environ)
         env.setdefault("TMPDIR", "/tmp")
         # the child's FULL record (its stdout line is the compact one, without the launch counts): a file of its own

@@ -8,7 +8,7 @@ mkdir -p $O/pmc
 for cfg in hbm_dense hbm_wide c2; do
   for ctr in FETCH_SIZE WRITE_SIZE; do
     rm -rf $O/pmc/${cfg}_$ctr
-    timeout 300 rocprofv3 --pmc $ctr -d $O/pmc/${cfg}_$ctr -o p -f csv -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --config $cfg > $O/pmc/${cfg}_$ctr.log 2>&1
+    timeout 300 rocprofv3 --pmc $ctr -d $O/pmc/${cfg}_$ctr -o p -f csv -- python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --config $cfg > $O/pmc/${cfg}_$ctr.log 2>&1
   done
 done
 python - "$O" <<'PY'
