@@ -9,6 +9,8 @@ LIB_PATH = os.path.join(HERE, "libemx.so")
 
 TARGET_HOST, TARGET_ISO, TARGET_DIAG, TARGET_DENSE, TARGET_ROSENBROCK, TARGET_BOX, TARGET_CALLBACK = range(7)
 MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER, MOVE_GAUSS = range(4)
+MOVE_WALK, MOVE_KDE = 5, 6          # native (Philox) mode only; 4 is not a public kind
+KDE_BW_SCOTT, KDE_BW_SILVERMAN, KDE_BW_SCALAR = range(3)
 GAUSS_VECTOR, GAUSS_RANDOM, GAUSS_SEQUENTIAL = range(3)
 RNG_INPUTS, RNG_MT19937, RNG_PHILOX = range(3)
 EXCHANGE_ALLGATHER, EXCHANGE_PULL, EXCHANGE_DIRECT, EXCHANGE_LOGPROB, EXCHANGE_REPLAY = range(5)
@@ -141,6 +143,7 @@ SIGNATURES = {
                                           _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_double)]),
     "emx_host_split_draws": (C.c_int, [_P, C.c_int64, C.POINTER(MoveDesc), _ip, _ip, C.c_int32, _ip, _ip, _ip, _dp]),
     "emx_host_plan_philox": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(MoveDesc), _ip, _ip, _ip, _ip, _ip, _dp, _dp]),
+    "emx_host_walk_kde_draws": (C.c_int64, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(MoveDesc), C.c_int32, _P, _dp]),
     "emx_host_move_choice_philox": (C.c_int32, [C.c_uint64, C.c_uint64, _dp, C.c_int32]),
 }
 

@@ -23,6 +23,7 @@
 #include "emx_mtdev.hpp"
 #include "emx_mtjump.hpp"
 #include "emx_mtpipe.hpp"
+#include "emx_walkkde.hpp"
 #include "emx_rng.hpp"
 #include "mt19937_legacy.hpp"
 
@@ -37,6 +38,12 @@ constexpr int PIPE_SINKS = PLAN_RING < 16 ? PLAN_RING : 16;      // exact-mode p
                                                                  // whole ring for ensembles that take their steps eight per persistent launch)
 constexpr int MTDEV_SLOTS = MTDEV_NBUF * MTDEV_BATCH;            // exact-mode device producer: its plan slots follow the ring's, allocated on first use
 static_assert(MTDEV_BATCH == NATIVE_BATCH_MAX, "a produced batch is one persistent launch");
+// launch_split takes a public move kind where the kernels take their internal one
+static_assert(EMX_MOVE_STRETCH == MOVE_STRETCH && EMX_MOVE_DE == MOVE_DE && EMX_MOVE_SNOOKER == MOVE_SNOOKER && EMX_MOVE_GAUSS == MOVE_GAUSS,
+              "public and internal move kinds");
+static_assert(EMX_MOVE_WALK == MOVE_WALK && EMX_MOVE_KDE == MOVE_KDE && MOVE_EVAL != EMX_MOVE_WALK && MOVE_EVAL != EMX_MOVE_KDE,
+              "public and internal move kinds");
+static inline bool is_walk_kde(int kind) { return kind == EMX_MOVE_WALK || kind == EMX_MOVE_KDE; }
 constexpr int EMX_MAX_RANKS = 1024;      // pull / all-gather exchanges: counter storage
 
 // ------------------------------------------------------------------------------------------
@@ -443,6 +450,7 @@ struct emx_ctx {
     double *qout = nullptr, *fout = nullptr, *newlp = nullptr;
     double* tp1_full = nullptr;        // dense target, ndim <= 112: the full image the wide-target kernels read (tuning "dense_wide")
     double *evalX = nullptr, *evallp = nullptr;
+    double* wk_work = nullptr;         // WalkMove / KDEMove scratch (emx_walkkde.hip), allocated by their first half-step
     // sharding
     int rank = 0, world = 1;
     double *sendbuf = nullptr, *gathered = nullptr;
@@ -759,8 +767,81 @@ int launch_split(emx_ctx* c, int move, int target, int S, int split, int pos0, i
                  double* X, double* lp, double* chain, double* chain_lp, double* sendbuf,
                  const StepDesc* step_desc = nullptr, const int32_t* t_hi_dev = nullptr) {
     if (t_hi <= t_lo) return 0;
-    const bool dense = target == EMX_TARGET_DENSE_GAUSS;
     const int D = c->D;
+    if (is_walk_kde(move)) {
+        // WalkMove / KDEMove (emx_walkkde.hip): their proposal kernels write qout / fout, then -- a device target -- the three-pass
+        // path's evaluation of the proposal block and k_wide_commit; a host target stops at the proposals (emx_propose / emx_accept)
+        if (!c->cur.active || !c->cur.native || !ps || !mv) {
+            c->err = "WalkMove / KDEMove steps run on the device in the Philox rng mode only";
+            return -1;
+        }
+        if (c->world != 1 || sendbuf || step_desc || t_hi_dev || X != c->X || order || t_lo != 0 || t_hi != ns) {
+            c->err = "WalkMove / KDEMove: one replica, the per-half-step path only (no exchange, graph or persistent kernel)";
+            return -1;
+        }
+        if (!c->wk_work) {
+            const hipError_t e = hipMalloc((void**)&c->wk_work, walk_kde_work_bytes(c->N, D));
+            if (e != hipSuccess) {
+                c->wk_work = nullptr;
+                c->err = "WalkMove / KDEMove: out of device memory for the proposal scratch";
+                return -2;
+            }
+        }
+        WalkKdeArgs w{};
+        w.X = X;
+        w.order = ps->order;
+        w.qout = c->qout;
+        w.fout = c->fout;
+        w.status = c->status;
+        w.work = c->wk_work;
+        w.seed = c->cur.nat.seed;
+        w.step = c->cur.nat.step;
+        w.N = (int32_t)c->N;
+        w.D = D;
+        w.pos0 = pos0;
+        w.ns = ns;
+        w.t_lo = t_lo;
+        w.t_hi = t_hi;
+        w.kind = move;
+        w.s = move == EMX_MOVE_WALK ? mv->reserved : 0;
+        w.bw_rule = move == EMX_MOVE_KDE ? mv->reserved : 0;
+        w.bw = mv->a;
+        if (launch_walk_kde(w, c->stream) != hipSuccess) {
+            c->err = "WalkMove / KDEMove: proposal kernel launch failed";
+            return -2;
+        }
+        if (target == EMX_TARGET_HOST) return 0;
+        // log-probs of the block (a non-finite proposal gets -inf: rejected, its status bit raised by the proposal kernel) ...
+        c->eval_check_bad = true;
+        const int rc = launch_split(c, MOVE_EVAL, target, 1, 0, 0, ns, t_lo, t_hi, mv, nullptr, c->iota, c->qout, c->newlp, nullptr,
+                                    nullptr, nullptr);
+        c->eval_check_bad = false;
+        if (rc) return rc;
+        // ... then decision + commit, red_blue.py:96-104
+        WideCommitArgs k{};
+        k.X = X;
+        k.lp = lp;
+        k.acc = c->acc;
+        k.acc_count = c->acc_count;
+        k.chain = chain;
+        k.chain_lp = chain_lp;
+        k.qout = c->qout;
+        k.fout = c->fout;
+        k.newlp = c->newlp;
+        k.order = ps->order;
+        k.logu = ps->logu;
+        k.status = c->status;
+        k.D = D;
+        k.pos0 = pos0;
+        k.t_lo = t_lo;
+        k.t_hi = t_hi;
+        if (launch_wide_commit(k, t_hi - t_lo, c->num_cu, c->stream) != hipSuccess) {
+            c->err = "WalkMove / KDEMove: commit kernel launch failed";
+            return -2;
+        }
+        return 0;
+    }
+    const bool dense = target == EMX_TARGET_DENSE_GAUSS;
     const bool callback = target == EMX_TARGET_DEVICE_CALLBACK;
     if ((dense && dense_is_wide(c)) || callback) {
         // Three passes on the stream -- the reference's compute_log_prob between get_proposal and the accept loop
@@ -1233,7 +1314,7 @@ int emx_destroy(emx_ctx* c) {
         if (c->bounce[k]) hipHostFree(c->bounce[k]);
         if (c->bounce_ev[k]) hipEventDestroy(c->bounce_ev[k]);
     }
-    void* ptrs[] = {c->X, c->lp, c->acc, c->acc_count, c->iota, c->qout, c->fout, c->newlp, c->evalX,
+    void* ptrs[] = {c->X, c->lp, c->acc, c->acc_count, c->iota, c->qout, c->fout, c->newlp, c->evalX, c->wk_work,
                     c->evallp, c->tp0, c->tp1, c->tp1_full, c->chain, c->chain_lp, c->own_shard_bufs ? c->sendbuf : nullptr,
                     c->own_shard_bufs ? c->gathered : nullptr};
     for (void* p : ptrs)
@@ -1344,7 +1425,7 @@ int emx_status(emx_ctx* c, uint32_t* bits) {
         if (rcs) return rcs;
     }
     uint32_t b = 0;
-    for (int k = 0; k < 5; ++k)
+    for (int k = 0; k < 6; ++k)
         if (__atomic_exchange_n(&c->status_host[k], 0u, __ATOMIC_ACQ_REL)) b |= 1u << k;
     if (b & ST_EXCHANGE_TIMEOUT) c->direct_dead = true;      // sticky on the host too: emx_direct_halfstep / emx_run refuse from here on
     if (b & ST_EXCHANGE_TIMEOUT) c->persist_grid = 0;        // the persistent kernel's barrier words (counters, the dead mark) restart with its next launch
@@ -1870,7 +1951,21 @@ int emx_set_moves(emx_ctx* c, int32_t nmoves, const emx_move_desc* moves, const 
     NEED(c, nmoves >= 1, "need at least one move");
     PIPE_STOP(c);
     for (int i = 0; i < nmoves; ++i) {
-        NEED(c, moves[i].kind >= 0 && moves[i].kind <= EMX_MOVE_GAUSS, "unknown move kind");
+        NEED(c, (moves[i].kind >= 0 && moves[i].kind <= EMX_MOVE_GAUSS) || is_walk_kde(moves[i].kind), "unknown move kind");
+        if (is_walk_kde(moves[i].kind)) {          // (the rng mode is checked by the step: set_moves may come before set_rng_mode)
+            NEED(c, c->D <= WK_MAX_D, "WalkMove / KDEMove on the device: ndim must be <= %d", WK_MAX_D);
+            if (moves[i].kind == EMX_MOVE_WALK) {
+                const int s = moves[i].reserved;
+                NEED(c, s == 0 || (s >= 2 && s <= WK_MAX_S), "WalkMove: s must be None (0) or in [2, %d]", WK_MAX_S);
+                // the smallest complement of any split: N - ceil(N / nsplits) (moves/walk.py: random.choice(Nc, s, replace=False))
+                NEED(c, moves[i].nsplits < 2 || moves[i].nsplits > c->N ||
+                            (int64_t)s <= c->N - (c->N + moves[i].nsplits - 1) / moves[i].nsplits,
+                     "Cannot take a larger sample than population when 'replace=False'");
+            } else {
+                NEED(c, moves[i].reserved >= 0 && moves[i].reserved <= 2, "KDEMove: unknown bandwidth rule");
+                NEED(c, moves[i].reserved != 2 || (moves[i].a > 0.0 && std::isfinite(moves[i].a)), "KDEMove: the bandwidth factor must be > 0");
+            }
+        }
         if (moves[i].kind == EMX_MOVE_GAUSS) {
             NEED(c, moves[i].nsplits == 1, "the Gaussian move updates the whole ensemble at once (nsplits must be 1)");
             NEED(c, moves[i].reserved >= EMX_GAUSS_VECTOR && moves[i].reserved <= EMX_GAUSS_SEQUENTIAL, "unknown Gaussian mode");
@@ -2612,6 +2707,7 @@ static int step_begin_impl(emx_ctx* c, int32_t store, int32_t forced_move, int32
     } else if (c->rng_mode == EMX_RNG_MT19937) {
         cur.move = forced_move >= 0 ? forced_move : c->mt.choice_cdf(c->cdf.data(), nm);   // ensemble.py:406
         const emx_move_desc& mv = c->moves[cur.move];
+        NEED(c, !is_walk_kde(mv.kind), "WalkMove / KDEMove steps run on the device in the Philox rng mode only");
         cur.S = mv.nsplits;
         NEED(c, c->N >= 2 && (mv.kind != EMX_MOVE_DE || c->N - (c->N + cur.S - 1) / cur.S >= 2),
              "complement too small for this move");
@@ -2725,6 +2821,7 @@ int emx_plan_set(emx_ctx* c, int32_t move_index, const int32_t* off, const int32
                  const int32_t* p1, const int32_t* p2, const double* s0, const double* uacc) {
     NEED(c, c->cur.active, "emx_plan_set outside a step");
     NEED(c, move_index >= 0 && move_index < (int)c->moves.size(), "bad move index");
+    NEED(c, !is_walk_kde(c->moves[move_index].kind), "WalkMove / KDEMove steps run on the device in the Philox rng mode only");
     auto& cur = c->cur;
     cur.move = move_index;
     cur.S = c->moves[move_index].nsplits;
@@ -2978,7 +3075,7 @@ static emx_ctx::GraphSlot* graph_ready(emx_ctx* c, int store) {
     if (store && c->stored + NB > c->cap) return nullptr;
     auto& g = c->gslot[store ? 1 : 0];
     const emx_move_desc& mv = c->moves[0];
-    if (mv.kind == EMX_MOVE_GAUSS) return nullptr;
+    if (mv.kind == EMX_MOVE_GAUSS || is_walk_kde(mv.kind)) return nullptr;
     if (g.valid && (g.spw != c->tune_spw || g.wpb != c->tune_wpb || g.bpc != c->tune_bpc || g.target != c->target)) graph_invalidate(c);
     if (!c->d_desc) {
         if (hipMalloc((void**)&c->d_desc, sizeof(StepDesc) * NB) != hipSuccess ||
@@ -3478,7 +3575,10 @@ static bool persist_wanted(const emx_ctx* c) {
     if (c->tune_ablate || (c->dbg && !EMX_OPT_STAMPS) || c->tune_spw || c->tune_wpb || c->tune_graph) return false;     // (an instrumented build stamps k_persist too)
     if (c->N < c->tune_persist_min_walkers) return false;
     bool any = false;
-    for (const auto& m : c->moves) any = any || persist_move_ok(c, m);
+    for (const auto& m : c->moves) {
+        if (is_walk_kde(m.kind)) return false;        // (a schedule with WalkMove / KDEMove steps runs the per-half-step launches)
+        any = any || persist_move_ok(c, m);
+    }
     if (!any) return false;
     if (c->Dp > 64) return true;           // (persist_slab_ok: even ndim 66 ... 128, odd 65 ... 127)
     // ndim up to 64: the row layouts k_persist is instantiated for -- even ndim: two coordinates per lane, rows of 8 lanes (emx_hot.hip);
@@ -3501,7 +3601,10 @@ static bool persist_valu_wanted(const emx_ctx* c) {
     const Shape sh = pick_shape(c->D, c->D);
     if (!persist_valu_shape(sh)) return false;      // (launch_persist_valu's instantiations)
     bool any = false;
-    for (const auto& m : c->moves) any = any || persist_local_ok(c, m) || persist_valu_wide_ok(c, m);
+    for (const auto& m : c->moves) {
+        if (is_walk_kde(m.kind)) return false;
+        any = any || persist_local_ok(c, m) || persist_valu_wide_ok(c, m);
+    }
     return any;
 }
 
@@ -5515,8 +5618,54 @@ int emx_host_plan_philox(uint64_t seed, uint64_t step, int64_t N, const emx_move
         case EMX_MOVE_STRETCH: host_native_plan<MOVE_STRETCH>(na, N, *mv, off, order, p0, p1, p2, s0, uacc); return 0;
         case EMX_MOVE_DE: host_native_plan<MOVE_DE>(na, N, *mv, off, order, p0, p1, p2, s0, uacc); return 0;
         case EMX_MOVE_SNOOKER: host_native_plan<MOVE_SNOOKER>(na, N, *mv, off, order, p0, p1, p2, s0, uacc); return 0;
+        case EMX_MOVE_WALK:
+        case EMX_MOVE_KDE: host_native_plan<MOVE_EVAL>(na, N, *mv, off, order, p0, p1, p2, s0, uacc); return 0;
     }
     return -1;
+}
+
+int64_t emx_host_walk_kde_draws(uint64_t seed, uint64_t step, int64_t N, int32_t D, const emx_move_desc* mv, int32_t split,
+                                int32_t* helpers, double* normals) {
+    if (!mv || !is_walk_kde(mv->kind) || mv->nsplits < 2 || mv->nsplits > N || split < 0 || split >= mv->nsplits || D < 1) return -1;
+    const int S = mv->nsplits;
+    const SplitSizes sz = split_sizes((int)N, S);
+    const int64_t ns = sz.of(split), Nc = N - ns;
+    const int s = mv->kind == EMX_MOVE_WALK ? mv->reserved : 0;
+    if (s < 0 || s == 1 || s > Nc) return -1;
+    const PermKey pk = make_perm_key((uint64_t)N, seed, step);
+    auto walker_of = [&](int64_t r) {          // complement rank -> walker (native_slot's partner map)
+        for (int j = 0; j < S; ++j) {
+            if (j == split) continue;
+            const int n = sz.of(j);
+            if (r < n) return (int32_t)perm_inv((uint32_t)(r * S + j), pk);
+            r -= n;
+        }
+        return (int32_t)-1;
+    };
+    std::vector<int64_t> taken((size_t)std::max(s, 1));
+    for (int64_t t = 0; t < ns; ++t) {
+        const uint32_t i = perm_inv((uint32_t)(t * S + split), pk);
+        const int nz = s >= 2 ? s : D;
+        for (int k = 0; k < nz; k += 2) {
+            double n0, n1;
+            wk_normal_pair(seed, step, i, k >> 1, n0, n1);
+            normals[t * nz + k] = n0;
+            if (k + 1 < nz) normals[t * nz + k + 1] = n1;
+        }
+        if (mv->kind == EMX_MOVE_KDE) {
+            if (helpers) helpers[t] = walker_of((int64_t)wk_centre_rank(seed, step, i, (uint64_t)Nc));
+        } else if (s >= 2) {
+            for (int k = 0; k < s; ++k) {              // Floyd
+                const int64_t c = (int64_t)wk_helper_draw(seed, step, i, k, s, (uint64_t)Nc);
+                bool hit = false;
+                for (int m = 0; m < k; ++m) hit = hit || taken[m] == c;
+                taken[k] = hit ? Nc - s + k : c;
+            }
+            if (helpers)
+                for (int k = 0; k < s; ++k) helpers[t * s + k] = walker_of(taken[k]);
+        }
+    }
+    return ns;
 }
 
 int32_t emx_host_move_choice_philox(uint64_t seed, uint64_t step, const double* cdf, int32_t n) {

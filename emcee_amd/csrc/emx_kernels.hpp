@@ -62,12 +62,15 @@
 
 namespace emx {
 
-enum : int { MOVE_STRETCH = 0, MOVE_DE = 1, MOVE_SNOOKER = 2, MOVE_GAUSS = 3, MOVE_EVAL = 4, MOVE_MIX = 8 /* k_persist_mix: DE and snooker steps in one launch */ };
+enum : int { MOVE_STRETCH = 0, MOVE_DE = 1, MOVE_SNOOKER = 2, MOVE_GAUSS = 3, MOVE_EVAL = 4,
+             MOVE_WALK = 5, MOVE_KDE = 6,      // emx_walkkde.hip: their own proposal kernels (4 is taken: the public kinds share these numbers)
+             MOVE_MIX = 8 /* k_persist_mix: DE and snooker steps in one launch */ };
 enum : int { GAUSS_VECTOR = 0, GAUSS_RANDOM = 1, GAUSS_SEQUENTIAL = 2 };
 enum : int { TGT_NONE = 0, TGT_ISO = 1, TGT_DIAG = 2, TGT_DENSE = 3, TGT_ROSEN = 4, TGT_BOX = 5,
              TGT_REPLAY = 7 };      // (6 is EMX_TARGET_DEVICE_CALLBACK, a host-side three-pass target: never a kernel's)     // replay exchange: no target, no decision -- the slot is a peer's ACCEPTED update, its new log-prob comes with the plan
 enum : uint32_t { ST_NAN_LOGP = 1u, ST_BAD_COORD = 2u, ST_EXCHANGE_OVERFLOW = 4u, ST_EXCHANGE_TIMEOUT = 8u,
-                  ST_PLAN_PRODUCER = 16u };     // bit 4: the device producer of exact-mode plans stalled or under-ran (emx_mtdev_kernels.hpp)
+                  ST_PLAN_PRODUCER = 16u,
+                  ST_SINGULAR_COV = 32u };      // bit 5: KDEMove's complement covariance is not positive definite (emx_walkkde.hip)     // bit 4: the device producer of exact-mode plans stalled or under-ran (emx_mtdev_kernels.hpp)
 constexpr int EMX_MAX_PEERS = 8;       // direct exchange: GPUs of one node
 
 // The sticky status lives in mapped host memory, one 32-bit flag per condition (index = bit number): raising one is
@@ -2724,6 +2727,8 @@ static __device__ __forceinline__ void native_plan_batch_body(const NativeBatchA
     const NativeArgs nat = (!ONLY_STRETCH && B.desc) ? B.desc[b].nat : B.nat[b];      // (graph replay: descriptors in device memory)
     if (mv == MOVE_GAUSS)
         native_gauss_slot(nat, B.D, B.gmode[b], B.gcol[b], pos, i, a0, a1, a2, z, u);
+    else if (mv == MOVE_WALK || mv == MOVE_KDE)      // split and accept uniform only: the proposal kernels draw the rest
+        native_slot<MOVE_EVAL>(nat, N, S, split, t, B.a[b], B.sigma[b], B.g0[b], i, a0, a1, a2, z, u);
     else if (mv == MOVE_STRETCH)
         native_slot<MOVE_STRETCH>(nat, N, S, split, t, B.a[b], B.sigma[b], B.g0[b], i, a0, a1, a2, z, u);
     else if (mv == MOVE_DE)

@@ -6,6 +6,7 @@
 // (red_blue.py:80 shuffle, stretch.py:30-32, red_blue.py:100) with draws that are a pure
 // function of (seed, step, walker): same distributions, different stream.
 #pragma once
+#include <cmath>
 #include <cstdint>
 
 #if defined(__HIPCC__)
@@ -244,6 +245,44 @@ EMX_HD PermKey make_perm_key(uint64_t n, uint64_t seed, uint64_t step) {
     k.s1 = bits > 1 ? (bits + 1) / 2 : 1;
     k.s2 = bits > 2 ? (bits + 2) / 3 : 1;
     return k;
+}
+
+// ---------------------------------------------------------------------------------------
+// WalkMove / KDEMove draws (native mode).  Counter = (walker, stream, step lo, step hi) as everywhere; the streams:
+//   * 0            words 0-1: the KDE centre (a complement rank), words 2-3: the accept uniform (native_slot)
+//   * WK_HELPER + b helper draw k = 2 b + h of the walk move's Floyd sample: words (2 h, 2 h + 1)
+//   * WK_NORMAL + p normal pair p: (2 p, 2 p + 1) from one f64 Box-Muller pair of u53 uniforms
+// (the other moves use streams 0 ... 2, the Gaussian move's noise 2 ... 2 + ndim / 4: the tags keep clear of them)
+// ---------------------------------------------------------------------------------------
+constexpr uint32_t WK_HELPER = 0x48000000u;    // 'H'
+constexpr uint32_t WK_NORMAL = 0x4E000000u;    // 'N'
+
+EMX_HD Philox4 wk_block(uint64_t seed, uint64_t step, uint32_t walker, uint32_t stream) {
+    return philox4x32_10(walker, stream, (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+// Floyd's draw k of s distinct ranks out of Nc: a uniform integer in [0, Nc - s + k]
+EMX_HD uint64_t wk_helper_draw(uint64_t seed, uint64_t step, uint32_t walker, int k, int s, uint64_t Nc) {
+    const Philox4 r = wk_block(seed, step, walker, WK_HELPER + (uint32_t)(k >> 1));
+    const int h = k & 1;
+    return bounded64(h ? r.v[2] : r.v[0], h ? r.v[3] : r.v[1], Nc - (uint64_t)s + (uint64_t)k + 1ull);
+}
+
+// normal pair p of a walker: f64 Box-Muller, u1 in (0, 1], u2 in [0, 1) (the DE move's gamma draw, with both outputs)
+EMX_HD void wk_normal_pair(uint64_t seed, uint64_t step, uint32_t walker, int p, double& n0, double& n1) {
+    const Philox4 r = wk_block(seed, step, walker, WK_NORMAL + (uint32_t)p);
+    const double u1 = 1.0 - u53(r.v[0], r.v[1]);
+    const double u2 = u53(r.v[2], r.v[3]);
+    const double rad = sqrt(-2.0 * log(u1));
+    const double ang = 6.283185307179586476925286766559 * u2;
+    n0 = rad * cos(ang);
+    n1 = rad * sin(ang);
+}
+
+// the KDE centre of a walker: a uniform complement rank (stream 0, words 0-1)
+EMX_HD uint64_t wk_centre_rank(uint64_t seed, uint64_t step, uint32_t walker, uint64_t Nc) {
+    const Philox4 r = wk_block(seed, step, walker, 0u);
+    return bounded64(r.v[0], r.v[1], Nc);
 }
 
 }  // namespace emx

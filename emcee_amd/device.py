@@ -18,6 +18,7 @@ _STATUS_BAD_COORD = 2
 _STATUS_EXCHANGE_OVERFLOW = 4
 _STATUS_EXCHANGE_TIMEOUT = 8
 _STATUS_PLAN_PRODUCER = 16
+_STATUS_SINGULAR_COV = 32
 
 
 def _as_f64(a, shape=None):
@@ -156,6 +157,10 @@ class DeviceEnsemble:
                                "cannot become co-resident is redone on the per-half-step path instead); the run is invalid -- "
                                "EMX_TUNE=persist=0 selects the per-half-step launches, persist_timeout_ms raises the bound")
             raise EmxError("direct exchange: a peer did not reach the device-side barrier in time; the sharded run is invalid")
+        if bits & _STATUS_SINGULAR_COV:
+            # KDEMove: scipy.stats.gaussian_kde raises this for a singular data covariance (moves/kde.py)
+            raise np.linalg.LinAlgError("The data appears to lie in a lower-dimensional subspace of the space in which it is "
+                                        "expressed; the covariance matrix of the complement is not positive definite (KDEMove)")
         if bits & _STATUS_BAD_COORD:
             raise ValueError("At least one parameter value was infinite or NaN")
         if bits & _STATUS_NAN_LOGP:

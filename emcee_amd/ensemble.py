@@ -16,7 +16,8 @@ GPUs; ``torch.distributed`` only bootstraps RCCL and replicates rank 0's RNG sta
 
 ``rng="mt19937"`` (default) replays NumPy's legacy MT19937 stream: the same seed gives the same
 chain as reference emcee.  ``rng="philox"`` generates all draws inside the kernels (counter
-based), the throughput mode.  There is no CPU fallback: a missing GPU raises.
+based), the throughput mode; there ``WalkMove`` and ``KDEMove`` are device moves too (the
+exact mode keeps their host ``get_proposal``: its draws go through LAPACK).  There is no CPU fallback: a missing GPU raises.
 """
 import warnings
 from itertools import count
@@ -27,6 +28,8 @@ from . import _lib
 from .backends import Backend
 from .model import Model
 from .moves import StretchMove
+from .moves.kde import kde_desc
+from .moves.walk import walk_desc
 from .pbar import get_progress_bar
 from .state import DeviceState, ResidentState, State
 from .targets import DeviceTarget
@@ -45,14 +48,19 @@ except ImportError:  # pragma: no cover
     from numpy import VisibleDeprecationWarning
 
 
-def _native_desc(move, ndim, can_fuse=True):
+def _native_desc(move, ndim, can_fuse=True, philox=False):
     """MoveDesc of a built-in move (ours, or a reference emcee instance of the same class name
     with an un-overridden get_proposal); None for anything else.  Whole-ensemble Metropolis moves
-    (``_fused_only``) are only worth a device step when the log-prob is evaluated there too."""
+    (``_fused_only``) are only worth a device step when the log-prob is evaluated there too.
+    WalkMove and KDEMove have a device proposal in the Philox mode only (``philox``)."""
     if getattr(move, "_fused_only", False) and not can_fuse:
         return None
     if hasattr(move, "_is_native"):
-        return move._desc(ndim) if move._is_native() else None
+        if move._is_native():
+            return move._desc(ndim)
+        if philox and getattr(move, "_philox_kind", None) is not None and move._is_native_philox():
+            return move._philox_desc(ndim)
+        return None
     for klass in type(move).__mro__:
         if "get_proposal" in klass.__dict__:
             owner, mod = klass.__name__, klass.__module__
@@ -70,6 +78,10 @@ def _native_desc(move, ndim, can_fuse=True):
             return _lib.MoveDesc(_lib.MOVE_DE, ns, rs, 0, 2.0, float(move.sigma), float(g0), 0.0)
         if owner == "DESnookerMove":
             return _lib.MoveDesc(_lib.MOVE_SNOOKER, ns, rs, 0, 2.0, 0.0, 0.0, float(move.gammas))
+        if owner == "WalkMove" and philox:
+            return walk_desc(move.s, ns, rs, ndim)
+        if owner == "KDEMove" and philox:
+            return kde_desc(move.bw_method, ns, rs, ndim)
     except AttributeError:
         return None
     return None
@@ -245,6 +257,10 @@ class EnsembleSampler(object):
             self._ens = DeviceEnsemble(self.nwalkers, self.ndim, device=self.device)
         return self._ens
 
+    def _philox_moves(self):
+        """WalkMove / KDEMove take the device proposal: Philox mode, one replica (a sharded run keeps its refusal of host moves)."""
+        return self.rng == "philox" and self._dist is None
+
     def _philox_seed(self):
         self._flush_rng()
         key = self._random.get_state()[1]
@@ -343,7 +359,7 @@ class EnsembleSampler(object):
 
         # which execution path
         can_fuse = self._device_target is not None and state.blobs is None
-        descs = [_native_desc(m, self.ndim, can_fuse) for m in self._moves]
+        descs = [_native_desc(m, self.ndim, can_fuse, self._philox_moves()) for m in self._moves]
         native = all(d is not None for d in descs)
         fused = native and can_fuse
         own_backend = isinstance(self.backend, Backend)
@@ -510,7 +526,7 @@ class EnsembleSampler(object):
             return None
         if not isinstance(self.backend, Backend) or nsteps is None or nsteps < 1:
             return None
-        descs = [_native_desc(m, self.ndim, True) for m in self._moves]
+        descs = [_native_desc(m, self.ndim, True, self._philox_moves()) for m in self._moves]
         if any(d is None for d in descs):
             return None
         thin_by = int(kw.get("thin_by", 1))

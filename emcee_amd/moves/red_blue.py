@@ -27,6 +27,9 @@ class RedBlueMove(Move):
     """
 
     _native_kind = None      # set by StretchMove / DEMove / DESnookerMove
+    # set by WalkMove / KDEMove: a device proposal in the sampler's Philox mode only (EnsembleSampler(rng="philox")).  Kept apart
+    # from _native_kind: propose() below plans with MT19937, where these moves keep the host get_proposal.
+    _philox_kind = None
 
     def __init__(self, nsplits=2, randomize_split=True, live_dangerously=False):
         self.nsplits = int(nsplits)
@@ -48,6 +51,19 @@ class RedBlueMove(Move):
             if "get_proposal" in klass.__dict__:
                 return klass.__module__.startswith("emcee_amd.moves")
         return False
+
+    def _is_native_philox(self):
+        """True when a Philox-only move (_philox_kind) still has the library's own get_proposal."""
+        if self._philox_kind is None:
+            return False
+        for klass in type(self).__mro__:
+            if "get_proposal" in klass.__dict__:
+                return klass.__module__.startswith("emcee_amd.moves")
+        return False
+
+    def _philox_desc(self, ndim):
+        """-> MoveDesc of a Philox-only move, or None where the device proposal does not apply."""
+        return None
 
     def _desc(self, ndim):
         """-> MoveDesc for emx_set_moves (subclasses fill their parameters)."""

@@ -41,7 +41,15 @@ enum emx_move_kind {
      * vector instead), a != 0 enables the step-size factor exp(U(-g0, g0)) with g0 = ln(factor)
      * (gaussian.py:81-84), gammas = the sequential mode's coordinate cursor (gaussian.py:96-97; the library
      * advances it, emx_get_move reads it back). */
-    EMX_MOVE_GAUSS = 3
+    EMX_MOVE_GAUSS = 3,
+    /* (4 is not a public kind: the kernels' proposal-evaluation pass carries it) */
+    /* moves/walk.py: WalkMove, rng mode EMX_RNG_PHILOX only, ndim <= 128.  Fields: reserved = s, the helper walkers per update
+     * (0: the whole complement; otherwise 2 <= s <= 1024 and s <= the complement of every split). */
+    EMX_MOVE_WALK = 5,
+    /* moves/kde.py: KDEMove, rng mode EMX_RNG_PHILOX only, ndim <= 128.  Fields: reserved = the bandwidth rule (0 Scott,
+     * 1 Silverman, 2 scalar), a = the scalar factor of rule 2.  A complement covariance that is not positive definite sets
+     * status bit 5 (scipy.stats.gaussian_kde's LinAlgError). */
+    EMX_MOVE_KDE = 6
 };
 enum emx_gauss_mode { EMX_GAUSS_VECTOR = 0, EMX_GAUSS_RANDOM = 1, EMX_GAUSS_SEQUENTIAL = 2 };
 
@@ -79,7 +87,8 @@ int emx_sync(emx_ctx* ctx);
  * (raised again by every later barrier of that attachment), bit4 the device producer of exact-mode plans (rng mode MT19937,
  * large ensembles) stalled -- a stage waited 20 s for another -- or its stream ran out under the tokenizer: the steps taken from
  * it are void; the call that retires the producer (emx_run's next start, emx_rng_get_mt19937, emx_set_moves ...) returns the
- * error as well and leaves the generator where it stood before the producer started.  Reading clears it. */
+ * error as well and leaves the generator where it stood before the producer started; bit5 EMX_MOVE_KDE: the complement's
+ * covariance is not positive definite (the proposals of that half-step are rejected).  Reading clears it. */
 int emx_status(emx_ctx* ctx, uint32_t* bits);
 /* Tuning keys (A/B measurements, parity tests; defaults are what the product runs).  An unknown key is an error.  The environment
  * variable EMX_TUNE="key=value,key=value" applies keys to every context at creation.  One table -- nothing measured-and-rejected is
@@ -481,6 +490,11 @@ int emx_host_split_draws(emx_mt* m, int64_t nwalkers, const emx_move_desc* mv, c
 int emx_host_plan_philox(uint64_t seed, uint64_t step, int64_t nwalkers, const emx_move_desc* mv, int32_t* off,
                          int32_t* order, int32_t* p0, int32_t* p1, int32_t* p2, double* s0, double* uacc);
 int32_t emx_host_move_choice_philox(uint64_t seed, uint64_t step, const double* cdf, int32_t n);
+/* EMX_MOVE_WALK / EMX_MOVE_KDE in native mode: the draws of every slot of `split` (slot order of emx_host_plan_philox).
+ * helpers: walk s >= 2 -> (ns, s) helper walkers in draw order, KDE -> (ns) kernel centres, walk s == 0 -> unused (may be NULL);
+ * normals: walk s >= 2 -> (ns, s), walk s == 0 and KDE -> (ns, ndim).  Returns ns, or -1 for bad arguments. */
+int64_t emx_host_walk_kde_draws(uint64_t seed, uint64_t step, int64_t nwalkers, int32_t ndim, const emx_move_desc* mv, int32_t split,
+                                int32_t* helpers, double* normals);
 /* pull exchange: records per (source, destination) pair of one half-step (what emx_pull_prepare returns) */
 int64_t emx_host_pull_capacity(int64_t nwalkers, int32_t world, int32_t nsplits, int32_t partners_per_walker);
 
