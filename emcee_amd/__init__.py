@@ -8,8 +8,9 @@ gfx950 behind a C ABI (``include/emx.h``, ``emcee_amd/libemx.so``).  See DESIGN.
 __version__ = "0.1.0"
 
 from . import autocorr, backends, moves, targets
+from .batch import EnsembleBatch
 from .ensemble import EnsembleSampler, walkers_independent
 from .state import State
 
-__all__ = ["EnsembleSampler", "walkers_independent", "State", "moves", "autocorr", "backends", "targets",
+__all__ = ["EnsembleSampler", "EnsembleBatch", "walkers_independent", "State", "moves", "autocorr", "backends", "targets",
            "__version__"]

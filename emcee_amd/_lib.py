@@ -36,6 +36,7 @@ _ip = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
+_u64p = np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")
 _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 
 # name -> (restype, argtypes); every symbol include/emx.h declares
@@ -145,6 +146,27 @@ SIGNATURES = {
     "emx_host_plan_philox": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(MoveDesc), _ip, _ip, _ip, _ip, _ip, _dp, _dp]),
     "emx_host_walk_kde_draws": (C.c_int64, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(MoveDesc), C.c_int32, _P, _dp]),
     "emx_host_move_choice_philox": (C.c_int32, [C.c_uint64, C.c_uint64, _dp, C.c_int32]),
+    "emx_batch_check": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MoveDesc), C.c_char_p, C.c_int32]),
+    "emx_batch_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(_P)]),
+    "emx_batch_destroy": (C.c_int, [_P]),
+    "emx_batch_last_error": (C.c_char_p, [_P]),
+    "emx_batch_set_tuning": (C.c_int, [_P, C.c_char_p, C.c_int64]),
+    "emx_batch_set_target": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32]),
+    "emx_batch_set_moves": (C.c_int, [_P, C.c_int32, C.POINTER(MoveDesc), _dp]),
+    "emx_batch_set_move_scale": (C.c_int, [_P, C.c_int32, _dp, C.c_int32]),
+    "emx_batch_get_move": (C.c_int, [_P, C.c_int32, C.POINTER(MoveDesc)]),
+    "emx_batch_set_philox": (C.c_int, [_P, _u64p, C.c_uint64]),
+    "emx_batch_get_philox": (C.c_int, [_P, _u64p, C.POINTER(C.c_uint64)]),
+    "emx_batch_set_state": (C.c_int, [_P, _dp, _P]),
+    "emx_batch_get_state": (C.c_int, [_P, _P, _P]),
+    "emx_batch_eval_state_log_prob": (C.c_int, [_P]),
+    "emx_batch_chain_config": (C.c_int, [_P, C.c_int64]),
+    "emx_batch_run": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32]),
+    "emx_batch_iteration": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "emx_batch_chain_read": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _dp]),
+    "emx_batch_accepted_counts": (C.c_int, [_P, _dp]),
+    "emx_batch_status": (C.c_int, [_P, _u32p]),
+    "emx_batch_launch_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
 }
 
 

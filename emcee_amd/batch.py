@@ -1,0 +1,339 @@
+"""Many independent small ensembles in one launch.
+
+:class:`EnsembleBatch` runs B ensembles of one shape ``(nwalkers, ndim)`` -- replicated runs of one posterior, one fit per
+object of a catalogue, a parameter sweep -- each with its own initial state, seed and (optionally) target parameters.  Every
+``run_mcmc`` chunk is ONE launch of the one-workgroup kernel (``emx_batch_*`` in ``include/emx.h``): workgroup b runs
+member b exactly as :class:`~emcee_amd.EnsembleSampler` with ``rng="philox"`` runs that ensemble, so member b is bit for bit
+the sampler built with the same target, moves and initial state whose private generator was seeded with ``seeds[b]``::
+
+    s = EnsembleSampler(nwalkers, ndim, target_b, moves, rng="philox")
+    s.random_state = np.random.RandomState(seeds[b]).get_state()
+
+Philox mode only; fused device targets (``IsoGaussian``, ``DiagGaussian``, ``DenseGaussian``, ``Rosenbrock``,
+``UniformBox``); stretch, DE, snooker and Gaussian moves; every member must fit one workgroup (``nwalkers <= 4096``,
+``ndim <= 256`` and the LDS bound).  Host callables, ``DeviceCallable`` and ``DeviceKernel`` targets run through
+:class:`~emcee_amd.EnsembleSampler`.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .autocorr import integrated_time
+from .ensemble import _native_desc, _parse_move_schedule, _refuse_extended_precision, philox_seed, walkers_independent
+from .state import State
+from .targets import DenseGaussian, DeviceCallable, DeviceKernel, DeviceTarget, DiagGaussian, IsoGaussian, Rosenbrock, UniformBox
+
+__all__ = ["EnsembleBatch"]
+
+_TARGETS = (IsoGaussian, DiagGaussian, DenseGaussian, Rosenbrock, UniformBox)
+_MOVES = (_lib.MOVE_STRETCH, _lib.MOVE_DE, _lib.MOVE_SNOOKER, _lib.MOVE_GAUSS)
+_ILL = ("Initial state has a large condition number. Make sure that your walkers are linearly independent for the best "
+        "performance")
+
+
+def _member_error(b, text):
+    return ValueError("member %d: %s" % (b, text))
+
+
+class EnsembleBatch(object):
+    """B independent ensembles of ``nwalkers`` walkers in ``ndim`` dimensions, run together on one GPU.
+
+    ``target``: one :class:`~emcee_amd.targets.DeviceTarget` for every member, or a sequence of B targets of one class (one
+    per member).  ``moves``: the schedule forms of :class:`~emcee_amd.EnsembleSampler` over StretchMove, DEMove,
+    DESnookerMove and GaussianMove.  ``seeds``: B integers; member b draws as a sampler whose generator was seeded with
+    ``np.random.RandomState(seeds[b])``.  ``None`` draws them from NumPy's global state."""
+
+    def __init__(self, nbatch, nwalkers, ndim, target, moves=None, seeds=None, device=None, rng="philox"):
+        if rng != "philox":
+            raise ValueError("EnsembleBatch runs rng='philox' only (the MT19937 stream is made by one host generator a "
+                             "sampler; use EnsembleSampler for rng=%r)" % (rng,))
+        self.nbatch, self.nwalkers, self.ndim = int(nbatch), int(nwalkers), int(ndim)
+        if self.nbatch < 1 or self.nwalkers < 1 or self.ndim < 1:
+            raise ValueError("nbatch, nwalkers and ndim must be positive")
+        self.rng = rng
+        self.device = 0 if device is None else int(device)
+        self._targets, self._per_member = self._parse_targets(target)
+        self._moves, self._weights = _parse_move_schedule(moves)
+        self._descs = []
+        for m in self._moves:
+            d = _native_desc(m, self.ndim, True, False)
+            if d is None or d.kind not in _MOVES:
+                raise ValueError("EnsembleBatch runs StretchMove, DEMove, DESnookerMove and GaussianMove; %s is not one of "
+                                 "them (use EnsembleSampler)" % type(m).__name__)
+            self._descs.append(d)
+        if any(d.kind == _lib.MOVE_GAUSS and d.reserved == _lib.GAUSS_SEQUENTIAL for d in self._descs) and len(self._descs) > 1:
+            raise ValueError("EnsembleBatch runs a sequential GaussianMove only as the one move of the schedule")
+        lib = _lib.load()
+        msg = C.create_string_buffer(256)
+        arr = (_lib.MoveDesc * len(self._descs))(*self._descs)
+        if lib.emx_batch_check(self.nwalkers, self.ndim, self._targets[0].kind, len(self._descs), arr, msg, 256) != 0:
+            raise ValueError("EnsembleBatch: %s" % msg.value.decode())
+        if seeds is None:
+            seeds = np.random.randint(0, 2 ** 32, size=self.nbatch, dtype=np.uint64)
+        seeds = [int(s) for s in np.asarray(seeds).reshape(-1)]
+        if len(seeds) != self.nbatch:
+            raise ValueError("seeds must hold nbatch = %d integers; got %d" % (self.nbatch, len(seeds)))
+        self.seeds = seeds
+        self._philox = np.array([philox_seed(np.random.RandomState(s)) for s in seeds], dtype=np.uint64)
+        self._h = None
+        self._tuning = {}
+        self._step = 0
+        self._ran = False
+
+    # ------------------------------------------------------------------ argument checks (no device involved)
+    def _parse_targets(self, target):
+        if isinstance(target, DeviceTarget) or callable(target):
+            targets, per_member = [target], False
+        else:
+            targets, per_member = list(target), True
+            if len(targets) != self.nbatch:
+                raise ValueError("target: one DeviceTarget for all members or a sequence of nbatch = %d; got %d"
+                                 % (self.nbatch, len(targets)))
+        for t in targets:
+            if isinstance(t, (DeviceCallable, DeviceKernel)) or not isinstance(t, _TARGETS):
+                raise TypeError("EnsembleBatch runs the fused device targets (%s); run %s with EnsembleSampler"
+                                % (", ".join(k.__name__ for k in _TARGETS), type(t).__name__))
+        if len({type(t) for t in targets}) != 1:
+            raise ValueError("the targets of a batch must be of one class; got %s" % sorted({type(t).__name__ for t in targets}))
+        for b, t in enumerate(targets):
+            if t.ndim is not None and t.ndim != self.ndim:
+                raise ValueError("member %d: target of ndim %d in a batch of ndim %d" % (b, t.ndim, self.ndim))
+        return targets, per_member
+
+    def _check_state(self, coords):
+        coords = np.asarray(coords)
+        _refuse_extended_precision(coords)
+        if coords.shape != (self.nbatch, self.nwalkers, self.ndim):
+            raise ValueError("incompatible input dimensions %s: expected (nbatch, nwalkers, ndim) = %s"
+                             % (coords.shape, (self.nbatch, self.nwalkers, self.ndim)))
+        coords = np.ascontiguousarray(coords, dtype=np.float64)
+        for b in range(self.nbatch):
+            if not np.all(np.isfinite(coords[b])):
+                raise _member_error(b, "At least one parameter value was infinite" if np.any(np.isinf(coords[b]))
+                                    else "At least one parameter value was NaN")
+        return coords
+
+    # ------------------------------------------------------------------ device plumbing
+    def _lib(self):
+        return _lib.load()
+
+    def _ck(self, rc):
+        if rc != 0:
+            msg = self._lib().emx_batch_last_error(self._h)
+            raise _lib.EmxError((msg or b"unknown error").decode() + " (code %d)" % rc)
+
+    def _handle(self):
+        if self._h is not None:
+            return self._h
+        lib = self._lib()
+        h = C.c_void_p()
+        if lib.emx_batch_create(self.device, self.nbatch, self.nwalkers, self.ndim, C.byref(h)) != 0:
+            raise _lib.EmxError("emx_batch_create failed (no usable HIP device %d, or out of memory)" % self.device)
+        self._h = h
+        kind = self._targets[0].kind
+        params = [t.emx_params() for t in self._targets]
+        p0 = p1 = None
+        if kind in (_lib.TARGET_DIAG, _lib.TARGET_DENSE):
+            p0 = np.ascontiguousarray(np.stack([p[1] for p in params]), dtype=np.float64)
+            p1 = np.ascontiguousarray(np.stack([p[2] for p in params]), dtype=np.float64)
+        scales = np.ascontiguousarray([p[3] for p in params], dtype=np.float64)
+        ptr = (lambda a: None if a is None else a.ctypes.data_as(C.c_void_p))
+        self._ck(lib.emx_batch_set_target(h, kind, ptr(p0), ptr(p1), ptr(scales), int(self._per_member)))
+        cdf = np.cumsum(self._weights)
+        cdf /= cdf[-1]
+        arr = (_lib.MoveDesc * len(self._descs))(*self._descs)
+        self._ck(lib.emx_batch_set_moves(h, len(self._descs), arr, np.ascontiguousarray(cdf)))
+        for i, m in enumerate(self._moves):
+            vec = getattr(m, "_scale_vector", None)
+            v = vec() if vec is not None and self._descs[i].kind == _lib.MOVE_GAUSS else None
+            if v is not None:              # per-coordinate standard deviations (None: the isotropic sigma)
+                v = np.ascontiguousarray(v, dtype=np.float64)
+                self._ck(lib.emx_batch_set_move_scale(h, i, v, len(v)))
+        for k, v in self._tuning.items():
+            self._ck(lib.emx_batch_set_tuning(h, k.encode(), int(v)))
+        self._ck(lib.emx_batch_set_philox(h, self._philox, self._step))
+        return h
+
+    def set_tuning(self, key, value):
+        """``"batch_threads"`` / ``"batch_plan_steps"`` (include/emx.h): the launch shape; no bit depends on it."""
+        self._tuning[key] = int(value)
+        if self._h is not None:
+            self._ck(self._lib().emx_batch_set_tuning(self._h, key.encode(), int(value)))
+
+    def launch_info(self):
+        """-> dict(threads, plan_steps, launches): the last launch's shape and the launches so far."""
+        t, p, n = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        if self._h is not None:
+            self._ck(self._lib().emx_batch_launch_info(self._h, C.byref(t), C.byref(p), C.byref(n)))
+        return dict(threads=t.value, plan_steps=p.value, launches=n.value)
+
+    def close(self):
+        if self._h is not None:
+            self._lib().emx_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _raise_on_status(self, what):
+        bits = np.zeros(self.nbatch, dtype=np.uint32)
+        self._ck(self._lib().emx_batch_status(self._h, bits))
+        bad = np.flatnonzero(bits)
+        if len(bad):
+            b = int(bad[0])
+            text = ("At least one parameter value was infinite or NaN" if bits[b] & 2 else
+                    "The initial log_prob was NaN" if what == "eval" else "Probability function returned NaN")
+            more = "" if len(bad) == 1 else " (and members %s)" % bad[1:].tolist()
+            raise ValueError("member %d: %s%s" % (b, text, more))
+
+    # ------------------------------------------------------------------ sampling
+    def run_mcmc(self, initial_state, nsteps, thin_by=1, store=True, skip_initial_state_check=False):
+        """Advance every member ``nsteps`` stored steps (``nsteps * thin_by`` proposals) -> :class:`State` with ``(B, nwalkers,
+        ndim)`` coordinates and ``(B, nwalkers)`` log-probs.  ``initial_state`` ``(B, nwalkers, ndim)`` (an array or a State),
+        or None to continue from where the last call stopped.  Checks as ``EnsembleSampler.run_mcmc``, member by member."""
+        nsteps, thin_by = int(nsteps), int(thin_by)
+        if thin_by <= 0:
+            raise ValueError("Invalid thinning argument")
+        if nsteps < 0:
+            raise ValueError("nsteps must be >= 0")
+        coords = None
+        if initial_state is None:
+            if not self._ran:
+                raise ValueError("Cannot have `initial_state=None` if run_mcmc has never been called.")
+        else:
+            coords = self._check_state(initial_state.coords if isinstance(initial_state, State) else initial_state)
+            if not skip_initial_state_check:
+                for b in range(self.nbatch):
+                    if not walkers_independent(coords[b]):
+                        raise _member_error(b, _ILL)
+        for m in self._moves:
+            if self.nwalkers < 2 * self.ndim and hasattr(m, "nsplits") and not getattr(m, "live_dangerously", False):
+                raise RuntimeError("It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions.")
+        lib = self._lib()
+        h = self._handle()
+        if coords is not None:
+            self._ck(lib.emx_batch_set_state(h, coords, None))
+            self._ck(lib.emx_batch_eval_state_log_prob(h))
+            self._raise_on_status("eval")
+            self._ran = True
+        if store:
+            self._ck(lib.emx_batch_chain_config(h, self.iteration + nsteps))
+        self._ck(lib.emx_batch_run(h, nsteps, thin_by, int(bool(store))))
+        self._sync_moves()
+        step = C.c_uint64(0)
+        self._ck(lib.emx_batch_get_philox(h, np.zeros(self.nbatch, dtype=np.uint64), C.byref(step)))
+        self._step = step.value
+        self._raise_on_status("run")
+        return self.get_last_sample()
+
+    def _sync_moves(self):
+        for i, m in enumerate(self._moves):          # the sequential Gaussian mode's cursor lives in the move
+            prop = getattr(m, "get_proposal", None)
+            if hasattr(m, "_scale_vector") and getattr(prop, "mode", None) == "sequential":
+                d = _lib.MoveDesc()
+                self._ck(self._lib().emx_batch_get_move(self._h, i, C.byref(d)))
+                prop.index = int(d.gammas)
+
+    # ------------------------------------------------------------------ results
+    @property
+    def iteration(self):
+        """Stored steps of every member."""
+        if self._h is None:
+            return 0
+        s, p = C.c_int64(0), C.c_int64(0)
+        self._ck(self._lib().emx_batch_iteration(self._h, C.byref(s), C.byref(p)))
+        return s.value
+
+    def _read(self, what, lo, hi, discard, thin, flat):
+        it = self.iteration
+        if it <= 0:
+            raise AttributeError("you must run the sampler with 'store == True' before accessing the results")
+        thin, discard = int(thin), int(discard)
+        start = min(discard + thin - 1, it)                 # reference backend.py:53
+        nsel = len(range(start, it, thin))
+        shape = (hi - lo, nsel, self.nwalkers) + ((self.ndim,) if what == 0 else ())
+        out = np.empty(shape)
+        if nsel and hi > lo:
+            self._ck(self._lib().emx_batch_chain_read(self._h, what, lo, hi, start, it, thin, out))
+        if flat:
+            out = out.reshape((hi - lo, nsel * self.nwalkers) + shape[3:])
+        return out
+
+    def get_chain(self, discard=0, thin=1, flat=False):
+        """``(B, nsteps, nwalkers, ndim)``; ``flat`` -> ``(B, nsteps * nwalkers, ndim)``."""
+        return self._read(0, 0, self.nbatch, discard, thin, flat)
+
+    def get_log_prob(self, discard=0, thin=1, flat=False):
+        """``(B, nsteps, nwalkers)``; ``flat`` -> ``(B, nsteps * nwalkers)``."""
+        return self._read(1, 0, self.nbatch, discard, thin, flat)
+
+    def _accepted(self):
+        out = np.zeros((self.nbatch, self.nwalkers))
+        if self._h is not None:
+            self._ck(self._lib().emx_batch_accepted_counts(self._h, out))
+        return out
+
+    @property
+    def acceptance_fraction(self):
+        """``(B, nwalkers)``: the fraction of proposed steps that were accepted."""
+        return self._accepted() / float(self.iteration)
+
+    def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False):
+        """``(B, ndim)``: :func:`emcee_amd.autocorr.integrated_time` of each member's chain, in steps."""
+        return np.stack([self[b].get_autocorr_time(discard=discard, thin=thin, c=c, tol=tol, quiet=quiet)
+                         for b in range(self.nbatch)])
+
+    def get_last_sample(self):
+        """:class:`State` with ``(B, nwalkers, ndim)`` coordinates and ``(B, nwalkers)`` log-probs."""
+        if self._h is None or not self._ran:
+            raise AttributeError("you must run the sampler before accessing the last sample")
+        coords = np.empty((self.nbatch, self.nwalkers, self.ndim))
+        lp = np.empty((self.nbatch, self.nwalkers))
+        self._ck(self._lib().emx_batch_get_state(self._h, coords.ctypes.data_as(C.c_void_p), lp.ctypes.data_as(C.c_void_p)))
+        return State(coords, log_prob=lp)
+
+    def __len__(self):
+        return self.nbatch
+
+    def __getitem__(self, b):
+        b = int(b)
+        if b < 0:
+            b += self.nbatch
+        if not 0 <= b < self.nbatch:
+            raise IndexError("member %d outside a batch of %d" % (b, self.nbatch))
+        return _Member(self, b)
+
+
+class _Member(object):
+    """Read-only view of member b: the getters of :class:`~emcee_amd.EnsembleSampler`, on that member's results."""
+
+    def __init__(self, batch, b):
+        self._batch, self.index = batch, b
+        self.nwalkers, self.ndim = batch.nwalkers, batch.ndim
+        self.seed = batch.seeds[b]
+
+    @property
+    def iteration(self):
+        return self._batch.iteration
+
+    def get_chain(self, discard=0, thin=1, flat=False):
+        return self._batch._read(0, self.index, self.index + 1, discard, thin, flat)[0]
+
+    def get_log_prob(self, discard=0, thin=1, flat=False):
+        return self._batch._read(1, self.index, self.index + 1, discard, thin, flat)[0]
+
+    @property
+    def acceptance_fraction(self):
+        return self._batch.acceptance_fraction[self.index]
+
+    def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False):
+        x = self.get_chain(discard=discard, thin=thin)
+        return thin * integrated_time(x, c=c, tol=tol, quiet=quiet)
+
+    def get_last_sample(self):
+        s = self._batch.get_last_sample()
+        return State(s.coords[self.index], log_prob=s.log_prob[self.index])

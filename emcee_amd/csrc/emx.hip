@@ -25,6 +25,7 @@
 #include "emx_mtpipe.hpp"
 #include "emx_walkkde.hpp"
 #include "emx_rng.hpp"
+#include "emx_small_host.hpp"
 #include "mt19937_legacy.hpp"
 
 using namespace emx;
@@ -249,10 +250,6 @@ int rccl_load(const char* path, std::string& err) {
     return 0;
 }
 
-struct Shape {
-    int G, V, CH;
-};
-
 // Layout of a plan slot, the same in the device block and in its pinned staging buffer: [order | p0] int32, [s0 | uacc]
 // f64, [p1 | p2] int32 -- what a stretch step needs (one partner, 24 bytes per walker) is a prefix, so its upload stops
 // there; DE / snooker / Gaussian plans go up whole (32 bytes per walker).  (The device block continues with logu | fac.)
@@ -264,25 +261,6 @@ struct HostPlan {
           s0((double*)(base + N * 8)), uacc((double*)(base + N * 8) + N) {}
 };
 inline size_t plan_upload_bytes(size_t N, int move_kind) { return N * (move_kind == EMX_MOVE_STRETCH ? 24 : 32); }
-
-// Row layout for a row of `Dcover` doubles: G lanes x CH chunks x V doubles, chosen to minimise
-// the instructions per walker (few lanes per walker -> short cross-lane reductions, many walkers per
-// pass) while every chunk of a row is still read as whole 128-byte lines (G*V*8 >= 128 B).
-constexpr int shape_g(int cols) {
-    return cols <= 4 ? 4 : cols <= 32 ? 8 : cols <= 64 ? 16 : cols <= 128 ? 32 : 64;
-}
-constexpr int shape_ch(int cols) {
-    return cols <= 8 ? 1 : cols <= 16 ? 2 : cols <= 256 ? 4 : cols <= 512 ? 8 : 16;
-}
-
-Shape pick_shape(int D, int Dcover) {
-    Shape s;
-    s.V = (D % 2 == 0) ? 2 : 1;
-    const int cols = (Dcover + s.V - 1) / s.V;
-    s.G = shape_g(cols);
-    s.CH = shape_ch(cols);
-    return s;
-}
 
 }  // namespace
 
@@ -758,7 +736,6 @@ int prefetch_depth_host(int G, int V, int CH, int move, bool dense) {
 // dense Gaussian targets whose Cholesky image does not fit LDS next to the MFMA tiles (or tuning "dense_wide" = 1, for tests)
 // The fused kernel holds the packed triangular image of L plus one 16-row tile per wave in LDS: up to padded ndim 128
 // (36 blocks = 72 KB + 4 waves x 16.6 KB; round 3 -- 112 with 8- and 4-wave groups before)
-constexpr int DENSE_FUSED_MAX_DP = 128;
 inline bool dense_is_wide(const emx_ctx* c) { return c->Dp > DENSE_FUSED_MAX_DP || c->tune_dense_wide; }
 
 // launch one fused (or propose-only) half-step over the slots [t_lo, t_hi) of `split`
@@ -1855,41 +1832,14 @@ int emx_set_target(emx_ctx* c, int32_t kind, const double* p0, const double* p1,
             NEED(c, nDp <= 2048, "dense Gaussian target supports ndim <= 2048; got %d", c->D);
             // -0.5 d^T A d with A = sym(icov) = L L^T  ==  -0.5 |L^T d|^2.  Factor once on the host and upload the
             // image the kernel stages into LDS: L in MFMA B-fragment order (zero padded) followed by the mean.
-            const int Dp = nDp, KK = Dp / 4, n = (int)D;
-            std::vector<double> Lm((size_t)n * n, 0.0);
-            for (int i = 0; i < n; ++i)
-                for (int j = 0; j <= i; ++j) {
-                    double sum = 0.5 * (p1[(size_t)i * n + j] + p1[(size_t)j * n + i]);
-                    for (int k = 0; k < j; ++k) sum -= Lm[(size_t)i * n + k] * Lm[(size_t)j * n + k];
-                    if (i == j) {
-                        NEED(c, sum > 0.0 && std::isfinite(sum),
-                             "dense Gaussian target: icov must be symmetric positive definite (Cholesky failed at row %d)", i);
-                        Lm[(size_t)i * n + i] = std::sqrt(sum);
-                    } else {
-                        Lm[(size_t)i * n + j] = sum / Lm[(size_t)j * n + j];
-                    }
-                }
-            img.assign((size_t)Dp * Dp + Dp, 0.0);
-            for (int nb = 0; nb < Dp / 16; ++nb)
-                for (int kk = 0; kk < KK; ++kk)
-                    for (int l = 0; l < 64; ++l) {
-                        const int k = 4 * kk + (l >> 4), col = 16 * nb + (l & 15);
-                        if (k < n && col < n && k >= col) img[((size_t)nb * KK + kk) * 64 + l] = Lm[(size_t)k * n + col];
-                    }
-            for (int d = 0; d < n; ++d) img[(size_t)Dp * Dp + d] = p0[d];
+            const int Dp = nDp, bad = dense_image((int)D, p0, p1, img);
+            NEED(c, bad < 0, "dense Gaussian target: icov must be symmetric positive definite (Cholesky failed at row %d)", bad);
             if (Dp <= DENSE_FUSED_MAX_DP) {
                 // the fused kernel and k_small_run stage only the non-zero 16 x 16 blocks (dense_block, emx_kernels.hpp); the
                 // full image stays next to it for the wide-target kernels (tuning "dense_wide")
                 HIPOK(c, hipMalloc((void**)&ntpf, img.size() * 8));
                 HIPOK(c, hipMemcpy(ntpf, img.data(), img.size() * 8, hipMemcpyHostToDevice));
-                const int B = Dp / 16;
-                std::vector<double> packed((size_t)dense_img_doubles(Dp) + Dp, 0.0);
-                for (int nb = 0; nb < B; ++nb)
-                    for (int kb = nb; kb < B; ++kb)
-                        for (int i = 0; i < 4; ++i)
-                            for (int l = 0; l < 64; ++l)
-                                packed[((size_t)dense_block(B, nb, kb) * 4 + i) * 64 + l] = img[((size_t)nb * KK + 4 * kb + i) * 64 + l];
-                for (int d = 0; d < Dp; ++d) packed[(size_t)dense_img_doubles(Dp) + d] = img[(size_t)Dp * Dp + d];
+                std::vector<double> packed = dense_pack(Dp, img);
                 img.swap(packed);
             }
         }
@@ -3158,32 +3108,7 @@ static int scatter_gathered(emx_ctx* c, int32_t split, int64_t block_rows);
 hipError_t emx_small_dispatch(int G, int V, int CH, int dpb, int movesel, int threads, size_t lds, hipStream_t st,
                               const emx::SmallRunArgs& a);
 
-// ---- small ensembles: whole runs inside one workgroup (k_small_run) ------------------------
-// steps whose plans one pass evaluates: as many as give every thread of the workgroup an entry
-static int small_batch(int64_t N) { return (int)std::max<int64_t>(1, std::min<int64_t>(64, 1024 / N)); }
-
-// dense_dp > 0: + the Cholesky image and one 16-row tile per wave
-static size_t small_lds_bytes(int64_t N, int D, int dense_dp = 0, int waves = 0) {
-    const size_t B = (size_t)small_batch(N);
-    size_t b = (size_t)N * ((size_t)D * 8 + 8 + 4 + 1) + B * (size_t)N * (3 * 8 + 4 * 4) + 64;
-    if (dense_dp > 0) b += 16 + ((size_t)dense_img_doubles(dense_dp) + dense_dp + (size_t)waves * (16 * (dense_dp + 2) + 16)) * 8;
-    return b;
-}
-
-// threads of the one workgroup: enough for one half-step's lanes and one plan entry each across the batch; the dense
-// variant keeps one LDS tile per wave, so it takes the largest power-of-two wave count that still fits
-static int small_threads(const emx_ctx* c, int G, int minsplits, bool dense) {
-    const int64_t nsmax = (c->N + minsplits - 1) / minsplits;
-    const int64_t want = std::max<int64_t>(dense ? ((nsmax + 15) / 16) * 64 : nsmax * G, (int64_t)small_batch(c->N) * c->N);
-    int threads = (int)std::min<int64_t>(1024, std::max<int64_t>(64, ((want + 63) / 64) * 64));
-    if (dense) {
-        int waves = threads / 64;
-        while (waves > 1 && small_lds_bytes(c->N, c->D, c->Dp, waves) > 150 * 1024) waves = (waves + 1) / 2;
-        threads = waves * 64;
-    }
-    return threads;
-}
-
+// ---- small ensembles: whole runs inside one workgroup (k_small_run; shape rules in emx_small_host.hpp) -------
 static bool small_eligible(const emx_ctx* c) {
     if (!c->tune_small || (c->rng_mode != EMX_RNG_PHILOX && c->rng_mode != EMX_RNG_MT19937)) return false;
     if (c->moves.empty() || (int)c->moves.size() > SMALL_MAX_MOVES) return false;
@@ -3201,8 +3126,8 @@ static bool small_eligible(const emx_ctx* c) {
     if (c->world != 1 || c->comm || c->sendbuf || c->prof_max > 0 || c->tune_ablate || c->cur.active) return false;
     if (c->N > 4096 || c->D > 256) return false;
     if (c->target == EMX_TARGET_DENSE_GAUSS)     // one CU's matrix pipe: worth it only while the contraction is small
-        return !dense_is_wide(c) && c->N * (int64_t)c->Dp * c->Dp <= 65536 && small_lds_bytes(c->N, c->D, c->Dp, 1) <= 150 * 1024;
-    return small_lds_bytes(c->N, c->D) <= 150 * 1024;
+        return !dense_is_wide(c) && c->N * (int64_t)c->Dp * c->Dp <= 65536 && small_lds_bytes(c->N, c->D, c->Dp, 1) <= SMALL_LDS_MAX;
+    return small_lds_bytes(c->N, c->D) <= SMALL_LDS_MAX;
 }
 
 // `nsteps` full steps starting at step index i0 of the current emx_run call
@@ -3336,7 +3261,7 @@ static int run_small(emx_ctx* c, int64_t i0, int64_t nsteps, int32_t thin_by, in
         a.step_col = (const int32_t*)(bp.dev + (size_t)nsteps * 8);
         gauss_bulk = &bp;
     }
-    const int threads = small_threads(c, sh.G, minsplits, dense);
+    const int threads = small_threads(c->N, c->D, c->Dp, sh.G, minsplits, dense);
     const size_t lds = dense ? small_lds_bytes(c->N, c->D, c->Dp, threads / 64) : small_lds_bytes(c->N, c->D);
     hipError_t e = hipErrorInvalidValue;
     const int movesel = (nm == 1 && (!dense || c->moves[0].kind == EMX_MOVE_STRETCH)) ? (int)c->moves[0].kind : SMALL_ANY_MOVE;

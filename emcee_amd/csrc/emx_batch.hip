@@ -1,0 +1,564 @@
+// Batches of independent small ensembles (include/emx.h: emx_batch_*; emcee_amd.EnsembleBatch): B ensembles of one shape
+// (nwalkers, ndim), each with its own state, Philox seed, target parameters, status and chain, run by ONE launch of
+// k_small_run<..., BATCH = true> per chunk of steps -- workgroup b runs member b exactly as a single-ensemble launch runs that
+// ensemble, so every member's bits are those of an emx_ctx with the same seed, target and initial state.  Philox mode only.
+// Host side of the handle and the batched instantiations of the kernel (emx_small_launch.hpp).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/emx.h"
+#include "emx_rng.hpp"
+#include "emx_small_host.hpp"
+#include "emx_small_launch.hpp"
+
+using namespace emx;
+
+struct emx_batch {
+    int device = 0;
+    int32_t B = 0, D = 0;
+    int64_t N = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    // member-strided state: X (B, N, D), lp (B, N), acc (B, N), acc_count (B, N); status: SMALL_STATUS_WORDS words a member
+    double *X = nullptr, *lp = nullptr;
+    uint8_t* acc = nullptr;
+    uint32_t* acc_count = nullptr;
+    uint32_t *status_host = nullptr, *status = nullptr;
+    // target: kind, per-member parameters at their strides (0: shared), per-member scales
+    int32_t target = -1;
+    int Dp = 0;
+    double *tp0 = nullptr, *tp1 = nullptr, *tscales = nullptr;
+    int64_t tp0_stride = 0, tp1_stride = 0;
+    // moves
+    std::vector<emx_move_desc> moves;
+    std::vector<double> cdf;
+    std::vector<double*> mscale;
+    // Philox
+    unsigned long long* seeds = nullptr;       // device copy
+    std::vector<uint64_t> seeds_host;
+    uint64_t step = 0;
+    // chain: member-major (B, cap, N, D) and (B, cap, N)
+    double *chain = nullptr, *chain_lp = nullptr;
+    int64_t cap = 0, stored = 0, proposals = 0;
+    // per-launch Gaussian-move factors (B x steps) and columns
+    double* fac_dev = nullptr;
+    int32_t* col_dev = nullptr;
+    size_t fac_cap = 0, col_cap = 0;
+    // tuning: batch_threads / batch_plan_steps (0: auto); what the last launch used
+    int64_t tune_threads = 0, tune_plan_steps = 0;
+    int32_t last_threads = 0, last_plan_steps = 0;
+    int64_t launches = 0;
+};
+
+namespace {
+
+int fail(emx_batch* b, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (b) b->err = buf;
+    return code;
+}
+
+#define BNEED(b, cond, ...) \
+    do { \
+        if (!(cond)) return fail(b, -1, __VA_ARGS__); \
+    } while (0)
+#define BHIP(b, expr) \
+    do { \
+        hipError_t e_ = (expr); \
+        if (e_ != hipSuccess) return fail(b, -2, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+// small_eligible's rules (emx.hip) applied to one member's shape; nullptr when the kernel takes it, else why not
+const char* shape_refusal(int64_t N, int32_t D, int32_t target, int32_t nmoves, const emx_move_desc* moves, char* buf, size_t n) {
+    if (N < 2 || D < 1) return "nwalkers must be >= 2 and ndim >= 1";
+    if (N > 4096 || D > 256) {
+        snprintf(buf, n, "nwalkers x ndim = %lld x %d is outside the one-workgroup kernel (nwalkers <= 4096, ndim <= 256)", (long long)N, D);
+        return buf;
+    }
+    if (target != EMX_TARGET_ISO_GAUSS && target != EMX_TARGET_DIAG_GAUSS && target != EMX_TARGET_DENSE_GAUSS &&
+        target != EMX_TARGET_ROSENBROCK && target != EMX_TARGET_BOX)
+        return "the batch runs the fused device targets only (IsoGaussian, DiagGaussian, DenseGaussian, Rosenbrock, UniformBox)";
+    if (nmoves < 1 || nmoves > SMALL_MAX_MOVES) {
+        snprintf(buf, n, "the batch takes 1 ... %d moves; got %d", SMALL_MAX_MOVES, nmoves);
+        return buf;
+    }
+    for (int m = 0; m < nmoves; ++m) {
+        const emx_move_desc& mv = moves[m];
+        if (mv.kind != EMX_MOVE_STRETCH && mv.kind != EMX_MOVE_DE && mv.kind != EMX_MOVE_SNOOKER && mv.kind != EMX_MOVE_GAUSS)
+            return "the batch runs StretchMove, DEMove, DESnookerMove and GaussianMove only";
+        if (mv.kind != EMX_MOVE_GAUSS && (mv.nsplits < 1 || mv.nsplits > N)) return "nsplits must be in [1, nwalkers]";
+        if (mv.kind == EMX_MOVE_DE && N - (N + mv.nsplits - 1) / mv.nsplits < 2) {
+            snprintf(buf, n, "DEMove with %d splits of %lld walkers: a complement has fewer than 2 walkers", mv.nsplits, (long long)N);
+            return buf;
+        }
+    }
+    if (target == EMX_TARGET_DENSE_GAUSS) {
+        const int Dp = (D + 15) / 16 * 16;
+        if (Dp > DENSE_FUSED_MAX_DP || N * (int64_t)Dp * Dp > 65536 || small_lds_bytes(N, D, Dp, 1) > SMALL_LDS_MAX) {
+            snprintf(buf, n, "dense Gaussian target at %lld x %d is outside the one-workgroup kernel (nwalkers x padded ndim^2 <= 65536)",
+                     (long long)N, D);
+            return buf;
+        }
+    } else if (small_lds_bytes(N, D) > SMALL_LDS_MAX) {
+        snprintf(buf, n, "nwalkers x ndim = %lld x %d does not fit one workgroup's LDS (%zu bytes > %zu)", (long long)N, D,
+                 small_lds_bytes(N, D), SMALL_LDS_MAX);
+        return buf;
+    }
+    return nullptr;
+}
+
+template <typename T>
+int grow(emx_batch* b, T*& p, size_t& cap, size_t n) {
+    if (n <= cap) return 0;
+    if (p) hipFree(p);
+    p = nullptr;
+    cap = 0;
+    BHIP(b, hipMalloc((void**)&p, n * sizeof(T)));
+    cap = n;
+    return 0;
+}
+
+// launch shape of a batched launch: `threads` of one workgroup and the plan steps a pass holds in LDS.  Auto: while the batch
+// has no more members than the device has CUs, each member has a CU of its own and the single-ensemble (latency) shape
+// is kept; beyond, the workgroup is cut to one half-step's lanes (>= one wave) with plan steps for one entry a thread, so
+// that several members share a CU (32 waves, 160 KB of LDS).  Neither changes a bit: plans do not depend on the state.
+void launch_shape(const emx_batch* b, int num_cu, const Shape& sh, int minsplits, bool dense, int* threads, int* plan_steps) {
+    int t = small_threads(b->N, b->D, b->Dp, sh.G, minsplits, dense), ps = small_batch(b->N);
+    if (b->B > num_cu) {
+        const int64_t nsmax = (b->N + minsplits - 1) / minsplits;
+        const int64_t want = dense ? ((nsmax + 15) / 16) * 64 : nsmax * sh.G;
+        t = std::min(t, (int)std::min<int64_t>(1024, std::max<int64_t>(64, (want + 63) / 64 * 64)));
+        ps = (int)std::max<int64_t>(1, std::min<int64_t>(64, t / b->N));
+    }
+    if (b->tune_threads > 0) t = (int)b->tune_threads;
+    if (b->tune_plan_steps > 0) ps = (int)b->tune_plan_steps;
+    if (dense)      // one LDS tile per wave
+        while (t > 64 && small_lds_bytes(b->N, b->D, b->Dp, t / 64, ps) > SMALL_LDS_MAX) t = (t / 64 + 1) / 2 * 64;
+    while (ps > 1 && small_lds_bytes(b->N, b->D, dense ? b->Dp : 0, t / 64, ps) > SMALL_LDS_MAX) ps = (ps + 1) / 2;
+    *threads = t;
+    *plan_steps = ps;
+}
+
+// one launch: `nsteps` steps (nsteps 0 with eval0: the initial log-probs only)
+int launch(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t store, bool eval0) {
+    const int nm = (int)b->moves.size();
+    const bool dense = b->target == EMX_TARGET_DENSE_GAUSS;
+    const Shape sh = pick_shape(b->D, dense ? b->Dp : b->D);
+    SmallRunArgs a{};
+    int minsplits = 64;
+    bool any_gauss = false;
+    for (int m = 0; m < nm; ++m) {
+        const emx_move_desc& mv = b->moves[m];
+        a.kind[m] = mv.kind;
+        a.nsplits[m] = mv.nsplits;
+        a.a[m] = mv.a;
+        a.sigma[m] = mv.sigma;
+        a.g0[m] = mv.g0;
+        a.gammas[m] = mv.gammas;
+        a.cdf[m] = b->cdf[m];
+        a.gmode[m] = mv.reserved;
+        a.gsigma[m] = mv.sigma;
+        a.gscale[m] = b->mscale[m];
+        any_gauss = any_gauss || mv.kind == EMX_MOVE_GAUSS;
+        minsplits = std::min(minsplits, (int)mv.nsplits);
+    }
+    a.nmoves = nm;
+    a.X = b->X;
+    a.lp = b->lp;
+    a.acc = b->acc;
+    a.acc_count = b->acc_count;
+    a.status = b->status;
+    if (store && nsteps > 0) {
+        a.chain = b->chain + (size_t)b->stored * b->N * b->D;
+        a.chain_lp = b->chain_lp + (size_t)b->stored * b->N;
+    }
+    a.cap = b->cap;
+    a.tp0 = b->tp0;
+    a.tp1 = b->tp1;
+    a.tp0_stride = b->tp0_stride;
+    a.tp1_stride = b->tp1_stride;
+    a.tscales = b->tscales;
+    a.seeds = b->seeds;
+    a.step0 = b->step;
+    a.i0 = i0;
+    a.N = (int32_t)b->N;
+    a.D = b->D;
+    a.target = b->target;
+    a.nsteps = (int32_t)nsteps;
+    a.thin_by = thin_by;
+    a.store = store;
+    a.eval0 = eval0 ? 1 : 0;
+    if (any_gauss && nsteps > 0) {
+        // per member and step the step-size factor (a function of the member's seed and the step: run_small's arithmetic),
+        // per step the sequential mode's column (a function of the step alone: one cursor for every member)
+        std::vector<double> facs((size_t)b->B * nsteps, 1.0);
+        std::vector<int32_t> cols((size_t)nsteps, 0);
+        for (int64_t s2 = 0; s2 < nsteps; ++s2) {
+            const uint64_t step = b->step + (uint64_t)s2;
+            for (int32_t mb = 0; mb < b->B; ++mb) {
+                const uint64_t seed = b->seeds_host[mb];
+                const int mi = nm == 1 ? 0 : native_move_choice(seed, step, b->cdf.data(), nm);
+                const emx_move_desc& mv = b->moves[mi];
+                if (mv.kind != EMX_MOVE_GAUSS || mv.a == 0.0) continue;
+                const Philox4 r = philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), 0x46414354u /*'FACT'*/, 0, (uint32_t)seed,
+                                                (uint32_t)(seed >> 32));
+                facs[(size_t)mb * nsteps + s2] = std::exp(-mv.g0 + 2.0 * mv.g0 * u53(r.v[0], r.v[1]));
+            }
+        }
+        // the sequential cursor advances on the steps that draw a Gaussian move -- the same steps for every member only when
+        // the move choice does not depend on the seed, i.e. with one move (emx_batch_set_moves refuses the other case)
+        for (int64_t s2 = 0; s2 < nsteps; ++s2) {
+            emx_move_desc& mv = b->moves[0];
+            if (mv.kind == EMX_MOVE_GAUSS && mv.reserved == EMX_GAUSS_SEQUENTIAL) {
+                cols[s2] = (int32_t)((int64_t)mv.gammas % b->D);
+                mv.gammas = (double)(((int64_t)mv.gammas + 1) % b->D);
+            }
+        }
+        BHIP(b, hipStreamSynchronize(b->stream));        // the previous launch no longer reads the buffers
+        if (grow(b, b->fac_dev, b->fac_cap, facs.size())) return -2;
+        if (grow(b, b->col_dev, b->col_cap, cols.size())) return -2;
+        BHIP(b, hipMemcpy(b->fac_dev, facs.data(), facs.size() * 8, hipMemcpyHostToDevice));
+        BHIP(b, hipMemcpy(b->col_dev, cols.data(), cols.size() * 4, hipMemcpyHostToDevice));
+        a.step_fac = b->fac_dev;
+        a.step_col = b->col_dev;
+    }
+    hipDeviceProp_t prop;
+    int num_cu = 256;
+    if (hipGetDeviceProperties(&prop, b->device) == hipSuccess) num_cu = prop.multiProcessorCount;
+    int threads = 0, plan_steps = 0;
+    launch_shape(b, num_cu, sh, minsplits, dense, &threads, &plan_steps);
+    a.batch = plan_steps;
+    const size_t lds = small_lds_bytes(b->N, b->D, dense ? b->Dp : 0, threads / 64, plan_steps);
+    BNEED(b, lds <= SMALL_LDS_MAX && threads >= 64 && threads <= 1024 && threads % 64 == 0,
+          "batch launch shape: %d threads and %d plan steps need %zu bytes of LDS", threads, plan_steps, lds);
+    const int movesel = (nm == 1 && (!dense || b->moves[0].kind == EMX_MOVE_STRETCH)) ? (int)b->moves[0].kind : SMALL_ANY_MOVE;
+    const hipError_t e = small_dispatch<true>(sh.G, sh.V, sh.CH, dense ? b->Dp / 16 : 0, movesel, b->B, threads, lds, b->stream, a);
+    if (e != hipSuccess)
+        return fail(b, -2, "k_small_run batch launch failed (G=%d V=%d CH=%d ndim=%d): %s", sh.G, sh.V, sh.CH, b->D, hipGetErrorString(e));
+    b->last_threads = threads;
+    b->last_plan_steps = plan_steps;
+    ++b->launches;
+    if (nsteps > 0) {
+        int64_t nstored = 0;
+        if (store)
+            for (int64_t s2 = 0; s2 < nsteps; ++s2) nstored += ((i0 + s2 + 1) % thin_by == 0) ? 1 : 0;
+        b->stored += nstored;
+        b->proposals += nsteps;
+        b->step += (uint64_t)nsteps;
+    }
+    return 0;
+}
+
+}  // namespace
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+const char* emx_batch_last_error(emx_batch* b) { return b ? b->err.c_str() : "no batch"; }
+
+int emx_batch_check(int64_t nwalkers, int32_t ndim, int32_t target, int32_t nmoves, const emx_move_desc* moves, char* msg,
+                    int32_t msglen) {
+    char buf[256];
+    const char* why = (nmoves > 0 && !moves) ? "no moves" : shape_refusal(nwalkers, ndim, target, nmoves, moves, buf, sizeof buf);
+    if (!why) return 0;
+    if (msg && msglen > 0) snprintf(msg, (size_t)msglen, "%s", why);
+    return -1;
+}
+
+int emx_batch_create(int32_t device, int32_t nbatch, int64_t nwalkers, int32_t ndim, emx_batch** out) {
+    if (!out) return -1;
+    *out = nullptr;
+    if (nbatch < 1 || nwalkers < 2 || nwalkers > 4096 || ndim < 1 || ndim > 256) return -1;
+    emx_batch* b = new emx_batch();
+    b->device = device;
+    b->B = nbatch;
+    b->N = nwalkers;
+    b->D = ndim;
+    const size_t BN = (size_t)nbatch * nwalkers;
+    bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) == hipSuccess &&
+              hipMalloc((void**)&b->X, BN * ndim * 8) == hipSuccess && hipMalloc((void**)&b->lp, BN * 8) == hipSuccess &&
+              hipMalloc((void**)&b->acc, BN) == hipSuccess && hipMalloc((void**)&b->acc_count, BN * 4) == hipSuccess &&
+              hipMalloc((void**)&b->seeds, (size_t)nbatch * 8) == hipSuccess &&
+              hipHostMalloc((void**)&b->status_host, (size_t)nbatch * SMALL_STATUS_WORDS * 4, hipHostMallocMapped) == hipSuccess &&
+              hipHostGetDevicePointer((void**)&b->status, b->status_host, 0) == hipSuccess;
+    if (ok) {
+        std::memset(b->status_host, 0, (size_t)nbatch * SMALL_STATUS_WORDS * 4);
+        ok = hipMemset(b->X, 0, BN * ndim * 8) == hipSuccess && hipMemset(b->lp, 0, BN * 8) == hipSuccess &&
+             hipMemset(b->acc, 0, BN) == hipSuccess && hipMemset(b->acc_count, 0, BN * 4) == hipSuccess &&
+             hipMemset(b->seeds, 0, (size_t)nbatch * 8) == hipSuccess;
+        b->seeds_host.assign(nbatch, 0);
+    }
+    if (!ok) {
+        emx_batch_destroy(b);
+        return -2;
+    }
+    *out = b;
+    return 0;
+}
+
+int emx_batch_destroy(emx_batch* b) {
+    if (!b) return 0;
+    hipSetDevice(b->device);
+    if (b->stream) hipStreamSynchronize(b->stream);
+    for (void* p : {(void*)b->X, (void*)b->lp, (void*)b->acc, (void*)b->acc_count, (void*)b->seeds, (void*)b->tp0, (void*)b->tp1,
+                    (void*)b->tscales, (void*)b->chain, (void*)b->chain_lp, (void*)b->fac_dev, (void*)b->col_dev})
+        if (p) hipFree(p);
+    for (double* p : b->mscale)
+        if (p) hipFree(p);
+    if (b->status_host) hipHostFree(b->status_host);
+    if (b->stream) hipStreamDestroy(b->stream);
+    delete b;
+    return 0;
+}
+
+int emx_batch_set_tuning(emx_batch* b, const char* key, int64_t value) {
+    BNEED(b, key != nullptr, "no tuning key");
+    if (!std::strcmp(key, "batch_threads")) {
+        BNEED(b, value == 0 || (value >= 64 && value <= 1024 && value % 64 == 0), "batch_threads: 0 or a multiple of 64 in [64, 1024]");
+        b->tune_threads = value;
+    } else if (!std::strcmp(key, "batch_plan_steps")) {
+        BNEED(b, value >= 0 && value <= 64, "batch_plan_steps: 0 ... 64");
+        b->tune_plan_steps = value;
+    } else {
+        return fail(b, -1, "unknown batch tuning key '%s'", key);
+    }
+    return 0;
+}
+
+int emx_batch_set_target(emx_batch* b, int32_t kind, const double* p0, const double* p1, const double* scales, int32_t per_member) {
+    BNEED(b, kind >= EMX_TARGET_ISO_GAUSS && kind <= EMX_TARGET_BOX, "the batch runs the fused device targets only (kind %d)", kind);
+    BHIP(b, hipSetDevice(b->device));
+    const int D = b->D, Dp = (D + 15) / 16 * 16;
+    const int64_t nset = per_member ? b->B : 1;
+    std::vector<double> h0, h1;
+    int64_t s0 = 0, s1 = 0;
+    if (kind == EMX_TARGET_DIAG_GAUSS || kind == EMX_TARGET_DENSE_GAUSS) {
+        BNEED(b, p0 && p1, "target needs (mu, ivar|icov)");
+        if (kind == EMX_TARGET_DIAG_GAUSS) {
+            s0 = s1 = D;
+            h0.assign(p0, p0 + nset * D);
+            h1.assign(p1, p1 + nset * D);
+        } else {
+            BNEED(b, Dp <= DENSE_FUSED_MAX_DP, "dense Gaussian target in a batch: ndim <= %d", DENSE_FUSED_MAX_DP);
+            s0 = D;
+            s1 = (int64_t)dense_img_doubles(Dp) + Dp;
+            h0.assign(p0, p0 + nset * D);
+            h1.resize((size_t)nset * s1);
+            std::vector<double> img;
+            for (int64_t m = 0; m < nset; ++m) {
+                const int bad = dense_image(D, p0 + m * D, p1 + m * (int64_t)D * D, img);
+                BNEED(b, bad < 0, "dense Gaussian target of member %lld: icov must be symmetric positive definite (Cholesky failed at row %d)",
+                      (long long)m, bad);
+                const std::vector<double> packed = dense_pack(Dp, img);
+                std::copy(packed.begin(), packed.end(), h1.begin() + m * s1);
+            }
+        }
+    }
+    std::vector<double> sc((size_t)b->B, 1.0);
+    if (kind == EMX_TARGET_ROSENBROCK)
+        for (int32_t m = 0; m < b->B; ++m) {
+            const double v = scales ? scales[per_member ? m : 0] : 0.0;
+            sc[m] = v != 0.0 ? v : 20.0;
+        }
+    BHIP(b, hipStreamSynchronize(b->stream));      // no kernel still reads the old parameters
+    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
+        if (*p) {
+            hipFree(*p);
+            *p = nullptr;
+        }
+    if (!h0.empty()) {
+        BHIP(b, hipMalloc((void**)&b->tp0, h0.size() * 8));
+        BHIP(b, hipMemcpy(b->tp0, h0.data(), h0.size() * 8, hipMemcpyHostToDevice));
+        BHIP(b, hipMalloc((void**)&b->tp1, h1.size() * 8));
+        BHIP(b, hipMemcpy(b->tp1, h1.data(), h1.size() * 8, hipMemcpyHostToDevice));
+    }
+    BHIP(b, hipMalloc((void**)&b->tscales, sc.size() * 8));
+    BHIP(b, hipMemcpy(b->tscales, sc.data(), sc.size() * 8, hipMemcpyHostToDevice));
+    b->tp0_stride = per_member ? s0 : 0;
+    b->tp1_stride = per_member ? s1 : 0;
+    b->target = kind;
+    b->Dp = kind == EMX_TARGET_DENSE_GAUSS ? Dp : D;
+    return 0;
+}
+
+int emx_batch_set_moves(emx_batch* b, int32_t nmoves, const emx_move_desc* moves, const double* cdf) {
+    BNEED(b, moves && cdf && nmoves >= 1, "need at least one move and its cdf");
+    char buf[256];
+    const char* why = shape_refusal(b->N, b->D, b->target >= 0 ? b->target : EMX_TARGET_ISO_GAUSS, nmoves, moves, buf, sizeof buf);
+    BNEED(b, !why, "%s", why);
+    for (int m = 0; m < nmoves; ++m)
+        BNEED(b, !(moves[m].kind == EMX_MOVE_GAUSS && moves[m].reserved == EMX_GAUSS_SEQUENTIAL && nmoves > 1),
+              "the batch runs the sequential GaussianMove as the only move");
+    BHIP(b, hipStreamSynchronize(b->stream));
+    for (double* p : b->mscale)
+        if (p) hipFree(p);
+    b->moves.assign(moves, moves + nmoves);
+    b->cdf.assign(cdf, cdf + nmoves);
+    b->mscale.assign(nmoves, nullptr);
+    return 0;
+}
+
+int emx_batch_set_move_scale(emx_batch* b, int32_t move, const double* scale, int32_t n) {
+    BNEED(b, move >= 0 && move < (int32_t)b->moves.size() && b->moves[move].kind == EMX_MOVE_GAUSS, "move %d is not a Gaussian move", move);
+    BNEED(b, scale && n == b->D, "the scale vector must have ndim entries");
+    BHIP(b, hipStreamSynchronize(b->stream));
+    if (!b->mscale[move]) BHIP(b, hipMalloc((void**)&b->mscale[move], (size_t)n * 8));
+    BHIP(b, hipMemcpy(b->mscale[move], scale, (size_t)n * 8, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int emx_batch_get_move(emx_batch* b, int32_t move, emx_move_desc* out) {
+    BNEED(b, move >= 0 && move < (int32_t)b->moves.size() && out, "no move %d", move);
+    *out = b->moves[move];
+    return 0;
+}
+
+int emx_batch_set_philox(emx_batch* b, const uint64_t* seeds, uint64_t step) {
+    BNEED(b, seeds != nullptr, "no seeds");
+    BHIP(b, hipStreamSynchronize(b->stream));
+    b->seeds_host.assign(seeds, seeds + b->B);
+    BHIP(b, hipMemcpy(b->seeds, seeds, (size_t)b->B * 8, hipMemcpyHostToDevice));
+    b->step = step;
+    return 0;
+}
+
+int emx_batch_get_philox(emx_batch* b, uint64_t* seeds, uint64_t* step) {
+    if (seeds) std::copy(b->seeds_host.begin(), b->seeds_host.end(), seeds);
+    if (step) *step = b->step;
+    return 0;
+}
+
+int emx_batch_set_state(emx_batch* b, const double* coords, const double* log_prob) {
+    BNEED(b, coords != nullptr, "no coordinates");
+    const size_t BN = (size_t)b->B * b->N;
+    BHIP(b, hipMemcpyAsync(b->X, coords, BN * b->D * 8, hipMemcpyHostToDevice, b->stream));
+    if (log_prob) BHIP(b, hipMemcpyAsync(b->lp, log_prob, BN * 8, hipMemcpyHostToDevice, b->stream));
+    BHIP(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int emx_batch_get_state(emx_batch* b, double* coords, double* log_prob) {
+    const size_t BN = (size_t)b->B * b->N;
+    if (coords) BHIP(b, hipMemcpyAsync(coords, b->X, BN * b->D * 8, hipMemcpyDeviceToHost, b->stream));
+    if (log_prob) BHIP(b, hipMemcpyAsync(log_prob, b->lp, BN * 8, hipMemcpyDeviceToHost, b->stream));
+    BHIP(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int emx_batch_eval_state_log_prob(emx_batch* b) {
+    BNEED(b, b->target >= 0, "no target set");
+    BNEED(b, !b->moves.empty(), "no moves set");
+    BHIP(b, hipSetDevice(b->device));
+    return launch(b, 0, 0, 1, 0, true);
+}
+
+int emx_batch_chain_config(emx_batch* b, int64_t capacity) {
+    BNEED(b, capacity >= 0, "negative capacity");
+    if (capacity <= b->cap) return 0;
+    BHIP(b, hipSetDevice(b->device));
+    const size_t ND = (size_t)b->N * b->D, N = (size_t)b->N;
+    double *nc = nullptr, *nl = nullptr;
+    BHIP(b, hipMalloc((void**)&nc, (size_t)b->B * capacity * ND * 8));
+    if (hipMalloc((void**)&nl, (size_t)b->B * capacity * N * 8) != hipSuccess) {
+        hipFree(nc);
+        return fail(b, -2, "chain allocation failed");
+    }
+    if (b->stored > 0) {      // what is stored stays: member by member, into the longer rows
+        BHIP(b, hipMemcpy2DAsync(nc, capacity * ND * 8, b->chain, b->cap * ND * 8, b->stored * ND * 8, b->B, hipMemcpyDeviceToDevice, b->stream));
+        BHIP(b, hipMemcpy2DAsync(nl, capacity * N * 8, b->chain_lp, b->cap * N * 8, b->stored * N * 8, b->B, hipMemcpyDeviceToDevice, b->stream));
+    }
+    BHIP(b, hipStreamSynchronize(b->stream));
+    if (b->chain) hipFree(b->chain);
+    if (b->chain_lp) hipFree(b->chain_lp);
+    b->chain = nc;
+    b->chain_lp = nl;
+    b->cap = capacity;
+    return 0;
+}
+
+int emx_batch_run(emx_batch* b, int64_t nsteps, int32_t thin_by, int32_t store) {
+    BNEED(b, thin_by >= 1, "Invalid thinning argument");
+    BNEED(b, nsteps >= 0, "negative nsteps");
+    BNEED(b, b->target >= 0, "no target set");
+    BNEED(b, !b->moves.empty(), "no moves set");
+    if (store) BNEED(b, b->stored + nsteps <= b->cap, "chain capacity exhausted (call emx_batch_chain_config)");
+    BHIP(b, hipSetDevice(b->device));
+    bool any_gauss = false;
+    for (const auto& mv : b->moves) any_gauss = any_gauss || mv.kind == EMX_MOVE_GAUSS;
+    // up to 4 096 steps a launch (as a single ensemble's); with Gaussian moves the per-member factors stay <= 32 MB a launch
+    const int64_t total = nsteps * thin_by;
+    const int64_t most = any_gauss ? std::max<int64_t>(1, std::min<int64_t>(4096, (4 << 20) / b->B)) : 4096;
+    for (int64_t i = 0; i < total;) {
+        const int64_t chunk = std::min<int64_t>(total - i, most);
+        const int rc = launch(b, i, chunk, thin_by, store, false);
+        if (rc) return rc;
+        i += chunk;
+    }
+    return 0;
+}
+
+int emx_batch_iteration(emx_batch* b, int64_t* stored, int64_t* proposals) {
+    if (stored) *stored = b->stored;
+    if (proposals) *proposals = b->proposals;
+    return 0;
+}
+
+int emx_batch_chain_read(emx_batch* b, int32_t what, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop,
+                         int64_t stride, double* out) {
+    BNEED(b, what == 0 || what == 1, "what: 0 coordinates, 1 log-probs");
+    BNEED(b, 0 <= member_lo && member_lo <= member_hi && member_hi <= b->B, "members [%d, %d) outside [0, %d)", member_lo, member_hi, b->B);
+    BNEED(b, stride >= 1 && 0 <= start && start <= stop && stop <= b->stored, "rows [%lld, %lld) outside the %lld stored",
+          (long long)start, (long long)stop, (long long)b->stored);
+    BNEED(b, out != nullptr, "no output buffer");
+    const int64_t nsel = (stop - start + stride - 1) / stride;
+    if (nsel == 0 || member_hi == member_lo) return 0;
+    BHIP(b, hipSetDevice(b->device));
+    const size_t row = (size_t)b->N * (what == 0 ? b->D : 1);
+    const double* base = what == 0 ? b->chain : b->chain_lp;
+    for (int32_t m = member_lo; m < member_hi; ++m)
+        BHIP(b, hipMemcpy2DAsync(out + (size_t)(m - member_lo) * nsel * row, row * 8, base + ((size_t)m * b->cap + start) * row, stride * row * 8,
+                                 row * 8, nsel, hipMemcpyDeviceToHost, b->stream));
+    BHIP(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int emx_batch_accepted_counts(emx_batch* b, double* out) {
+    const size_t BN = (size_t)b->B * b->N;
+    std::vector<uint32_t> h(BN);
+    BHIP(b, hipMemcpyAsync(h.data(), b->acc_count, BN * 4, hipMemcpyDeviceToHost, b->stream));
+    BHIP(b, hipStreamSynchronize(b->stream));
+    for (size_t k = 0; k < BN; ++k) out[k] = (double)h[k];
+    return 0;
+}
+
+int emx_batch_status(emx_batch* b, uint32_t* bits) {
+    BHIP(b, hipStreamSynchronize(b->stream));      // every launch that could still raise a bit has finished
+    for (int32_t m = 0; m < b->B; ++m) {
+        uint32_t v = 0;
+        for (int k = 0; k < SMALL_STATUS_WORDS; ++k)
+            if (__atomic_exchange_n(&b->status_host[(size_t)m * SMALL_STATUS_WORDS + k], 0u, __ATOMIC_ACQ_REL)) v |= 1u << k;
+        if (bits) bits[m] = v;
+    }
+    return 0;
+}
+
+int emx_batch_launch_info(emx_batch* b, int32_t* threads, int32_t* plan_steps, int64_t* launches) {
+    if (threads) *threads = b->last_threads;
+    if (plan_steps) *plan_steps = b->last_plan_steps;
+    if (launches) *launches = b->launches;
+    return 0;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

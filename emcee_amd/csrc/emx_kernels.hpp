@@ -2004,6 +2004,36 @@ struct SmallRunArgs {
     // the staging layout [order|p0|p1|p2] int32, [s0|uacc] f64, and the move the host's choice() picked for each step
     const char* plans;
     const int32_t* step_moves;
+    // batched launches (k_small_run<..., BATCH>, emx_batch.hip): workgroup b runs member b of a batch of independent ensembles
+    // of one shape.  X / lp / acc / acc_count / status are member-strided (N D, N, N, N, SMALL_STATUS_WORDS), the chain member-major with `cap`
+    // rows a member, step_fac `nsteps` apart; seeds[b] and tscales[b] are the member's, tp0 / tp1 advance by their strides
+    // (0: one target shared by every member).  eval0: the log-probs of X are evaluated before the first step.
+    const unsigned long long* seeds;
+    const double* tscales;
+    long long tp0_stride, tp1_stride, cap;
+    int32_t eval0;
+};
+
+constexpr int SMALL_STATUS_WORDS = 8;      // a member's status flags (raise_status: one word per bit)
+
+// what differs between the members of a batched launch, read where it is used (as the single-ensemble kernel reads
+// SmallRunArgs: nothing extra stays live across the run); !BATCH: the fields of SmallRunArgs themselves
+template <bool BATCH>
+struct SmallMember {
+    const SmallRunArgs& A;
+    __device__ __forceinline__ size_t m() const { return BATCH ? (size_t)blockIdx.x : 0; }
+    __device__ __forceinline__ double* X() const { return A.X + m() * (size_t)A.N * A.D; }
+    __device__ __forceinline__ double* lp() const { return A.lp + m() * (size_t)A.N; }
+    __device__ __forceinline__ uint8_t* acc() const { return A.acc + m() * (size_t)A.N; }
+    __device__ __forceinline__ uint32_t* acc_count() const { return A.acc_count + m() * (size_t)A.N; }
+    __device__ __forceinline__ uint32_t* status() const { return A.status + m() * SMALL_STATUS_WORDS; }
+    __device__ __forceinline__ double* chain() const { return A.chain + m() * (size_t)A.cap * A.N * A.D; }
+    __device__ __forceinline__ double* chain_lp() const { return A.chain_lp + m() * (size_t)A.cap * A.N; }
+    __device__ __forceinline__ const double* tp0() const { return BATCH && A.tp0 ? A.tp0 + m() * (size_t)A.tp0_stride : A.tp0; }
+    __device__ __forceinline__ const double* tp1() const { return BATCH && A.tp1 ? A.tp1 + m() * (size_t)A.tp1_stride : A.tp1; }
+    __device__ __forceinline__ const double* step_fac() const { return BATCH && A.step_fac ? A.step_fac + m() * (size_t)A.nsteps : A.step_fac; }
+    __device__ __forceinline__ double tscale() const { return BATCH ? A.tscales[m()] : A.tscale; }
+    __device__ __forceinline__ unsigned long long seed() const { return BATCH ? A.seeds[m()] : A.seed; }
 };
 
 // one entry of a step's plan (k_native_plan_batch's arithmetic for this move)
@@ -2025,8 +2055,8 @@ __device__ __forceinline__ void small_plan_entry(const NativeArgs& na, int N, in
 
 // one group's (walker's) update inside a half-step: the general kernel's element-wise-target branch
 // the proposal of one walker from the LDS-resident ensemble (+ the non-finite check of ensemble.py:476-479)
-template <int G, int V, int CH, int MOVE>
-__device__ __forceinline__ void small_propose(const SmallRunArgs& A, const double* Xs, bool live, int i, int j0, int j1, int j2,
+template <int G, int V, int CH, int MOVE, typename Member>
+__device__ __forceinline__ void small_propose(const Member& M, const double* Xs, bool live, int i, int j0, int j1, int j2,
                                               double s0, double fac, double gammas, int D, int gl, int sub, Row<G, V, CH>& q,
                                               double& factor, bool& badq, const GaussGen* gg = nullptr) {
     constexpr int NR = rows_per_pass<MOVE>();
@@ -2047,20 +2077,20 @@ __device__ __forceinline__ void small_propose(const SmallRunArgs& A, const doubl
 #pragma unroll
         for (int v = 0; v < V; ++v) bl |= !(fabs(q.x[c][v]) <= 1.79769313486231570815e308);
     badq = group_any<G>(bl, sub);
-    if (live && badq && gl == 0) raise_status(A.status, ST_BAD_COORD);
+    if (live && badq && gl == 0) raise_status(M.status(), ST_BAD_COORD);
 }
 
-template <int G, int V, int CH, int MOVE>
-__device__ __forceinline__ void small_update(const SmallRunArgs& A, double* Xs, double* lps, uint8_t* accs, bool live, int i,
+template <int G, int V, int CH, int MOVE, typename Member>
+__device__ __forceinline__ void small_update(const SmallRunArgs& A, const Member& M, double* Xs, double* lps, uint8_t* accs, bool live, int i,
                                              int j0, int j1, int j2, double s0, double fac, double logu, double gammas,
                                              const Row<G, V, CH>& mu, const Row<G, V, CH>& iv, int D, int gl, int sub, int lane,
                                              const GaussGen* gg = nullptr) {
     Row<G, V, CH> q;
     double factor;
     bool badq;
-    small_propose<G, V, CH, MOVE>(A, Xs, live, i, j0, j1, j2, s0, fac, gammas, D, gl, sub, q, factor, badq, gg);
-    const double lp_new = eval_valu_target<G, V, CH>(q, mu, iv, A.tp0, A.tp1, A.target, A.tscale, D, gl, lane);
-    if (live && gl == 0 && (lp_new != lp_new)) raise_status(A.status, ST_NAN_LOGP);
+    small_propose<G, V, CH, MOVE>(M, Xs, live, i, j0, j1, j2, s0, fac, gammas, D, gl, sub, q, factor, badq, gg);
+    const double lp_new = eval_valu_target<G, V, CH>(q, mu, iv, M.tp0(), M.tp1(), A.target, M.tscale(), D, gl, lane);
+    if (live && gl == 0 && (lp_new != lp_new)) raise_status(M.status(), ST_NAN_LOGP);
     const double lp_old = lps[i];
     const double lnpdiff = factor + lp_new - lp_old;                  // red_blue.py:99
     const bool accept = live && !badq && (lnpdiff > logu);            // red_blue.py:100
@@ -2071,7 +2101,39 @@ __device__ __forceinline__ void small_update(const SmallRunArgs& A, double* Xs, 
     if (live && gl == 0) accs[i] = accept ? 1 : 0;
 }
 
-template <int G, int V, int CH, int MOVESEL, bool PLANNED, int DPB = 0>
+// the dense target's quadratic form of the 16 tile rows a wave holds, through the f64 MFMA against the LDS image (k_halfstep's
+// instructions in k_halfstep's order); the value of tile row (lane >> 4) + 4 (lane & 3) lands in lanes with (lane & 15) < 4
+template <int DPB, int KK, int RT>
+__device__ __forceinline__ double small_dense_qf(const double* tile, const double* muS, const double* Sfrag, int lane) {
+    double qf;
+    const int am = lane & 15, ak = lane >> 4;
+    typedef double d4 __attribute__((ext_vector_type(4)));
+    double afr[KK];
+#pragma unroll
+    for (int kk = 0; kk < KK; ++kk) afr[kk] = tile[am * RT + 4 * kk + ak] - muS[4 * kk + ak];
+    double part[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int nb = 0; nb < DPB; ++nb) {
+        d4 accv = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int kk = 4 * nb; kk < KK; ++kk)
+            accv = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[kk], Sfrag[(dense_block(DPB, nb, kk >> 2) * 4 + (kk & 3)) * 64 + lane], accv, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) part[r] = fma(accv[r], accv[r], part[r]);
+    }
+#if EMX_OPT_RED4
+    qf = row16_sum4(part[0], part[1], part[2], part[3], lane);
+#else
+#pragma unroll
+    for (int r = 0; r < 4; ++r) part[r] = group_sum<16>(part[r]);
+    qf = part[0];
+#pragma unroll
+    for (int r = 1; r < 4; ++r) qf = (am == r) ? part[r] : qf;
+#endif
+    return qf;
+}
+
+template <int G, int V, int CH, int MOVESEL, bool PLANNED, int DPB = 0, bool BATCH = false>
 static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int WPW = 64 / G;
@@ -2095,12 +2157,13 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
     double* muS = Sfrag + dense_img_doubles(Dp);
     double* tile = muS + Dp + (size_t)wv * (16 * RT + 16);
     double* facS = tile + 16 * RT;
+    const SmallMember<BATCH> M{A};
     if constexpr (DENSE)
-        for (int e = tid; e < dense_img_doubles(Dp) + Dp; e += T) Sfrag[e] = A.tp1[e];
+        for (int e = tid; e < dense_img_doubles(Dp) + Dp; e += T) Sfrag[e] = M.tp1()[e];
 
-    for (int e = tid; e < N * D; e += T) Xs[e] = A.X[e];
+    for (int e = tid; e < N * D; e += T) Xs[e] = M.X()[e];
     for (int e = tid; e < N; e += T) {
-        lps[e] = A.lp[e];
+        lps[e] = M.lp()[e];
         acnt[e] = 0u;
         accs[e] = 0;
     }
@@ -2110,14 +2173,61 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
 #pragma unroll
         for (int v = 0; v < V; ++v) mu.x[c][v] = iv.x[c][v] = 0.0;
     if (CH <= 4 && A.target == TGT_DIAG) {
-        load_row<G, V, CH>(mu, A.tp0, D, gl);
-        load_row<G, V, CH>(iv, A.tp1, D, gl);
+        load_row<G, V, CH>(mu, M.tp0(), D, gl);
+        load_row<G, V, CH>(iv, M.tp1(), D, gl);
+    }
+    if constexpr (BATCH) {
+        // a batch's initial log-probs (emx_batch_eval_state_log_prob): every walker's row through the same evaluation as a
+        // proposal's -- eval_valu_target, or the dense tile and MFMA contraction -- which is eval_rows' arithmetic
+        if (A.eval0) {
+            __syncthreads();
+            if constexpr (DENSE) {
+                for (int base = wv * 16; base < N; base += nwave * 16) {          // wave-uniform
+                    const int nslot = min(16, N - base);
+#pragma unroll
+                    for (int pp = 0; pp < PPT; ++pp) {
+                        const int trow = pp * WPW + sub;
+                        const bool live = trow < nslot;
+                        Row<G, V, CH> q;
+                        load_row<G, V, CH>(q, Xs + (size_t)(base + (live ? trow : 0)) * D, D, gl);
+#pragma unroll
+                        for (int c = 0; c < CH; ++c)
+#pragma unroll
+                            for (int v = 0; v < V; ++v) {
+                                const int d = (c * G + gl) * V + v;
+                                if (d < Dp) tile[trow * RT + d] = live ? q.x[c][v] : muS[d];
+                            }
+                    }
+                    const int myrow = (lane >> 4) + 4 * (lane & 3);
+                    EMX_WAVE_SYNC();
+                    const double qf = small_dense_qf<DPB, KK, RT>(tile, muS, Sfrag, lane);
+                    if ((lane & 15) < 4 && myrow < nslot) {
+                        const double lpn = -0.5 * qf;
+                        if (lpn != lpn) raise_status(M.status(), ST_NAN_LOGP);
+                        lps[base + myrow] = lpn;
+                    }
+                    EMX_WAVE_SYNC();
+                }
+            } else {
+                for (int base = wv * WPW; base < N; base += nwave * WPW) {        // wave-uniform
+                    const int t = base + sub;
+                    Row<G, V, CH> q;
+                    load_row<G, V, CH>(q, Xs + (size_t)(t < N ? t : 0) * D, D, gl);
+                    const double lpn = eval_valu_target<G, V, CH>(q, mu, iv, M.tp0(), M.tp1(), A.target, M.tscale(), D, gl, lane);
+                    if (t < N && gl == 0) {
+                        if (lpn != lpn) raise_status(M.status(), ST_NAN_LOGP);
+                        lps[t] = lpn;
+                    }
+                }
+            }
+            __syncthreads();
+        }
     }
     // the move of step s: the host's choice() (exact mode) or one Philox draw against the cdf (native mode)
     auto move_of = [&](int s) -> int {
         if (A.nmoves == 1) return 0;
         if constexpr (PLANNED) return A.step_moves[s];
-        return native_move_choice(A.seed, A.step0 + (unsigned long long)s, A.cdf, A.nmoves);
+        return native_move_choice(M.seed(), A.step0 + (unsigned long long)s, A.cdf, A.nmoves);
     };
 
     int row = 0;                                     // stored rows appended by this launch
@@ -2147,7 +2257,7 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                 continue;
             }
             NativeArgs na;
-            na.seed = A.seed;
+            na.seed = M.seed();
             na.step = A.step0 + (unsigned long long)(sb + b);
             na.pk = make_perm_key((uint64_t)N, na.seed, na.step);
             int i = 0, a0 = 0, a1 = 0, a2 = 0;
@@ -2180,9 +2290,9 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
             const int S = A.nsplits[m];
             const double gam = A.gammas[m];
             GaussGen gg;
-            gg.gseed = A.seed;
+            gg.gseed = M.seed();
             gg.gstep = A.step0 + (unsigned long long)s;
-            gg.gfac = A.step_fac ? A.step_fac[s] : 1.0;
+            gg.gfac = M.step_fac() ? M.step_fac()[s] : 1.0;
             gg.gsigma = A.gsigma[m];
             gg.gscale = A.gscale[m];
             // ---- the half-steps: a barrier where the general path has a kernel boundary ----
@@ -2204,13 +2314,13 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                             bool badq = false;
                             const int i = orders[pos], j0 = p0s[pos], j1 = p1s[pos], j2 = p2s[pos];
                             if (!PLANNED && (MOVESEL == MOVE_GAUSS || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_GAUSS)))
-                                small_propose<G, V, CH, MOVE_GAUSS>(A, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq, &gg);
+                                small_propose<G, V, CH, MOVE_GAUSS>(M, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq, &gg);
                             else if (MOVESEL == MOVE_STRETCH || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_STRETCH))
-                                small_propose<G, V, CH, MOVE_STRETCH>(A, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq);
+                                small_propose<G, V, CH, MOVE_STRETCH>(M, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq);
                             else if (MOVESEL == MOVE_DE || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_DE))
-                                small_propose<G, V, CH, MOVE_DE>(A, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq);
+                                small_propose<G, V, CH, MOVE_DE>(M, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq);
                             else
-                                small_propose<G, V, CH, MOVE_SNOOKER>(A, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq);
+                                small_propose<G, V, CH, MOVE_SNOOKER>(M, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq);
 #pragma unroll
                             for (int c = 0; c < CH; ++c)
 #pragma unroll
@@ -2226,37 +2336,11 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                         const int my_i = orders[mypos];
                         const double my_lpo = lps[my_i], my_logu = logus[mypos];
                         EMX_WAVE_SYNC();
-                        double my_qf;
-                        {
-                            const int am = lane & 15, ak = lane >> 4;
-                            typedef double d4 __attribute__((ext_vector_type(4)));
-                            double afr[KK];
-#pragma unroll
-                            for (int kk = 0; kk < KK; ++kk) afr[kk] = tile[am * RT + 4 * kk + ak] - muS[4 * kk + ak];
-                            double part[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                            for (int nb = 0; nb < DPB; ++nb) {
-                                d4 accv = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                                for (int kk = 4 * nb; kk < KK; ++kk)
-                                    accv = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[kk], Sfrag[(dense_block(DPB, nb, kk >> 2) * 4 + (kk & 3)) * 64 + lane], accv, 0, 0, 0);
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) part[r] = fma(accv[r], accv[r], part[r]);
-                            }
-#if EMX_OPT_RED4
-                            my_qf = row16_sum4(part[0], part[1], part[2], part[3], lane);
-#else
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) part[r] = group_sum<16>(part[r]);
-                            my_qf = part[0];
-#pragma unroll
-                            for (int r = 1; r < 4; ++r) my_qf = (am == r) ? part[r] : my_qf;
-#endif
-                        }
+                        const double my_qf = small_dense_qf<DPB, KK, RT>(tile, muS, Sfrag, lane);
                         bool acc = false;
                         if (mine) {
                             const double lpn = -0.5 * my_qf;
-                            if (lpn != lpn) raise_status(A.status, ST_NAN_LOGP);
+                            if (lpn != lpn) raise_status(M.status(), ST_NAN_LOGP);
                             const double lnpdiff = facS[myrow] + lpn - my_lpo;
                             acc = lnpdiff > my_logu;
                             accs[my_i] = acc ? 1 : 0;
@@ -2287,21 +2371,21 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                     const int i = orders[pos], j0 = p0s[pos], j1 = p1s[pos], j2 = p2s[pos];
                     const double s0 = s0s[pos], fac = facs[pos], logu = logus[pos];
                     if (!PLANNED && (MOVESEL == MOVE_GAUSS || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_GAUSS)))
-                        small_update<G, V, CH, MOVE_GAUSS>(A, Xs, lps, accs, live, i, j0, j1, j2, s0, fac, logu, gam, mu, iv, D, gl, sub, lane, &gg);
+                        small_update<G, V, CH, MOVE_GAUSS>(A, M, Xs, lps, accs, live, i, j0, j1, j2, s0, fac, logu, gam, mu, iv, D, gl, sub, lane, &gg);
                     else if (MOVESEL == MOVE_STRETCH || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_STRETCH))
-                        small_update<G, V, CH, MOVE_STRETCH>(A, Xs, lps, accs, live, i, j0, j1, j2, s0, fac, logu, gam, mu, iv, D, gl, sub, lane);
+                        small_update<G, V, CH, MOVE_STRETCH>(A, M, Xs, lps, accs, live, i, j0, j1, j2, s0, fac, logu, gam, mu, iv, D, gl, sub, lane);
                     else if (MOVESEL == MOVE_DE || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_DE))
-                        small_update<G, V, CH, MOVE_DE>(A, Xs, lps, accs, live, i, j0, j1, j2, s0, fac, logu, gam, mu, iv, D, gl, sub, lane);
+                        small_update<G, V, CH, MOVE_DE>(A, M, Xs, lps, accs, live, i, j0, j1, j2, s0, fac, logu, gam, mu, iv, D, gl, sub, lane);
                     else
-                        small_update<G, V, CH, MOVE_SNOOKER>(A, Xs, lps, accs, live, i, j0, j1, j2, s0, fac, logu, gam, mu, iv, D, gl, sub, lane);
+                        small_update<G, V, CH, MOVE_SNOOKER>(A, M, Xs, lps, accs, live, i, j0, j1, j2, s0, fac, logu, gam, mu, iv, D, gl, sub, lane);
                 }
                 __syncthreads();
                 pos0 += ns;
             }
             // ---- chain append (ensemble.py:416, backend.py:229) ----
             if (A.store && ((A.i0 + s + 1) % A.thin_by == 0)) {
-                double* cr = A.chain + (size_t)row * N * D;
-                double* cl = A.chain_lp + (size_t)row * N;
+                double* cr = M.chain() + (size_t)row * N * D;
+                double* cl = M.chain_lp() + (size_t)row * N;
                 for (int e = tid; e < N * D; e += T) cr[e] = Xs[e];
                 for (int e = tid; e < N; e += T) {
                     cl[e] = lps[e];
@@ -2313,11 +2397,11 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
         }
     }
     __syncthreads();
-    for (int e = tid; e < N * D; e += T) A.X[e] = Xs[e];
+    for (int e = tid; e < N * D; e += T) M.X()[e] = Xs[e];
     for (int e = tid; e < N; e += T) {
-        A.lp[e] = lps[e];
-        A.acc[e] = accs[e];
-        A.acc_count[e] += acnt[e];
+        M.lp()[e] = lps[e];
+        M.acc()[e] = accs[e];
+        M.acc_count()[e] += acnt[e];
     }
 }
 

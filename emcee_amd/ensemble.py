@@ -87,6 +87,15 @@ def _native_desc(move, ndim, can_fuse=True, philox=False):
     return None
 
 
+def philox_seed(random_state):
+    """The Philox seed (``rng="philox"``) of a sampler whose private generator is in ``random_state`` (a
+    ``numpy.random.RandomState`` or its ``get_state()``): the first words of its MT19937 key."""
+    if isinstance(random_state, np.random.RandomState):
+        random_state = random_state.get_state()
+    key = random_state[1]
+    return (int(key[0]) << 32 | int(key[1])) ^ (int(key[2]) << 16)
+
+
 class EnsembleSampler(object):
     """An ensemble MCMC sampler (see the module docstring; arguments as in reference
     ``ensemble.py:41-77``, plus ``rng`` and ``device``)."""
@@ -263,8 +272,7 @@ class EnsembleSampler(object):
 
     def _philox_seed(self):
         self._flush_rng()
-        key = self._random.get_state()[1]
-        return (int(key[0]) << 32 | int(key[1])) ^ (int(key[2]) << 16)
+        return philox_seed(self._random.get_state())
 
     def _configure_device(self, descs, fused):
         ens = self._device_ensemble()

@@ -498,6 +498,53 @@ int64_t emx_host_walk_kde_draws(uint64_t seed, uint64_t step, int64_t nwalkers, 
 /* pull exchange: records per (source, destination) pair of one half-step (what emx_pull_prepare returns) */
 int64_t emx_host_pull_capacity(int64_t nwalkers, int32_t world, int32_t nsplits, int32_t partners_per_walker);
 
+/* ---- batches of independent small ensembles (emcee_amd.EnsembleBatch; csrc/emx_batch.hip) ----
+ * B ensembles of one shape (nwalkers, ndim), each with its own state, Philox seed, target parameters, chain and status, run by
+ * ONE launch of the one-workgroup kernel k_small_run per chunk of up to 4 096 steps: workgroup b runs member b exactly as an
+ * emx_ctx in Philox mode runs that ensemble (same bits).  Shapes: small_kernel's rules per member (nwalkers <= 4 096, ndim <= 256,
+ * the LDS bound, the dense contraction bound, <= 8 stretch / DE / snooker / Gaussian moves, DE with >= 2 walkers a complement);
+ * fused device targets only (not EMX_TARGET_HOST / EMX_TARGET_DEVICE_CALLBACK).  Arrays are member-major: coordinates
+ * (B, nwalkers, ndim), log-probs and accept counts (B, nwalkers), the chain (B, capacity, nwalkers, ndim).
+ * Tuning keys (emx_batch_set_tuning; neither changes a bit, plans do not depend on the state):
+ *   "batch_threads"      0 (auto)  threads of a member's workgroup (a multiple of 64, <= 1 024)
+ *   "batch_plan_steps"   0 (auto)  steps whose plans one pass keeps in LDS (<= 64)
+ *   auto: up to one member a CU, the single-ensemble shape (small_threads / small_batch); more members than CUs, one
+ *   half-step's lanes and one plan entry a thread, so that several members share a CU. */
+typedef struct emx_batch emx_batch;
+/* host only (no device touched): 0 when the kernel takes the shape, else -1 and the reason in msg */
+int emx_batch_check(int64_t nwalkers, int32_t ndim, int32_t target, int32_t nmoves, const emx_move_desc* moves, char* msg,
+                    int32_t msglen);
+int emx_batch_create(int32_t device, int32_t nbatch, int64_t nwalkers, int32_t ndim, emx_batch** out);
+int emx_batch_destroy(emx_batch* b);
+const char* emx_batch_last_error(emx_batch* b);
+int emx_batch_set_tuning(emx_batch* b, const char* key, int64_t value);
+/* per_member 0: one target for every member (p0 / p1 as emx_set_target, scales[0]); 1: B of them, member-major
+ * (p0 (B, ndim); p1 (B, ndim) ivar or (B, ndim, ndim) icov; scales (B) Rosenbrock scales, 0 or NULL: 20) */
+int emx_batch_set_target(emx_batch* b, int32_t kind, const double* p0, const double* p1, const double* scales, int32_t per_member);
+/* the move schedule (as emx_set_moves); a sequential GaussianMove only as the one move */
+int emx_batch_set_moves(emx_batch* b, int32_t nmoves, const emx_move_desc* moves, const double* cdf);
+int emx_batch_set_move_scale(emx_batch* b, int32_t move, const double* scale, int32_t n);
+int emx_batch_get_move(emx_batch* b, int32_t move, emx_move_desc* out);
+/* seeds[B]: member b draws exactly as an emx_ctx with emx_rng_set_philox(seeds[b], step) */
+int emx_batch_set_philox(emx_batch* b, const uint64_t* seeds, uint64_t step);
+int emx_batch_get_philox(emx_batch* b, uint64_t* seeds, uint64_t* step);
+int emx_batch_set_state(emx_batch* b, const double* coords, const double* log_prob);     /* log_prob may be NULL */
+int emx_batch_get_state(emx_batch* b, double* coords, double* log_prob);                 /* either may be NULL */
+/* every member's log-probs of its coordinates in one launch, with emx_eval_state_log_prob's arithmetic */
+int emx_batch_eval_state_log_prob(emx_batch* b);
+/* capacity: stored steps a member can hold; growing keeps what is stored */
+int emx_batch_chain_config(emx_batch* b, int64_t capacity);
+int emx_batch_run(emx_batch* b, int64_t nsteps, int32_t thin_by, int32_t store);
+int emx_batch_iteration(emx_batch* b, int64_t* stored, int64_t* proposals);
+/* rows start, start + stride, ... < stop of members [member_lo, member_hi): what 0 -> (members, rows, nwalkers, ndim), 1 -> log-probs */
+int emx_batch_chain_read(emx_batch* b, int32_t what, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop,
+                         int64_t stride, double* out);
+int emx_batch_accepted_counts(emx_batch* b, double* out);           /* (B, nwalkers) */
+/* bits[B]: each member's status (emx_status's bits), read and cleared */
+int emx_batch_status(emx_batch* b, uint32_t* bits);
+/* the last launch's shape and the launches so far */
+int emx_batch_launch_info(emx_batch* b, int32_t* threads, int32_t* plan_steps, int64_t* launches);
+
 #ifdef __cplusplus
 }
 #endif
