@@ -29,6 +29,8 @@ _lib = None
 
 # emx_device_log_prob_fn (include/emx.h): (user, coords_dev, n, ndim, log_prob_dev, hip_stream) -> int
 DEVICE_LOG_PROB_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p)
+# emx_batch_log_prob_fn: (user, coords_dev, nbatch, rows, ndim, log_prob_dev, hip_stream) -> int
+BATCH_LOG_PROB_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p)
 
 _P = C.c_void_p
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -167,6 +169,7 @@ SIGNATURES = {
     "emx_batch_accepted_counts": (C.c_int, [_P, _dp]),
     "emx_batch_status": (C.c_int, [_P, _u32p]),
     "emx_batch_launch_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "emx_set_batch_target_callback": (C.c_int, [_P, BATCH_LOG_PROB_FN, _P]),
 }
 
 

@@ -11,8 +11,17 @@ the sampler built with the same target, moves and initial state whose private ge
 
 Philox mode only; fused device targets (``IsoGaussian``, ``DiagGaussian``, ``DenseGaussian``, ``Rosenbrock``,
 ``UniformBox``); stretch, DE, snooker and Gaussian moves; every member must fit one workgroup (``nwalkers <= 4096``,
-``ndim <= 256`` and the LDS bound).  Host callables, ``DeviceCallable`` and ``DeviceKernel`` targets run through
-:class:`~emcee_amd.EnsembleSampler`.
+``ndim <= 256`` and the LDS bound).
+
+The user's own model -- one fit per catalogue object, with per-object data -- is a
+:class:`~emcee_amd.targets.BatchCallable` (or its native form, :class:`~emcee_amd.targets.BatchKernel`): one function called
+once per phase of a step on the proposals of ALL members, a ``(B, R, ndim)`` block on the device, with the per-member data in
+its closure.  A step is then ``S_max`` launches of the library's kernel (``k_batch_cb``: every member's commit and next
+proposals) and ``S_max`` calls of that function, whatever B; member b is bit for bit the sampler above with
+``DeviceCallable`` of the function restricted to member b.  ``S_max`` / ``S_min`` are the largest / smallest ``nsplits`` of the
+schedule (a GaussianMove, one split, only as the sole move); ``R = ceil(nwalkers / S_min)``, and rows of ``q[b]`` past the
+member's current split are padding -- copies of its walkers, their values ignored.  The LDS bound does not apply there.
+Host callables, ``DeviceCallable`` and ``DeviceKernel`` targets run through :class:`~emcee_amd.EnsembleSampler`.
 """
 import ctypes as C
 
@@ -22,7 +31,8 @@ from . import _lib
 from .autocorr import integrated_time
 from .ensemble import _native_desc, _parse_move_schedule, _refuse_extended_precision, philox_seed, walkers_independent
 from .state import State
-from .targets import DenseGaussian, DeviceCallable, DeviceKernel, DeviceTarget, DiagGaussian, IsoGaussian, Rosenbrock, UniformBox
+from .targets import (BatchKernel, BatchTarget, DenseGaussian, DeviceCallable, DeviceKernel, DeviceTarget, DiagGaussian, IsoGaussian,
+                      Rosenbrock, UniformBox)
 
 __all__ = ["EnsembleBatch"]
 
@@ -40,7 +50,8 @@ class EnsembleBatch(object):
     """B independent ensembles of ``nwalkers`` walkers in ``ndim`` dimensions, run together on one GPU.
 
     ``target``: one :class:`~emcee_amd.targets.DeviceTarget` for every member, or a sequence of B targets of one class (one
-    per member).  ``moves``: the schedule forms of :class:`~emcee_amd.EnsembleSampler` over StretchMove, DEMove,
+    per member); or one :class:`~emcee_amd.targets.BatchCallable` / :class:`~emcee_amd.targets.BatchKernel` evaluating every
+    member (its per-member parameters are its own).  ``moves``: the schedule forms of :class:`~emcee_amd.EnsembleSampler` over StretchMove, DEMove,
     DESnookerMove and GaussianMove.  ``seeds``: B integers; member b draws as a sampler whose generator was seeded with
     ``np.random.RandomState(seeds[b])``.  ``None`` draws them from NumPy's global state."""
 
@@ -77,23 +88,30 @@ class EnsembleBatch(object):
         self.seeds = seeds
         self._philox = np.array([philox_seed(np.random.RandomState(s)) for s in seeds], dtype=np.uint64)
         self._h = None
+        self._cb_box = [None]             # an exception raised by a BatchCallable, handed to the caller by _ck
+        self._cb_keep = None
         self._tuning = {}
         self._step = 0
         self._ran = False
 
     # ------------------------------------------------------------------ argument checks (no device involved)
     def _parse_targets(self, target):
+        if isinstance(target, BatchTarget):
+            return [target], False
         if isinstance(target, DeviceTarget) or callable(target):
             targets, per_member = [target], False
         else:
             targets, per_member = list(target), True
+            if any(isinstance(t, BatchTarget) for t in targets):
+                raise TypeError("EnsembleBatch takes ONE BatchCallable / BatchKernel for all members: per-member parameters "
+                                "belong to its function")
             if len(targets) != self.nbatch:
                 raise ValueError("target: one DeviceTarget for all members or a sequence of nbatch = %d; got %d"
                                  % (self.nbatch, len(targets)))
         for t in targets:
             if isinstance(t, (DeviceCallable, DeviceKernel)) or not isinstance(t, _TARGETS):
-                raise TypeError("EnsembleBatch runs the fused device targets (%s); run %s with EnsembleSampler"
-                                % (", ".join(k.__name__ for k in _TARGETS), type(t).__name__))
+                raise TypeError("EnsembleBatch runs the fused device targets (%s) or a BatchCallable / BatchKernel; run %s with "
+                                "EnsembleSampler" % (", ".join(k.__name__ for k in _TARGETS), type(t).__name__))
         if len({type(t) for t in targets}) != 1:
             raise ValueError("the targets of a batch must be of one class; got %s" % sorted({type(t).__name__ for t in targets}))
         for b, t in enumerate(targets):
@@ -119,6 +137,10 @@ class EnsembleBatch(object):
         return _lib.load()
 
     def _ck(self, rc):
+        exc = self._cb_box[0]
+        if exc is not None:               # raised inside the batched log-prob callback: the caller's own exception
+            self._cb_box[0] = None
+            raise exc
         if rc != 0:
             msg = self._lib().emx_batch_last_error(self._h)
             raise _lib.EmxError((msg or b"unknown error").decode() + " (code %d)" % rc)
@@ -131,15 +153,10 @@ class EnsembleBatch(object):
         if lib.emx_batch_create(self.device, self.nbatch, self.nwalkers, self.ndim, C.byref(h)) != 0:
             raise _lib.EmxError("emx_batch_create failed (no usable HIP device %d, or out of memory)" % self.device)
         self._h = h
-        kind = self._targets[0].kind
-        params = [t.emx_params() for t in self._targets]
-        p0 = p1 = None
-        if kind in (_lib.TARGET_DIAG, _lib.TARGET_DENSE):
-            p0 = np.ascontiguousarray(np.stack([p[1] for p in params]), dtype=np.float64)
-            p1 = np.ascontiguousarray(np.stack([p[2] for p in params]), dtype=np.float64)
-        scales = np.ascontiguousarray([p[3] for p in params], dtype=np.float64)
-        ptr = (lambda a: None if a is None else a.ctypes.data_as(C.c_void_p))
-        self._ck(lib.emx_batch_set_target(h, kind, ptr(p0), ptr(p1), ptr(scales), int(self._per_member)))
+        if isinstance(self._targets[0], BatchTarget):
+            self._bind_callback(h)
+        else:
+            self._bind_fused(h)
         cdf = np.cumsum(self._weights)
         cdf /= cdf[-1]
         arr = (_lib.MoveDesc * len(self._descs))(*self._descs)
@@ -154,6 +171,27 @@ class EnsembleBatch(object):
             self._ck(lib.emx_batch_set_tuning(h, k.encode(), int(v)))
         self._ck(lib.emx_batch_set_philox(h, self._philox, self._step))
         return h
+
+    def _bind_fused(self, h):
+        kind = self._targets[0].kind
+        params = [t.emx_params() for t in self._targets]
+        p0 = p1 = None
+        if kind in (_lib.TARGET_DIAG, _lib.TARGET_DENSE):
+            p0 = np.ascontiguousarray(np.stack([p[1] for p in params]), dtype=np.float64)
+            p1 = np.ascontiguousarray(np.stack([p[2] for p in params]), dtype=np.float64)
+        scales = np.ascontiguousarray([p[3] for p in params], dtype=np.float64)
+        ptr = (lambda a: None if a is None else a.ctypes.data_as(C.c_void_p))
+        self._ck(self._lib().emx_batch_set_target(h, kind, ptr(p0), ptr(p1), ptr(scales), int(self._per_member)))
+
+    def _bind_callback(self, h):
+        t = self._targets[0]
+        if isinstance(t, BatchKernel):
+            fn = t.fn_ptr if isinstance(t.fn_ptr, _lib.BATCH_LOG_PROB_FN) else C.cast(t.fn_ptr, _lib.BATCH_LOG_PROB_FN)
+            user = t.user_ptr if isinstance(t.user_ptr, C.c_void_p) else C.c_void_p(t.user_ptr)
+        else:
+            fn, user = _lib.BATCH_LOG_PROB_FN(_trampoline(t.fn, self.device, self._cb_box)), None
+        self._cb_keep = fn                # the library holds the pointer: keep the object alive
+        self._ck(self._lib().emx_set_batch_target_callback(h, fn, user))
 
     def set_tuning(self, key, value):
         """``"batch_threads"`` / ``"batch_plan_steps"`` (include/emx.h): the launch shape; no bit depends on it."""
@@ -306,6 +344,34 @@ class EnsembleBatch(object):
         if not 0 <= b < self.nbatch:
             raise IndexError("member %d outside a batch of %d" % (b, self.nbatch))
         return _Member(self, b)
+
+
+def _trampoline(fn, device, box):
+    """emx_batch_log_prob_fn over a BatchCallable's ``fn`` (DeviceEnsemble.set_target_callback's eager form): ``fn`` sees the
+    library's block as a ``(B, rows, ndim)`` tensor and runs on the handle's stream; an exception is kept in ``box[0]``."""
+    import torch
+    from .parallel import _DevView
+    streams = {}
+    dev = torch.device("cuda", device)
+
+    def tramp(user, q_ptr, nb, rows, ndim, lp_ptr, stream):
+        try:
+            s = streams.get(stream)
+            if s is None:
+                s = streams[stream] = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
+            n = nb * rows
+            with torch.cuda.stream(s):
+                q = torch.as_tensor(_DevView(q_ptr, n * ndim), device=dev).view(nb, rows, ndim)
+                out = torch.as_tensor(_DevView(lp_ptr, n), device=dev)
+                res = torch.as_tensor(fn(q), dtype=torch.float64, device=dev).reshape(-1)
+                if res.numel() != n:
+                    raise ValueError("the batched log_prob_fn returned %d values for %d members x %d rows" % (res.numel(), nb, rows))
+                out.copy_(res)
+            return 0
+        except BaseException as e:  # noqa: BLE001  (handed to the caller by EnsembleBatch._ck)
+            box[0] = e
+            return -1
+    return tramp
 
 
 class _Member(object):

@@ -2,7 +2,8 @@
 // (nwalkers, ndim), each with its own state, Philox seed, target parameters, status and chain, run by ONE launch of
 // k_small_run<..., BATCH = true> per chunk of steps -- workgroup b runs member b exactly as a single-ensemble launch runs that
 // ensemble, so every member's bits are those of an emx_ctx with the same seed, target and initial state.  Philox mode only.
-// Host side of the handle and the batched instantiations of the kernel (emx_small_launch.hpp).
+// Host side of the handle and the batched instantiations of the kernel (emx_small_launch.hpp).  With the caller's batched
+// log-prob (emx_set_batch_target_callback) a run is k_batch_cb launches and calls of that function instead (emx_batch_cb.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "../../include/emx.h"
+#include "emx_batch_cb.hpp"
 #include "emx_rng.hpp"
 #include "emx_small_host.hpp"
 #include "emx_small_launch.hpp"
@@ -55,6 +57,13 @@ struct emx_batch {
     int64_t tune_threads = 0, tune_plan_steps = 0;
     int32_t last_threads = 0, last_plan_steps = 0;
     int64_t launches = 0;
+    // EMX_TARGET_DEVICE_CALLBACK: the caller's function, the (B, R, D) block it is handed and its (B, R) results, the commit's
+    // scratch (factor, log-uniform, walker of every row; real rows of every member)
+    emx_batch_log_prob_fn cb_fn = nullptr;
+    void* cb_user = nullptr;
+    double *cb_q = nullptr, *cb_lp = nullptr, *cb_fac = nullptr, *cb_logu = nullptr;
+    int32_t *cb_wi = nullptr, *cb_nrows = nullptr;
+    size_t cb_rows = 0;       // B R rows allocated
 };
 
 namespace {
@@ -86,9 +95,11 @@ const char* shape_refusal(int64_t N, int32_t D, int32_t target, int32_t nmoves, 
         snprintf(buf, n, "nwalkers x ndim = %lld x %d is outside the one-workgroup kernel (nwalkers <= 4096, ndim <= 256)", (long long)N, D);
         return buf;
     }
-    if (target != EMX_TARGET_ISO_GAUSS && target != EMX_TARGET_DIAG_GAUSS && target != EMX_TARGET_DENSE_GAUSS &&
+    const bool callback = target == EMX_TARGET_DEVICE_CALLBACK;      // the caller's batched log-prob (k_batch_cb)
+    if (!callback && target != EMX_TARGET_ISO_GAUSS && target != EMX_TARGET_DIAG_GAUSS && target != EMX_TARGET_DENSE_GAUSS &&
         target != EMX_TARGET_ROSENBROCK && target != EMX_TARGET_BOX)
-        return "the batch runs the fused device targets only (IsoGaussian, DiagGaussian, DenseGaussian, Rosenbrock, UniformBox)";
+        return "the batch runs the fused device targets only (IsoGaussian, DiagGaussian, DenseGaussian, Rosenbrock, UniformBox) "
+               "or a batched callback (emx_set_batch_target_callback)";
     if (nmoves < 1 || nmoves > SMALL_MAX_MOVES) {
         snprintf(buf, n, "the batch takes 1 ... %d moves; got %d", SMALL_MAX_MOVES, nmoves);
         return buf;
@@ -102,7 +113,10 @@ const char* shape_refusal(int64_t N, int32_t D, int32_t target, int32_t nmoves, 
             snprintf(buf, n, "DEMove with %d splits of %lld walkers: a complement has fewer than 2 walkers", mv.nsplits, (long long)N);
             return buf;
         }
+        if (callback && mv.kind == EMX_MOVE_GAUSS && nmoves > 1)
+            return "with a batched callback target a GaussianMove runs only as the one move of the schedule";
     }
+    if (callback) return nullptr;         // k_batch_cb keeps no member in LDS
     if (target == EMX_TARGET_DENSE_GAUSS) {
         const int Dp = (D + 15) / 16 * 16;
         if (Dp > DENSE_FUSED_MAX_DP || N * (int64_t)Dp * Dp > 65536 || small_lds_bytes(N, D, Dp, 1) > SMALL_LDS_MAX) {
@@ -260,6 +274,162 @@ int launch(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t st
     return 0;
 }
 
+// ---- the caller's batched log-prob (EMX_TARGET_DEVICE_CALLBACK) ----
+
+// splits of a move (a Gaussian move is one split of the whole ensemble)
+int move_splits(const emx_move_desc& mv) { return mv.kind == EMX_MOVE_GAUSS ? 1 : (int)mv.nsplits; }
+
+// the caller's function on `rows` rows of every member: coords (B, rows, D) -> log_prob (B, rows), enqueued on the stream
+int call_back(emx_batch* b, const double* coords, int64_t rows, double* out) {
+    const int rc = b->cb_fn(b->cb_user, coords, b->B, rows, b->D, out, (void*)b->stream);
+    if (rc != 0) return fail(b, -7, "the batched device log-prob callback failed (returned %d)", rc);
+    return 0;
+}
+
+// the initial log-probs: one call on the whole state, then the per-member NaN check
+int eval_callback(emx_batch* b) {
+    BNEED(b, b->cb_fn != nullptr, "device callback target without a callback (emx_set_batch_target_callback)");
+    if (int rc = call_back(b, b->X, b->N, b->lp)) return rc;
+    BHIP(b, batch_lp_check(b->lp, b->status, b->B, (int32_t)b->N, b->stream));
+    ++b->launches;
+    return 0;
+}
+
+// `total` proposal steps: per step and phase k < S_max one k_batch_cb launch (commit phase k - 1, propose phase k) and one call of
+// the caller's function on the (B, R, D) block; one commit-only launch at the end.  Nothing is synchronised inside the loop
+// except, with Gaussian moves, the upload of the step-size factors once per chunk of steps (as the fused path does).
+int run_callback(emx_batch* b, int64_t total, int32_t thin_by, int32_t store) {
+    BNEED(b, b->cb_fn != nullptr, "device callback target without a callback (emx_set_batch_target_callback)");
+    if (total == 0) return 0;
+    const int nm = (int)b->moves.size();
+    int smin = 1 << 30, smax = 0;
+    bool any_gauss = false;
+    BatchCbArgs a{};
+    for (int m = 0; m < nm; ++m) {
+        const emx_move_desc& mv = b->moves[m];
+        smin = std::min(smin, move_splits(mv));
+        smax = std::max(smax, move_splits(mv));
+        any_gauss = any_gauss || mv.kind == EMX_MOVE_GAUSS;
+        a.kind[m] = mv.kind;
+        a.nsplits[m] = mv.nsplits;
+        a.a[m] = mv.a;
+        a.sigma[m] = mv.sigma;
+        a.g0[m] = mv.g0;
+        a.gammas[m] = mv.gammas;
+        a.cdf[m] = b->cdf[m];
+        a.gmode[m] = mv.reserved;
+        a.gsigma[m] = mv.sigma;
+        a.gscale[m] = b->mscale[m];
+    }
+    const int64_t R = (b->N + smin - 1) / smin;
+    const size_t rows = (size_t)b->B * R;
+    if (rows > b->cb_rows) {
+        BHIP(b, hipStreamSynchronize(b->stream));
+        for (void* p : {(void*)b->cb_q, (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi})
+            if (p) hipFree(p);
+        b->cb_q = b->cb_lp = b->cb_fac = b->cb_logu = nullptr;
+        b->cb_wi = nullptr;
+        b->cb_rows = 0;
+        BHIP(b, hipMalloc((void**)&b->cb_q, rows * b->D * 8));
+        BHIP(b, hipMalloc((void**)&b->cb_lp, rows * 8));
+        BHIP(b, hipMalloc((void**)&b->cb_fac, rows * 8));
+        BHIP(b, hipMalloc((void**)&b->cb_logu, rows * 8));
+        BHIP(b, hipMalloc((void**)&b->cb_wi, rows * 4));
+        b->cb_rows = rows;
+    }
+    if (!b->cb_nrows) BHIP(b, hipMalloc((void**)&b->cb_nrows, (size_t)b->B * 4));
+    a.nmoves = nm;
+    a.X = b->X;
+    a.lp = b->lp;
+    a.acc = b->acc;
+    a.acc_count = b->acc_count;
+    a.status = b->status;
+    a.chain = b->chain;
+    a.chain_lp = b->chain_lp;
+    a.cap = b->cap;
+    a.q = b->cb_q;
+    a.lpq = b->cb_lp;
+    a.fac = b->cb_fac;
+    a.logu = b->cb_logu;
+    a.wi = b->cb_wi;
+    a.nrows = b->cb_nrows;
+    a.seeds = b->seeds;
+    a.N = (int32_t)b->N;
+    a.D = b->D;
+    a.R = (int32_t)R;
+    const Shape sh = pick_shape(b->D, b->D);
+    // one phase's rows in one pass (R G lanes); no bit depends on the shape
+    int threads = (int)std::min<int64_t>(CB_MAX_THREADS, std::max<int64_t>(64, (R * sh.G + 63) / 64 * 64));
+    if (b->tune_threads > 0) threads = (int)b->tune_threads;
+    BNEED(b, threads <= CB_MAX_THREADS, "batch_threads: at most %d with a batched callback target", CB_MAX_THREADS);
+    b->last_threads = threads;
+    b->last_plan_steps = 0;
+    const int64_t most = any_gauss ? std::max<int64_t>(1, std::min<int64_t>(4096, (4 << 20) / b->B)) : total;
+    int64_t stored_row = -1, nstored = 0;     // chain row of the pending phase's step
+    bool pending = false;
+    auto launch_cb = [&](bool propose, int phase, uint64_t step) -> int {
+        a.commit = pending ? 1 : 0;
+        a.chain_row = stored_row;
+        a.propose = propose ? 1 : 0;
+        a.phase = phase;
+        a.step = step;
+        const hipError_t e = batch_cb_dispatch(sh.G, sh.V, sh.CH, b->B, threads, b->stream, a);
+        if (e != hipSuccess)
+            return fail(b, -2, "k_batch_cb launch failed (G=%d V=%d CH=%d ndim=%d): %s", sh.G, sh.V, sh.CH, b->D, hipGetErrorString(e));
+        ++b->launches;
+        return 0;
+    };
+    for (int64_t i = 0; i < total;) {
+        const int64_t chunk = std::min<int64_t>(total - i, most);
+        std::vector<int32_t> cols((size_t)chunk, 0);
+        if (any_gauss) {
+            // the step-size factors and the sequential column: the fused path's host arithmetic (launch)
+            std::vector<double> facs((size_t)b->B * chunk, 1.0);
+            for (int64_t s2 = 0; s2 < chunk; ++s2) {
+                const uint64_t step = b->step + (uint64_t)(i + s2);
+                for (int32_t mb = 0; mb < b->B; ++mb) {
+                    const uint64_t seed = b->seeds_host[mb];
+                    const int mi = nm == 1 ? 0 : native_move_choice(seed, step, b->cdf.data(), nm);
+                    const emx_move_desc& mv = b->moves[mi];
+                    if (mv.kind != EMX_MOVE_GAUSS || mv.a == 0.0) continue;
+                    const Philox4 r = philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), 0x46414354u /*'FACT'*/, 0, (uint32_t)seed,
+                                                    (uint32_t)(seed >> 32));
+                    facs[(size_t)mb * chunk + s2] = std::exp(-mv.g0 + 2.0 * mv.g0 * u53(r.v[0], r.v[1]));
+                }
+                emx_move_desc& mv = b->moves[0];
+                if (mv.kind == EMX_MOVE_GAUSS && mv.reserved == EMX_GAUSS_SEQUENTIAL) {
+                    cols[s2] = (int32_t)((int64_t)mv.gammas % b->D);
+                    mv.gammas = (double)(((int64_t)mv.gammas + 1) % b->D);
+                }
+            }
+            BHIP(b, hipStreamSynchronize(b->stream));        // the previous chunk's launches no longer read the factors
+            if (grow(b, b->fac_dev, b->fac_cap, facs.size())) return -2;
+            BHIP(b, hipMemcpy(b->fac_dev, facs.data(), facs.size() * 8, hipMemcpyHostToDevice));
+            a.gfac_stride = chunk;
+        }
+        for (int64_t s2 = 0; s2 < chunk; ++s2) {
+            const int64_t s = i + s2;
+            const uint64_t step = b->step + (uint64_t)s;
+            a.gfac = any_gauss ? b->fac_dev + s2 : nullptr;
+            a.gcol = cols[s2];
+            const int64_t row = (store && (s + 1) % thin_by == 0) ? b->stored + nstored : -1;
+            for (int k = 0; k < smax; ++k) {
+                if (int rc = launch_cb(true, k, step)) return rc;
+                if (int rc = call_back(b, b->cb_q, R, b->cb_lp)) return rc;
+                pending = true;
+                stored_row = row;
+            }
+            if (row >= 0) ++nstored;
+        }
+        i += chunk;
+    }
+    if (int rc = launch_cb(false, 0, 0)) return rc;          // commit the last phase
+    b->stored += nstored;
+    b->proposals += total;
+    b->step += (uint64_t)total;
+    return 0;
+}
+
 }  // namespace
 
 #pragma GCC visibility push(default)
@@ -312,7 +482,8 @@ int emx_batch_destroy(emx_batch* b) {
     hipSetDevice(b->device);
     if (b->stream) hipStreamSynchronize(b->stream);
     for (void* p : {(void*)b->X, (void*)b->lp, (void*)b->acc, (void*)b->acc_count, (void*)b->seeds, (void*)b->tp0, (void*)b->tp1,
-                    (void*)b->tscales, (void*)b->chain, (void*)b->chain_lp, (void*)b->fac_dev, (void*)b->col_dev})
+                    (void*)b->tscales, (void*)b->chain, (void*)b->chain_lp, (void*)b->fac_dev, (void*)b->col_dev, (void*)b->cb_q,
+                    (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi, (void*)b->cb_nrows})
         if (p) hipFree(p);
     for (double* p : b->mscale)
         if (p) hipFree(p);
@@ -392,6 +563,23 @@ int emx_batch_set_target(emx_batch* b, int32_t kind, const double* p0, const dou
     return 0;
 }
 
+int emx_set_batch_target_callback(emx_batch* b, emx_batch_log_prob_fn fn, void* user) {
+    BNEED(b, fn != nullptr, "emx_set_batch_target_callback: no function");
+    BHIP(b, hipSetDevice(b->device));
+    BHIP(b, hipStreamSynchronize(b->stream));
+    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
+        if (*p) {
+            hipFree(*p);
+            *p = nullptr;
+        }
+    b->tp0_stride = b->tp1_stride = 0;
+    b->cb_fn = fn;
+    b->cb_user = user;
+    b->target = EMX_TARGET_DEVICE_CALLBACK;
+    b->Dp = b->D;
+    return 0;
+}
+
 int emx_batch_set_moves(emx_batch* b, int32_t nmoves, const emx_move_desc* moves, const double* cdf) {
     BNEED(b, moves && cdf && nmoves >= 1, "need at least one move and its cdf");
     char buf[256];
@@ -460,6 +648,7 @@ int emx_batch_eval_state_log_prob(emx_batch* b) {
     BNEED(b, b->target >= 0, "no target set");
     BNEED(b, !b->moves.empty(), "no moves set");
     BHIP(b, hipSetDevice(b->device));
+    if (b->target == EMX_TARGET_DEVICE_CALLBACK) return eval_callback(b);
     return launch(b, 0, 0, 1, 0, true);
 }
 
@@ -494,6 +683,7 @@ int emx_batch_run(emx_batch* b, int64_t nsteps, int32_t thin_by, int32_t store) 
     BNEED(b, !b->moves.empty(), "no moves set");
     if (store) BNEED(b, b->stored + nsteps <= b->cap, "chain capacity exhausted (call emx_batch_chain_config)");
     BHIP(b, hipSetDevice(b->device));
+    if (b->target == EMX_TARGET_DEVICE_CALLBACK) return run_callback(b, nsteps * thin_by, thin_by, store);
     bool any_gauss = false;
     for (const auto& mv : b->moves) any_gauss = any_gauss || mv.kind == EMX_MOVE_GAUSS;
     // up to 4 096 steps a launch (as a single ensemble's); with Gaussian moves the per-member factors stay <= 32 MB a launch

@@ -1,0 +1,55 @@
+// Batches of independent small ensembles with the caller's batched log-prob (emx_set_batch_target_callback; csrc/emx_batch_cb.hip):
+// the arguments of k_batch_cb and its dispatch, shared by the batch handle (emx_batch.hip) and the kernel's translation unit.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "emx_kernels.hpp"
+
+namespace emx {
+
+// One launch of k_batch_cb: commit the pending phase (the caller's log-probs of the block it was handed), then propose the
+// next one.  Workgroup b is member b; every array is member-strided as in SmallRunArgs.
+struct BatchCbArgs {
+    double* X;                 // (B, N, D)
+    double* lp;                // (B, N)
+    uint8_t* acc;              // (B, N)
+    uint32_t* acc_count;       // (B, N)
+    uint32_t* status;          // (B, SMALL_STATUS_WORDS)
+    double* chain;             // (B, cap, N, D) member-major
+    double* chain_lp;          // (B, cap, N)
+    long long cap;
+    double* q;                 // (B, R, D): the block the caller evaluates; rows >= the member's split size are padding
+    const double* lpq;         // (B, R): the caller's log-probs of q
+    double* fac;               // (B, R) scratch for the commit: factor (-inf: a non-finite proposal), log-uniform, walker
+    double* logu;
+    int32_t* wi;
+    int32_t* nrows;            // (B): real rows of the pending phase
+    const unsigned long long* seeds;
+    // the move schedule (as SmallRunArgs)
+    double a[SMALL_MAX_MOVES], sigma[SMALL_MAX_MOVES], g0[SMALL_MAX_MOVES], gammas[SMALL_MAX_MOVES], cdf[SMALL_MAX_MOVES];
+    int32_t kind[SMALL_MAX_MOVES], nsplits[SMALL_MAX_MOVES], gmode[SMALL_MAX_MOVES];
+    double gsigma[SMALL_MAX_MOVES];
+    const double* gscale[SMALL_MAX_MOVES];
+    int32_t nmoves;
+    const double* gfac;        // Gaussian moves: the proposal step's factor of member b at gfac[b * gfac_stride] (nullptr: 1)
+    long long gfac_stride;
+    int32_t gcol;              // the sequential Gaussian mode's column of the proposal step
+    int32_t N, D, R;
+    int32_t commit;            // a pending phase to commit
+    long long chain_row;       // chain row of the pending phase's step (-1: not stored)
+    int32_t propose;           // propose `phase` of Philox step `step`
+    int32_t phase;
+    unsigned long long step;
+};
+
+// threads of a k_batch_cb workgroup: at most 512, for 256 VGPRs a lane (with 1 024 threads' 128, 12 to 46 of them spilled)
+constexpr int CB_MAX_THREADS = 512;
+
+// (G, V, CH): pick_shape(D, D); `grid` = B workgroups of `threads`
+hipError_t batch_cb_dispatch(int G, int V, int CH, int grid, int threads, hipStream_t st, const BatchCbArgs& a);
+// the initial log-probs' NaN check: ST_NAN_LOGP in the status words of every member with a NaN among its N values
+hipError_t batch_lp_check(const double* lp, uint32_t* status, int32_t B, int32_t N, hipStream_t st);
+
+}  // namespace emx

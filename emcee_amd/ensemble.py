@@ -32,7 +32,7 @@ from .moves.kde import kde_desc
 from .moves.walk import walk_desc
 from .pbar import get_progress_bar
 from .state import DeviceState, ResidentState, State
-from .targets import DeviceTarget
+from .targets import BatchTarget, DeviceTarget
 from .utils import deprecation_warning
 
 __all__ = ["EnsembleSampler", "walkers_independent"]
@@ -106,6 +106,9 @@ class EnsembleSampler(object):
                  a=None, postargs=None, threads=None, live_dangerously=None, runtime_sortingfn=None,
                  # emcee_amd extensions
                  rng="mt19937", device=None, distributed=False, exchange="allgather"):
+        if isinstance(log_prob_fn, BatchTarget):
+            raise TypeError("%s evaluates every member of a batch at once: run it with EnsembleBatch (a single ensemble takes a "
+                            "DeviceCallable or DeviceKernel)" % type(log_prob_fn).__name__)
         for value, text in ((a, "The 'a' argument is deprecated, use 'moves' instead"),
                             (threads, "The 'threads' argument is deprecated"),
                             (runtime_sortingfn, "The 'runtime_sortingfn' argument is deprecated"),

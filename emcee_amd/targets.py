@@ -9,11 +9,14 @@ Calling a target object evaluates it ON THE DEVICE (through ``emx_eval_log_prob`
 no NumPy twin in the product.  The formulas are restated for the parity tests in
 ``oracle/sampler_oracle.py`` only.
 """
+import ctypes
+
 import numpy as np
 
 from . import _lib
 
-__all__ = ["DeviceTarget", "IsoGaussian", "DiagGaussian", "DenseGaussian", "Rosenbrock", "UniformBox", "DeviceCallable", "DeviceKernel"]
+__all__ = ["DeviceTarget", "IsoGaussian", "DiagGaussian", "DenseGaussian", "Rosenbrock", "UniformBox", "DeviceCallable", "DeviceKernel",
+           "BatchCallable", "BatchKernel"]
 
 
 class DeviceTarget(object):
@@ -149,3 +152,51 @@ class DeviceKernel(DeviceTarget):
         if getattr(ens, "_cb_owner", None) is not self:
             ens.set_target_callback_c(self.fn_ptr, self.user_ptr)
             ens._cb_owner = self
+
+
+class BatchTarget(DeviceTarget):
+    """Base of the batched callback targets of :class:`~emcee_amd.EnsembleBatch` (``emx_set_batch_target_callback``): one call
+    evaluates the proposals of every member of a batch.  They are not targets of a single ensemble."""
+    kind = _lib.TARGET_CALLBACK
+
+    def bind(self, ens):
+        raise TypeError("%s is a target of EnsembleBatch, not of a single ensemble (use DeviceCallable with EnsembleSampler)"
+                        % type(self).__name__)
+
+    def __call__(self, x):
+        raise TypeError("%s is evaluated by EnsembleBatch on the device" % type(self).__name__)
+
+
+class BatchCallable(BatchTarget):
+    """A user's log-probability over every member of an :class:`~emcee_amd.EnsembleBatch` at once: ``fn(q)`` receives a float64
+    CUDA tensor ``(B, n, ndim)`` -- a zero-copy view of the library's proposal block, ``q[b]`` member b's rows -- and returns
+    ``(B, n)`` (or ``B * n``) log-probabilities, anything ``torch.as_tensor`` takes on the device.  Per-member data (catalogue
+    rows, per-object parameters) lives in ``fn``'s closure as ``(B, ...)`` tensors.  ``-inf`` is legal; NaN raises the
+    reference's error naming the member; an exception raised by ``fn`` comes out of ``run_mcmc`` as itself.  Every row must be
+    computed on its own, independently of the block's shape: rows past a member's split size are padding (copies of its current
+    walkers) whose values are ignored.
+
+        mu_t, ivar_t = torch.as_tensor(mu).cuda()[:, None, :], torch.as_tensor(ivar).cuda()[:, None, :]    # (B, 1, ndim)
+        def log_prob(q):                       # q: torch.float64 (B, n, ndim) on the GPU
+            d = q - mu_t
+            return -0.5 * (ivar_t * d * d).sum(-1)
+        batch = EnsembleBatch(B, nwalkers, ndim, BatchCallable(log_prob), seeds=seeds)
+    """
+
+    def __init__(self, fn):
+        if not callable(fn):
+            raise TypeError("BatchCallable needs a callable")
+        self.fn = fn
+
+
+class BatchKernel(BatchTarget):
+    """A native batched log-probability: a C function with the signature ``emx_batch_log_prob_fn`` of ``include/emx.h``
+    (typically one that launches the user's own HIP kernel on the stream it is handed) and its opaque ``user`` pointer.  A
+    proposal step is then library launches and calls of that function alone, with no Python in between."""
+
+    def __init__(self, fn_ptr, user_ptr=None):
+        if not isinstance(fn_ptr, ctypes._CFuncPtr):
+            addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
+            if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
+                raise TypeError("BatchKernel needs an emx_batch_log_prob_fn: a ctypes function or a non-null address")
+        self.fn_ptr, self.user_ptr = fn_ptr, user_ptr

@@ -503,7 +503,8 @@ int64_t emx_host_pull_capacity(int64_t nwalkers, int32_t world, int32_t nsplits,
  * ONE launch of the one-workgroup kernel k_small_run per chunk of up to 4 096 steps: workgroup b runs member b exactly as an
  * emx_ctx in Philox mode runs that ensemble (same bits).  Shapes: small_kernel's rules per member (nwalkers <= 4 096, ndim <= 256,
  * the LDS bound, the dense contraction bound, <= 8 stretch / DE / snooker / Gaussian moves, DE with >= 2 walkers a complement);
- * fused device targets only (not EMX_TARGET_HOST / EMX_TARGET_DEVICE_CALLBACK).  Arrays are member-major: coordinates
+ * fused device targets, or the caller's batched log-prob (emx_set_batch_target_callback below; not EMX_TARGET_HOST).  Arrays are
+ * member-major: coordinates
  * (B, nwalkers, ndim), log-probs and accept counts (B, nwalkers), the chain (B, capacity, nwalkers, ndim).
  * Tuning keys (emx_batch_set_tuning; neither changes a bit, plans do not depend on the state):
  *   "batch_threads"      0 (auto)  threads of a member's workgroup (a multiple of 64, <= 1 024)
@@ -521,6 +522,21 @@ int emx_batch_set_tuning(emx_batch* b, const char* key, int64_t value);
 /* per_member 0: one target for every member (p0 / p1 as emx_set_target, scales[0]); 1: B of them, member-major
  * (p0 (B, ndim); p1 (B, ndim) ivar or (B, ndim, ndim) icov; scales (B) Rosenbrock scales, 0 or NULL: 20) */
 int emx_batch_set_target(emx_batch* b, int32_t kind, const double* p0, const double* p1, const double* scales, int32_t per_member);
+/* The caller's own batched log-prob over every member at once (EMX_TARGET_DEVICE_CALLBACK of a batch; emcee_amd.targets.BatchCallable /
+ * BatchKernel): the rules of emx_device_log_prob_fn -- called on the host thread that drives the run, it must ENQUEUE work on
+ * `hip_stream` that reads coords_dev (nbatch, rows, ndim) and writes log_prob_dev (nbatch, rows), return 0 (non-zero aborts the run
+ * with an error) and never synchronise; -inf is legal, NaN raises the reference's error naming the member.  Each row must be
+ * computed independently of the others and of the block's shape.  A proposal step is S_max calls (S_max, S_min: the largest and
+ * smallest nsplits of the schedule, 1 for a GaussianMove), each on rows = ceil(nwalkers / S_min): at phase k, rows [0, n) of
+ * member b are its split k's proposals in the order the single-ensemble callback receives them (n that split's size), the
+ * other rows padding -- copies of the member's current walkers, whose results are ignored (NaN included).  The initial
+ * log-probs (emx_batch_eval_state_log_prob) are one call on the state itself, rows = nwalkers.  Per run of n proposal steps:
+ * n S_max + 1 launches of the library's k_batch_cb (one workgroup a member: commit the previous phase, propose the next) and n S_max
+ * calls, whatever B.  A GaussianMove runs only as the one move of such a schedule.  Replaces the fused target; "batch_threads"
+ * applies (auto: one phase's rows in one pass), "batch_plan_steps" does not. */
+typedef int (*emx_batch_log_prob_fn)(void* user, const double* coords_dev, int32_t nbatch, int64_t rows, int32_t ndim,
+                                     double* log_prob_dev, void* hip_stream);
+int emx_set_batch_target_callback(emx_batch* b, emx_batch_log_prob_fn fn, void* user);
 /* the move schedule (as emx_set_moves); a sequential GaussianMove only as the one move */
 int emx_batch_set_moves(emx_batch* b, int32_t nmoves, const emx_move_desc* moves, const double* cdf);
 int emx_batch_set_move_scale(emx_batch* b, int32_t move, const double* scale, int32_t n);
@@ -530,7 +546,8 @@ int emx_batch_set_philox(emx_batch* b, const uint64_t* seeds, uint64_t step);
 int emx_batch_get_philox(emx_batch* b, uint64_t* seeds, uint64_t* step);
 int emx_batch_set_state(emx_batch* b, const double* coords, const double* log_prob);     /* log_prob may be NULL */
 int emx_batch_get_state(emx_batch* b, double* coords, double* log_prob);                 /* either may be NULL */
-/* every member's log-probs of its coordinates in one launch, with emx_eval_state_log_prob's arithmetic */
+/* every member's log-probs of its coordinates in one launch, with emx_eval_state_log_prob's arithmetic (a batched callback: one
+ * call and one NaN-check launch) */
 int emx_batch_eval_state_log_prob(emx_batch* b);
 /* capacity: stored steps a member can hold; growing keeps what is stored */
 int emx_batch_chain_config(emx_batch* b, int64_t capacity);
