@@ -170,6 +170,7 @@ SIGNATURES = {
     "emx_batch_status": (C.c_int, [_P, _u32p]),
     "emx_batch_launch_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "emx_set_batch_target_callback": (C.c_int, [_P, BATCH_LOG_PROB_FN, _P]),
+    "emx_autocorr_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double, _dp, _ip, C.POINTER(C.c_int64)]),
 }
 
 

@@ -28,6 +28,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import autocorr
 from .autocorr import integrated_time
 from .ensemble import _native_desc, _parse_move_schedule, _refuse_extended_precision, philox_seed, walkers_independent
 from .state import State
@@ -194,7 +195,8 @@ class EnsembleBatch(object):
         self._ck(self._lib().emx_set_batch_target_callback(h, fn, user))
 
     def set_tuning(self, key, value):
-        """``"batch_threads"`` / ``"batch_plan_steps"`` (include/emx.h): the launch shape; no bit depends on it."""
+        """``"batch_threads"`` / ``"batch_plan_steps"`` (include/emx.h): the launch shape; ``"batch_acf_series"``: series per
+        FFT chunk of ``get_autocorr_time(on_device=True)``.  No bit depends on them."""
         self._tuning[key] = int(value)
         if self._h is not None:
             self._ck(self._lib().emx_batch_set_tuning(self._h, key.encode(), int(value)))
@@ -320,10 +322,41 @@ class EnsembleBatch(object):
         """``(B, nwalkers)``: the fraction of proposed steps that were accepted."""
         return self._accepted() / float(self.iteration)
 
-    def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False):
-        """``(B, ndim)``: :func:`emcee_amd.autocorr.integrated_time` of each member's chain, in steps."""
-        return np.stack([self[b].get_autocorr_time(discard=discard, thin=thin, c=c, tol=tol, quiet=quiet)
-                         for b in range(self.nbatch)])
+    def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False, on_device=False):
+        """``(B, ndim)``: :func:`emcee_amd.autocorr.integrated_time` of each member's chain, in steps.
+
+        The default copies each member's chain to the host and runs the NumPy estimator.  ``on_device=True`` computes the same
+        estimator for every member next to the chain (``emx_autocorr_batch``: batched hipFFT, Sokal's window on the device) and
+        copies back only the ``(B, ndim)`` results; the ``tol`` rule is then applied per member, and the error names the
+        members that fail it.  A device failure raises :class:`emcee_amd._lib.EmxError` (no fallback)."""
+        if not on_device:
+            return np.stack([self[b].get_autocorr_time(discard=discard, thin=thin, c=c, tol=tol, quiet=quiet)
+                             for b in range(self.nbatch)])
+        tau, _, nt = self._autocorr_device(discard, thin, c, 0, self.nbatch)
+        _check_tol(tau, nt, tol, quiet, list(range(self.nbatch)), tau)
+        return thin * tau
+
+    def _autocorr_device(self, discard=0, thin=1, c=5, lo=0, hi=None):
+        """-> (tau (hi - lo, ndim) in units of the selected samples, Sokal windows (hi - lo, ndim), series length nt):
+        ``emx_autocorr_batch`` on members [lo, hi).  Arguments are checked before any device is touched."""
+        hi = self.nbatch if hi is None else int(hi)
+        lo = int(lo)
+        if int(thin) != thin or thin < 1:
+            raise ValueError("thin must be an integer >= 1; got %r" % (thin,))
+        if int(discard) != discard or discard < 0:
+            raise ValueError("discard must be an integer >= 0; got %r" % (discard,))
+        if not 0 <= lo < hi <= self.nbatch:
+            raise ValueError("members [%d, %d) outside a batch of %d" % (lo, hi, self.nbatch))
+        if self._h is None or self.iteration <= 0:
+            raise ValueError("you must run the sampler with 'store == True' before computing autocorrelation times")
+        from .device import DeviceEnsemble
+        lib = self._lib()
+        DeviceEnsemble._load_hipfft(lib)
+        tau = np.empty((hi - lo, self.ndim))
+        win = np.empty((hi - lo, self.ndim), dtype=np.int32)
+        nt = C.c_int64(0)
+        self._ck(lib.emx_autocorr_batch(self._h, lo, hi, int(discard), int(thin), float(c), tau, win, C.byref(nt)))
+        return tau, win, nt.value
 
     def get_last_sample(self):
         """:class:`State` with ``(B, nwalkers, ndim)`` coordinates and ``(B, nwalkers)`` log-probs."""
@@ -344,6 +377,25 @@ class EnsembleBatch(object):
         if not 0 <= b < self.nbatch:
             raise IndexError("member %d outside a batch of %d" % (b, self.nbatch))
         return _Member(self, b)
+
+
+def _check_tol(tau, nt, tol, quiet, members, err_tau):
+    """integrated_time's ``tol`` rule (autocorr.py:110-121) on ``tau`` (one row per member of ``members``) of ``nt`` samples: a
+    member is flagged when ``tol * tau > nt`` for any parameter (NaN never is).  Raise AutocorrError(err_tau, msg) naming the
+    flagged members, or only log the message with ``quiet``."""
+    flag = tol * tau > nt
+    rows = np.flatnonzero(flag.any(axis=1))
+    if not len(rows):
+        return
+    named = [str(members[r]) for r in rows]
+    who = ("member " if len(named) == 1 else "members ") + ", ".join(named[:8]) + (
+        " and %d more" % (len(named) - 8) if len(named) > 8 else "")
+    msg = ("The chain is shorter than {0} times the integrated autocorrelation time for {1} parameter(s) of {2}. "
+           "Use this estimate with caution and run a longer chain!\n").format(tol, int(flag.sum()), who)
+    msg += "N/{0} = {1:.0f};\ntau: {2}".format(tol, nt / tol, tau[rows[0]] if len(rows) == 1 else tau[rows])
+    if not quiet:
+        raise autocorr.AutocorrError(err_tau, msg)
+    autocorr.logger.warning(msg)
 
 
 def _trampoline(fn, device, box):
@@ -396,7 +448,11 @@ class _Member(object):
     def acceptance_fraction(self):
         return self._batch.acceptance_fraction[self.index]
 
-    def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False):
+    def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False, on_device=False):
+        if on_device:
+            tau, _, nt = self._batch._autocorr_device(discard, thin, c, self.index, self.index + 1)
+            _check_tol(tau, nt, tol, quiet, [self.index], tau[0])
+            return thin * tau[0]
         x = self.get_chain(discard=discard, thin=thin)
         return thin * integrated_time(x, c=c, tol=tol, quiet=quiet)
 

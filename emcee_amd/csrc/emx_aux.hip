@@ -18,28 +18,8 @@
 #include "../../include/emx.h"
 #include "emx_internal.hpp"
 
-namespace {
-
-#define AUX_HIP(ctx, expr)                                                                                    \
-    do {                                                                                                      \
-        hipError_t _e = (expr);                                                                               \
-        if (_e != hipSuccess) {                                                                               \
-            char _b[384];                                                                                     \
-            snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            return emx_internal_fail(ctx, -2, _b);                                                            \
-        }                                                                                                     \
-    } while (0)
-
-// ---- hipFFT, resolved at run time (PyTorch bundles its own copy; the process should hold one) ----------------------
-struct FftApi {
-    void* h = nullptr;
-    int (*PlanMany)(void**, int, int*, int*, int, int, int*, int, int, int, int) = nullptr;
-    int (*SetStream)(void*, hipStream_t) = nullptr;
-    int (*ExecD2Z)(void*, double*, void*) = nullptr;
-    int (*ExecZ2D)(void*, void*, double*) = nullptr;
-    int (*Destroy)(void*) = nullptr;
-} g_fft;
-constexpr int FFT_D2Z = 0x6a, FFT_Z2D = 0x6c;
+// ---- hipFFT, resolved at run time (emx_internal.hpp) ---------------------------------------------------------------
+FftApi g_fft;
 
 int fft_load(const char* path, std::string& err) {
     if (g_fft.h) return 0;
@@ -66,6 +46,18 @@ int fft_load(const char* path, std::string& err) {
     g_fft.h = h;
     return 0;
 }
+
+namespace {
+
+#define AUX_HIP(ctx, expr)                                                                                    \
+    do {                                                                                                      \
+        hipError_t _e = (expr);                                                                               \
+        if (_e != hipSuccess) {                                                                               \
+            char _b[384];                                                                                     \
+            snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+            return emx_internal_fail(ctx, -2, _b);                                                            \
+        }                                                                                                     \
+    } while (0)
 
 // ---- autocorrelation kernels ----------------------------------------------------------------------------------------
 // series s = (walker, dim) of the chunk, sample t = stored step t0 + t * thin.  The chain is [step][walker][dim]: threads

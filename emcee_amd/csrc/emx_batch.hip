@@ -16,6 +16,7 @@
 
 #include "../../include/emx.h"
 #include "emx_batch_cb.hpp"
+#include "emx_internal.hpp"
 #include "emx_rng.hpp"
 #include "emx_small_host.hpp"
 #include "emx_small_launch.hpp"
@@ -64,6 +65,9 @@ struct emx_batch {
     double *cb_q = nullptr, *cb_lp = nullptr, *cb_fac = nullptr, *cb_logu = nullptr;
     int32_t *cb_wi = nullptr, *cb_nrows = nullptr;
     size_t cb_rows = 0;       // B R rows allocated
+    // emx_autocorr_batch (emx_batch_acf.hip): its hipFFT plans and scratch; tuning "batch_acf_series" (0: auto)
+    BatchAcf* acf = nullptr;
+    int64_t tune_acf_series = 0;
 };
 
 namespace {
@@ -432,6 +436,23 @@ int run_callback(emx_batch* b, int64_t total, int32_t thin_by, int32_t store) {
 
 }  // namespace
 
+int emx_internal_batch_view(emx_batch* b, EmxBatchView* v) {
+    if (!b || !v) return -1;
+    v->chain = b->chain;
+    v->B = b->B;
+    v->D = b->D;
+    v->N = b->N;
+    v->cap = b->cap;
+    v->stored = b->stored;
+    v->acf_series = b->tune_acf_series;
+    v->stream = b->stream;
+    v->device = b->device;
+    v->acf = &b->acf;
+    return 0;
+}
+
+int emx_internal_batch_fail(emx_batch* b, int code, const char* msg) { return fail(b, code, "%s", msg); }
+
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -481,6 +502,7 @@ int emx_batch_destroy(emx_batch* b) {
     if (!b) return 0;
     hipSetDevice(b->device);
     if (b->stream) hipStreamSynchronize(b->stream);
+    if (b->acf) emx_internal_batch_acf_release(b->acf);
     for (void* p : {(void*)b->X, (void*)b->lp, (void*)b->acc, (void*)b->acc_count, (void*)b->seeds, (void*)b->tp0, (void*)b->tp1,
                     (void*)b->tscales, (void*)b->chain, (void*)b->chain_lp, (void*)b->fac_dev, (void*)b->col_dev, (void*)b->cb_q,
                     (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi, (void*)b->cb_nrows})
@@ -501,6 +523,9 @@ int emx_batch_set_tuning(emx_batch* b, const char* key, int64_t value) {
     } else if (!std::strcmp(key, "batch_plan_steps")) {
         BNEED(b, value >= 0 && value <= 64, "batch_plan_steps: 0 ... 64");
         b->tune_plan_steps = value;
+    } else if (!std::strcmp(key, "batch_acf_series")) {
+        BNEED(b, value >= 0, "batch_acf_series: 0 (auto) or a positive number of series");
+        b->tune_acf_series = value;
     } else {
         return fail(b, -1, "unknown batch tuning key '%s'", key);
     }

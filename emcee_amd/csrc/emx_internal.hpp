@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
 
 #include "../../include/emx.h"
 
@@ -20,3 +21,34 @@ struct EmxChainView {
 int emx_internal_chain_view(emx_ctx* c, EmxChainView* v);
 int emx_internal_state_view(emx_ctx* c, const double** X, int64_t* N, int32_t* D, int* device);      // settles and synchronises the context first
 int emx_internal_fail(emx_ctx* c, int code, const char* msg);      // records the message for emx_last_error, returns code
+
+// ---- hipFFT, resolved at run time (PyTorch bundles its own copy; the process should hold one).  Implemented in emx_aux.hip;
+// emx_autocorr and emx_autocorr_batch (emx_batch_acf.hip) share the one dlopen.
+struct FftApi {
+    void* h = nullptr;
+    int (*PlanMany)(void**, int, int*, int*, int, int, int*, int, int, int, int) = nullptr;
+    int (*SetStream)(void*, hipStream_t) = nullptr;
+    int (*ExecD2Z)(void*, double*, void*) = nullptr;
+    int (*ExecZ2D)(void*, void*, double*) = nullptr;
+    int (*Destroy)(void*) = nullptr;
+};
+extern FftApi g_fft;
+constexpr int FFT_D2Z = 0x6a, FFT_Z2D = 0x6c;
+int fft_load(const char* path, std::string& err);      // 0, or -5 with the reason in err
+
+// ---- the batch handle seen from emx_batch_acf.hip (the handle itself lives in emx_batch.hip)
+struct BatchAcf;     // emx_autocorr_batch's hipFFT plans and scratch, kept on the handle between calls
+struct EmxBatchView {
+    const double* chain;     // (B, cap, N, D) member-major, or nullptr
+    int32_t B, D;
+    int64_t N, cap, stored;
+    int64_t acf_series;      // tuning "batch_acf_series" (0: auto)
+    hipStream_t stream;
+    int device;
+    BatchAcf** acf;          // the handle's slot (nullptr until the first call)
+};
+// implemented in emx_batch.hip
+int emx_internal_batch_view(emx_batch* b, EmxBatchView* v);
+int emx_internal_batch_fail(emx_batch* b, int code, const char* msg);      // records the message for emx_batch_last_error, returns code
+// implemented in emx_batch_acf.hip: destroys the plans and frees the scratch (emx_batch_destroy)
+void emx_internal_batch_acf_release(BatchAcf* a);

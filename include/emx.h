@@ -510,7 +510,9 @@ int64_t emx_host_pull_capacity(int64_t nwalkers, int32_t world, int32_t nsplits,
  *   "batch_threads"      0 (auto)  threads of a member's workgroup (a multiple of 64, <= 1 024)
  *   "batch_plan_steps"   0 (auto)  steps whose plans one pass keeps in LDS (<= 64)
  *   auto: up to one member a CU, the single-ensemble shape (small_threads / small_batch); more members than CUs, one
- *   half-step's lanes and one plan entry a thread, so that several members share a CU. */
+ *   half-step's lanes and one plan entry a thread, so that several members share a CU.
+ *   "batch_acf_series"   0 (auto)  emx_autocorr_batch: at most this many (member, walker, dim) series per FFT chunk (auto: the
+ *                                  scratch within ~3 GB); a chunk may begin and end inside a member */
 typedef struct emx_batch emx_batch;
 /* host only (no device touched): 0 when the kernel takes the shape, else -1 and the reason in msg */
 int emx_batch_check(int64_t nwalkers, int32_t ndim, int32_t target, int32_t nmoves, const emx_move_desc* moves, char* msg,
@@ -556,6 +558,14 @@ int emx_batch_iteration(emx_batch* b, int64_t* stored, int64_t* proposals);
 /* rows start, start + stride, ... < stop of members [member_lo, member_hi): what 0 -> (members, rows, nwalkers, ndim), 1 -> log-probs */
 int emx_batch_chain_read(emx_batch* b, int32_t what, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop,
                          int64_t stride, double* out);
+/* Integrated autocorrelation time of members [member_lo, member_hi) per parameter (autocorr.py:20-123 on
+ * backend.get_value("chain", discard, thin)), computed next to the chain as emx_autocorr does for one ensemble: tau_out
+ * (members, ndim) in units of the selected samples, window_out (members, ndim) the Sokal windows (may be NULL), *nsamples_out
+ * the series length nt, against which the caller applies the reference's "tol" rule.  Sokal's window runs on the device too:
+ * only the (members, ndim) results cross to the host.  hipFFT plans and scratch stay on the handle between calls (new plans
+ * when 2 next_pow_two(nt) changes); libhipfft as emx_autocorr (emx_fft_load), -5 when it cannot be loaded. */
+int emx_autocorr_batch(emx_batch* b, int32_t member_lo, int32_t member_hi, int64_t discard, int64_t thin, double c,
+                       double* tau_out, int32_t* window_out, int64_t* nsamples_out);
 int emx_batch_accepted_counts(emx_batch* b, double* out);           /* (B, nwalkers) */
 /* bits[B]: each member's status (emx_status's bits), read and cleared */
 int emx_batch_status(emx_batch* b, uint32_t* bits);
