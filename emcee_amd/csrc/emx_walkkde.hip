@@ -6,10 +6,12 @@
 //      per-workgroup partial sums over fixed slices, added in slice order by one workgroup -- no float atomics, so a chain is
 //      bit-reproducible run to run;
 //   2. factor (one workgroup, the covariance in LDS): Cholesky L.  KDE: strict (a pivot <= 0 or not finite raises
-//      ST_SINGULAR_COV, scipy's LinAlgError), scaled by the bandwidth factor h, and L_h^-1.  Walk: a pivot <= tol * trace / D
-//      zeroes its column (the reference's SVD-based multivariate_normal takes semidefinite matrices);
-//   3. proposal, one wave per slot: walk s >= 2  q = x + sum_j w_j c_hj, w_j = (z_j - mean z) / sqrt(s - 1), which is exactly
-//      N(x, cov(c_h)); walk s = 0  q = x + L z; KDE  q = c_k + L_h z;
+//      ST_SINGULAR_COV, scipy's LinAlgError), scaled by the bandwidth factor h, and L_h^-1.  Walk: a pivot <= 1e-12 S_jj (that
+//      column's variance before the factorisation: scale invariant) zeroes its column (the reference's SVD-based
+//      multivariate_normal takes semidefinite matrices);
+//   3. proposal, one wave per slot: walk s >= 2  q = x + sum_j w_j (c_hj - x), w_j = (z_j - mean z) / sqrt(s - 1), which is
+//      exactly N(x, cov(c_h)) (sum_j w_j = 0; centred on x the rounding error scales with the helpers' spread, not with |x|);
+//      walk s = 0  q = x + L z; KDE  q = c_k + L_h z;
 //   4. KDE: whitened complement Y_C = (C - mu) L_h^-T, b_j = -|Y_C,j|^2 / 2, queries y_s = L_h^-1 (s - mu), y_q = Y_C[k] + z, and
 //      factor = [LSE_j(y_s . Y_C,j + b_j) - |y_s|^2 / 2] - [LSE_j(y_q . Y_C,j + b_j) - |y_q|^2 / 2]  (the normalising constants of
 //      the two Gaussian mixtures cancel).  The LSE is a tiled f64 GEMM with an online max / sum epilogue, split over the data
@@ -147,6 +149,7 @@ __global__ __launch_bounds__(WK_NT) void k_wk_cov_part(const WalkKdeArgs A) {
 // KDE: L_h = h L and L_h^-1 (column j of the inverse by forward substitution, thread j).  Walk: semidefinite-tolerant.
 __global__ __launch_bounds__(WK_NT) void k_wk_factor(const WalkKdeArgs A) {
     extern __shared__ double S[];       // D x D
+    __shared__ double tol[WK_MAX_D];    // walk: 1e-12 S_jj of the covariance before the factorisation
     __shared__ int bad;
     const int D = A.D, tid = threadIdx.x, DD = D * D;
     const int64_t Nc = (int64_t)A.N - A.ns;
@@ -160,12 +163,11 @@ __global__ __launch_bounds__(WK_NT) void k_wk_factor(const WalkKdeArgs A) {
     }
     if (tid == 0) bad = 0;
     __syncthreads();
-    double tol = 0.0;
-    if (!kde) {
-        double tr = 0.0;
-        for (int d = 0; d < D; ++d) tr += S[d * D + d];
-        tol = 1e-12 * tr / (double)D;
-    }
+    // a column's own variance sets its threshold, so the rule commutes with scaling a coordinate (a trace-based threshold zeroed
+    // the column of a coordinate far smaller than the others); a constant or exactly collinear coordinate still gives a pivot at
+    // or below it
+    for (int j = tid; j < D; j += WK_NT) tol[j] = 1e-12 * S[j * D + j];
+    __syncthreads();
     for (int j = 0; j < D; ++j) {
         const double piv = S[j * D + j];
         bool zero = false;
@@ -175,7 +177,7 @@ __global__ __launch_bounds__(WK_NT) void k_wk_factor(const WalkKdeArgs A) {
                 zero = true;
             }
         } else {
-            zero = !(piv > tol) || !(piv < __builtin_inf());
+            zero = !(piv > tol[j]) || !(piv < __builtin_inf());
         }
         const double ljj = zero ? 0.0 : sqrt(piv);
         const double inv = zero ? 0.0 : 1.0 / ljj;
@@ -298,19 +300,21 @@ __global__ __launch_bounds__(WK_NT) void k_wk_propose(const WalkKdeArgs A) {
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             for (int d = lane; d < D; d += 64) {
-                double acc = A.X[(size_t)i * D + d];
+                // sum_k w_k (c_k - x), not sum_k w_k c_k: the weights sum to zero only in exact arithmetic, so the raw form loses
+                // eps |x| per step; centred on x the error is eps times the helpers' spread (a constant coordinate stays put)
+                const double xd = A.X[(size_t)i * D + d];
                 double dq = 0.0;
                 int k = 0;
                 for (; k + 4 <= s; k += 4) {            // four helper loads in flight, accumulated in draw order
                     const double c0 = A.X[(size_t)hs[wv][k] * D + d], c1 = A.X[(size_t)hs[wv][k + 1] * D + d];
                     const double c2 = A.X[(size_t)hs[wv][k + 2] * D + d], c3 = A.X[(size_t)hs[wv][k + 3] * D + d];
-                    dq = fma(zs[wv][k], c0, dq);
-                    dq = fma(zs[wv][k + 1], c1, dq);
-                    dq = fma(zs[wv][k + 2], c2, dq);
-                    dq = fma(zs[wv][k + 3], c3, dq);
+                    dq = fma(zs[wv][k], c0 - xd, dq);
+                    dq = fma(zs[wv][k + 1], c1 - xd, dq);
+                    dq = fma(zs[wv][k + 2], c2 - xd, dq);
+                    dq = fma(zs[wv][k + 3], c3 - xd, dq);
                 }
-                for (; k < s; ++k) dq = fma(zs[wv][k], A.X[(size_t)hs[wv][k] * D + d], dq);
-                acc += dq;
+                for (; k < s; ++k) dq = fma(zs[wv][k], A.X[(size_t)hs[wv][k] * D + d] - xd, dq);
+                const double acc = xd + dq;
                 q[d] = acc;
                 nonfinite = nonfinite || !(fabs(acc) < __builtin_inf());
             }
