@@ -10,7 +10,8 @@ __version__ = "0.1.0"
 from . import autocorr, backends, moves, targets
 from .batch import EnsembleBatch
 from .ensemble import EnsembleSampler, walkers_independent
+from .pt import PTSampler
 from .state import State
 
-__all__ = ["EnsembleSampler", "EnsembleBatch", "walkers_independent", "State", "moves", "autocorr", "backends", "targets",
+__all__ = ["EnsembleSampler", "EnsembleBatch", "PTSampler", "walkers_independent", "State", "moves", "autocorr", "backends", "targets",
            "__version__"]

@@ -170,6 +170,15 @@ SIGNATURES = {
     "emx_batch_status": (C.c_int, [_P, _u32p]),
     "emx_batch_launch_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "emx_set_batch_target_callback": (C.c_int, [_P, BATCH_LOG_PROB_FN, _P]),
+    "emx_pt_set_tempering": (C.c_int, [_P, C.c_int32, _dp, _P, _P]),
+    "emx_set_batch_prior_callback": (C.c_int, [_P, BATCH_LOG_PROB_FN, _P]),
+    "emx_pt_set_swap_every": (C.c_int, [_P, C.c_int64]),
+    "emx_pt_swap": (C.c_int, [_P]),
+    "emx_pt_swap_counts": (C.c_int, [_P, _u64p, _u64p]),
+    "emx_pt_mean_loglike": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _dp]),
+    "emx_pt_set_state": (C.c_int, [_P, _dp, _dp, _dp]),
+    "emx_pt_get_state": (C.c_int, [_P, _dp, _dp]),
+    "emx_host_pt_swap_draws": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, _ip, _dp]),
     "emx_autocorr_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double, _dp, _ip, C.POINTER(C.c_int64)]),
 }
 

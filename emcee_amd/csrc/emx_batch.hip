@@ -17,6 +17,7 @@
 #include "../../include/emx.h"
 #include "emx_batch_cb.hpp"
 #include "emx_internal.hpp"
+#include "emx_pt.hpp"
 #include "emx_rng.hpp"
 #include "emx_small_host.hpp"
 #include "emx_small_launch.hpp"
@@ -68,6 +69,16 @@ struct emx_batch {
     // emx_autocorr_batch (emx_batch_acf.hip): its hipFFT plans and scratch; tuning "batch_acf_series" (0: auto)
     BatchAcf* acf = nullptr;
     int64_t tune_acf_series = 0;
+    // parallel tempering (emx_pt_set_tempering; pt_T 0: untempered): groups of pt_T members, member m at rung m % pt_T; each
+    // member's beta, the box prior, L and P per walker, the L chain, the caller's prior, the swap cadence and counters
+    int32_t pt_T = 0;
+    std::vector<double> pt_betas;              // (pt_T)
+    double *pt_beta = nullptr, *pt_lo = nullptr, *pt_hi = nullptr, *pt_L = nullptr, *pt_P = nullptr, *chain_L = nullptr;
+    emx_batch_log_prob_fn pr_fn = nullptr;
+    void* pr_user = nullptr;
+    double* cb_pr = nullptr;                   // (B, R) the caller's prior of the block
+    int64_t swap_every = 1;
+    unsigned long long *sw_att = nullptr, *sw_acc = nullptr;     // (B / pt_T, pt_T - 1)
 };
 
 namespace {
@@ -290,9 +301,54 @@ int call_back(emx_batch* b, const double* coords, int64_t rows, double* out) {
     return 0;
 }
 
+// the caller's prior (emx_set_batch_prior_callback) on `rows` rows of every member
+int call_prior(emx_batch* b, const double* coords, int64_t rows, double* out) {
+    const int rc = b->pr_fn(b->pr_user, coords, b->B, rows, b->D, out, (void*)b->stream);
+    if (rc != 0) return fail(b, -7, "the batched device log-prior callback failed (returned %d)", rc);
+    return 0;
+}
+
+// one k_pt_swap launch after Philox step `step`: the swap pass (swap) and / or the stored rows of chain row `row` (-1: none)
+int swap_pass(emx_batch* b, uint64_t step, int64_t row, bool swap) {
+    PtSwapArgs s{};
+    s.X = b->X;
+    s.lp = b->lp;
+    s.L = b->pt_L;
+    s.P = b->pt_P;
+    s.beta = b->pt_beta;
+    s.seeds = b->seeds;
+    s.attempts = b->sw_att;
+    s.accepts = b->sw_acc;
+    s.chain = b->chain;
+    s.chain_lp = b->chain_lp;
+    s.chain_L = b->chain_L;
+    s.cap = b->cap;
+    s.chain_row = row;
+    s.swap = swap ? 1 : 0;
+    s.T = b->pt_T;
+    s.N = (int32_t)b->N;
+    s.D = b->D;
+    s.step = step;
+    BHIP(b, pt_swap_launch(b->B / b->pt_T, b->stream, s));
+    ++b->launches;
+    return 0;
+}
+
 // the initial log-probs: one call on the whole state, then the per-member NaN check
 int eval_callback(emx_batch* b) {
     BNEED(b, b->cb_fn != nullptr, "device callback target without a callback (emx_set_batch_target_callback)");
+    if (b->pt_T > 0) {       // tempered: P (the caller's prior, the box or 0), L, then lp and the NaN check in one launch
+        if (b->pr_fn) {
+            if (int rc = call_prior(b, b->X, b->N, b->pt_P)) return rc;
+        } else {
+            BHIP(b, hipMemsetAsync(b->pt_P, 0, (size_t)b->B * b->N * 8, b->stream));
+        }
+        if (int rc = call_back(b, b->X, b->N, b->pt_L)) return rc;
+        BHIP(b, pt_init_launch(b->X, b->lp, b->pt_L, b->pt_P, b->pt_beta, b->pr_fn ? nullptr : b->pt_lo, b->pt_hi, b->status, b->B,
+                               (int32_t)b->N, b->D, b->stream));
+        ++b->launches;
+        return 0;
+    }
     if (int rc = call_back(b, b->X, b->N, b->lp)) return rc;
     BHIP(b, batch_lp_check(b->lp, b->status, b->B, (int32_t)b->N, b->stream));
     ++b->launches;
@@ -329,9 +385,9 @@ int run_callback(emx_batch* b, int64_t total, int32_t thin_by, int32_t store) {
     const size_t rows = (size_t)b->B * R;
     if (rows > b->cb_rows) {
         BHIP(b, hipStreamSynchronize(b->stream));
-        for (void* p : {(void*)b->cb_q, (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi})
+        for (void* p : {(void*)b->cb_q, (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi, (void*)b->cb_pr})
             if (p) hipFree(p);
-        b->cb_q = b->cb_lp = b->cb_fac = b->cb_logu = nullptr;
+        b->cb_q = b->cb_lp = b->cb_fac = b->cb_logu = b->cb_pr = nullptr;
         b->cb_wi = nullptr;
         b->cb_rows = 0;
         BHIP(b, hipMalloc((void**)&b->cb_q, rows * b->D * 8));
@@ -361,6 +417,17 @@ int run_callback(emx_batch* b, int64_t total, int32_t thin_by, int32_t store) {
     a.N = (int32_t)b->N;
     a.D = b->D;
     a.R = (int32_t)R;
+    const bool pt = b->pt_T > 0;
+    if (pt) {
+        if (b->pr_fn && !b->cb_pr) BHIP(b, hipMalloc((void**)&b->cb_pr, b->cb_rows * 8));
+        a.beta = b->pt_beta;
+        a.box_lo = b->pt_lo;
+        a.box_hi = b->pt_hi;
+        a.lpr = b->pr_fn ? b->cb_pr : nullptr;
+        a.L = b->pt_L;
+        a.P = b->pt_P;
+        a.chain_L = b->chain_L;
+    }
     const Shape sh = pick_shape(b->D, b->D);
     // one phase's rows in one pass (R G lanes); no bit depends on the shape
     int threads = (int)std::min<int64_t>(CB_MAX_THREADS, std::max<int64_t>(64, (R * sh.G + 63) / 64 * 64));
@@ -370,10 +437,11 @@ int run_callback(emx_batch* b, int64_t total, int32_t thin_by, int32_t store) {
     b->last_plan_steps = 0;
     const int64_t most = any_gauss ? std::max<int64_t>(1, std::min<int64_t>(4096, (4 << 20) / b->B)) : total;
     int64_t stored_row = -1, nstored = 0;     // chain row of the pending phase's step
-    bool pending = false;
+    bool pending = false, pending_swap = false;
     auto launch_cb = [&](bool propose, int phase, uint64_t step) -> int {
         a.commit = pending ? 1 : 0;
         a.chain_row = stored_row;
+        a.rows_in_commit = pending_swap ? 0 : 1;
         a.propose = propose ? 1 : 0;
         a.phase = phase;
         a.step = step;
@@ -417,17 +485,27 @@ int run_callback(emx_batch* b, int64_t total, int32_t thin_by, int32_t store) {
             a.gfac = any_gauss ? b->fac_dev + s2 : nullptr;
             a.gcol = cols[s2];
             const int64_t row = (store && (s + 1) % thin_by == 0) ? b->stored + nstored : -1;
+            const bool swap = pt && b->swap_every > 0 && (step + 1) % (uint64_t)b->swap_every == 0;
             for (int k = 0; k < smax; ++k) {
                 if (int rc = launch_cb(true, k, step)) return rc;
+                if (pt && b->pr_fn)                  // the prior first, on the same block
+                    if (int rc = call_prior(b, b->cb_q, R, b->cb_pr)) return rc;
                 if (int rc = call_back(b, b->cb_q, R, b->cb_lp)) return rc;
                 pending = true;
+                pending_swap = swap;
                 stored_row = row;
+            }
+            if (swap) {                          // commit the last phase, then the swap pass (it writes the stored rows)
+                if (int rc = launch_cb(false, 0, 0)) return rc;
+                pending = pending_swap = false;
+                if (int rc = swap_pass(b, step, row, true)) return rc;
             }
             if (row >= 0) ++nstored;
         }
         i += chunk;
     }
-    if (int rc = launch_cb(false, 0, 0)) return rc;          // commit the last phase
+    if (pending)
+        if (int rc = launch_cb(false, 0, 0)) return rc;      // commit the last phase
     b->stored += nstored;
     b->proposals += total;
     b->step += (uint64_t)total;
@@ -505,7 +583,9 @@ int emx_batch_destroy(emx_batch* b) {
     if (b->acf) emx_internal_batch_acf_release(b->acf);
     for (void* p : {(void*)b->X, (void*)b->lp, (void*)b->acc, (void*)b->acc_count, (void*)b->seeds, (void*)b->tp0, (void*)b->tp1,
                     (void*)b->tscales, (void*)b->chain, (void*)b->chain_lp, (void*)b->fac_dev, (void*)b->col_dev, (void*)b->cb_q,
-                    (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi, (void*)b->cb_nrows})
+                    (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi, (void*)b->cb_nrows, (void*)b->pt_beta,
+                    (void*)b->pt_lo, (void*)b->pt_hi, (void*)b->pt_L, (void*)b->pt_P, (void*)b->chain_L, (void*)b->cb_pr, (void*)b->sw_att,
+                    (void*)b->sw_acc})
         if (p) hipFree(p);
     for (double* p : b->mscale)
         if (p) hipFree(p);
@@ -688,11 +768,20 @@ int emx_batch_chain_config(emx_batch* b, int64_t capacity) {
         hipFree(nc);
         return fail(b, -2, "chain allocation failed");
     }
+    double* nL = nullptr;
+    if (b->pt_T > 0 && hipMalloc((void**)&nL, (size_t)b->B * capacity * N * 8) != hipSuccess) {
+        hipFree(nc);
+        hipFree(nl);
+        return fail(b, -2, "chain allocation failed");
+    }
     if (b->stored > 0) {      // what is stored stays: member by member, into the longer rows
         BHIP(b, hipMemcpy2DAsync(nc, capacity * ND * 8, b->chain, b->cap * ND * 8, b->stored * ND * 8, b->B, hipMemcpyDeviceToDevice, b->stream));
         BHIP(b, hipMemcpy2DAsync(nl, capacity * N * 8, b->chain_lp, b->cap * N * 8, b->stored * N * 8, b->B, hipMemcpyDeviceToDevice, b->stream));
+        if (nL) BHIP(b, hipMemcpy2DAsync(nL, capacity * N * 8, b->chain_L, b->cap * N * 8, b->stored * N * 8, b->B, hipMemcpyDeviceToDevice, b->stream));
     }
     BHIP(b, hipStreamSynchronize(b->stream));
+    if (b->chain_L) hipFree(b->chain_L);
+    b->chain_L = nL;
     if (b->chain) hipFree(b->chain);
     if (b->chain_lp) hipFree(b->chain_lp);
     b->chain = nc;
@@ -731,7 +820,7 @@ int emx_batch_iteration(emx_batch* b, int64_t* stored, int64_t* proposals) {
 
 int emx_batch_chain_read(emx_batch* b, int32_t what, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop,
                          int64_t stride, double* out) {
-    BNEED(b, what == 0 || what == 1, "what: 0 coordinates, 1 log-probs");
+    BNEED(b, what == 0 || what == 1 || (what == 2 && b->chain_L), "what: 0 coordinates, 1 log-probs, 2 log-likelihoods (tempered)");
     BNEED(b, 0 <= member_lo && member_lo <= member_hi && member_hi <= b->B, "members [%d, %d) outside [0, %d)", member_lo, member_hi, b->B);
     BNEED(b, stride >= 1 && 0 <= start && start <= stop && stop <= b->stored, "rows [%lld, %lld) outside the %lld stored",
           (long long)start, (long long)stop, (long long)b->stored);
@@ -740,7 +829,7 @@ int emx_batch_chain_read(emx_batch* b, int32_t what, int32_t member_lo, int32_t 
     if (nsel == 0 || member_hi == member_lo) return 0;
     BHIP(b, hipSetDevice(b->device));
     const size_t row = (size_t)b->N * (what == 0 ? b->D : 1);
-    const double* base = what == 0 ? b->chain : b->chain_lp;
+    const double* base = what == 0 ? b->chain : what == 1 ? b->chain_lp : b->chain_L;
     for (int32_t m = member_lo; m < member_hi; ++m)
         BHIP(b, hipMemcpy2DAsync(out + (size_t)(m - member_lo) * nsel * row, row * 8, base + ((size_t)m * b->cap + start) * row, stride * row * 8,
                                  row * 8, nsel, hipMemcpyDeviceToHost, b->stream));
@@ -772,6 +861,133 @@ int emx_batch_launch_info(emx_batch* b, int32_t* threads, int32_t* plan_steps, i
     if (threads) *threads = b->last_threads;
     if (plan_steps) *plan_steps = b->last_plan_steps;
     if (launches) *launches = b->launches;
+    return 0;
+}
+
+// ---- parallel tempering (emx_pt.hip) ----
+
+int emx_pt_set_tempering(emx_batch* b, int32_t ntemps, const double* betas, const double* box_lo, const double* box_hi) {
+    BNEED(b, b->target == EMX_TARGET_DEVICE_CALLBACK, "tempering needs a batched callback target (emx_set_batch_target_callback)");
+    BNEED(b, ntemps >= 1 && b->B % ntemps == 0, "ntemps = %d does not divide the batch of %d members", ntemps, b->B);
+    BNEED(b, betas != nullptr, "no betas");
+    BNEED(b, betas[0] == 1.0, "betas[0] must be 1");
+    for (int t = 0; t < ntemps; ++t) {
+        BNEED(b, betas[t] >= 0.0 && betas[t] <= 1.0, "betas must lie in [0, 1]; betas[%d] = %g", t, betas[t]);
+        if (t > 0) BNEED(b, betas[t] <= betas[t - 1], "betas must not increase (betas[%d] = %g, betas[%d] = %g)", t - 1,
+                         betas[t - 1], t, betas[t]);
+    }
+    BNEED(b, (box_lo == nullptr) == (box_hi == nullptr), "a box prior needs both bounds");
+    BNEED(b, b->stored == 0, "tempering is set before anything is stored");
+    BHIP(b, hipSetDevice(b->device));
+    BHIP(b, hipStreamSynchronize(b->stream));
+    for (double** p : {&b->pt_beta, &b->pt_lo, &b->pt_hi, &b->pt_L, &b->pt_P, &b->chain_L})
+        if (*p) {
+            hipFree(*p);
+            *p = nullptr;
+        }
+    for (unsigned long long** p : {&b->sw_att, &b->sw_acc})
+        if (*p) {
+            hipFree(*p);
+            *p = nullptr;
+        }
+    const size_t BN = (size_t)b->B * b->N;
+    std::vector<double> mb((size_t)b->B);
+    for (int32_t m = 0; m < b->B; ++m) mb[m] = betas[m % ntemps];
+    BHIP(b, hipMalloc((void**)&b->pt_beta, mb.size() * 8));
+    BHIP(b, hipMemcpy(b->pt_beta, mb.data(), mb.size() * 8, hipMemcpyHostToDevice));
+    if (box_lo) {
+        for (int d = 0; d < b->D; ++d) BNEED(b, box_lo[d] <= box_hi[d], "box prior: lo[%d] > hi[%d]", d, d);
+        BHIP(b, hipMalloc((void**)&b->pt_lo, (size_t)b->D * 8));
+        BHIP(b, hipMalloc((void**)&b->pt_hi, (size_t)b->D * 8));
+        BHIP(b, hipMemcpy(b->pt_lo, box_lo, (size_t)b->D * 8, hipMemcpyHostToDevice));
+        BHIP(b, hipMemcpy(b->pt_hi, box_hi, (size_t)b->D * 8, hipMemcpyHostToDevice));
+    }
+    BHIP(b, hipMalloc((void**)&b->pt_L, BN * 8));
+    BHIP(b, hipMalloc((void**)&b->pt_P, BN * 8));
+    BHIP(b, hipMemset(b->pt_L, 0, BN * 8));
+    BHIP(b, hipMemset(b->pt_P, 0, BN * 8));
+    const size_t npairs = (size_t)(b->B / ntemps) * (ntemps > 1 ? ntemps - 1 : 1);
+    BHIP(b, hipMalloc((void**)&b->sw_att, npairs * 8));
+    BHIP(b, hipMalloc((void**)&b->sw_acc, npairs * 8));
+    BHIP(b, hipMemset(b->sw_att, 0, npairs * 8));
+    BHIP(b, hipMemset(b->sw_acc, 0, npairs * 8));
+    if (b->cap > 0) BHIP(b, hipMalloc((void**)&b->chain_L, (size_t)b->B * b->cap * b->N * 8));
+    b->pt_betas.assign(betas, betas + ntemps);
+    b->pt_T = ntemps;
+    return 0;
+}
+
+int emx_set_batch_prior_callback(emx_batch* b, emx_batch_log_prob_fn fn, void* user) {
+    BNEED(b, b->pt_T > 0, "a prior callback needs tempering (emx_pt_set_tempering)");
+    BNEED(b, b->pt_lo == nullptr || fn == nullptr, "the batch has a box prior already");
+    BHIP(b, hipStreamSynchronize(b->stream));
+    b->pr_fn = fn;
+    b->pr_user = user;
+    return 0;
+}
+
+int emx_pt_set_swap_every(emx_batch* b, int64_t n) {
+    BNEED(b, n >= 0, "swap_every must be >= 0 (0: never)");
+    b->swap_every = n;
+    return 0;
+}
+
+int emx_pt_swap(emx_batch* b) {
+    BNEED(b, b->pt_T > 0, "no tempering set (emx_pt_set_tempering)");
+    BNEED(b, b->step > 0, "no step taken: the swap pass uses the draws of the last step");
+    BHIP(b, hipSetDevice(b->device));
+    if (b->pt_T < 2) return 0;
+    return swap_pass(b, b->step - 1, -1, true);
+}
+
+int emx_pt_swap_counts(emx_batch* b, uint64_t* attempts, uint64_t* accepts) {
+    BNEED(b, b->pt_T > 0, "no tempering set (emx_pt_set_tempering)");
+    const size_t n = (size_t)(b->B / b->pt_T) * (b->pt_T - 1);
+    if (n == 0) return 0;
+    if (attempts) BHIP(b, hipMemcpyAsync(attempts, b->sw_att, n * 8, hipMemcpyDeviceToHost, b->stream));
+    if (accepts) BHIP(b, hipMemcpyAsync(accepts, b->sw_acc, n * 8, hipMemcpyDeviceToHost, b->stream));
+    BHIP(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int emx_pt_mean_loglike(emx_batch* b, int64_t start, int64_t stop, int64_t stride, double* out) {
+    BNEED(b, b->pt_T > 0 && b->chain_L, "no tempered chain");
+    BNEED(b, stride >= 1 && 0 <= start && start < stop && stop <= b->stored, "rows [%lld, %lld) outside the %lld stored",
+          (long long)start, (long long)stop, (long long)b->stored);
+    BNEED(b, out != nullptr, "no output buffer");
+    BHIP(b, hipSetDevice(b->device));
+    double* dev = nullptr;
+    BHIP(b, hipMalloc((void**)&dev, (size_t)b->B * 8));
+    hipError_t e = pt_mean_launch(b->chain_L, b->cap, b->B, (int32_t)b->N, start, stop, stride, dev, b->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dev, (size_t)b->B * 8, hipMemcpyDeviceToHost, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    hipStreamSynchronize(b->stream);
+    hipFree(dev);
+    BHIP(b, e);
+    ++b->launches;
+    return 0;
+}
+
+int emx_pt_set_state(emx_batch* b, const double* coords, const double* loglike, const double* logprior) {
+    BNEED(b, b->pt_T > 0, "no tempering set (emx_pt_set_tempering)");
+    BNEED(b, coords && loglike && logprior, "coords, loglike and logprior are all needed");
+    const size_t BN = (size_t)b->B * b->N;
+    std::vector<double> lp(BN);
+    for (size_t r = 0; r < BN; ++r) lp[r] = pt_tempered(b->pt_betas[(r / b->N) % b->pt_T], loglike[r], logprior[r]);
+    BHIP(b, hipMemcpyAsync(b->X, coords, BN * b->D * 8, hipMemcpyHostToDevice, b->stream));
+    BHIP(b, hipMemcpyAsync(b->pt_L, loglike, BN * 8, hipMemcpyHostToDevice, b->stream));
+    BHIP(b, hipMemcpyAsync(b->pt_P, logprior, BN * 8, hipMemcpyHostToDevice, b->stream));
+    BHIP(b, hipMemcpyAsync(b->lp, lp.data(), BN * 8, hipMemcpyHostToDevice, b->stream));
+    BHIP(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int emx_pt_get_state(emx_batch* b, double* loglike, double* logprior) {
+    BNEED(b, b->pt_T > 0, "no tempering set (emx_pt_set_tempering)");
+    const size_t BN = (size_t)b->B * b->N;
+    if (loglike) BHIP(b, hipMemcpyAsync(loglike, b->pt_L, BN * 8, hipMemcpyDeviceToHost, b->stream));
+    if (logprior) BHIP(b, hipMemcpyAsync(logprior, b->pt_P, BN * 8, hipMemcpyDeviceToHost, b->stream));
+    BHIP(b, hipStreamSynchronize(b->stream));
     return 0;
 }
 

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "emx_batch_cb.hpp"
+#include "emx_pt.hpp"
 
 namespace emx {
 
@@ -27,7 +28,22 @@ struct CbMember {          // what small_propose needs of a member
     __device__ __forceinline__ uint32_t* status() const { return st; }
 };
 
-template <int G, int V, int CH>
+// the box prior of row q (D values): 0 inside [lo, hi] (bounds included), -inf outside; the row's G lanes share the answer
+template <int G>
+__device__ __forceinline__ double box_prior(const double* q, const double* lo, const double* hi, int D, int gl) {
+    int out = 0;
+    for (int d = gl; d < D; d += G) {
+        const double x = q[d];
+        out |= (x >= lo[d] && x <= hi[d]) ? 0 : 1;
+    }
+#pragma unroll
+    for (int m = 1; m < G; m <<= 1) out |= __shfl_xor(out, m);
+    return out ? -__builtin_inf() : 0.0;
+}
+
+// TEMPERED: the commit of parallel tempering (BatchCbArgs' tempering fields); the untempered instantiation is the kernel as it
+// was, bit for bit and instruction for instruction
+template <int G, int V, int CH, bool TEMPERED>
 __global__ __launch_bounds__(CB_MAX_THREADS) void k_batch_cb(const BatchCbArgs A) {
     constexpr int WPW = 64 / G;
     const int N = A.N, D = A.D, R = A.R, T = blockDim.x, tid = threadIdx.x;
@@ -40,7 +56,55 @@ __global__ __launch_bounds__(CB_MAX_THREADS) void k_batch_cb(const BatchCbArgs A
     const CbMember M{A.status + b * SMALL_STATUS_WORDS};
 
     // ---- 1. commit the pending phase (red_blue.py:96-104) ----
-    if (A.commit) {
+    if (TEMPERED && A.commit) {
+        // the decision on the tempered lp = pt_tempered(beta, L, P); L and P follow the accepted rows.  On a stored step the
+        // accept counts always move; the rows are written here unless the step ends with a swap pass (which writes them then).
+        const int n = A.nrows[b];
+        const bool stored = A.chain_row >= 0;
+        const bool rows = stored && A.rows_in_commit;
+        const double beta = A.beta[b];
+        double* Lm = A.L + b * (size_t)N;
+        double* Pm = A.P + b * (size_t)N;
+        double* cr = rows ? A.chain + ((size_t)b * A.cap + A.chain_row) * (size_t)N * D : nullptr;
+        double* cl = rows ? A.chain_lp + ((size_t)b * A.cap + A.chain_row) * (size_t)N : nullptr;
+        double* cL = rows ? A.chain_L + ((size_t)b * A.cap + A.chain_row) * (size_t)N : nullptr;
+        for (int base = wv * WPW; base < n; base += nwave * WPW) {
+            const int t = base + sub;
+            if (t < n) {                                                   // group-uniform
+                const size_t r = b * R + t;
+                const int i = A.wi[r];
+                double pq = 0.0;
+                if (A.lpr) pq = A.lpr[r];
+                else if (A.box_lo) pq = box_prior<G>(A.q + r * D, A.box_lo, A.box_hi, D, gl);
+                const double lraw = A.lpq[r];
+                const bool pinf = pq == -__builtin_inf();
+                const double lq = pinf ? -__builtin_inf() : lraw;             // the likelihood of a row outside the prior is ignored
+                const double lpn = pt_tempered(beta, lq, pq), lpo = lp[i];
+                if (gl == 0 && ((!pinf && lraw != lraw) || lpn != lpn)) raise_status(M.status(), ST_NAN_LOGP);
+                const double lnpdiff = A.fac[r] + lpn - lpo;
+                const bool accept = lnpdiff > A.logu[r];
+                Row<G, V, CH> x;
+                if (accept || rows) load_row<G, V, CH>(x, accept ? A.q + r * D : X + (size_t)i * D, D, gl);
+                if (accept) store_row<G, V, CH>(x, X + (size_t)i * D, D, gl);
+                if (rows) store_row_stream<G, V, CH>(x, cr + (size_t)i * D, D, gl);
+                if (gl == 0) {
+                    const double lo = Lm[i];
+                    if (accept) {
+                        lp[i] = lpn;
+                        Lm[i] = lq;
+                        Pm[i] = pq;
+                    }
+                    acc[i] = accept ? 1 : 0;
+                    if (stored) acc_count[i] += accept ? 1u : 0u;
+                    if (rows) {
+                        cl[i] = accept ? lpn : lpo;
+                        cL[i] = accept ? lq : lo;
+                    }
+                }
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else if (A.commit) {
         const int n = A.nrows[b];
         const bool stored = A.chain_row >= 0;
         double* cr = stored ? A.chain + ((size_t)b * A.cap + A.chain_row) * (size_t)N * D : nullptr;
@@ -151,7 +215,7 @@ __global__ __launch_bounds__(64) void k_batch_lp_check(const double* lp, uint32_
 
 template <int G, int V, int CH>
 hipError_t launch_cb(int grid, int threads, hipStream_t st, const BatchCbArgs& a) {
-    auto kern = k_batch_cb<G, V, CH>;
+    auto kern = a.beta ? k_batch_cb<G, V, CH, true> : k_batch_cb<G, V, CH, false>;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, st, a);
     return hipGetLastError();
 }

@@ -1,0 +1,175 @@
+// Parallel tempering on a batch handle (include/emx.h: emx_pt_*; emcee_amd.PTSampler).  Rung t of group g is member g T + t of the
+// batch, sampling pt_tempered(beta_t, L, P) with k_batch_cb's tempered commit; this file holds what is new:
+//
+// k_pt_swap: one workgroup a group.  The pairs run in turn from the hottest, i = T - 1 ... 1 (ptemcee's order); inside a pair the
+//   lanes run over the walkers k of rung i, each against walker pi_i(k) of rung i - 1 (pi_i a bijection: no two lanes touch the
+//   same row).  Accepted when (beta_{i-1} - beta_i) (L_i[k] - L_{i-1}[pi_i(k)]) > log u_{i,k} (IEEE: NaN is rejected); then x, L
+//   and P change places and lp is recomputed at both destinations.  Each pair ends by waiting for its stores and meeting the
+//   workgroup barrier (k_batch_cb's hand-off from commit to propose), so that pair i - 1 sees what pair i left.  On a stored step
+//   the pass then writes every rung's chain, lp and L rows: the stored state is the state after the swap pass.
+// k_pt_init: the tempered initial state (box prior, -inf likelihood outside the prior, tempered lp, NaN check).
+// k_pt_mean_loglike: one workgroup a member, the mean of its L chain rows over the walkers (thermodynamic integration's input).
+// emx_host_pt_swap_draws: the host twin of the swap draws, for tests that rebuild every decision.
+#include <hip/hip_runtime.h>
+
+#include "../../include/emx.h"
+#include "emx_kernels.hpp"
+#include "emx_pt.hpp"
+
+namespace emx {
+
+namespace {
+
+constexpr int PT_THREADS = 256;
+
+__global__ __launch_bounds__(PT_THREADS) void k_pt_swap(const PtSwapArgs A) {
+    __shared__ unsigned int nacc;
+    const int T = A.T, N = A.N, D = A.D, tid = threadIdx.x, nt = blockDim.x;
+    const size_t g = blockIdx.x, m0 = g * (size_t)T;
+    if (A.swap) {
+        const unsigned long long seed = A.seeds[m0];
+        for (int i = T - 1; i >= 1; --i) {
+            if (tid == 0) nacc = 0u;
+            __syncthreads();
+            const size_t hot = m0 + i, cold = hot - 1;
+            const double bh = A.beta[hot], bc = A.beta[cold];
+            const double dbeta = bc - bh;
+            const PermKey pk = pt_perm_key((uint64_t)N, seed, A.step, i);
+            unsigned int mine = 0u;
+            for (int k = tid; k < N; k += nt) {
+                const int j = (int)perm_fwd((uint32_t)k, pk);
+                const double lu = plan_log_uniform(pt_swap_uniform(seed, A.step, i, (uint32_t)k, (uint32_t)N));
+                const size_t rh = hot * N + k, rc = cold * N + j;
+                const double Lh = A.L[rh], Lc = A.L[rc];
+                const double diff = Lh - Lc;
+                if (dbeta * diff > lu) {
+                    const double Ph = A.P[rh], Pc = A.P[rc];
+                    double* xh = A.X + rh * D;
+                    double* xc = A.X + rc * D;
+                    for (int d = 0; d < D; ++d) {
+                        const double v = xh[d];
+                        xh[d] = xc[d];
+                        xc[d] = v;
+                    }
+                    A.L[rh] = Lc;
+                    A.P[rh] = Pc;
+                    A.lp[rh] = pt_tempered(bh, Lc, Pc);
+                    A.L[rc] = Lh;
+                    A.P[rc] = Ph;
+                    A.lp[rc] = pt_tempered(bc, Lh, Ph);
+                    ++mine;
+                }
+            }
+            if (mine) atomicAdd(&nacc, mine);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this pair's rows are stored before the next pair reads them
+            __syncthreads();
+            if (tid == 0) {
+                const size_t c = g * (size_t)(T - 1) + (i - 1);
+                A.attempts[c] += (unsigned long long)N;
+                A.accepts[c] += (unsigned long long)nacc;
+            }
+        }
+    }
+    if (A.chain_row < 0) return;
+    // the stored step's rows of every rung of the group: coordinates, tempered lp, L
+    for (int t = 0; t < T; ++t) {
+        const size_t m = m0 + t;
+        const size_t crow = (size_t)m * A.cap + A.chain_row;
+        const double* x = A.X + m * (size_t)N * D;
+        double* cx = A.chain + crow * (size_t)N * D;
+        for (int e = tid; e < N * D; e += nt) cx[e] = x[e];
+        for (int e = tid; e < N; e += nt) {
+            A.chain_lp[crow * N + e] = A.lp[m * N + e];
+            A.chain_L[crow * N + e] = A.L[m * N + e];
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_pt_init(const double* X, double* lp, double* L, double* P, const double* beta,
+                                                const double* box_lo, const double* box_hi, uint32_t* status, int N, int D) {
+    const size_t b = blockIdx.x;
+    bool nan = false;
+    for (int w = threadIdx.x; w < N; w += 64) {
+        const size_t r = b * N + w;
+        double p = P[r];
+        if (box_lo) {
+            bool in = true;
+            for (int d = 0; d < D; ++d) {
+                const double x = X[r * D + d];
+                in = in && x >= box_lo[d] && x <= box_hi[d];
+            }
+            p = in ? 0.0 : -__builtin_inf();
+            P[r] = p;
+        }
+        const double lraw = L[r];
+        const bool pinf = p == -__builtin_inf();
+        const double l = pinf ? -__builtin_inf() : lraw;
+        const double v = pt_tempered(beta[b], l, p);
+        L[r] = l;
+        lp[r] = v;
+        nan |= (!pinf && lraw != lraw) || v != v;
+    }
+    if (__ballot(nan) != 0ull && threadIdx.x == 0) raise_status(status + b * SMALL_STATUS_WORDS, ST_NAN_LOGP);
+}
+
+__global__ __launch_bounds__(PT_THREADS) void k_pt_mean_loglike(const double* chain_L, long long cap, int N, long long start,
+                                                                long long stop, long long stride, double* out) {
+    __shared__ double part[PT_THREADS / 64];
+    const size_t m = blockIdx.x;
+    const long long nsel = (stop - start + stride - 1) / stride;
+    const long long total = nsel * N;
+    double s = 0.0;
+    for (long long e = threadIdx.x; e < total; e += blockDim.x) {
+        const long long row = start + (e / N) * stride, w = e % N;
+        s += chain_L[((size_t)m * cap + row) * N + w];
+    }
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += part[w];
+        out[m] = total > 0 ? t / (double)total : __builtin_nan("");
+    }
+}
+
+}  // namespace
+
+hipError_t pt_swap_launch(int groups, hipStream_t st, const PtSwapArgs& a) {
+    hipLaunchKernelGGL(k_pt_swap, dim3(groups), dim3(PT_THREADS), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t pt_init_launch(const double* X, double* lp, double* L, double* P, const double* beta, const double* box_lo,
+                          const double* box_hi, uint32_t* status, int32_t B, int32_t N, int32_t D, hipStream_t st) {
+    hipLaunchKernelGGL(k_pt_init, dim3(B), dim3(64), 0, st, X, lp, L, P, beta, box_lo, box_hi, status, N, D);
+    return hipGetLastError();
+}
+
+hipError_t pt_mean_launch(const double* chain_L, long long cap, int32_t B, int32_t N, long long start, long long stop,
+                          long long stride, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_pt_mean_loglike, dim3(B), dim3(PT_THREADS), 0, st, chain_L, cap, N, start, stop, stride, out);
+    return hipGetLastError();
+}
+
+}  // namespace emx
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int emx_host_pt_swap_draws(uint64_t seed, uint64_t step, int64_t nwalkers, int32_t ntemps, int32_t* perm_out, double* logu_out) {
+    if (nwalkers < 1 || nwalkers > (int64_t)1 << 30 || ntemps < 1 || (ntemps > 1 && (!perm_out || !logu_out))) return -1;
+    if ((int64_t)(ntemps - 1) * nwalkers > (int64_t)0xffffffff) return -1;
+    for (int i = 1; i < ntemps; ++i) {
+        const emx::PermKey pk = emx::pt_perm_key((uint64_t)nwalkers, seed, step, i);
+        for (int64_t k = 0; k < nwalkers; ++k) {
+            const size_t o = (size_t)(i - 1) * nwalkers + k;
+            perm_out[o] = (int32_t)emx::perm_fwd((uint32_t)k, pk);
+            logu_out[o] = emx::plan_log_tab(emx::pt_swap_uniform(seed, step, i, (uint32_t)k, (uint32_t)nwalkers), emx::h_plan_log_rows);
+        }
+    }
+    return 0;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -218,17 +218,17 @@ EMX_HD uint32_t modinv_pow2(uint32_t a) {  // a odd; inverse mod 2^32 (Newton)
     return x;
 }
 
-EMX_HD PermKey make_perm_key(uint64_t n, uint64_t seed, uint64_t step) {
+// the key of a bijection on [0, n) drawn from Philox words (step lo, step hi, tag, c3) and (..., c3 + 1) under `seed`: the split
+// permutation is tag 'PERM' with c3 = 0 (make_perm_key); parallel tempering's swap pairings use their own tag (emx_pt.hpp)
+EMX_HD PermKey make_perm_key_tagged(uint64_t n, uint64_t seed, uint64_t step, uint32_t tag, uint32_t c3) {
     PermKey k{};
     k.n = n;
     uint32_t bits = 1;
     while ((1ull << bits) < n) ++bits;
     k.bits = bits;
     k.mask = bits >= 32 ? 0xffffffffu : (uint32_t)((1ull << bits) - 1);
-    const Philox4 a = philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), 0x5045524du /*'PERM'*/, 0, (uint32_t)seed,
-                                    (uint32_t)(seed >> 32));
-    const Philox4 b = philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), 0x5045524du, 1, (uint32_t)seed,
-                                    (uint32_t)(seed >> 32));
+    const Philox4 a = philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), tag, c3, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const Philox4 b = philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), tag, c3 + 1u, (uint32_t)seed, (uint32_t)(seed >> 32));
     k.m1 = a.v[0] | 1u;
     k.c1 = a.v[1];
     k.m2 = a.v[2] | 1u;
@@ -245,6 +245,10 @@ EMX_HD PermKey make_perm_key(uint64_t n, uint64_t seed, uint64_t step) {
     k.s1 = bits > 1 ? (bits + 1) / 2 : 1;
     k.s2 = bits > 2 ? (bits + 2) / 3 : 1;
     return k;
+}
+
+EMX_HD PermKey make_perm_key(uint64_t n, uint64_t seed, uint64_t step) {
+    return make_perm_key_tagged(n, seed, step, 0x5045524du /*'PERM'*/, 0u);
 }
 
 // ---------------------------------------------------------------------------------------

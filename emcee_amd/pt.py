@@ -1,0 +1,354 @@
+"""Parallel tempering: one ensemble per rung of a temperature ladder, swaps between adjacent rungs on the device.
+
+:class:`PTSampler` is the ptemcee algorithm (Vousden, Farr & Mandel 2016) for ``nbatch`` independent objects at once.  Group g
+(one object of a catalogue) has ``ntemps`` ensembles of ``nwalkers`` walkers; rung t samples ``beta_t * L(x) + P(x)``.  They run
+as the members of one :class:`~emcee_amd.EnsembleBatch` handle, member ``g * ntemps + t`` being rung t of group g, with the
+user's :class:`~emcee_amd.targets.BatchCallable` / :class:`~emcee_amd.targets.BatchKernel` as the untempered likelihood.
+
+Tempered log-probability.  ``lp = beta * L + P`` as two separate IEEE operations (no contraction).  At ``beta == 0``,
+``lp = P``, so ``0 * -inf`` never occurs.  Where ``P == -inf`` the row's ``L`` is ignored (NaN included) and kept as ``-inf``.
+The commit is :class:`~emcee_amd.EnsembleBatch`'s Metropolis rule on the tempered ``lp``; ``L`` and ``lp`` are kept per walker.
+A NaN ``L`` where ``P`` is finite raises the reference's "Probability function returned NaN", naming the object and the rung.
+
+Swap pass (ptemcee's order), after every ``swap_every``-th proposal step (``0``: never).  Pairs run from the hottest,
+``i = ntemps-1 ... 1``.  Walker k of rung i is paired with walker ``pi_i(k)`` of rung i-1, and the swap is accepted when
+``(beta_{i-1} - beta_i) * (L_i[k] - L_{i-1}[pi_i(k)]) > log u_{i,k}``; NaN (``-inf - -inf`` included) is rejected.  An accepted
+swap exchanges ``x``, ``L`` and ``P`` and recomputes ``lp`` at both destinations.  Each pair sees the result of the pair
+before it.  ``pi_i`` and ``u`` are keyed by group g's rung-0 Philox seed and the step just taken
+(``emx_host_pt_swap_draws`` in ``include/emx.h`` rebuilds them on the host).
+
+Stored rows are the state after the step's swap pass: coordinates, tempered ``lp`` (:meth:`get_log_prob`) and ``L``
+(:meth:`get_log_likelihood`).  Accept counts are per member; swap attempts and accepts per (group, pair).
+
+Seeds.  ``seeds`` holds ``nbatch`` integers.  Member (g, t) draws as the :class:`~emcee_amd.EnsembleBatch` member seeded with
+``s[g, t] = np.random.RandomState(seeds[g]).randint(0, 2**32, size=ntemps, dtype=np.uint64)[t]``, i.e. its Philox seed is
+``philox_seed(np.random.RandomState(s[g, t]))``.
+
+Evidence (:meth:`log_evidence_estimate`).  ``mean_logL[g, t]``, the mean of ``L`` over the stored steps after
+``int(fburnin * iteration)`` and over all walkers, is computed on the device; thermodynamic integration over the ladder
+(:func:`thermodynamic_integration_log_evidence`) gives ``log Z`` and ptemcee's error estimate.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .batch import EnsembleBatch, _trampoline
+from .ensemble import _refuse_extended_precision, walkers_independent
+from .state import State
+from .targets import BatchCallable, BatchKernel, BatchTarget, DeviceTarget
+
+__all__ = ["PTSampler", "default_betas", "thermodynamic_integration_log_evidence"]
+
+_ILL = ("Initial state has a large condition number. Make sure that your walkers are linearly independent for the best "
+        "performance")
+
+
+def default_betas(ntemps, ndim, Tmax=None):
+    """The default ladder: ``geomspace(1, 1/Tmax, ntemps)`` for a finite ``Tmax``; otherwise temperatures in the ratio
+    ``1 + sqrt(2 / ndim)``, with a last rung at ``beta = 0`` when ``Tmax`` is ``np.inf``."""
+    ntemps, ndim = int(ntemps), int(ndim)
+    if ntemps < 1 or ndim < 1:
+        raise ValueError("ntemps and ndim must be positive")
+    if ntemps == 1:
+        return np.ones(1)
+    if Tmax is not None and np.isfinite(Tmax):
+        if not Tmax > 1:
+            raise ValueError("Tmax must be > 1; got %r" % (Tmax,))
+        return np.geomspace(1.0, 1.0 / float(Tmax), ntemps)
+    if Tmax is not None and Tmax != np.inf:
+        raise ValueError("Tmax must be None, a finite number > 1 or np.inf; got %r" % (Tmax,))
+    ratio = 1.0 + np.sqrt(2.0 / ndim)
+    if Tmax is None:
+        return ratio ** -np.arange(ntemps, dtype=np.float64)
+    return np.concatenate([ratio ** -np.arange(ntemps - 1, dtype=np.float64), [0.0]])
+
+
+def _check_betas(betas):
+    betas = np.asarray(betas, dtype=np.float64).reshape(-1)
+    if betas.size < 1 or betas[0] != 1.0:
+        raise ValueError("betas[0] must be 1")
+    if not np.all(np.isfinite(betas)) or betas[-1] < 0:
+        raise ValueError("betas must be finite and >= 0")
+    if np.any(np.diff(betas) >= 0):
+        raise ValueError("betas must be strictly decreasing")
+    return np.ascontiguousarray(betas)
+
+
+def _trapezoid(y, x):
+    return np.sum(0.5 * (x[1:] - x[:-1]) * (y[..., 1:] + y[..., :-1]), axis=-1)
+
+
+def thermodynamic_integration_log_evidence(betas, logls):
+    """ptemcee's estimate: ``logls[..., t]`` the mean log-likelihood at ``betas[t]`` (decreasing).  When ``betas[-1] > 0`` a rung
+    at ``beta = 0`` with the hottest rung's mean is appended.  -> ``(logZ, dlogZ)``: the negative trapezoid integral over the
+    ladder, and its distance from the same integral over every other rung."""
+    betas = np.asarray(betas, dtype=np.float64)
+    logls = np.asarray(logls, dtype=np.float64)
+    if betas[-1] != 0:
+        betas = np.concatenate([betas, [0.0]])
+        logls = np.concatenate([logls, logls[..., -1:]], axis=-1)
+    betas2 = np.concatenate([betas[:-1:2], [0.0]])
+    logls2 = np.concatenate([logls[..., :-1:2], logls[..., -1:]], axis=-1)
+    logz = -_trapezoid(logls, betas)
+    logz2 = -_trapezoid(logls2, betas2)
+    return logz, np.abs(logz - logz2)
+
+
+class PTSampler(object):
+    """``nbatch`` independent parallel-tempered ensembles: ``ntemps`` rungs of ``nwalkers`` walkers in ``ndim`` dimensions each.
+
+    ``log_likelihood``: a :class:`~emcee_amd.targets.BatchCallable` (``fn(q)`` gets a ``(nbatch, ntemps, R, ndim)`` view of the
+    proposal block and returns ``(nbatch, ntemps, R)``) or a :class:`~emcee_amd.targets.BatchKernel` (``nbatch * ntemps`` members
+    in (object, rung) order), evaluated untempered.  ``log_prior``: None (flat, improper), ``(lo, hi)`` (a box the kernel
+    evaluates: 0 inside, -inf outside), or a BatchCallable / BatchKernel called on the same block before the likelihood.
+    ``betas``: strictly decreasing from 1 to >= 0, else :func:`default_betas` ``(ntemps, ndim, Tmax)``.  ``moves``: the schedule
+    forms of :class:`~emcee_amd.EnsembleBatch`'s callback path."""
+
+    def __init__(self, ntemps, nwalkers, ndim, log_likelihood, log_prior=None, betas=None, Tmax=None, nbatch=1, moves=None,
+                 seeds=None, swap_every=1, device=None, rng="philox"):
+        if rng != "philox":
+            raise ValueError("PTSampler runs rng='philox' only (the MT19937 stream is made by one host generator a sampler; use "
+                             "EnsembleSampler for rng=%r)" % (rng,))
+        self.ntemps, self.nwalkers, self.ndim, self.nbatch = int(ntemps), int(nwalkers), int(ndim), int(nbatch)
+        if min(self.ntemps, self.nwalkers, self.ndim, self.nbatch) < 1:
+            raise ValueError("ntemps, nwalkers, ndim and nbatch must be positive")
+        if not isinstance(log_likelihood, BatchTarget):
+            kind = "fused device target" if isinstance(log_likelihood, DeviceTarget) else type(log_likelihood).__name__
+            raise TypeError("PTSampler's log_likelihood is a targets.BatchCallable or targets.BatchKernel; a %s is not (wrap the "
+                            "model in BatchCallable)" % kind)
+        self.betas = _check_betas(betas) if betas is not None else default_betas(self.ntemps, self.ndim, Tmax)
+        if len(self.betas) != self.ntemps:
+            raise ValueError("betas holds %d rungs for ntemps = %d" % (len(self.betas), self.ntemps))
+        self._box, self._prior = None, None
+        if log_prior is not None:
+            if isinstance(log_prior, BatchTarget):
+                self._prior = log_prior
+            elif isinstance(log_prior, DeviceTarget) or callable(log_prior):
+                raise TypeError("log_prior is None, (lo, hi) or a targets.BatchCallable / BatchKernel")
+            else:
+                lo, hi = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1)) for v in log_prior)
+                if lo.shape != (self.ndim,) or hi.shape != (self.ndim,):
+                    raise ValueError("a box prior is (lo, hi) of ndim = %d values each" % self.ndim)
+                if not np.all(lo <= hi):
+                    raise ValueError("a box prior needs lo <= hi")
+                self._box = (lo, hi)
+        self.swap_every = int(swap_every)
+        if self.swap_every < 0:
+            raise ValueError("swap_every must be >= 0 (0: never)")
+        if seeds is None:
+            seeds = np.random.randint(0, 2 ** 32, size=self.nbatch, dtype=np.uint64)
+        seeds = [int(s) for s in np.asarray(seeds).reshape(-1)]
+        if len(seeds) != self.nbatch:
+            raise ValueError("seeds must hold nbatch = %d integers; got %d" % (self.nbatch, len(seeds)))
+        self.seeds = seeds
+        self.member_seeds = np.stack([np.random.RandomState(s).randint(0, 2 ** 32, size=self.ntemps, dtype=np.uint64)
+                                      for s in seeds])
+        self._b = EnsembleBatch(self.nbatch * self.ntemps, self.nwalkers, self.ndim, self._wrap(log_likelihood), moves=moves,
+                                seeds=self.member_seeds.reshape(-1), device=device)
+        self.device = self._b.device
+        self._h = None
+        self._prior_keep = None
+
+    def _wrap(self, t):
+        """a BatchCallable's fn sees (nbatch, ntemps, R, ndim); a BatchKernel the handle's members as they are"""
+        if isinstance(t, BatchKernel):
+            return t
+        fn, G, T, D = t.fn, self.nbatch, self.ntemps, self.ndim
+        return BatchCallable(lambda q: fn(q.view(G, T, q.shape[1], D)))
+
+    # ------------------------------------------------------------------ device plumbing
+    def _ck(self, rc):
+        self._b._ck(rc)
+
+    def _handle(self):
+        lib = _lib.load()
+        if self._h is None:
+            h = self._b._handle()
+            ptr = (lambda a: None if a is None else a.ctypes.data_as(C.c_void_p))
+            lo, hi = self._box if self._box is not None else (None, None)
+            self._ck(lib.emx_pt_set_tempering(h, self.ntemps, self.betas, ptr(lo), ptr(hi)))
+            if self._prior is not None:
+                p = self._wrap(self._prior)
+                if isinstance(p, BatchKernel):
+                    fn = p.fn_ptr if isinstance(p.fn_ptr, _lib.BATCH_LOG_PROB_FN) else C.cast(p.fn_ptr, _lib.BATCH_LOG_PROB_FN)
+                    user = p.user_ptr if isinstance(p.user_ptr, C.c_void_p) else C.c_void_p(p.user_ptr)
+                else:
+                    fn, user = _lib.BATCH_LOG_PROB_FN(_trampoline(p.fn, self.device, self._b._cb_box)), None
+                self._prior_keep = fn
+                self._ck(lib.emx_set_batch_prior_callback(h, fn, user))
+            self._h = h
+        self._ck(lib.emx_pt_set_swap_every(self._h, self.swap_every))
+        return self._h
+
+    def _who(self, m):
+        return "object %d, rung %d" % divmod(int(m), self.ntemps)
+
+    def _raise_on_status(self, what):
+        bits = np.zeros(self.nbatch * self.ntemps, dtype=np.uint32)
+        self._ck(_lib.load().emx_batch_status(self._h, bits))
+        bad = np.flatnonzero(bits)
+        if len(bad):
+            m = int(bad[0])
+            text = ("At least one parameter value was infinite or NaN" if bits[m] & 2 else
+                    "The initial log_prob was NaN" if what == "eval" else "Probability function returned NaN")
+            more = "" if len(bad) == 1 else " (and %d more members)" % (len(bad) - 1)
+            raise ValueError("(%s): %s%s" % (self._who(m), text, more))
+
+    def set_tuning(self, key, value):
+        """as :meth:`EnsembleBatch.set_tuning`"""
+        self._b.set_tuning(key, value)
+
+    def launch_info(self):
+        """-> dict(threads, plan_steps, launches): the last launch's shape and the library's launches so far."""
+        return self._b.launch_info()
+
+    def close(self):
+        self._b.close()
+        self._h = None
+
+    # ------------------------------------------------------------------ sampling
+    def _check_state(self, coords):
+        coords = np.asarray(coords)
+        _refuse_extended_precision(coords)
+        want = (self.nbatch, self.ntemps, self.nwalkers, self.ndim)
+        if coords.shape != want:
+            raise ValueError("incompatible input dimensions %s: expected (nbatch, ntemps, nwalkers, ndim) = %s" % (coords.shape, want))
+        coords = np.ascontiguousarray(coords, dtype=np.float64)
+        for g in range(self.nbatch):
+            for t in range(self.ntemps):
+                if not np.all(np.isfinite(coords[g, t])):
+                    raise ValueError("(object %d, rung %d): %s" % (g, t, "At least one parameter value was infinite"
+                                     if np.any(np.isinf(coords[g, t])) else "At least one parameter value was NaN"))
+        return coords
+
+    def run_mcmc(self, initial_state, nsteps, thin_by=1, store=True, skip_initial_state_check=False):
+        """Advance every rung of every object ``nsteps`` stored steps (``nsteps * thin_by`` proposals, each followed by the swap
+        pass on the ``swap_every`` cadence) -> :class:`State` with ``(nbatch, ntemps, nwalkers, ndim)`` coordinates and the
+        tempered ``(nbatch, ntemps, nwalkers)`` log-probs.  ``initial_state``: ``(nbatch, ntemps, nwalkers, ndim)`` or None to
+        continue.  Checks as :meth:`EnsembleBatch.run_mcmc`; errors name ``(object, rung)``."""
+        nsteps, thin_by = int(nsteps), int(thin_by)
+        if thin_by <= 0:
+            raise ValueError("Invalid thinning argument")
+        if nsteps < 0:
+            raise ValueError("nsteps must be >= 0")
+        b = self._b
+        coords = None
+        if initial_state is None:
+            if not b._ran:
+                raise ValueError("Cannot have `initial_state=None` if run_mcmc has never been called.")
+        else:
+            coords = self._check_state(initial_state.coords if isinstance(initial_state, State) else initial_state)
+            if not skip_initial_state_check:
+                for g in range(self.nbatch):
+                    for t in range(self.ntemps):
+                        if not walkers_independent(coords[g, t]):
+                            raise ValueError("(object %d, rung %d): %s" % (g, t, _ILL))
+        for m in b._moves:
+            if self.nwalkers < 2 * self.ndim and hasattr(m, "nsplits") and not getattr(m, "live_dangerously", False):
+                raise RuntimeError("It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions.")
+        lib = _lib.load()
+        h = self._handle()
+        if coords is not None:
+            self._ck(lib.emx_batch_set_state(h, coords.reshape(-1, self.nwalkers, self.ndim), None))
+            self._ck(lib.emx_batch_eval_state_log_prob(h))
+            self._raise_on_status("eval")
+            b._ran = True
+        if store:
+            self._ck(lib.emx_batch_chain_config(h, self.iteration + nsteps))
+        self._ck(lib.emx_batch_run(h, nsteps, thin_by, int(bool(store))))
+        b._sync_moves()
+        step = C.c_uint64(0)
+        self._ck(lib.emx_batch_get_philox(h, np.zeros(self.nbatch * self.ntemps, dtype=np.uint64), C.byref(step)))
+        b._step = step.value
+        self._raise_on_status("run")
+        return self.get_last_sample()
+
+    def _swap(self):
+        """one swap pass on the current state with the last step's draws (emx_pt_swap; tests)"""
+        self._ck(_lib.load().emx_pt_swap(self._handle()))
+
+    def _pt_state(self):
+        """-> (L, P), each (nbatch, ntemps, nwalkers)"""
+        L = np.empty((self.nbatch, self.ntemps, self.nwalkers))
+        P = np.empty_like(L)
+        self._ck(_lib.load().emx_pt_get_state(self._handle(), L, P))
+        return L, P
+
+    def _set_pt_state(self, coords, L, P):
+        """set (coords, L, P) and lp from them (emx_pt_set_state; tests)"""
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+        self._ck(_lib.load().emx_pt_set_state(self._handle(), f(coords), f(L), f(P)))
+
+    # ------------------------------------------------------------------ results
+    @property
+    def iteration(self):
+        """Stored steps of every rung."""
+        return self._b.iteration
+
+    def _read(self, what, discard, thin, flat):
+        out = self._b._read(what, 0, self.nbatch * self.ntemps, discard, thin, flat)
+        return out.reshape((self.nbatch, self.ntemps) + out.shape[1:])
+
+    def get_chain(self, discard=0, thin=1, flat=False):
+        """``(nbatch, ntemps, nsteps, nwalkers, ndim)``; ``flat`` -> ``(nbatch, ntemps, nsteps * nwalkers, ndim)``."""
+        return self._read(0, discard, thin, flat)
+
+    def get_log_prob(self, discard=0, thin=1, flat=False):
+        """the tempered log-probs, ``(nbatch, ntemps, nsteps, nwalkers)``."""
+        return self._read(1, discard, thin, flat)
+
+    def get_log_likelihood(self, discard=0, thin=1, flat=False):
+        """the untempered log-likelihoods, ``(nbatch, ntemps, nsteps, nwalkers)``."""
+        return self._read(2, discard, thin, flat)
+
+    @property
+    def acceptance_fraction(self):
+        """``(nbatch, ntemps, nwalkers)``"""
+        return self._b.acceptance_fraction.reshape(self.nbatch, self.ntemps, self.nwalkers)
+
+    def _swap_counts(self):
+        att = np.zeros((self.nbatch, max(self.ntemps - 1, 0)), dtype=np.uint64)
+        acc = np.zeros_like(att)
+        if self._h is not None and self.ntemps > 1:
+            self._ck(_lib.load().emx_pt_swap_counts(self._h, att, acc))
+        return att, acc
+
+    @property
+    def tswap_acceptance_fraction(self):
+        """``(nbatch, ntemps - 1)``: accepted / attempted swaps of each pair (rung i with i + 1); 0 before any attempt."""
+        att, acc = self._swap_counts()
+        return np.where(att > 0, acc / np.maximum(att, 1).astype(np.float64), 0.0)
+
+    def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False, on_device=True):
+        """``(nbatch, ntemps, ndim)``: :meth:`EnsembleBatch.get_autocorr_time` of every rung (``emx_autocorr_batch`` on the
+        device by default)."""
+        tau = self._b.get_autocorr_time(discard=discard, thin=thin, c=c, tol=tol, quiet=quiet, on_device=on_device)
+        return tau.reshape(self.nbatch, self.ntemps, self.ndim)
+
+    def mean_log_likelihood(self, discard=0):
+        """``(nbatch, ntemps)``: the mean of ``L`` over the stored steps from ``discard`` on and every walker, on the device."""
+        it = self.iteration
+        if it <= 0:
+            raise AttributeError("you must run the sampler with 'store == True' before accessing the results")
+        discard = int(discard)
+        if not 0 <= discard < it:
+            raise ValueError("discard = %d leaves none of the %d stored steps" % (discard, it))
+        out = np.empty(self.nbatch * self.ntemps)
+        self._ck(_lib.load().emx_pt_mean_loglike(self._h, discard, it, 1, out))
+        return out.reshape(self.nbatch, self.ntemps)
+
+    def log_evidence_estimate(self, fburnin=0.1):
+        """-> ``(logZ, dlogZ)``, each ``(nbatch,)``: thermodynamic integration over the ladder of the mean ``L`` of the stored
+        steps after ``int(fburnin * iteration)``.  Needs a normalised prior (a box, or a prior callable)."""
+        if self._box is None and self._prior is None:
+            raise ValueError("the evidence needs a normalised prior: with log_prior=None the prior is flat and improper")
+        means = self.mean_log_likelihood(int(fburnin * self.iteration))
+        return thermodynamic_integration_log_evidence(self.betas, means)
+
+    def get_last_sample(self):
+        """:class:`State` with ``(nbatch, ntemps, nwalkers, ndim)`` coordinates and tempered ``(nbatch, ntemps, nwalkers)``
+        log-probs."""
+        s = self._b.get_last_sample()
+        return State(s.coords.reshape(self.nbatch, self.ntemps, self.nwalkers, self.ndim),
+                     log_prob=s.log_prob.reshape(self.nbatch, self.ntemps, self.nwalkers))

@@ -572,6 +572,45 @@ int emx_batch_status(emx_batch* b, uint32_t* bits);
 /* the last launch's shape and the launches so far */
 int emx_batch_launch_info(emx_batch* b, int32_t* threads, int32_t* plan_steps, int64_t* launches);
 
+/* ---- parallel tempering on a batch handle (emcee_amd.PTSampler; csrc/emx_pt.hip) ----
+ * The members of a batched-callback handle grouped in runs of ntemps: member m = g ntemps + t is rung t (beta_t) of group g, so a
+ * batched callback sees its nbatch = groups x ntemps members in (object, rung) order.  Each rung samples the tempered
+ *   lp = beta L + P    (two IEEE operations, no contraction; lp = P at beta 0, so that 0 x -inf never occurs; lp = -inf where P is)
+ * with L the callback's untempered log-likelihood and P the prior: none (0, improper), the box [box_lo, box_hi] evaluated by the
+ * library (0 inside, bounds included, -inf outside), or the caller's prior callback, called on the same block before L.  Where P
+ * is -inf the row's L is ignored (NaN included) and kept as -inf.  The commit is k_batch_cb's Metropolis rule on the tempered lp;
+ * lp, L and P are kept per walker.  A NaN L where P > -inf (or a NaN lp) raises ST_NAN_LOGP in the member's status.
+ *
+ * Swap pass, after every swap_every-th proposal step (Philox step s with (s + 1) % swap_every == 0; 0: never), ptemcee's order:
+ * pairs i = ntemps - 1 ... 1, walker k of rung i against walker pi_i(k) of rung i - 1, accepted when
+ *   (beta_{i-1} - beta_i) (L_i[k] - L_{i-1}[pi_i(k)]) > log u_{i,k}          (IEEE: -inf - -inf is NaN, and NaN is rejected)
+ * An accepted swap exchanges x, L and P and recomputes lp at both destinations; each pair sees the result of the one before.
+ * Draws (emx_host_pt_swap_draws is their host twin): keyed by the group's rung-0 Philox seed and the step just taken, pi_i is
+ * a keyed bijection of [0, nwalkers) (the split permutation's construction under the tag 'SWPM', counter 2 (i - 1)), u_{i,k} is u53
+ * of the Philox words (step lo, step hi, 'SWAP', (i - 1) nwalkers + k), log u the plan logarithm (host and device bits agree).
+ * A step with a swap pass is S_max + 2 launches (the phases, a commit-only launch, k_pt_swap), else S_max; S_max calls of the
+ * likelihood a step (and S_max of a prior callback).  Stored rows hold the state after the step's swap pass (ptemcee's rule):
+ * coordinates, tempered lp (what 1) and L (emx_batch_chain_read what 2).  Accept counts stay per member; swap attempts and
+ * accepts are counted per (group, pair i - 1). */
+/* ntemps must divide the batch; betas (ntemps) non-increasing (PTSampler asks strictly decreasing), betas[0] == 1, betas[ntemps-1] >= 0; box_lo / box_hi (ndim)
+ * or both NULL.  Before anything is stored. */
+int emx_pt_set_tempering(emx_batch* b, int32_t ntemps, const double* betas, const double* box_lo, const double* box_hi);
+/* the caller's batched log-prior (the emx_batch_log_prob_fn contract), in place of a box; NULL removes it */
+int emx_set_batch_prior_callback(emx_batch* b, emx_batch_log_prob_fn fn, void* user);
+int emx_pt_set_swap_every(emx_batch* b, int64_t n);                 /* default 1 */
+/* one swap pass on the current state with the draws of the last step taken (step - 1); writes no chain row */
+int emx_pt_swap(emx_batch* b);
+/* attempts / accepts (groups, ntemps - 1) */
+int emx_pt_swap_counts(emx_batch* b, uint64_t* attempts, uint64_t* accepts);
+/* out (B): the mean of each member's L chain over rows start, start + stride, ... < stop and every walker, on the device */
+int emx_pt_mean_loglike(emx_batch* b, int64_t start, int64_t stop, int64_t stride, double* out);
+/* the tempered state: coords (B, nwalkers, ndim), L and P (B, nwalkers); set computes lp with the formula above */
+int emx_pt_set_state(emx_batch* b, const double* coords, const double* loglike, const double* logprior);
+int emx_pt_get_state(emx_batch* b, double* loglike, double* logprior);
+/* the swap draws of every pair after Philox step `step` under `seed`: perm_out / logu_out (ntemps - 1, nwalkers), row i - 1 for
+ * pair i: pi_i(k) and log u_{i,k}.  0, or -1 for bad arguments. */
+int emx_host_pt_swap_draws(uint64_t seed, uint64_t step, int64_t nwalkers, int32_t ntemps, int32_t* perm_out, double* logu_out);
+
 #ifdef __cplusplus
 }
 #endif

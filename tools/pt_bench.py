@@ -1,0 +1,91 @@
+"""PTSampler throughput against EnsembleBatch's callback path at the same members and the same callable.
+
+    python tools/pt_bench.py [--nbatch 64 --ntemps 16 --nwalkers 32 --ndim 5 --steps 200 --reps 3] [--json out.json]
+
+Shape: nbatch objects x ntemps rungs x nwalkers x ndim with a torch two-component Gaussian mixture likelihood.  Reports member-steps
+per second (members = nbatch * ntemps) of PTSampler with swap_every = 1 and 0, and of EnsembleBatch on the tempered callable
+(beta_t L + box prior), best of `reps` timed runs of `steps` steps without storing."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from emcee_amd import EnsembleBatch, PTSampler  # noqa: E402
+from emcee_amd.targets import BatchCallable  # noqa: E402
+
+
+def mixture(D):
+    s2 = 0.3 ** 2
+    lw1, lw2, norm = np.log(0.25), np.log(0.75), -0.5 * D * np.log(2 * np.pi * s2)
+
+    def fn(q):
+        d1 = ((q + 4.0) ** 2).sum(-1)
+        d2 = ((q - 4.0) ** 2).sum(-1)
+        return torch.logaddexp(lw1 - 0.5 * d1 / s2, lw2 - 0.5 * d2 / s2) + norm
+    return fn
+
+
+def timed(run, steps, reps):
+    best = 0.0
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run(steps)
+        torch.cuda.synchronize()
+        best = max(best, steps / (time.perf_counter() - t0))
+    return best
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nbatch", type=int, default=64)
+    ap.add_argument("--ntemps", type=int, default=16)
+    ap.add_argument("--nwalkers", type=int, default=32)
+    ap.add_argument("--ndim", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    G, T, N, D = a.nbatch, a.ntemps, a.nwalkers, a.ndim
+    fn = mixture(D)
+    box = (-10 * np.ones(D), 10 * np.ones(D))
+    p0 = -4.0 + 0.3 * np.random.RandomState(0).randn(G, T, N, D)
+    out = dict(nbatch=G, ntemps=T, nwalkers=N, ndim=D, steps=a.steps, members=G * T)
+    for every in (1, 0):
+        pt = PTSampler(T, N, D, BatchCallable(fn), log_prior=box, Tmax=1e3, nbatch=G, seeds=list(range(G)), swap_every=every)
+        pt.run_mcmc(p0, 10, store=False)
+        out["pt_swap_every_%d_member_steps_per_s" % every] = G * T * timed(lambda n: pt.run_mcmc(None, n, store=False), a.steps, a.reps)
+        if every == 1:
+            out["pt_launches_per_step"] = None
+            n0 = pt.launch_info()["launches"]
+            pt.run_mcmc(None, 10, store=False)
+            out["pt_launches_per_step"] = (pt.launch_info()["launches"] - n0) / 10.0
+            out["tswap_acceptance_mean"] = float(pt.tswap_acceptance_fraction.mean())
+        pt.close()
+    betas = PTSampler(T, N, D, BatchCallable(fn), Tmax=1e3).betas
+    bt = torch.as_tensor(np.tile(betas, G), device="cuda")[:, None]
+    lo, hi = (torch.as_tensor(v, device="cuda") for v in box)
+
+    def tempered(q):
+        inside = ((q >= lo) & (q <= hi)).all(-1)
+        return bt * fn(q) + torch.where(inside, 0.0, -float("inf")).to(torch.float64)
+    eb = EnsembleBatch(G * T, N, D, BatchCallable(tempered), seeds=list(range(G * T)))
+    eb.run_mcmc(p0.reshape(G * T, N, D), 10, store=False)
+    out["batch_member_steps_per_s"] = G * T * timed(lambda n: eb.run_mcmc(None, n, store=False), a.steps, a.reps)
+    out["pt_over_batch"] = out["pt_swap_every_1_member_steps_per_s"] / out["batch_member_steps_per_s"]
+    line = json.dumps(out)
+    print(line)
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
