@@ -179,6 +179,10 @@ SIGNATURES = {
     "emx_pt_set_state": (C.c_int, [_P, _dp, _dp, _dp]),
     "emx_pt_get_state": (C.c_int, [_P, _dp, _dp]),
     "emx_host_pt_swap_draws": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, _ip, _dp]),
+    "emx_pt_set_adaptation": (C.c_int, [_P, C.c_int32, C.c_double, C.c_double]),
+    "emx_pt_get_ladder": (C.c_int, [_P, _P, C.POINTER(C.c_int64)]),
+    "emx_pt_set_ladder": (C.c_int, [_P, _dp, C.POINTER(C.c_int64)]),
+    "emx_host_pt_adapt_ladder": (C.c_int, [_dp, _i64p, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_int64, _dp]),
     "emx_autocorr_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double, _dp, _ip, C.POINTER(C.c_int64)]),
 }
 

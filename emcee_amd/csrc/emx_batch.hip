@@ -79,6 +79,11 @@ struct emx_batch {
     double* cb_pr = nullptr;                   // (B, R) the caller's prior of the block
     int64_t swap_every = 1;
     unsigned long long *sw_att = nullptr, *sw_acc = nullptr;     // (B / pt_T, pt_T - 1)
+    double* chain_beta = nullptr;              // (B, cap): the beta of every stored row of every member
+    // the adaptive ladder (emx_pt_set_adaptation): on / off, ptemcee's lag and time, the updates made so far (t)
+    int32_t pt_adapt = 0;
+    double pt_lag = 10000.0, pt_time = 100.0;
+    int64_t pt_updates = 0;
 };
 
 namespace {
@@ -308,6 +313,18 @@ int call_prior(emx_batch* b, const double* coords, int64_t rows, double* out) {
     return 0;
 }
 
+// a ladder row of group g (betas[0 ... T - 1]) as emx_pt_set_tempering checks it, plus betas[0 ... T - 2] > 0 when adapting
+int check_ladder_row(emx_batch* b, const double* betas, int32_t T, int64_t g, bool adapting) {
+    BNEED(b, betas[0] == 1.0, "group %lld: betas[0] must be 1", (long long)g);
+    for (int t = 0; t < T; ++t) {
+        BNEED(b, betas[t] >= 0.0 && betas[t] <= 1.0, "group %lld: betas must lie in [0, 1]; betas[%d] = %g", (long long)g, t, betas[t]);
+        if (t > 0) BNEED(b, betas[t] <= betas[t - 1], "group %lld: betas must not increase (betas[%d] = %g, betas[%d] = %g)",
+                         (long long)g, t - 1, betas[t - 1], t, betas[t]);
+        if (adapting && t < T - 1) BNEED(b, betas[t] > 0.0, "group %lld: an adaptive ladder needs betas[%d] > 0", (long long)g, t);
+    }
+    return 0;
+}
+
 // one k_pt_swap launch after Philox step `step`: the swap pass (swap) and / or the stored rows of chain row `row` (-1: none)
 int swap_pass(emx_batch* b, uint64_t step, int64_t row, bool swap) {
     PtSwapArgs s{};
@@ -329,8 +346,14 @@ int swap_pass(emx_batch* b, uint64_t step, int64_t row, bool swap) {
     s.N = (int32_t)b->N;
     s.D = b->D;
     s.step = step;
+    s.chain_beta = b->chain_beta;
+    s.adapt = swap && b->pt_adapt ? 1 : 0;
+    s.lag = b->pt_lag;
+    s.time = b->pt_time;
+    s.adapt_t = (long long)b->pt_updates;
     BHIP(b, pt_swap_launch(b->B / b->pt_T, b->stream, s));
     ++b->launches;
+    if (s.adapt) ++b->pt_updates;
     return 0;
 }
 
@@ -427,6 +450,7 @@ int run_callback(emx_batch* b, int64_t total, int32_t thin_by, int32_t store) {
         a.L = b->pt_L;
         a.P = b->pt_P;
         a.chain_L = b->chain_L;
+        a.chain_beta = b->chain_beta;
     }
     const Shape sh = pick_shape(b->D, b->D);
     // one phase's rows in one pass (R G lanes); no bit depends on the shape
@@ -585,7 +609,7 @@ int emx_batch_destroy(emx_batch* b) {
                     (void*)b->tscales, (void*)b->chain, (void*)b->chain_lp, (void*)b->fac_dev, (void*)b->col_dev, (void*)b->cb_q,
                     (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi, (void*)b->cb_nrows, (void*)b->pt_beta,
                     (void*)b->pt_lo, (void*)b->pt_hi, (void*)b->pt_L, (void*)b->pt_P, (void*)b->chain_L, (void*)b->cb_pr, (void*)b->sw_att,
-                    (void*)b->sw_acc})
+                    (void*)b->sw_acc, (void*)b->chain_beta})
         if (p) hipFree(p);
     for (double* p : b->mscale)
         if (p) hipFree(p);
@@ -768,20 +792,25 @@ int emx_batch_chain_config(emx_batch* b, int64_t capacity) {
         hipFree(nc);
         return fail(b, -2, "chain allocation failed");
     }
-    double* nL = nullptr;
-    if (b->pt_T > 0 && hipMalloc((void**)&nL, (size_t)b->B * capacity * N * 8) != hipSuccess) {
+    double *nL = nullptr, *nb = nullptr;
+    if (b->pt_T > 0 && (hipMalloc((void**)&nL, (size_t)b->B * capacity * N * 8) != hipSuccess ||
+                        hipMalloc((void**)&nb, (size_t)b->B * capacity * 8) != hipSuccess)) {
         hipFree(nc);
         hipFree(nl);
+        if (nL) hipFree(nL);
         return fail(b, -2, "chain allocation failed");
     }
     if (b->stored > 0) {      // what is stored stays: member by member, into the longer rows
         BHIP(b, hipMemcpy2DAsync(nc, capacity * ND * 8, b->chain, b->cap * ND * 8, b->stored * ND * 8, b->B, hipMemcpyDeviceToDevice, b->stream));
         BHIP(b, hipMemcpy2DAsync(nl, capacity * N * 8, b->chain_lp, b->cap * N * 8, b->stored * N * 8, b->B, hipMemcpyDeviceToDevice, b->stream));
         if (nL) BHIP(b, hipMemcpy2DAsync(nL, capacity * N * 8, b->chain_L, b->cap * N * 8, b->stored * N * 8, b->B, hipMemcpyDeviceToDevice, b->stream));
+        if (nb) BHIP(b, hipMemcpy2DAsync(nb, capacity * 8, b->chain_beta, b->cap * 8, b->stored * 8, b->B, hipMemcpyDeviceToDevice, b->stream));
     }
     BHIP(b, hipStreamSynchronize(b->stream));
     if (b->chain_L) hipFree(b->chain_L);
     b->chain_L = nL;
+    if (b->chain_beta) hipFree(b->chain_beta);
+    b->chain_beta = nb;
     if (b->chain) hipFree(b->chain);
     if (b->chain_lp) hipFree(b->chain_lp);
     b->chain = nc;
@@ -820,7 +849,8 @@ int emx_batch_iteration(emx_batch* b, int64_t* stored, int64_t* proposals) {
 
 int emx_batch_chain_read(emx_batch* b, int32_t what, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop,
                          int64_t stride, double* out) {
-    BNEED(b, what == 0 || what == 1 || (what == 2 && b->chain_L), "what: 0 coordinates, 1 log-probs, 2 log-likelihoods (tempered)");
+    BNEED(b, what == 0 || what == 1 || ((what == 2 || what == 3) && b->chain_L),
+          "what: 0 coordinates, 1 log-probs, 2 log-likelihoods, 3 betas (the last two tempered)");
     BNEED(b, 0 <= member_lo && member_lo <= member_hi && member_hi <= b->B, "members [%d, %d) outside [0, %d)", member_lo, member_hi, b->B);
     BNEED(b, stride >= 1 && 0 <= start && start <= stop && stop <= b->stored, "rows [%lld, %lld) outside the %lld stored",
           (long long)start, (long long)stop, (long long)b->stored);
@@ -828,8 +858,8 @@ int emx_batch_chain_read(emx_batch* b, int32_t what, int32_t member_lo, int32_t 
     const int64_t nsel = (stop - start + stride - 1) / stride;
     if (nsel == 0 || member_hi == member_lo) return 0;
     BHIP(b, hipSetDevice(b->device));
-    const size_t row = (size_t)b->N * (what == 0 ? b->D : 1);
-    const double* base = what == 0 ? b->chain : what == 1 ? b->chain_lp : b->chain_L;
+    const size_t row = what == 3 ? 1 : (size_t)b->N * (what == 0 ? b->D : 1);
+    const double* base = what == 0 ? b->chain : what == 1 ? b->chain_lp : what == 2 ? b->chain_L : b->chain_beta;
     for (int32_t m = member_lo; m < member_hi; ++m)
         BHIP(b, hipMemcpy2DAsync(out + (size_t)(m - member_lo) * nsel * row, row * 8, base + ((size_t)m * b->cap + start) * row, stride * row * 8,
                                  row * 8, nsel, hipMemcpyDeviceToHost, b->stream));
@@ -869,6 +899,7 @@ int emx_batch_launch_info(emx_batch* b, int32_t* threads, int32_t* plan_steps, i
 int emx_pt_set_tempering(emx_batch* b, int32_t ntemps, const double* betas, const double* box_lo, const double* box_hi) {
     BNEED(b, b->target == EMX_TARGET_DEVICE_CALLBACK, "tempering needs a batched callback target (emx_set_batch_target_callback)");
     BNEED(b, ntemps >= 1 && b->B % ntemps == 0, "ntemps = %d does not divide the batch of %d members", ntemps, b->B);
+    BNEED(b, !b->pt_adapt || ntemps <= PT_ADAPT_MAX_T, "an adaptive ladder has at most %d rungs; ntemps = %d", PT_ADAPT_MAX_T, ntemps);
     BNEED(b, betas != nullptr, "no betas");
     BNEED(b, betas[0] == 1.0, "betas[0] must be 1");
     for (int t = 0; t < ntemps; ++t) {
@@ -880,7 +911,7 @@ int emx_pt_set_tempering(emx_batch* b, int32_t ntemps, const double* betas, cons
     BNEED(b, b->stored == 0, "tempering is set before anything is stored");
     BHIP(b, hipSetDevice(b->device));
     BHIP(b, hipStreamSynchronize(b->stream));
-    for (double** p : {&b->pt_beta, &b->pt_lo, &b->pt_hi, &b->pt_L, &b->pt_P, &b->chain_L})
+    for (double** p : {&b->pt_beta, &b->pt_lo, &b->pt_hi, &b->pt_L, &b->pt_P, &b->chain_L, &b->chain_beta})
         if (*p) {
             hipFree(*p);
             *p = nullptr;
@@ -912,8 +943,10 @@ int emx_pt_set_tempering(emx_batch* b, int32_t ntemps, const double* betas, cons
     BHIP(b, hipMemset(b->sw_att, 0, npairs * 8));
     BHIP(b, hipMemset(b->sw_acc, 0, npairs * 8));
     if (b->cap > 0) BHIP(b, hipMalloc((void**)&b->chain_L, (size_t)b->B * b->cap * b->N * 8));
+    if (b->cap > 0) BHIP(b, hipMalloc((void**)&b->chain_beta, (size_t)b->B * b->cap * 8));
     b->pt_betas.assign(betas, betas + ntemps);
     b->pt_T = ntemps;
+    b->pt_updates = 0;
     return 0;
 }
 
@@ -936,7 +969,10 @@ int emx_pt_swap(emx_batch* b) {
     BNEED(b, b->pt_T > 0, "no tempering set (emx_pt_set_tempering)");
     BNEED(b, b->step > 0, "no step taken: the swap pass uses the draws of the last step");
     BHIP(b, hipSetDevice(b->device));
-    if (b->pt_T < 2) return 0;
+    if (b->pt_T < 2) {
+        if (b->pt_adapt) ++b->pt_updates;      // no pair, nothing moves; the update still counts
+        return 0;
+    }
     return swap_pass(b, b->step - 1, -1, true);
 }
 
@@ -972,13 +1008,60 @@ int emx_pt_set_state(emx_batch* b, const double* coords, const double* loglike, 
     BNEED(b, b->pt_T > 0, "no tempering set (emx_pt_set_tempering)");
     BNEED(b, coords && loglike && logprior, "coords, loglike and logprior are all needed");
     const size_t BN = (size_t)b->B * b->N;
-    std::vector<double> lp(BN);
-    for (size_t r = 0; r < BN; ++r) lp[r] = pt_tempered(b->pt_betas[(r / b->N) % b->pt_T], loglike[r], logprior[r]);
+    std::vector<double> mb((size_t)b->B), lp(BN);       // each member's current beta (the ladder may have adapted)
+    BHIP(b, hipMemcpyAsync(mb.data(), b->pt_beta, mb.size() * 8, hipMemcpyDeviceToHost, b->stream));
+    BHIP(b, hipStreamSynchronize(b->stream));
+    for (size_t r = 0; r < BN; ++r) lp[r] = pt_tempered(mb[r / b->N], loglike[r], logprior[r]);
     BHIP(b, hipMemcpyAsync(b->X, coords, BN * b->D * 8, hipMemcpyHostToDevice, b->stream));
     BHIP(b, hipMemcpyAsync(b->pt_L, loglike, BN * 8, hipMemcpyHostToDevice, b->stream));
     BHIP(b, hipMemcpyAsync(b->pt_P, logprior, BN * 8, hipMemcpyHostToDevice, b->stream));
     BHIP(b, hipMemcpyAsync(b->lp, lp.data(), BN * 8, hipMemcpyHostToDevice, b->stream));
     BHIP(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int emx_pt_set_adaptation(emx_batch* b, int32_t on, double lag, double time) {
+    BNEED(b, b->pt_T > 0, "no tempering set (emx_pt_set_tempering)");
+    BNEED(b, lag > 0.0 && lag < __builtin_inf(), "adaptation_lag must be finite and > 0; got %g", lag);
+    BNEED(b, time > 0.0 && time < __builtin_inf(), "adaptation_time must be finite and > 0; got %g", time);
+    if (on) {
+        BNEED(b, b->pt_T <= PT_ADAPT_MAX_T, "an adaptive ladder has at most %d rungs; ntemps = %d", PT_ADAPT_MAX_T, b->pt_T);
+        if (!b->pt_adapt) {       // the current ladders must suit the update
+            std::vector<double> mb((size_t)b->B);
+            BHIP(b, hipMemcpyAsync(mb.data(), b->pt_beta, mb.size() * 8, hipMemcpyDeviceToHost, b->stream));
+            BHIP(b, hipStreamSynchronize(b->stream));
+            for (int64_t g = 0; g < b->B / b->pt_T; ++g)
+                if (int rc = check_ladder_row(b, mb.data() + g * b->pt_T, b->pt_T, g, true)) return rc;
+        }
+    }
+    b->pt_adapt = on ? 1 : 0;
+    b->pt_lag = lag;
+    b->pt_time = time;
+    return 0;
+}
+
+int emx_pt_get_ladder(emx_batch* b, double* betas, int64_t* updates) {
+    BNEED(b, b->pt_T > 0, "no tempering set (emx_pt_set_tempering)");
+    if (betas) {
+        BHIP(b, hipMemcpyAsync(betas, b->pt_beta, (size_t)b->B * 8, hipMemcpyDeviceToHost, b->stream));
+        BHIP(b, hipStreamSynchronize(b->stream));
+    }
+    if (updates) *updates = b->pt_updates;
+    return 0;
+}
+
+int emx_pt_set_ladder(emx_batch* b, const double* betas, const int64_t* updates) {
+    BNEED(b, b->pt_T > 0, "no tempering set (emx_pt_set_tempering)");
+    BNEED(b, betas != nullptr, "no betas");
+    BNEED(b, !updates || *updates >= 0, "updates must be >= 0");
+    for (int64_t g = 0; g < b->B / b->pt_T; ++g)
+        if (int rc = check_ladder_row(b, betas + g * b->pt_T, b->pt_T, g, b->pt_adapt != 0)) return rc;
+    BHIP(b, hipSetDevice(b->device));
+    BHIP(b, hipMemcpyAsync(b->pt_beta, betas, (size_t)b->B * 8, hipMemcpyHostToDevice, b->stream));
+    BHIP(b, pt_relp_launch(b->lp, b->pt_L, b->pt_P, b->pt_beta, b->B, (int32_t)b->N, b->stream));
+    ++b->launches;
+    BHIP(b, hipStreamSynchronize(b->stream));
+    if (updates) b->pt_updates = *updates;
     return 0;
 }
 

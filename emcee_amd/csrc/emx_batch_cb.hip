@@ -68,6 +68,7 @@ __global__ __launch_bounds__(CB_MAX_THREADS) void k_batch_cb(const BatchCbArgs A
         double* cr = rows ? A.chain + ((size_t)b * A.cap + A.chain_row) * (size_t)N * D : nullptr;
         double* cl = rows ? A.chain_lp + ((size_t)b * A.cap + A.chain_row) * (size_t)N : nullptr;
         double* cL = rows ? A.chain_L + ((size_t)b * A.cap + A.chain_row) * (size_t)N : nullptr;
+        if (rows && tid == 0) A.chain_beta[(size_t)b * A.cap + A.chain_row] = beta;      // the member's beta row
         for (int base = wv * WPW; base < n; base += nwave * WPW) {
             const int t = base + sub;
             if (t < n) {                                                   // group-uniform

@@ -44,7 +44,8 @@ struct BatchCbArgs {
     unsigned long long step;
     // parallel tempering (emx_pt_set_tempering; nullptr beta: untempered, the kernel above bit for bit): lpq holds the untempered
     // log-likelihood L, the prior P is the box [box_lo, box_hi] or the caller's prior of the block (lpr), and the decision is
-    // small_update's on the tempered pt_tempered(beta[b], L, P); L and P are kept per walker, chain_L holds the L rows
+    // small_update's on the tempered pt_tempered(beta[b], L, P); L and P are kept per walker, chain_L holds the L rows and
+    // chain_beta the beta of each stored row
     const double* beta;        // (B)
     const double* box_lo;      // (D) or nullptr
     const double* box_hi;
@@ -53,6 +54,7 @@ struct BatchCbArgs {
     double* P;                 // (B, N)
     double* chain_L;           // (B, cap, N)
     int32_t rows_in_commit;    // the commit writes the stored step's rows (0: the swap pass writes them after the step)
+    double* chain_beta;        // (B, cap): the stored step's beta of each member, written with its rows
 };
 
 // threads of a k_batch_cb workgroup: at most 512, for 256 VGPRs a lane (with 1 024 threads' 128, 12 to 46 of them spilled)

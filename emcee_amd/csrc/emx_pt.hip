@@ -6,10 +6,15 @@
 //   same row).  Accepted when (beta_{i-1} - beta_i) (L_i[k] - L_{i-1}[pi_i(k)]) > log u_{i,k} (IEEE: NaN is rejected); then x, L
 //   and P change places and lp is recomputed at both destinations.  Each pair ends by waiting for its stores and meeting the
 //   workgroup barrier (k_batch_cb's hand-off from commit to propose), so that pair i - 1 sees what pair i left.  On a stored step
-//   the pass then writes every rung's chain, lp and L rows: the stored state is the state after the swap pass.
+//   the pass then writes every rung's chain, lp, L and beta rows: the stored state is the state after the swap pass.
+//   With adaptation on (PtSwapArgs::adapt), the pair loop also keeps each pair's accepts in LDS; after it one lane computes the
+//   group's new ladder (pt_adapt_ladder, rung order) and writes beta[1 ... T - 2], then, after vmcnt(0) and the barrier, the
+//   lanes recompute lp of every walker of the moved rungs, and after a second wait and barrier the stored rows are written.
+//   With adaptation off the pass is the loop above alone.
 // k_pt_init: the tempered initial state (box prior, -inf likelihood outside the prior, tempered lp, NaN check).
 // k_pt_mean_loglike: one workgroup a member, the mean of its L chain rows over the walkers (thermodynamic integration's input).
-// emx_host_pt_swap_draws: the host twin of the swap draws, for tests that rebuild every decision.
+// k_pt_relp: lp from L, P and each member's beta (emx_pt_set_ladder).
+// emx_host_pt_swap_draws / emx_host_pt_adapt_ladder: the host twins of the swap draws and of the ladder update.
 #include <hip/hip_runtime.h>
 
 #include "../../include/emx.h"
@@ -24,6 +29,8 @@ constexpr int PT_THREADS = 256;
 
 __global__ __launch_bounds__(PT_THREADS) void k_pt_swap(const PtSwapArgs A) {
     __shared__ unsigned int nacc;
+    __shared__ unsigned int pacc[PT_ADAPT_MAX_T];     // adaptation: each pair's accepts of this pass, pair i at i - 1
+    __shared__ double lad[PT_ADAPT_MAX_T];            // adaptation: the group's new ladder
     const int T = A.T, N = A.N, D = A.D, tid = threadIdx.x, nt = blockDim.x;
     const size_t g = blockIdx.x, m0 = g * (size_t)T;
     if (A.swap) {
@@ -67,10 +74,28 @@ __global__ __launch_bounds__(PT_THREADS) void k_pt_swap(const PtSwapArgs A) {
                 const size_t c = g * (size_t)(T - 1) + (i - 1);
                 A.attempts[c] += (unsigned long long)N;
                 A.accepts[c] += (unsigned long long)nacc;
+                if (A.adapt) pacc[i - 1] = nacc;
             }
+        }
+        if (A.adapt && T > 2) {
+            // the ladder update in rung order in one lane; then lp of every walker of the moved rungs from the new betas
+            if (tid == 0) {
+                for (int t = 0; t < T; ++t) lad[t] = A.beta[m0 + t];
+                pt_adapt_ladder(lad, pacc, T, (long long)N, A.lag, A.time, A.adapt_t, lad);
+                for (int t = 1; t < T - 1; ++t) A.beta[m0 + t] = lad[t];
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            for (int e = tid; e < (T - 2) * N; e += nt) {
+                const size_t r = (m0 + 1) * N + e;
+                A.lp[r] = pt_tempered(lad[1 + e / N], A.L[r], A.P[r]);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the new lp is stored before the rows below read it
+            __syncthreads();
         }
     }
     if (A.chain_row < 0) return;
+    for (int t = tid; t < T; t += nt) A.chain_beta[(m0 + t) * (size_t)A.cap + A.chain_row] = A.beta[m0 + t];
     // the stored step's rows of every rung of the group: coordinates, tempered lp, L
     for (int t = 0; t < T; ++t) {
         const size_t m = m0 + t;
@@ -83,6 +108,12 @@ __global__ __launch_bounds__(PT_THREADS) void k_pt_swap(const PtSwapArgs A) {
             A.chain_L[crow * N + e] = A.L[m * N + e];
         }
     }
+}
+
+__global__ __launch_bounds__(PT_THREADS) void k_pt_relp(double* lp, const double* L, const double* P, const double* beta, int N) {
+    const size_t m = blockIdx.x;
+    const double bm = beta[m];
+    for (int w = threadIdx.x; w < N; w += blockDim.x) lp[m * N + w] = pt_tempered(bm, L[m * N + w], P[m * N + w]);
 }
 
 __global__ __launch_bounds__(64) void k_pt_init(const double* X, double* lp, double* L, double* P, const double* beta,
@@ -146,6 +177,11 @@ hipError_t pt_init_launch(const double* X, double* lp, double* L, double* P, con
     return hipGetLastError();
 }
 
+hipError_t pt_relp_launch(double* lp, const double* L, const double* P, const double* beta, int32_t B, int32_t N, hipStream_t st) {
+    hipLaunchKernelGGL(k_pt_relp, dim3(B), dim3(PT_THREADS), 0, st, lp, L, P, beta, N);
+    return hipGetLastError();
+}
+
 hipError_t pt_mean_launch(const double* chain_L, long long cap, int32_t B, int32_t N, long long start, long long stop,
                           long long stride, double* out, hipStream_t st) {
     hipLaunchKernelGGL(k_pt_mean_loglike, dim3(B), dim3(PT_THREADS), 0, st, chain_L, cap, N, start, stop, stride, out);
@@ -168,6 +204,15 @@ int emx_host_pt_swap_draws(uint64_t seed, uint64_t step, int64_t nwalkers, int32
             logu_out[o] = emx::plan_log_tab(emx::pt_swap_uniform(seed, step, i, (uint32_t)k, (uint32_t)nwalkers), emx::h_plan_log_rows);
         }
     }
+    return 0;
+}
+
+int emx_host_pt_adapt_ladder(const double* betas, const int64_t* accepts, int32_t ntemps, int64_t nwalkers, double lag,
+                             double time, int64_t t, double* out) {
+    if (ntemps < 1 || nwalkers < 1 || !betas || !out || (ntemps > 1 && !accepts) || t < 0) return -1;
+    if (!(lag > 0.0) || !(time > 0.0) || lag == __builtin_inf() || time == __builtin_inf()) return -1;
+    for (int i = 0; i < ntemps; ++i) out[i] = betas[i];
+    emx::pt_adapt_ladder(betas, accepts, ntemps, (long long)nwalkers, lag, time, (long long)t, out);
     return 0;
 }
 

@@ -24,9 +24,20 @@ Seeds.  ``seeds`` holds ``nbatch`` integers.  Member (g, t) draws as the :class:
 ``s[g, t] = np.random.RandomState(seeds[g]).randint(0, 2**32, size=ntemps, dtype=np.uint64)[t]``, i.e. its Philox seed is
 ``philox_seed(np.random.RandomState(s[g, t]))``.
 
+Adaptive ladder (``adaptive=True``; ptemcee's rule, Vousden, Farr & Mandel 2016).  Each swap pass ends with an update of every
+object's own ladder from that pass's accepted swaps, on the device (``emx_pt_set_adaptation`` in ``include/emx.h``): with
+``r[j]`` the acceptance of pair ``j + 1`` in the pass and ``t`` the updates made before (:attr:`adaptation_updates`),
+``kappa = (lag / (t + lag)) / time``, the temperature gaps ``1/b[j+1] - 1/b[j]`` are scaled by ``exp(kappa (r[j] - r[j+1]))`` and
+the ladder rebuilt from rung 0; rungs 0 and ``ntemps - 1`` stay.  Pairs that accept more than their hotter neighbour widen,
+so acceptance evens out along the ladder.  Two departures from ptemcee: the new betas are stored as computed (ptemcee adds the
+difference), and the moved rungs' ``lp`` is recomputed as ``beta' L + P`` (ptemcee adds ``L dbeta``), which keeps the
+two-roundings rule and the ``P = -inf`` / ``beta = 0`` cases.  :attr:`ladder` is the current ladder, :meth:`get_betas` the
+ladder of every stored step; :attr:`betas` stays the initial one.  At most 256 rungs while adapting.
+
 Evidence (:meth:`log_evidence_estimate`).  ``mean_logL[g, t]``, the mean of ``L`` over the stored steps after
-``int(fburnin * iteration)`` and over all walkers, is computed on the device; thermodynamic integration over the ladder
-(:func:`thermodynamic_integration_log_evidence`) gives ``log Z`` and ptemcee's error estimate.
+``int(fburnin * iteration)`` and over all walkers, is computed on the device; thermodynamic integration over each object's
+ladder (:func:`thermodynamic_integration_log_evidence`) gives ``log Z`` and ptemcee's error estimate.  The ladder must be
+constant over those steps: freeze adaptation (``adaptive = False``) and discard the adaptive phase first.
 """
 import ctypes as C
 
@@ -39,6 +50,8 @@ from .state import State
 from .targets import BatchCallable, BatchKernel, BatchTarget, DeviceTarget
 
 __all__ = ["PTSampler", "default_betas", "thermodynamic_integration_log_evidence"]
+
+_ADAPT_MAX_T = 256          # k_pt_swap keeps an adapting ladder in LDS (PT_ADAPT_MAX_T)
 
 _ILL = ("Initial state has a large condition number. Make sure that your walkers are linearly independent for the best "
         "performance")
@@ -76,23 +89,41 @@ def _check_betas(betas):
 
 
 def _trapezoid(y, x):
-    return np.sum(0.5 * (x[1:] - x[:-1]) * (y[..., 1:] + y[..., :-1]), axis=-1)
+    return np.sum(0.5 * (x[..., 1:] - x[..., :-1]) * (y[..., 1:] + y[..., :-1]), axis=-1)
 
 
-def thermodynamic_integration_log_evidence(betas, logls):
-    """ptemcee's estimate: ``logls[..., t]`` the mean log-likelihood at ``betas[t]`` (decreasing).  When ``betas[-1] > 0`` a rung
-    at ``beta = 0`` with the hottest rung's mean is appended.  -> ``(logZ, dlogZ)``: the negative trapezoid integral over the
-    ladder, and its distance from the same integral over every other rung."""
-    betas = np.asarray(betas, dtype=np.float64)
-    logls = np.asarray(logls, dtype=np.float64)
-    if betas[-1] != 0:
-        betas = np.concatenate([betas, [0.0]])
+def _ti(betas, logls):
+    """the rule on ladders (..., T) that all end at beta 0 or all end above it"""
+    zero = np.zeros(betas.shape[:-1] + (1,))
+    if betas[..., -1].flat[0] != 0:
+        betas = np.concatenate([betas, zero], axis=-1)
         logls = np.concatenate([logls, logls[..., -1:]], axis=-1)
-    betas2 = np.concatenate([betas[:-1:2], [0.0]])
+    betas2 = np.concatenate([betas[..., :-1:2], zero], axis=-1)
     logls2 = np.concatenate([logls[..., :-1:2], logls[..., -1:]], axis=-1)
     logz = -_trapezoid(logls, betas)
     logz2 = -_trapezoid(logls2, betas2)
     return logz, np.abs(logz - logz2)
+
+
+def thermodynamic_integration_log_evidence(betas, logls):
+    """ptemcee's estimate: ``logls[..., t]`` the mean log-likelihood at ``betas[..., t]`` (decreasing along the last axis).  When
+    a ladder's last beta is > 0 a rung at ``beta = 0`` with the hottest rung's mean is appended.  -> ``(logZ, dlogZ)``: the
+    negative trapezoid integral over the ladder, and its distance from the same integral over every other rung.  ``betas`` of
+    shape ``(T,)`` serves every row of ``logls``; ``(..., T)`` (one ladder a row, e.g. :attr:`PTSampler.ladder`) broadcasts
+    against ``logls``."""
+    betas = np.asarray(betas, dtype=np.float64)
+    logls = np.asarray(logls, dtype=np.float64)
+    if betas.ndim <= 1:
+        return _ti(betas, logls)
+    betas, logls = np.broadcast_arrays(betas, logls)
+    shape = betas.shape[:-1]
+    fb, fl = betas.reshape(-1, betas.shape[-1]), logls.reshape(-1, logls.shape[-1])
+    logz, dlogz = np.empty(len(fb)), np.empty(len(fb))
+    last0 = fb[:, -1] == 0
+    for sel in (last0, ~last0):          # the ladders that end at beta 0 and those that get the beta = 0 rung appended
+        if sel.any():
+            logz[sel], dlogz[sel] = _ti(fb[sel], fl[sel])
+    return logz.reshape(shape), dlogz.reshape(shape)
 
 
 class PTSampler(object):
@@ -102,11 +133,13 @@ class PTSampler(object):
     proposal block and returns ``(nbatch, ntemps, R)``) or a :class:`~emcee_amd.targets.BatchKernel` (``nbatch * ntemps`` members
     in (object, rung) order), evaluated untempered.  ``log_prior``: None (flat, improper), ``(lo, hi)`` (a box the kernel
     evaluates: 0 inside, -inf outside), or a BatchCallable / BatchKernel called on the same block before the likelihood.
-    ``betas``: strictly decreasing from 1 to >= 0, else :func:`default_betas` ``(ntemps, ndim, Tmax)``.  ``moves``: the schedule
-    forms of :class:`~emcee_amd.EnsembleBatch`'s callback path."""
+    ``betas``: strictly decreasing from 1 to >= 0, else :func:`default_betas` ``(ntemps, ndim, Tmax)``; every object starts on
+    it.  ``moves``: the schedule forms of :class:`~emcee_amd.EnsembleBatch`'s callback path.  ``adaptive``: adapt each object's
+    ladder after every swap pass (module docstring; ptemcee's ``adaptation_lag`` and ``adaptation_time``, both > 0).
+    ``adaptive`` and ``swap_every`` may be changed between runs."""
 
     def __init__(self, ntemps, nwalkers, ndim, log_likelihood, log_prior=None, betas=None, Tmax=None, nbatch=1, moves=None,
-                 seeds=None, swap_every=1, device=None, rng="philox"):
+                 seeds=None, swap_every=1, device=None, rng="philox", adaptive=False, adaptation_lag=10000, adaptation_time=100):
         if rng != "philox":
             raise ValueError("PTSampler runs rng='philox' only (the MT19937 stream is made by one host generator a sampler; use "
                              "EnsembleSampler for rng=%r)" % (rng,))
@@ -136,6 +169,13 @@ class PTSampler(object):
         self.swap_every = int(swap_every)
         if self.swap_every < 0:
             raise ValueError("swap_every must be >= 0 (0: never)")
+        self.adaptation_lag, self.adaptation_time = float(adaptation_lag), float(adaptation_time)
+        for name, v in (("adaptation_lag", self.adaptation_lag), ("adaptation_time", self.adaptation_time)):
+            if not (np.isfinite(v) and v > 0):
+                raise ValueError("%s must be finite and > 0; got %r" % (name, v))
+        self.adaptive = bool(adaptive)
+        if self.adaptive:
+            self._check_adaptive()
         if seeds is None:
             seeds = np.random.randint(0, 2 ** 32, size=self.nbatch, dtype=np.uint64)
         seeds = [int(s) for s in np.asarray(seeds).reshape(-1)]
@@ -149,6 +189,12 @@ class PTSampler(object):
         self.device = self._b.device
         self._h = None
         self._prior_keep = None
+
+    def _check_adaptive(self):
+        if self.ntemps > _ADAPT_MAX_T:
+            raise ValueError("an adaptive ladder has at most %d rungs; ntemps = %d" % (_ADAPT_MAX_T, self.ntemps))
+        if self.ntemps > 1 and not self.betas[-2] > 0:
+            raise ValueError("an adaptive ladder needs betas[0 ... ntemps - 2] > 0")
 
     def _wrap(self, t):
         """a BatchCallable's fn sees (nbatch, ntemps, R, ndim); a BatchKernel the handle's members as they are"""
@@ -179,6 +225,9 @@ class PTSampler(object):
                 self._ck(lib.emx_set_batch_prior_callback(h, fn, user))
             self._h = h
         self._ck(lib.emx_pt_set_swap_every(self._h, self.swap_every))
+        if self.adaptive:
+            self._check_adaptive()
+        self._ck(lib.emx_pt_set_adaptation(self._h, int(bool(self.adaptive)), self.adaptation_lag, self.adaptation_time))
         return self._h
 
     def _who(self, m):
@@ -302,6 +351,38 @@ class PTSampler(object):
         """the untempered log-likelihoods, ``(nbatch, ntemps, nsteps, nwalkers)``."""
         return self._read(2, discard, thin, flat)
 
+    def get_betas(self, discard=0, thin=1):
+        """the ladder of every stored step, ``(nbatch, nsteps, ntemps)`` (each row as stored: after the step's swap pass and
+        ladder update)."""
+        it = self.iteration
+        if it <= 0:
+            raise AttributeError("you must run the sampler with 'store == True' before accessing the results")
+        thin, discard = int(thin), int(discard)
+        start = min(discard + thin - 1, it)
+        nsel = len(range(start, it, thin))
+        out = np.empty((self.nbatch * self.ntemps, nsel))
+        if nsel:
+            self._ck(_lib.load().emx_batch_chain_read(self._h, 3, 0, self.nbatch * self.ntemps, start, it, thin, out))
+        return np.ascontiguousarray(out.reshape(self.nbatch, self.ntemps, nsel).transpose(0, 2, 1))
+
+    @property
+    def ladder(self):
+        """``(nbatch, ntemps)``: every object's current ladder (:attr:`betas` for each before the first run)."""
+        if self._h is None:
+            return np.tile(self.betas, (self.nbatch, 1))
+        out = np.empty((self.nbatch, self.ntemps))
+        self._ck(_lib.load().emx_pt_get_ladder(self._h, out.ctypes.data_as(C.c_void_p), None))
+        return out
+
+    @property
+    def adaptation_updates(self):
+        """the ladder updates made so far (the counter ``t`` of the adaptation rule; one per swap pass while adapting)."""
+        if self._h is None:
+            return 0
+        t = C.c_int64(0)
+        self._ck(_lib.load().emx_pt_get_ladder(self._h, None, C.byref(t)))
+        return t.value
+
     @property
     def acceptance_fraction(self):
         """``(nbatch, ntemps, nwalkers)``"""
@@ -339,12 +420,19 @@ class PTSampler(object):
         return out.reshape(self.nbatch, self.ntemps)
 
     def log_evidence_estimate(self, fburnin=0.1):
-        """-> ``(logZ, dlogZ)``, each ``(nbatch,)``: thermodynamic integration over the ladder of the mean ``L`` of the stored
-        steps after ``int(fburnin * iteration)``.  Needs a normalised prior (a box, or a prior callable)."""
+        """-> ``(logZ, dlogZ)``, each ``(nbatch,)``: thermodynamic integration over each object's ladder of the mean ``L`` of the
+        stored steps after ``int(fburnin * iteration)``.  Needs a normalised prior (a box, or a prior callable), and a ladder
+        that did not change over those steps."""
         if self._box is None and self._prior is None:
             raise ValueError("the evidence needs a normalised prior: with log_prior=None the prior is flat and improper")
-        means = self.mean_log_likelihood(int(fburnin * self.iteration))
-        return thermodynamic_integration_log_evidence(self.betas, means)
+        discard = int(fburnin * self.iteration)
+        means = self.mean_log_likelihood(discard)
+        lad = self.get_betas(discard=discard)
+        if not np.array_equal(lad, np.broadcast_to(lad[:, :1], lad.shape)):
+            raise ValueError("the ladder changed within the %d stored steps after %d: thermodynamic integration needs one ladder. "
+                             "Freeze adaptation (adaptive = False), run on, and discard the adaptive phase (fburnin)"
+                             % (lad.shape[1], discard))
+        return thermodynamic_integration_log_evidence(lad[:, 0], means)
 
     def get_last_sample(self):
         """:class:`State` with ``(nbatch, ntemps, nwalkers, ndim)`` coordinates and tempered ``(nbatch, ntemps, nwalkers)``

@@ -555,7 +555,8 @@ int emx_batch_eval_state_log_prob(emx_batch* b);
 int emx_batch_chain_config(emx_batch* b, int64_t capacity);
 int emx_batch_run(emx_batch* b, int64_t nsteps, int32_t thin_by, int32_t store);
 int emx_batch_iteration(emx_batch* b, int64_t* stored, int64_t* proposals);
-/* rows start, start + stride, ... < stop of members [member_lo, member_hi): what 0 -> (members, rows, nwalkers, ndim), 1 -> log-probs */
+/* rows start, start + stride, ... < stop of members [member_lo, member_hi): what 0 -> (members, rows, nwalkers, ndim), 1 -> log-probs;
+ * tempered handles also 2 -> log-likelihoods (members, rows, nwalkers) and 3 -> betas (members, rows) */
 int emx_batch_chain_read(emx_batch* b, int32_t what, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop,
                          int64_t stride, double* out);
 /* Integrated autocorrelation time of members [member_lo, member_hi) per parameter (autocorr.py:20-123 on
@@ -590,8 +591,8 @@ int emx_batch_launch_info(emx_batch* b, int32_t* threads, int32_t* plan_steps, i
  * of the Philox words (step lo, step hi, 'SWAP', (i - 1) nwalkers + k), log u the plan logarithm (host and device bits agree).
  * A step with a swap pass is S_max + 2 launches (the phases, a commit-only launch, k_pt_swap), else S_max; S_max calls of the
  * likelihood a step (and S_max of a prior callback).  Stored rows hold the state after the step's swap pass (ptemcee's rule):
- * coordinates, tempered lp (what 1) and L (emx_batch_chain_read what 2).  Accept counts stay per member; swap attempts and
- * accepts are counted per (group, pair i - 1). */
+ * coordinates, tempered lp (what 1), L (emx_batch_chain_read what 2) and each member's beta (what 3, one value a row).
+ * Accept counts stay per member; swap attempts and accepts are counted per (group, pair i - 1). */
 /* ntemps must divide the batch; betas (ntemps) non-increasing (PTSampler asks strictly decreasing), betas[0] == 1, betas[ntemps-1] >= 0; box_lo / box_hi (ndim)
  * or both NULL.  Before anything is stored. */
 int emx_pt_set_tempering(emx_batch* b, int32_t ntemps, const double* betas, const double* box_lo, const double* box_hi);
@@ -604,12 +605,33 @@ int emx_pt_swap(emx_batch* b);
 int emx_pt_swap_counts(emx_batch* b, uint64_t* attempts, uint64_t* accepts);
 /* out (B): the mean of each member's L chain over rows start, start + stride, ... < stop and every walker, on the device */
 int emx_pt_mean_loglike(emx_batch* b, int64_t start, int64_t stop, int64_t stride, double* out);
-/* the tempered state: coords (B, nwalkers, ndim), L and P (B, nwalkers); set computes lp with the formula above */
+/* the tempered state: coords (B, nwalkers, ndim), L and P (B, nwalkers); set computes lp with the formula above and each member's
+ * current beta */
 int emx_pt_set_state(emx_batch* b, const double* coords, const double* loglike, const double* logprior);
 int emx_pt_get_state(emx_batch* b, double* loglike, double* logprior);
 /* the swap draws of every pair after Philox step `step` under `seed`: perm_out / logu_out (ntemps - 1, nwalkers), row i - 1 for
  * pair i: pi_i(k) and log u_{i,k}.  0, or -1 for bad arguments. */
 int emx_host_pt_swap_draws(uint64_t seed, uint64_t step, int64_t nwalkers, int32_t ntemps, int32_t* perm_out, double* logu_out);
+/* The adaptive ladder (Vousden, Farr & Mandel 2016; ptemcee's adaptive=True).  When on, every swap pass ends, in k_pt_swap, with
+ * an update of each group's ladder from that pass's accepted counts acc[i - 1] of pair i, after the handle's t-th earlier update:
+ *   r[j] = acc[j] / nwalkers,  kappa = (lag / (t + lag)) / time,  dS[j] = kappa (r[j] - r[j + 1]),
+ *   dT[j] = (1 / b[j + 1] - 1 / b[j]) exp(dS[j]),  c_j = dT[0] + ... + dT[j],  b'[j + 1] = 1 / (c_j + 1 / b[0])   (j = 0 ... T - 3)
+ * in that order, in IEEE + - * / (exp too is made of them: host and device bits agree); rungs 0 and T - 1 stay, and with
+ * ntemps <= 2 nothing moves but t still advances.  lp of the moved rungs is recomputed as beta' L + P (as everywhere else; ptemcee
+ * adds L dbeta instead), and the new betas are stored as computed (ptemcee adds the difference).  Then the stored rows are
+ * written: emx_batch_chain_read what 3 gives each stored row's beta, (B, rows).  ntemps <= 256 while adapting.
+ * lag > 0 and time > 0, finite (ptemcee: 10000, 100); on 1 checks that every ladder has betas[0 ... ntemps - 2] > 0.  It may change
+ * between runs; t is kept. */
+int emx_pt_set_adaptation(emx_batch* b, int32_t on, double lag, double time);
+/* betas (groups, ntemps): every group's current ladder; updates: the update counter t (either may be NULL) */
+int emx_pt_get_ladder(emx_batch* b, double* betas, int64_t* updates);
+/* set every group's ladder (each row checked as emx_pt_set_tempering checks its betas, and betas[0 ... ntemps - 2] > 0 while
+ * adapting) and, unless NULL, the counter t; lp is recomputed on the device.  Allowed after rows have been stored. */
+int emx_pt_set_ladder(emx_batch* b, const double* betas, const int64_t* updates);
+/* the host twin of one group's update: out (ntemps) from betas (ntemps) and accepts (ntemps - 1) of a pass over nwalkers walkers
+ * after t earlier updates.  0, or -1 for bad arguments. */
+int emx_host_pt_adapt_ladder(const double* betas, const int64_t* accepts, int32_t ntemps, int64_t nwalkers, double lag, double time,
+                             int64_t t, double* out);
 
 #ifdef __cplusplus
 }

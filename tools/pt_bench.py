@@ -1,10 +1,11 @@
 """PTSampler throughput against EnsembleBatch's callback path at the same members and the same callable.
 
-    python tools/pt_bench.py [--nbatch 64 --ntemps 16 --nwalkers 32 --ndim 5 --steps 200 --reps 3] [--json out.json]
+    python tools/pt_bench.py [--nbatch 64 --ntemps 16 --nwalkers 32 --ndim 5 --steps 200 --reps 3] [--adaptive] [--json out.json]
 
 Shape: nbatch objects x ntemps rungs x nwalkers x ndim with a torch two-component Gaussian mixture likelihood.  Reports member-steps
 per second (members = nbatch * ntemps) of PTSampler with swap_every = 1 and 0, and of EnsembleBatch on the tempered callable
-(beta_t L + box prior), best of `reps` timed runs of `steps` steps without storing."""
+(beta_t L + box prior), best of `reps` timed runs of `steps` steps without storing.  --adaptive also times PTSampler with
+swap_every = 1 and the adaptive ladder (ptemcee's lag and time)."""
 import argparse
 import json
 import os
@@ -51,6 +52,7 @@ def main():
     ap.add_argument("--ndim", type=int, default=5)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--adaptive", action="store_true", help="also time swap_every=1 with the adaptive ladder")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     G, T, N, D = a.nbatch, a.ntemps, a.nwalkers, a.ndim
@@ -58,11 +60,18 @@ def main():
     box = (-10 * np.ones(D), 10 * np.ones(D))
     p0 = -4.0 + 0.3 * np.random.RandomState(0).randn(G, T, N, D)
     out = dict(nbatch=G, ntemps=T, nwalkers=N, ndim=D, steps=a.steps, members=G * T)
-    for every in (1, 0):
-        pt = PTSampler(T, N, D, BatchCallable(fn), log_prior=box, Tmax=1e3, nbatch=G, seeds=list(range(G)), swap_every=every)
+    for every, adaptive in ((1, False), (0, False)) + (((1, True),) if a.adaptive else ()):
+        pt = PTSampler(T, N, D, BatchCallable(fn), log_prior=box, Tmax=1e3, nbatch=G, seeds=list(range(G)), swap_every=every,
+                       adaptive=adaptive)
         pt.run_mcmc(p0, 10, store=False)
-        out["pt_swap_every_%d_member_steps_per_s" % every] = G * T * timed(lambda n: pt.run_mcmc(None, n, store=False), a.steps, a.reps)
-        if every == 1:
+        key = "pt_swap_every_%d%s_member_steps_per_s" % (every, "_adaptive" if adaptive else "")
+        out[key] = G * T * timed(lambda n: pt.run_mcmc(None, n, store=False), a.steps, a.reps)
+        if adaptive:
+            n0 = pt.launch_info()["launches"]
+            pt.run_mcmc(None, 10, store=False)
+            out["pt_adaptive_launches_per_step"] = (pt.launch_info()["launches"] - n0) / 10.0
+            out["tswap_acceptance_mean_adaptive"] = float(pt.tswap_acceptance_fraction.mean())
+        elif every == 1:
             out["pt_launches_per_step"] = None
             n0 = pt.launch_info()["launches"]
             pt.run_mcmc(None, 10, store=False)
