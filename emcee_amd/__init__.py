@@ -7,11 +7,12 @@ gfx950 behind a C ABI (``include/emx.h``, ``emcee_amd/libemx.so``).  See DESIGN.
 """
 __version__ = "0.1.0"
 
-from . import autocorr, backends, moves, targets
+from . import autocorr, backends, moves, summary, targets
 from .batch import EnsembleBatch
 from .ensemble import EnsembleSampler, walkers_independent
 from .pt import PTSampler
 from .state import State
+from .summary import BatchSummary
 
-__all__ = ["EnsembleSampler", "EnsembleBatch", "PTSampler", "walkers_independent", "State", "moves", "autocorr", "backends", "targets",
+__all__ = ["EnsembleSampler", "EnsembleBatch", "BatchSummary", "PTSampler", "walkers_independent", "State", "moves", "autocorr", "backends", "summary", "targets",
            "__version__"]

@@ -184,6 +184,9 @@ SIGNATURES = {
     "emx_pt_set_ladder": (C.c_int, [_P, _dp, C.POINTER(C.c_int64)]),
     "emx_host_pt_adapt_ladder": (C.c_int, [_dp, _i64p, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_int64, _dp]),
     "emx_autocorr_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double, _dp, _ip, C.POINTER(C.c_int64)]),
+    "emx_summary_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int32, _P, _P, _P, _P,
+                                    C.POINTER(C.c_int64)]),
+    "emx_host_order_stats": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int32, _i64p, _dp]),
 }
 
 

@@ -29,6 +29,7 @@ import numpy as np
 
 from . import _lib
 from . import autocorr
+from . import summary as _summary
 from .autocorr import integrated_time
 from .ensemble import _native_desc, _parse_move_schedule, _refuse_extended_precision, philox_seed, walkers_independent
 from .state import State
@@ -196,7 +197,8 @@ class EnsembleBatch(object):
 
     def set_tuning(self, key, value):
         """``"batch_threads"`` / ``"batch_plan_steps"`` (include/emx.h): the launch shape; ``"batch_acf_series"``: series per
-        FFT chunk of ``get_autocorr_time(on_device=True)``.  No bit depends on them."""
+        FFT chunk of ``get_autocorr_time(on_device=True)``; ``"batch_summary_members"``: members per pass of
+        ``get_summary``.  No bit depends on them."""
         self._tuning[key] = int(value)
         if self._h is not None:
             self._ck(self._lib().emx_batch_set_tuning(self._h, key.encode(), int(value)))
@@ -358,6 +360,64 @@ class EnsembleBatch(object):
         self._ck(lib.emx_autocorr_batch(self._h, lo, hi, int(discard), int(thin), float(c), tau, win, C.byref(nt)))
         return tau, win, nt.value
 
+    def get_summary(self, discard=0, thin=1, quantiles=(0.16, 0.5, 0.84), cov=True):
+        """-> :class:`~emcee_amd.summary.BatchSummary` of every member over the selected steps (``get_chain``'s ``discard`` /
+        ``thin``) and all walkers, computed next to the chain (``emx_summary_batch``): ``mean`` ``(B, ndim)``, ``cov``
+        ``(B, ndim, ndim)`` (``np.cov(flat.T)``, exactly symmetric; None with ``cov=False``), ``quantiles`` ``(B, nq, ndim)``
+        (``np.quantile``'s default rule, at most 16), ``map_coords`` ``(B, ndim)`` / ``map_log_prob`` ``(B,)``: the stored sample
+        with the largest stored log-prob, the earliest step and then the lowest walker among equals.  Only these cross to the
+        host.  A device failure raises :class:`emcee_amd._lib.EmxError` (no fallback)."""
+        return self._summary(discard, thin, quantiles, cov, 0, self.nbatch)
+
+    def _summary(self, discard, thin, quantiles, cov, lo, hi):
+        q = _summary.check_quantiles(quantiles)
+        _, _, nt = self._summary_rows(discard, thin)
+        ranks, ilo, ihi, g = _summary.plan_ranks(nt * self.nwalkers, q)
+        n, mean, c, order, mx, mlp = self._summary_device(discard, thin, ranks, cov, lo, hi)
+        return _summary.BatchSummary(n, mean, c, _summary.interpolate(order, ilo, ihi, g), mx, mlp)
+
+    def _summary_rows(self, discard, thin):
+        """-> (start, stop, nt): ``_read``'s selection of stored rows, after the argument checks (no device is touched)."""
+        if int(thin) != thin or thin < 1:
+            raise ValueError("thin must be an integer >= 1; got %r" % (thin,))
+        if int(discard) != discard or discard < 0:
+            raise ValueError("discard must be an integer >= 0; got %r" % (discard,))
+        if self._h is None or self.iteration <= 0:
+            raise ValueError("you must run the sampler with 'store == True' before computing summaries")
+        thin, discard, it = int(thin), int(discard), self.iteration
+        start = min(discard + thin - 1, it)                 # reference backend.py:53
+        nt = len(range(start, it, thin))
+        if nt < 1:
+            raise ValueError("discard = %d, thin = %d select none of the %d stored steps" % (discard, thin, it))
+        return start, it, nt
+
+    def _summary_device(self, discard=0, thin=1, ranks=(), cov=True, lo=0, hi=None):
+        """-> (n, mean (hi - lo, ndim), cov (hi - lo, ndim, ndim) or None, order statistics (hi - lo, len(ranks), ndim), MAP
+        coordinates (hi - lo, ndim), MAP log-probs (hi - lo)): ``emx_summary_batch`` on members [lo, hi), ``order[:, r, d]``
+        being the ``ranks[r]``-th smallest (0-based) of the ``n`` selected samples of parameter d.  Arguments are checked
+        before any device is touched."""
+        hi = self.nbatch if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo < hi <= self.nbatch:
+            raise ValueError("members [%d, %d) outside a batch of %d" % (lo, hi, self.nbatch))
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
+        if len(ranks) > 2 * _summary.MAX_QUANTILES:
+            raise ValueError("at most %d ranks in one call; got %d" % (2 * _summary.MAX_QUANTILES, len(ranks)))
+        start, it, nt = self._summary_rows(discard, thin)
+        thin, n = int(thin), nt * self.nwalkers
+        if len(ranks) and not (0 <= ranks.min() and ranks.max() < n):
+            raise ValueError("ranks must lie in [0, %d)" % n)
+        M, D = hi - lo, self.ndim
+        mean, mx, mlp = np.empty((M, D)), np.empty((M, D)), np.empty(M)
+        c = np.empty((M, D, D)) if cov else None
+        order = np.empty((M, len(ranks), D))
+        ptr = (lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p))
+        ns = C.c_int64(0)
+        self._ck(self._lib().emx_summary_batch(self._h, lo, hi, start, it, thin, ptr(mean), ptr(c), len(ranks), ptr(ranks), ptr(order),
+                                               ptr(mx), ptr(mlp), C.byref(ns)))
+        assert ns.value == n
+        return n, mean, c, order, mx, mlp
+
     def get_last_sample(self):
         """:class:`State` with ``(B, nwalkers, ndim)`` coordinates and ``(B, nwalkers)`` log-probs."""
         if self._h is None or not self._ran:
@@ -455,6 +515,11 @@ class _Member(object):
             return thin * tau[0]
         x = self.get_chain(discard=discard, thin=thin)
         return thin * integrated_time(x, c=c, tol=tol, quiet=quiet)
+
+    def get_summary(self, discard=0, thin=1, quantiles=(0.16, 0.5, 0.84), cov=True):
+        """:meth:`EnsembleBatch.get_summary` of this member alone, without the leading axis."""
+        r = self._batch._summary(discard, thin, quantiles, cov, self.index, self.index + 1)
+        return _summary.BatchSummary(r.nsamples, *[None if a is None else a[0] for a in r[1:]])
 
     def get_last_sample(self):
         s = self._batch.get_last_sample()

@@ -69,6 +69,9 @@ struct emx_batch {
     // emx_autocorr_batch (emx_batch_acf.hip): its hipFFT plans and scratch; tuning "batch_acf_series" (0: auto)
     BatchAcf* acf = nullptr;
     int64_t tune_acf_series = 0;
+    // emx_summary_batch (emx_batch_summary.hip): its scratch; tuning "batch_summary_members" (0: auto)
+    BatchSummary* summary = nullptr;
+    int64_t tune_summary_members = 0;
     // parallel tempering (emx_pt_set_tempering; pt_T 0: untempered): groups of pt_T members, member m at rung m % pt_T; each
     // member's beta, the box prior, L and P per walker, the L chain, the caller's prior, the swap cadence and counters
     int32_t pt_T = 0;
@@ -541,6 +544,7 @@ int run_callback(emx_batch* b, int64_t total, int32_t thin_by, int32_t store) {
 int emx_internal_batch_view(emx_batch* b, EmxBatchView* v) {
     if (!b || !v) return -1;
     v->chain = b->chain;
+    v->chain_lp = b->chain_lp;
     v->B = b->B;
     v->D = b->D;
     v->N = b->N;
@@ -550,6 +554,8 @@ int emx_internal_batch_view(emx_batch* b, EmxBatchView* v) {
     v->stream = b->stream;
     v->device = b->device;
     v->acf = &b->acf;
+    v->summary_members = b->tune_summary_members;
+    v->summary = &b->summary;
     return 0;
 }
 
@@ -605,6 +611,7 @@ int emx_batch_destroy(emx_batch* b) {
     hipSetDevice(b->device);
     if (b->stream) hipStreamSynchronize(b->stream);
     if (b->acf) emx_internal_batch_acf_release(b->acf);
+    if (b->summary) emx_internal_batch_summary_release(b->summary);
     for (void* p : {(void*)b->X, (void*)b->lp, (void*)b->acc, (void*)b->acc_count, (void*)b->seeds, (void*)b->tp0, (void*)b->tp1,
                     (void*)b->tscales, (void*)b->chain, (void*)b->chain_lp, (void*)b->fac_dev, (void*)b->col_dev, (void*)b->cb_q,
                     (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi, (void*)b->cb_nrows, (void*)b->pt_beta,
@@ -630,6 +637,9 @@ int emx_batch_set_tuning(emx_batch* b, const char* key, int64_t value) {
     } else if (!std::strcmp(key, "batch_acf_series")) {
         BNEED(b, value >= 0, "batch_acf_series: 0 (auto) or a positive number of series");
         b->tune_acf_series = value;
+    } else if (!std::strcmp(key, "batch_summary_members")) {
+        BNEED(b, value >= 0, "batch_summary_members: 0 (auto) or a positive number of members");
+        b->tune_summary_members = value;
     } else {
         return fail(b, -1, "unknown batch tuning key '%s'", key);
     }

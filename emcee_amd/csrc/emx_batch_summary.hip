@@ -1,0 +1,636 @@
+// libemx, emx_summary_batch: the posterior summaries of every member of an emx_batch, computed next to the member-major chain
+// (B, cap, N, D) -- per member the mean, the ddof = 1 covariance, order statistics (from which the caller interpolates
+// quantiles) and the stored sample of the largest log-prob, over rows t0, t0 + stride, ... (nt of them) and every walker:
+// n = nt N samples.  Only O(members D^2) numbers cross to the host.  The kernels take (chain, cap, N, D, first member), not
+// the handle, so that they can run on a single ensemble's chain (one member, cap = its capacity).
+//
+// A member's rows are cut into S slices of R rows, R and S fixed by nt alone.  Members go in passes of at most
+// "batch_summary_members"; every member is reduced on its own.  Per pass
+//   k_bsum_mean_part    slab[member][slice][j = w D + d]: sum over the slice's rows, lane = j (coalesced), the 4 waves of a
+//                       workgroup sum consecutive quarters of the slice and are added in wave order
+//   k_bsum_mean_fin     mean[d] = (sum over walkers in order of (sum over slices in order)) / n
+//   k_bsum_gram_small   D < 16: centred Gram sum (x_j - m_j)(x_k - m_k), j <= k, per slice: 256 samples at a time are centred
+//                       into LDS; thread (pair, group g) adds the samples g, g + G, ... of every tile with an explicit fma
+//                       (the file is built with -ffp-contract=off: nothing else is fused), groups are added in order
+//   k_bsum_gram_mfma    D >= 16: the same per slice on v_mfma_f64_16x16x4_f64, D padded to 16 Dp' with zero columns: a wave
+//                       holds up to 8 of the 16 x 16 blocks (jb <= kb) and runs the tile's samples four at a time; a diagonal
+//                       block's A and B operands are one LDS value
+//   k_bsum_gram_fin_*   cov[j][k] = cov[k][j] = (sum over slices in order) / (n - 1)
+//   k_bsum_map          arg-max of the member's selected log-probs, ties to the smallest (row, walker) index -- (value, index)
+//                       pairs under that rule form a total order, so the reduction's shape does not matter; then the D coordinates
+//   k_bsum_sel_init / k_bsum_hist / k_bsum_scan, 8 passes of 8 bits, most significant first: radix select of every requested
+//                       rank of every series (member, d) in place.  A double maps to an order-preserving uint64 key; in a pass
+//                       every element whose higher bits equal a rank's prefix counts into that rank's 256 bins (LDS uint32
+//                       atomics, then one global 64-bit integer atomic per non-empty bin per workgroup); the scan picks the
+//                       digit, lowers the remaining rank and extends the prefix.  Ranks with one prefix share one histogram
+//                       (their "leader", the lowest such rank).  After the last pass the prefix is the key of the order
+//                       statistic.  The key transform and the bin scan are shared with the host twin emx_host_order_stats.
+// Floating-point sums run in an order fixed by (nt, N, D); the selection only counts integers: no bit depends on the member
+// range, the pass size or the launch shape.  No floating-point atomics.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../../include/emx.h"
+#include "emx_internal.hpp"
+#include "emx_rng.hpp"
+
+namespace {
+
+constexpr int SEL_MAX_RANKS = 32;
+constexpr int SEL_PASSES = 8;
+typedef unsigned long long u64;
+
+// ---- shared with the host twin ----------------------------------------------------------------------------------------
+// order-preserving key: negatives have every bit flipped, non-negatives the sign bit set (-0.0 sorts just below +0.0)
+EMX_HD u64 sel_key(u64 bits) { return (bits >> 63) ? ~bits : (bits | 0x8000000000000000ull); }
+EMX_HD u64 sel_unkey(u64 key) { return (key >> 63) ? (key ^ 0x8000000000000000ull) : ~key; }
+// the digit holding the *rem-th smallest (0-based) of the elements counted in bins[256]; *rem becomes the rank inside that bin
+EMX_HD int sel_scan_bins(const u64* bins, int64_t* rem) {
+    u64 cum = 0;
+    const u64 want = (u64)*rem;
+    int digit = 255;
+    for (int b = 0; b < 256; ++b) {
+        const u64 c = bins[b];
+        if (want < cum + c) {
+            digit = b;
+            break;
+        }
+        cum += c;
+    }
+    *rem = (int64_t)(want - cum);
+    return digit;
+}
+// leader[r]: the lowest rank with r's prefix
+EMX_HD void sel_leaders(const u64* prefix, int32_t* leader, int nr) {
+    for (int r = 0; r < nr; ++r) {
+        int l = r;
+        for (int q = 0; q < r; ++q)
+            if (prefix[q] == prefix[r]) {
+                l = q;
+                break;
+            }
+        leader[r] = l;
+    }
+}
+
+// ---- kernels ------------------------------------------------------------------------------------------------------------
+// Selection of one launch: member m = m0 + blockIdx.z (scratch is indexed by blockIdx.z), slice s = blockIdx.y covers the
+// selected rows [s R, min(s R + R, nt)); selected row t is stored row t0 + t stride.
+struct Sel {
+    const double* chain;       // (., cap, N, D)
+    const double* chain_lp;    // (., cap, N)
+    int64_t cap, N, ND, t0, stride, nt, R, m0;
+    int32_t D, S;
+};
+
+__global__ __launch_bounds__(256) void k_bsum_mean_part(const Sel g, double* __restrict__ mpart) {
+    __shared__ double part[4][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t j = (int64_t)blockIdx.x * 64 + lane, s = blockIdx.y, ml = blockIdx.z;
+    const int64_t ra = s * g.R, rb = ra + g.R < g.nt ? ra + g.R : g.nt;
+    const int64_t q = g.R / 4, ta = ra + wv * q, tb = ta + q < rb ? ta + q : rb;
+    double acc = 0.0;
+    if (j < g.ND) {
+        const double* p = g.chain + ((g.m0 + ml) * g.cap + g.t0) * g.ND + j;
+        const int64_t step = g.stride * g.ND;
+#pragma unroll 8
+        for (int64_t t = ta; t < tb; ++t) acc += p[t * step];
+    }
+    part[wv][lane] = acc;
+    __syncthreads();
+    if (wv == 0 && j < g.ND) mpart[(ml * g.S + s) * g.ND + j] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+}
+
+// mean (mp, D) of the pass; one thread a (member, d)
+__global__ __launch_bounds__(256) void k_bsum_mean_fin(const Sel g, const double* __restrict__ mpart, double* __restrict__ mean, int64_t mp) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= mp * g.D) return;
+    const int64_t ml = i / g.D, d = i - ml * g.D;
+    double acc = 0.0;
+    for (int64_t w = 0; w < g.N; ++w) {
+        double col = 0.0;
+        for (int64_t s = 0; s < g.S; ++s) col += mpart[(ml * g.S + s) * g.ND + w * g.D + d];
+        acc += col;
+    }
+    mean[i] = acc / (double)(g.nt * g.N);
+}
+
+// pair p of the upper triangle of an L x L matrix in row order -> (j, k), j <= k
+__device__ __forceinline__ void tri_pair(int p, int L, int* j, int* k) {
+    int row = 0, len = L;
+    while (p >= len) {
+        p -= len;
+        ++row;
+        --len;
+    }
+    *j = row;
+    *k = row + p;
+}
+
+constexpr int GS_TILE = 256;       // samples a tile of k_bsum_gram_small
+// D < 16.  gpart (mp, S, P), P = D (D + 1) / 2
+__global__ __launch_bounds__(256) void k_bsum_gram_small(const Sel g, const double* __restrict__ mean, double* __restrict__ gpart) {
+    __shared__ double tile[GS_TILE * 15];
+    __shared__ double red[256];
+    __shared__ double mu[16];
+    const int tid = threadIdx.x, D = g.D, P = D * (D + 1) / 2, G = 256 / P;
+    const int64_t s = blockIdx.y, ml = blockIdx.z;
+    if (tid < D) mu[tid] = mean[ml * D + tid];
+    const int p = tid % P, grp = tid / P;
+    int j, k;
+    tri_pair(p, D, &j, &k);
+    const int64_t ra = s * g.R, rb = ra + g.R < g.nt ? ra + g.R : g.nt;
+    const int64_t ns = (rb - ra) * g.N;                         // samples of the slice; its elements f = sample D + d = row ND + j
+    const double* base = g.chain + ((g.m0 + ml) * g.cap + g.t0 + ra * g.stride) * g.ND;
+    const int64_t rowstep = g.stride * g.ND;
+    // this thread's next element f = tid + 256 it as (row, col, d), advanced without a division
+    int64_t row = tid / g.ND, col = tid - row * g.ND;
+    int d = tid % D;
+    const int64_t qstep = 256 / g.ND, cstep = 256 - qstep * g.ND;
+    const int dstep = 256 % D;
+    double acc = 0.0;
+    for (int64_t i0 = 0; i0 < ns; i0 += GS_TILE) {
+        const int cnt = (int)(ns - i0 < GS_TILE ? ns - i0 : GS_TILE);
+        const int nel = cnt * D;
+        __syncthreads();                                        // the previous tile is consumed (and mu is written)
+        for (int slot = tid; slot < nel; slot += 256) {
+            tile[slot] = base[row * rowstep + col] - mu[d];
+            row += qstep;
+            col += cstep;
+            if (col >= g.ND) {
+                col -= g.ND;
+                ++row;
+            }
+            d += dstep;
+            if (d >= D) d -= D;
+        }
+        __syncthreads();
+        if (grp < G)
+            for (int i = grp; i < cnt; i += G) acc = fma(tile[i * D + j], tile[i * D + k], acc);
+    }
+    red[tid] = acc;
+    __syncthreads();
+    if (tid < P) {
+        double tot = 0.0;
+        for (int q = 0; q < G; ++q) tot += red[q * P + tid];
+        gpart[(ml * g.S + s) * P + tid] = tot;
+    }
+}
+
+// cov (mp, D, D) of the pass from gpart (mp, S, P)
+__global__ __launch_bounds__(256) void k_bsum_gram_fin_small(const Sel g, const double* __restrict__ gpart, double* __restrict__ cov, int64_t mp) {
+    const int D = g.D, P = D * (D + 1) / 2;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= mp * P) return;
+    const int64_t ml = i / P;
+    const int p = (int)(i - ml * P);
+    int j, k;
+    tri_pair(p, D, &j, &k);
+    double acc = 0.0;
+    for (int64_t s = 0; s < g.S; ++s) acc += gpart[(ml * g.S + s) * P + p];
+    const double c = acc / (double)(g.nt * g.N - 1);
+    cov[(ml * D + j) * D + k] = c;
+    cov[(ml * D + k) * D + j] = c;
+}
+
+constexpr int GM_TILE_DOUBLES = 4608;      // T (Dp + 2) <= 4096 + 2 T, T <= 256
+constexpr int GM_PAIRS_WAVE = 8, GM_PAIRS_WG = 4 * GM_PAIRS_WAVE;
+__host__ __device__ constexpr int gm_tile_samples(int Dp) { return (4096 / Dp) & ~3; }
+
+// D >= 16.  Block pairs (jb <= kb) of the Dp / 16 column blocks; workgroup blockIdx.x holds pairs [32 x, 32 x + 32), pair
+// 32 x + 4 a + wave in accumulator a of that wave.  gpart (mp, S, NP, 4, 64): the accumulators as the MFMA leaves them,
+// register r of lane l being C[row = (l >> 4) + 4 r][col = l & 15] of the block.
+__global__ __launch_bounds__(256) void k_bsum_gram_mfma(const Sel g, const double* __restrict__ mean, double* __restrict__ gpart, int Dp, int NP) {
+    typedef double d4 __attribute__((ext_vector_type(4)));
+    __shared__ double tile[GM_TILE_DOUBLES];
+    __shared__ double mu[256];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, D = g.D;
+    const int T = gm_tile_samples(Dp), LS = Dp + 2, DPB = Dp / 16;
+    const int64_t s = blockIdx.y, ml = blockIdx.z;
+    for (int c = tid; c < Dp; c += 256) mu[c] = c < D ? mean[ml * D + c] : 0.0;
+    int ja[GM_PAIRS_WAVE], ka[GM_PAIRS_WAVE];
+    bool live[GM_PAIRS_WAVE];
+    d4 acc[GM_PAIRS_WAVE];
+#pragma unroll
+    for (int a = 0; a < GM_PAIRS_WAVE; ++a) {
+        const int pi = blockIdx.x * GM_PAIRS_WG + 4 * a + wv;
+        live[a] = pi < NP;
+        int jb = 0, kb = 0;
+        if (live[a]) tri_pair(pi, DPB, &jb, &kb);
+        ja[a] = jb * 16 + (lane & 15);
+        ka[a] = kb * 16 + (lane & 15);
+        acc[a] = d4{0.0, 0.0, 0.0, 0.0};
+    }
+    const int64_t ra = s * g.R, rb = ra + g.R < g.nt ? ra + g.R : g.nt;
+    const int64_t ns = (rb - ra) * g.N;
+    const double* base = g.chain + ((g.m0 + ml) * g.cap + g.t0 + ra * g.stride) * g.ND;
+    const int64_t rowstep = g.stride * g.ND;
+    // staging: a wave's lanes cover CPL columns of 64 / CPL samples at a time
+    const int CPL = Dp <= 16 ? 16 : Dp <= 32 ? 32 : 64, SPW = 64 / CPL;
+    const int ls = lane / CPL, c0 = lane - ls * CPL;
+    __syncthreads();
+    for (int64_t i0 = 0; i0 < ns; i0 += T) {
+        for (int i = wv * SPW + ls; i < T; i += 4 * SPW) {
+            const int64_t si = i0 + i;
+            const bool in = si < ns;
+            const int64_t row = in ? si / g.N : 0, w = si - row * g.N;
+            const double* src = base + row * rowstep + w * D;
+            for (int c = c0; c < Dp; c += CPL) tile[i * LS + c] = (in && c < D) ? src[c] - mu[c] : 0.0;
+        }
+        __syncthreads();
+        for (int ks = 0; ks < T / 4; ++ks) {
+            const double* trow = tile + (ks * 4 + (lane >> 4)) * LS;
+#pragma unroll
+            for (int a = 0; a < GM_PAIRS_WAVE; ++a)
+                if (live[a]) acc[a] = __builtin_amdgcn_mfma_f64_16x16x4f64(trow[ja[a]], trow[ka[a]], acc[a], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int a = 0; a < GM_PAIRS_WAVE; ++a) {
+        if (!live[a]) continue;
+        const int pi = blockIdx.x * GM_PAIRS_WG + 4 * a + wv;
+        double* out = gpart + ((ml * g.S + s) * NP + pi) * 256;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) out[r * 64 + lane] = acc[a][r];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bsum_gram_fin_mfma(const Sel g, const double* __restrict__ gpart, double* __restrict__ cov, int64_t mp,
+                                                            int Dp, int NP) {
+    const int D = g.D;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= mp * NP * 256) return;
+    const int e = (int)(i & 255), lane = e & 63, r = e >> 6;
+    const int64_t mpi = i >> 8, ml = mpi / NP;
+    const int pi = (int)(mpi - ml * NP);
+    int jb, kb;
+    tri_pair(pi, Dp / 16, &jb, &kb);
+    const int j = jb * 16 + (lane >> 4) + 4 * r, k = kb * 16 + (lane & 15);
+    if (j >= D || k >= D || j > k) return;
+    double acc = 0.0;
+    for (int64_t s = 0; s < g.S; ++s) acc += gpart[((ml * g.S + s) * NP + pi) * 256 + e];
+    const double c = acc / (double)(g.nt * g.N - 1);
+    cov[(ml * D + j) * D + k] = c;
+    cov[(ml * D + k) * D + j] = c;
+}
+
+// a better than b: larger value, then smaller index; an index < 0 marks "nothing seen"
+__device__ __forceinline__ bool map_better(double va, int64_t ia, double vb, int64_t ib) {
+    if (ia < 0) return false;
+    if (ib < 0) return true;
+    return va > vb || (va == vb && ia < ib);
+}
+
+// one workgroup a member: map_lp (mp), map_x (mp, D)
+__global__ __launch_bounds__(256) void k_bsum_map(const Sel g, double* __restrict__ map_x, double* __restrict__ map_lp) {
+    __shared__ double bv[256];
+    __shared__ int64_t bi[256];
+    const int tid = threadIdx.x;
+    const int64_t ml = blockIdx.x, m = g.m0 + ml, total = g.nt * g.N;
+    const double* base = g.chain_lp + (m * g.cap + g.t0) * g.N;
+    const int64_t rowstep = g.stride * g.N;
+    int64_t row = tid / g.N, w = tid - row * g.N;
+    const int64_t qstep = 256 / g.N, wstep = 256 - qstep * g.N;
+    double best = 0.0;
+    int64_t idx = -1;
+    for (int64_t e = tid; e < total; e += 256) {
+        const double v = base[row * rowstep + w];
+        if (idx < 0 || v > best) {
+            best = v;
+            idx = e;
+        }
+        row += qstep;
+        w += wstep;
+        if (w >= g.N) {
+            w -= g.N;
+            ++row;
+        }
+    }
+    bv[tid] = best;
+    bi[tid] = idx;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h && map_better(bv[tid + h], bi[tid + h], bv[tid], bi[tid])) {
+            bv[tid] = bv[tid + h];
+            bi[tid] = bi[tid + h];
+        }
+        __syncthreads();
+    }
+    const int64_t e = bi[0], r = e / g.N, ww = e - r * g.N;
+    if (tid == 0) map_lp[ml] = bv[0];
+    const double* x = g.chain + ((m * g.cap + g.t0 + r * g.stride) * g.N + ww) * g.D;
+    for (int d = tid; d < g.D; d += 256) map_x[ml * g.D + d] = x[d];
+}
+
+// selection state of the pass: prefix / rem / leader (mp, D, nr); hist (mp, D, nr, 256)
+__global__ __launch_bounds__(256) void k_bsum_sel_init(u64* __restrict__ prefix, int64_t* __restrict__ rem, int32_t* __restrict__ leader,
+                                                       const int64_t* __restrict__ ranks, int nr, int64_t count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    prefix[i] = 0;
+    rem[i] = ranks[i % nr];
+    leader[i] = 0;               // every rank starts with the empty prefix: rank 0 leads
+}
+
+// pass `pass` (digit = bits [shift, shift + 8), shift = 56 - 8 pass).  grid (dim tiles of DT dims, S, mp)
+__global__ __launch_bounds__(256) void k_bsum_hist(const Sel g, const u64* __restrict__ prefix, const int32_t* __restrict__ leader,
+                                                   u64* __restrict__ hist, int nr, int DT, int pass) {
+    __shared__ uint32_t h[SEL_MAX_RANKS * 256];
+    __shared__ u64 pf[SEL_MAX_RANKS];
+    __shared__ int32_t lead[SEL_MAX_RANKS];
+    const int tid = threadIdx.x, D = g.D;
+    const int d0 = blockIdx.x * DT, dc = D - d0 < DT ? D - d0 : DT;          // this workgroup's dims [d0, d0 + dc)
+    const int64_t s = blockIdx.y, ml = blockIdx.z;
+    const int nslot = dc * nr, shift = 56 - 8 * pass;
+    for (int i = tid; i < nslot * 256; i += 256) h[i] = 0;
+    if (tid < nslot) {
+        const int64_t at = (ml * D + d0) * nr + tid;
+        pf[tid] = pass ? prefix[at] >> (shift + 8) : 0;
+        lead[tid] = leader[at];
+    }
+    __syncthreads();
+    const int64_t ra = s * g.R, rb = ra + g.R < g.nt ? ra + g.R : g.nt;
+    const int64_t nel = (rb - ra) * g.ND;
+    const double* base = g.chain + ((g.m0 + ml) * g.cap + g.t0 + ra * g.stride) * g.ND;
+    const int64_t rowstep = g.stride * g.ND;
+    int64_t row = tid / g.ND, col = tid - row * g.ND;
+    int d = tid % D;
+    const int64_t qstep = 256 / g.ND, cstep = 256 - qstep * g.ND;
+    const int dstep = 256 % D;
+    for (int64_t f = tid; f < nel; f += 256) {
+        const int dl = d - d0;
+        if (dl >= 0 && dl < dc) {
+            const u64 key = sel_key((u64)__double_as_longlong(base[row * rowstep + col]));
+            const u64 hi = pass ? key >> (shift + 8) : 0;
+            const uint32_t digit = (uint32_t)(key >> shift) & 255u;
+            for (int r = 0; r < nr; ++r) {
+                const int sl = dl * nr + r;
+                if (lead[sl] == r && pf[sl] == hi) atomicAdd(&h[sl * 256 + digit], 1u);
+            }
+        }
+        row += qstep;
+        col += cstep;
+        if (col >= g.ND) {
+            col -= g.ND;
+            ++row;
+        }
+        d += dstep;
+        if (d >= D) d -= D;
+    }
+    __syncthreads();
+    u64* out = hist + ((ml * D + d0) * nr) * 256;
+    for (int i = tid; i < nslot * 256; i += 256)
+        if (h[i]) atomicAdd(&out[i], (u64)h[i]);
+}
+
+// one thread a series (member, d): every rank takes its digit from its leader's bins; after the last pass order (mp, nr, D)
+__global__ __launch_bounds__(64) void k_bsum_scan(u64* __restrict__ prefix, int64_t* __restrict__ rem, int32_t* __restrict__ leader,
+                                                  const u64* __restrict__ hist, double* __restrict__ order, int nr, int D, int64_t nseries,
+                                                  int pass) {
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= nseries) return;
+    const int shift = 56 - 8 * pass;
+    u64 pfx[SEL_MAX_RANKS];
+    int32_t ld[SEL_MAX_RANKS];
+    for (int r = 0; r < nr; ++r) {
+        int64_t want = rem[i * nr + r];
+        const int digit = sel_scan_bins(hist + (i * nr + leader[i * nr + r]) * 256, &want);
+        rem[i * nr + r] = want;
+        pfx[r] = prefix[i * nr + r] | ((u64)digit << shift);
+        prefix[i * nr + r] = pfx[r];
+    }
+    sel_leaders(pfx, ld, nr);
+    for (int r = 0; r < nr; ++r) leader[i * nr + r] = ld[r];
+    if (pass == SEL_PASSES - 1) {
+        const int64_t ml = i / D, d = i - ml * D;
+        for (int r = 0; r < nr; ++r) order[(ml * nr + r) * D + d] = __longlong_as_double((long long)sel_unkey(pfx[r]));
+    }
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------
+int sfail(emx_batch* b, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
+int sfail(emx_batch* b, int code, const char* fmt, ...) {
+    char buf[384];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return emx_internal_batch_fail(b, code, buf);
+}
+
+struct Buf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
+int grow(emx_batch* b, Buf& u, size_t bytes, const char* what) {
+    if (bytes <= u.bytes) return 0;
+    if (u.p) hipFree(u.p);
+    u.p = nullptr;
+    u.bytes = 0;
+    const hipError_t e = hipMalloc(&u.p, bytes);
+    if (e != hipSuccess) return sfail(b, -2, "emx_summary_batch: %s allocation (%zu bytes): %s", what, bytes, hipGetErrorString(e));
+    u.bytes = bytes;
+    return 0;
+}
+
+#define SUM_HIP(what, expr)                                                                                            \
+    do {                                                                                                               \
+        const hipError_t e_ = (expr);                                                                                  \
+        if (e_ != hipSuccess) return sfail(b, -2, "emx_summary_batch: %s: %s", what, hipGetErrorString(e_));           \
+    } while (0)
+
+}  // namespace
+
+struct BatchSummary {
+    Buf mpart, gpart, mean, cov, order, map_x, map_lp, hist, prefix, rem, leader, ranks;
+};
+
+void emx_internal_batch_summary_release(BatchSummary* s) {
+    if (!s) return;
+    for (Buf* u : {&s->mpart, &s->gpart, &s->mean, &s->cov, &s->order, &s->map_x, &s->map_lp, &s->hist, &s->prefix, &s->rem, &s->leader,
+                   &s->ranks})
+        if (u->p) hipFree(u->p);
+    delete s;
+}
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int emx_summary_batch(emx_batch* b, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop, int64_t stride, double* mean_out,
+                      double* cov_out, int32_t nranks, const int64_t* ranks, double* order_out, double* map_coords_out,
+                      double* map_log_prob_out, int64_t* nsamples_out) {
+    EmxBatchView v;
+    if (emx_internal_batch_view(b, &v)) return -1;
+    if (!(0 <= member_lo && member_lo < member_hi && member_hi <= v.B))
+        return sfail(b, -1, "emx_summary_batch: members [%d, %d) outside [0, %d) or empty", member_lo, member_hi, v.B);
+    if (!v.chain || !v.chain_lp || v.stored <= 0) return sfail(b, -1, "emx_summary_batch: no stored chain (emx_batch_chain_config + a stored run)");
+    if (stride < 1 || start < 0 || stop > v.stored) return sfail(b, -1, "emx_summary_batch: rows need 0 <= start, stop <= stored, stride >= 1");
+    const int64_t nt = start < stop ? (stop - start + stride - 1) / stride : 0;
+    const int64_t N = v.N, D = v.D, ND = N * D, M = member_hi - member_lo, n = nt * N;
+    if (nsamples_out) *nsamples_out = n;
+    if (nt < 1) return sfail(b, -1, "emx_summary_batch: the selection is empty");
+    if (nranks < 0 || nranks > SEL_MAX_RANKS || (nranks > 0 && !ranks))
+        return sfail(b, -1, "emx_summary_batch: 0 ... %d ranks", SEL_MAX_RANKS);
+    for (int r = 0; r < nranks; ++r)
+        if (ranks[r] < 0 || ranks[r] >= n) return sfail(b, -1, "emx_summary_batch: rank %lld outside [0, %lld)", (long long)ranks[r], (long long)n);
+    const bool want_cov = cov_out != nullptr, want_mean = mean_out != nullptr || want_cov;
+    const bool want_sel = order_out != nullptr && nranks > 0, want_map = map_coords_out != nullptr || map_log_prob_out != nullptr;
+    const int nr = want_sel ? nranks : 0;
+
+    // slices: R rows each, from nt alone (grid.y <= 65 535)
+    int64_t R = 256;
+    while ((nt + R - 1) / R > 65535) R *= 2;
+    const int64_t S = (nt + R - 1) / R;
+    const bool mfma = D >= 16;
+    const int Dp = (int)((D + 15) / 16 * 16), DPB = Dp / 16, NP = DPB * (DPB + 1) / 2, P = (int)(D * (D + 1) / 2);
+    const size_t gram_member = want_cov ? (size_t)S * (mfma ? (size_t)NP * 256 : (size_t)P) * 8 : 0;
+    const size_t sel_member = (size_t)D * nr * (256 * 8 + 8 + 8 + 4);
+    const size_t per_member = (want_mean ? (size_t)S * ND * 8 : 0) + gram_member + sel_member + (size_t)(D * D + nr * D + 2 * D + 1) * 8;
+    int64_t mp = std::max<int64_t>(1, (int64_t)(((size_t)512 << 20) / per_member));
+    mp = std::min<int64_t>(mp, std::min<int64_t>(M, 65535));
+    if (v.summary_members > 0) mp = std::min<int64_t>(mp, v.summary_members);
+
+    SUM_HIP("hipSetDevice", hipSetDevice(v.device));
+    if (!*v.summary) *v.summary = new BatchSummary();
+    BatchSummary* a = *v.summary;
+    if (want_mean) {
+        if (int rc = grow(b, a->mpart, (size_t)mp * S * ND * 8, "mean slab")) return rc;
+        if (int rc = grow(b, a->mean, (size_t)mp * D * 8, "mean")) return rc;
+    }
+    if (want_cov) {
+        if (int rc = grow(b, a->gpart, (size_t)mp * gram_member, "Gram slab")) return rc;
+        if (int rc = grow(b, a->cov, (size_t)mp * D * D * 8, "covariance")) return rc;
+    }
+    if (want_map) {
+        if (int rc = grow(b, a->map_x, (size_t)mp * D * 8, "MAP coordinates")) return rc;
+        if (int rc = grow(b, a->map_lp, (size_t)mp * 8, "MAP log-prob")) return rc;
+    }
+    if (want_sel) {
+        const size_t slots = (size_t)mp * D * nr;
+        if (int rc = grow(b, a->hist, slots * 256 * 8, "histograms")) return rc;
+        if (int rc = grow(b, a->prefix, slots * 8, "prefixes")) return rc;
+        if (int rc = grow(b, a->rem, slots * 8, "ranks left")) return rc;
+        if (int rc = grow(b, a->leader, slots * 4, "leaders")) return rc;
+        if (int rc = grow(b, a->order, slots * 8, "order statistics")) return rc;
+        if (int rc = grow(b, a->ranks, (size_t)SEL_MAX_RANKS * 8, "ranks")) return rc;
+        SUM_HIP("copy", hipMemcpyAsync(a->ranks.p, ranks, (size_t)nr * 8, hipMemcpyHostToDevice, v.stream));
+    }
+    const int DT = nr ? (int)std::min<int64_t>(D, std::max(1, SEL_MAX_RANKS / nr)) : 1;      // dims a histogram workgroup: DT nr <= 32 slots
+
+    Sel g;
+    g.chain = v.chain;
+    g.chain_lp = v.chain_lp;
+    g.cap = v.cap;
+    g.N = N;
+    g.ND = ND;
+    g.t0 = start;
+    g.stride = stride;
+    g.nt = nt;
+    g.R = R;
+    g.D = (int32_t)D;
+    g.S = (int32_t)S;
+    auto blocks = [](int64_t count, int64_t per) { return dim3((unsigned)((count + per - 1) / per)); };
+    for (int64_t m0 = member_lo; m0 < member_hi; m0 += mp) {
+        const int64_t mc = std::min<int64_t>(mp, member_hi - m0), mo = m0 - member_lo;
+        g.m0 = m0;
+        const dim3 slices_j((unsigned)((ND + 63) / 64), (unsigned)S, (unsigned)mc);
+        if (want_mean) {
+            hipLaunchKernelGGL(k_bsum_mean_part, slices_j, dim3(256), 0, v.stream, g, (double*)a->mpart.p);
+            SUM_HIP("mean launch", hipGetLastError());
+            hipLaunchKernelGGL(k_bsum_mean_fin, blocks(mc * D, 256), dim3(256), 0, v.stream, g, (const double*)a->mpart.p, (double*)a->mean.p, mc);
+            SUM_HIP("mean launch", hipGetLastError());
+            if (mean_out) SUM_HIP("copy", hipMemcpyAsync(mean_out + mo * D, a->mean.p, (size_t)mc * D * 8, hipMemcpyDeviceToHost, v.stream));
+        }
+        if (want_cov) {
+            if (mfma) {
+                hipLaunchKernelGGL(k_bsum_gram_mfma, dim3((unsigned)((NP + GM_PAIRS_WG - 1) / GM_PAIRS_WG), (unsigned)S, (unsigned)mc), dim3(256), 0,
+                                   v.stream, g, (const double*)a->mean.p, (double*)a->gpart.p, Dp, NP);
+                SUM_HIP("Gram launch", hipGetLastError());
+                hipLaunchKernelGGL(k_bsum_gram_fin_mfma, blocks(mc * NP * 256, 256), dim3(256), 0, v.stream, g, (const double*)a->gpart.p,
+                                   (double*)a->cov.p, mc, Dp, NP);
+            } else {
+                hipLaunchKernelGGL(k_bsum_gram_small, dim3(1, (unsigned)S, (unsigned)mc), dim3(256), 0, v.stream, g, (const double*)a->mean.p,
+                                   (double*)a->gpart.p);
+                SUM_HIP("Gram launch", hipGetLastError());
+                hipLaunchKernelGGL(k_bsum_gram_fin_small, blocks(mc * P, 256), dim3(256), 0, v.stream, g, (const double*)a->gpart.p, (double*)a->cov.p,
+                                   mc);
+            }
+            SUM_HIP("Gram launch", hipGetLastError());
+            SUM_HIP("copy", hipMemcpyAsync(cov_out + mo * D * D, a->cov.p, (size_t)mc * D * D * 8, hipMemcpyDeviceToHost, v.stream));
+        }
+        if (want_map) {
+            hipLaunchKernelGGL(k_bsum_map, dim3((unsigned)mc), dim3(256), 0, v.stream, g, (double*)a->map_x.p, (double*)a->map_lp.p);
+            SUM_HIP("MAP launch", hipGetLastError());
+            if (map_coords_out)
+                SUM_HIP("copy", hipMemcpyAsync(map_coords_out + mo * D, a->map_x.p, (size_t)mc * D * 8, hipMemcpyDeviceToHost, v.stream));
+            if (map_log_prob_out)
+                SUM_HIP("copy", hipMemcpyAsync(map_log_prob_out + mo, a->map_lp.p, (size_t)mc * 8, hipMemcpyDeviceToHost, v.stream));
+        }
+        if (want_sel) {
+            const int64_t slots = mc * D * nr;
+            hipLaunchKernelGGL(k_bsum_sel_init, blocks(slots, 256), dim3(256), 0, v.stream, (u64*)a->prefix.p, (int64_t*)a->rem.p,
+                               (int32_t*)a->leader.p, (const int64_t*)a->ranks.p, nr, slots);
+            SUM_HIP("selection launch", hipGetLastError());
+            for (int pass = 0; pass < SEL_PASSES; ++pass) {
+                SUM_HIP("memset", hipMemsetAsync(a->hist.p, 0, (size_t)slots * 256 * 8, v.stream));
+                hipLaunchKernelGGL(k_bsum_hist, dim3((unsigned)((D + DT - 1) / DT), (unsigned)S, (unsigned)mc), dim3(256), 0, v.stream, g,
+                                   (const u64*)a->prefix.p, (const int32_t*)a->leader.p, (u64*)a->hist.p, nr, DT, pass);
+                SUM_HIP("histogram launch", hipGetLastError());
+                hipLaunchKernelGGL(k_bsum_scan, blocks(mc * D, 64), dim3(64), 0, v.stream, (u64*)a->prefix.p, (int64_t*)a->rem.p, (int32_t*)a->leader.p,
+                                   (const u64*)a->hist.p, (double*)a->order.p, nr, (int)D, mc * D, pass);
+                SUM_HIP("scan launch", hipGetLastError());
+            }
+            SUM_HIP("copy", hipMemcpyAsync(order_out + mo * nr * D, a->order.p, (size_t)slots * 8, hipMemcpyDeviceToHost, v.stream));
+        }
+        // the pass's outputs leave before the next pass reuses the buffers
+        SUM_HIP("synchronize", hipStreamSynchronize(v.stream));
+    }
+    return 0;
+}
+
+int emx_host_order_stats(const double* x, int64_t n, int64_t stride, int32_t nranks, const int64_t* ranks, double* out) {
+    if (!x || n < 1 || stride < 1 || nranks < 0 || nranks > SEL_MAX_RANKS || (nranks > 0 && (!ranks || !out))) return -1;
+    for (int r = 0; r < nranks; ++r)
+        if (ranks[r] < 0 || ranks[r] >= n) return -1;
+    const int nr = nranks;
+    u64 prefix[SEL_MAX_RANKS];
+    int64_t rem[SEL_MAX_RANKS];
+    int32_t leader[SEL_MAX_RANKS];
+    for (int r = 0; r < nr; ++r) {
+        prefix[r] = 0;
+        rem[r] = ranks[r];
+        leader[r] = 0;
+    }
+    std::vector<u64> hist((size_t)SEL_MAX_RANKS * 256);
+    for (int pass = 0; pass < SEL_PASSES; ++pass) {
+        const int shift = 56 - 8 * pass;
+        std::fill(hist.begin(), hist.end(), 0);
+        for (int64_t i = 0; i < n; ++i) {
+            u64 bits;
+            std::memcpy(&bits, x + i * stride, 8);
+            const u64 key = sel_key(bits), hi = pass ? key >> (shift + 8) : 0;
+            const unsigned digit = (unsigned)(key >> shift) & 255u;
+            for (int r = 0; r < nr; ++r)
+                if (leader[r] == r && (pass ? prefix[r] >> (shift + 8) : 0) == hi) ++hist[(size_t)r * 256 + digit];
+        }
+        for (int r = 0; r < nr; ++r) prefix[r] |= (u64)sel_scan_bins(&hist[(size_t)leader[r] * 256], &rem[r]) << shift;
+        sel_leaders(prefix, leader, nr);
+    }
+    for (int r = 0; r < nr; ++r) {
+        const u64 bits = sel_unkey(prefix[r]);
+        std::memcpy(out + r, &bits, 8);
+    }
+    return 0;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -36,19 +36,25 @@ extern FftApi g_fft;
 constexpr int FFT_D2Z = 0x6a, FFT_Z2D = 0x6c;
 int fft_load(const char* path, std::string& err);      // 0, or -5 with the reason in err
 
-// ---- the batch handle seen from emx_batch_acf.hip (the handle itself lives in emx_batch.hip)
+// ---- the batch handle seen from emx_batch_acf.hip and emx_batch_summary.hip (the handle itself lives in emx_batch.hip)
 struct BatchAcf;     // emx_autocorr_batch's hipFFT plans and scratch, kept on the handle between calls
+struct BatchSummary;     // emx_summary_batch's scratch (emx_batch_summary.hip), kept on the handle between calls
 struct EmxBatchView {
     const double* chain;     // (B, cap, N, D) member-major, or nullptr
+    const double* chain_lp;  // (B, cap, N)
     int32_t B, D;
     int64_t N, cap, stored;
     int64_t acf_series;      // tuning "batch_acf_series" (0: auto)
     hipStream_t stream;
     int device;
     BatchAcf** acf;          // the handle's slot (nullptr until the first call)
+    int64_t summary_members; // tuning "batch_summary_members" (0: auto)
+    BatchSummary** summary;  // the handle's slot (nullptr until the first call)
 };
 // implemented in emx_batch.hip
 int emx_internal_batch_view(emx_batch* b, EmxBatchView* v);
 int emx_internal_batch_fail(emx_batch* b, int code, const char* msg);      // records the message for emx_batch_last_error, returns code
 // implemented in emx_batch_acf.hip: destroys the plans and frees the scratch (emx_batch_destroy)
 void emx_internal_batch_acf_release(BatchAcf* a);
+// implemented in emx_batch_summary.hip: frees the scratch (emx_batch_destroy)
+void emx_internal_batch_summary_release(BatchSummary* s);

@@ -407,6 +407,13 @@ class PTSampler(object):
         tau = self._b.get_autocorr_time(discard=discard, thin=thin, c=c, tol=tol, quiet=quiet, on_device=on_device)
         return tau.reshape(self.nbatch, self.ntemps, self.ndim)
 
+    def get_summary(self, discard=0, thin=1, quantiles=(0.16, 0.5, 0.84), cov=True):
+        """:meth:`EnsembleBatch.get_summary` of every rung, with ``(nbatch, ntemps, ...)`` leading axes.  The best sample is
+        taken on the stored tempered log-prob (rung 0 is the posterior)."""
+        r = self._b.get_summary(discard=discard, thin=thin, quantiles=quantiles, cov=cov)
+        lead = (self.nbatch, self.ntemps)
+        return type(r)(r.nsamples, *[None if a is None else a.reshape(lead + a.shape[1:]) for a in r[1:]])
+
     def mean_log_likelihood(self, discard=0):
         """``(nbatch, ntemps)``: the mean of ``L`` over the stored steps from ``discard`` on and every walker, on the device."""
         it = self.iteration

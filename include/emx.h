@@ -512,7 +512,9 @@ int64_t emx_host_pull_capacity(int64_t nwalkers, int32_t world, int32_t nsplits,
  *   auto: up to one member a CU, the single-ensemble shape (small_threads / small_batch); more members than CUs, one
  *   half-step's lanes and one plan entry a thread, so that several members share a CU.
  *   "batch_acf_series"   0 (auto)  emx_autocorr_batch: at most this many (member, walker, dim) series per FFT chunk (auto: the
- *                                  scratch within ~3 GB); a chunk may begin and end inside a member */
+ *                                  scratch within ~3 GB); a chunk may begin and end inside a member
+ *   "batch_summary_members" 0 (auto) emx_summary_batch: at most this many members per pass (auto: the scratch within ~512 MB);
+ *                                  every member is reduced on its own in an order fixed by its shape, so no bit depends on it */
 typedef struct emx_batch emx_batch;
 /* host only (no device touched): 0 when the kernel takes the shape, else -1 and the reason in msg */
 int emx_batch_check(int64_t nwalkers, int32_t ndim, int32_t target, int32_t nmoves, const emx_move_desc* moves, char* msg,
@@ -567,6 +569,25 @@ int emx_batch_chain_read(emx_batch* b, int32_t what, int32_t member_lo, int32_t 
  * when 2 next_pow_two(nt) changes); libhipfft as emx_autocorr (emx_fft_load), -5 when it cannot be loaded. */
 int emx_autocorr_batch(emx_batch* b, int32_t member_lo, int32_t member_hi, int64_t discard, int64_t thin, double c,
                        double* tau_out, int32_t* window_out, int64_t* nsamples_out);
+/* Posterior summaries of members [member_lo, member_hi) over rows start, start + stride, ... < stop of each
+ * (emx_batch_chain_read's selection) and every walker, n = rows * nwalkers samples a member, computed next to the chain
+ * (csrc/emx_batch_summary.hip): only O(members ndim^2) numbers cross to the host.  Any output may be NULL.
+ *   mean_out (members, ndim); cov_out (members, ndim, ndim) the ddof = 1 covariance, exactly symmetric (NaN for n = 1);
+ *   ranks (nranks <= 32, each in [0, n)): order_out (members, nranks, ndim) holds the ranks[r]-th smallest stored value of every
+ *   parameter (0-based; exactly a stored value; of -0.0 and +0.0, which sort apart here and compare equal, either);
+ *   map_coords_out (members, ndim), map_log_prob_out (members): the sample of the largest stored log-prob, the first in
+ *   (row, walker) order (-inf is a value like any other); *nsamples_out = n.
+ * Sums run in an order fixed by (rows, nwalkers, ndim) alone and the selection counts integers: the results do not depend on
+ * the member range or on "batch_summary_members".  Scratch stays on the handle.  -1 for bad arguments, -2 for a device failure.
+ * (Named like emx_autocorr_batch: the emx_batch_ prefix is the handle's own closed set of entry points, which
+ * tests/test_batch_cpu.py pins.) */
+int emx_summary_batch(emx_batch* b, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop, int64_t stride,
+                      double* mean_out, double* cov_out, int32_t nranks, const int64_t* ranks, double* order_out,
+                      double* map_coords_out, double* map_log_prob_out, int64_t* nsamples_out);
+/* host twin of the selection (no device): the ranks[r]-th smallest of x[0], x[stride], ..., n values, with the same key
+ * transform and digit search as the kernels.  0, or -1 for bad arguments (n < 1, stride < 1, nranks outside [0, 32], a rank
+ * outside [0, n)). */
+int emx_host_order_stats(const double* x, int64_t n, int64_t stride, int32_t nranks, const int64_t* ranks, double* out);
 int emx_batch_accepted_counts(emx_batch* b, double* out);           /* (B, nwalkers) */
 /* bits[B]: each member's status (emx_status's bits), read and cleared */
 int emx_batch_status(emx_batch* b, uint32_t* bits);
