@@ -13,6 +13,7 @@ from .ensemble import EnsembleSampler, walkers_independent
 from .pt import PTSampler
 from .state import State
 from .summary import BatchSummary
+from .targets import get_include
 
 __all__ = ["EnsembleSampler", "EnsembleBatch", "BatchSummary", "PTSampler", "walkers_independent", "State", "moves", "autocorr", "backends", "summary", "targets",
-           "__version__"]
+           "get_include", "__version__"]

@@ -8,6 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libemx.so")
 
 TARGET_HOST, TARGET_ISO, TARGET_DIAG, TARGET_DENSE, TARGET_ROSENBROCK, TARGET_BOX, TARGET_CALLBACK = range(7)
+TARGET_FUSED_USER = 8               # batches only (emx_set_batch_target_fused); 7 is taken inside the kernels
 MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER, MOVE_GAUSS = range(4)
 MOVE_WALK, MOVE_KDE = 5, 6          # native (Philox) mode only; 4 is not a public kind
 KDE_BW_SCOTT, KDE_BW_SILVERMAN, KDE_BW_SCALAR = range(3)
@@ -31,6 +32,8 @@ _lib = None
 DEVICE_LOG_PROB_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p)
 # emx_batch_log_prob_fn: (user, coords_dev, nbatch, rows, ndim, log_prob_dev, hip_stream) -> int
 BATCH_LOG_PROB_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p)
+# emx_fused_batch_fn: (const emx_fused_launch*) -> int
+FUSED_BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 
 _P = C.c_void_p
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -170,6 +173,7 @@ SIGNATURES = {
     "emx_batch_status": (C.c_int, [_P, _u32p]),
     "emx_batch_launch_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "emx_set_batch_target_callback": (C.c_int, [_P, BATCH_LOG_PROB_FN, _P]),
+    "emx_set_batch_target_fused": (C.c_int, [_P, FUSED_BATCH_FN, C.c_int32, _P]),
     "emx_pt_set_tempering": (C.c_int, [_P, C.c_int32, _dp, _P, _P]),
     "emx_set_batch_prior_callback": (C.c_int, [_P, BATCH_LOG_PROB_FN, _P]),
     "emx_pt_set_swap_every": (C.c_int, [_P, C.c_int64]),

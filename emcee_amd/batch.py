@@ -11,7 +11,8 @@ the sampler built with the same target, moves and initial state whose private ge
 
 Philox mode only; fused device targets (``IsoGaussian``, ``DiagGaussian``, ``DenseGaussian``, ``Rosenbrock``,
 ``UniformBox``); stretch, DE, snooker and Gaussian moves; every member must fit one workgroup (``nwalkers <= 4096``,
-``ndim <= 256`` and the LDS bound).
+``ndim <= 256`` and the LDS bound).  A :class:`~emcee_amd.targets.BatchFused` -- the user's per-row ``__device__`` function
+compiled into that kernel (:func:`~emcee_amd.targets.compile_fused`) -- runs the same way, at the same one launch per chunk.
 
 The user's own model -- one fit per catalogue object, with per-object data -- is a
 :class:`~emcee_amd.targets.BatchCallable` (or its native form, :class:`~emcee_amd.targets.BatchKernel`): one function called
@@ -33,7 +34,7 @@ from . import summary as _summary
 from .autocorr import integrated_time
 from .ensemble import _native_desc, _parse_move_schedule, _refuse_extended_precision, philox_seed, walkers_independent
 from .state import State
-from .targets import (BatchKernel, BatchTarget, DenseGaussian, DeviceCallable, DeviceKernel, DeviceTarget, DiagGaussian, IsoGaussian,
+from .targets import (BatchFused, BatchKernel, BatchTarget, DenseGaussian, DeviceCallable, DeviceKernel, DeviceTarget, DiagGaussian, IsoGaussian,
                       Rosenbrock, UniformBox)
 
 __all__ = ["EnsembleBatch"]
@@ -52,8 +53,8 @@ class EnsembleBatch(object):
     """B independent ensembles of ``nwalkers`` walkers in ``ndim`` dimensions, run together on one GPU.
 
     ``target``: one :class:`~emcee_amd.targets.DeviceTarget` for every member, or a sequence of B targets of one class (one
-    per member); or one :class:`~emcee_amd.targets.BatchCallable` / :class:`~emcee_amd.targets.BatchKernel` evaluating every
-    member (its per-member parameters are its own).  ``moves``: the schedule forms of :class:`~emcee_amd.EnsembleSampler` over StretchMove, DEMove,
+    per member); or one :class:`~emcee_amd.targets.BatchCallable` / :class:`~emcee_amd.targets.BatchKernel` /
+    :class:`~emcee_amd.targets.BatchFused` evaluating every member (its per-member parameters are its own).  ``moves``: the schedule forms of :class:`~emcee_amd.EnsembleSampler` over StretchMove, DEMove,
     DESnookerMove and GaussianMove.  ``seeds``: B integers; member b draws as a sampler whose generator was seeded with
     ``np.random.RandomState(seeds[b])``.  ``None`` draws them from NumPy's global state."""
 
@@ -98,6 +99,8 @@ class EnsembleBatch(object):
 
     # ------------------------------------------------------------------ argument checks (no device involved)
     def _parse_targets(self, target):
+        if isinstance(target, BatchFused) and target.ndim != self.ndim:
+            raise ValueError("the BatchFused target was compiled for ndim %d; the batch has ndim %d" % (target.ndim, self.ndim))
         if isinstance(target, BatchTarget):
             return [target], False
         if isinstance(target, DeviceTarget) or callable(target):
@@ -155,7 +158,9 @@ class EnsembleBatch(object):
         if lib.emx_batch_create(self.device, self.nbatch, self.nwalkers, self.ndim, C.byref(h)) != 0:
             raise _lib.EmxError("emx_batch_create failed (no usable HIP device %d, or out of memory)" % self.device)
         self._h = h
-        if isinstance(self._targets[0], BatchTarget):
+        if isinstance(self._targets[0], BatchFused):
+            self._bind_user_fused(h)
+        elif isinstance(self._targets[0], BatchTarget):
             self._bind_callback(h)
         else:
             self._bind_fused(h)
@@ -194,6 +199,12 @@ class EnsembleBatch(object):
             fn, user = _lib.BATCH_LOG_PROB_FN(_trampoline(t.fn, self.device, self._cb_box)), None
         self._cb_keep = fn                # the library holds the pointer: keep the object alive
         self._ck(self._lib().emx_set_batch_target_callback(h, fn, user))
+
+    def _bind_user_fused(self, h):
+        t = self._targets[0]
+        fn = t.fn_ptr if isinstance(t.fn_ptr, _lib.FUSED_BATCH_FN) else C.cast(t.fn_ptr, _lib.FUSED_BATCH_FN)
+        self._cb_keep = (fn, t)           # the library holds the launcher and the user's device pointer: keep both alive
+        self._ck(self._lib().emx_set_batch_target_fused(h, fn, t.ndim, C.c_void_p(t.user_address())))
 
     def set_tuning(self, key, value):
         """``"batch_threads"`` / ``"batch_plan_steps"`` (include/emx.h): the launch shape; ``"batch_acf_series"``: series per

@@ -4,6 +4,8 @@
 // ensemble, so every member's bits are those of an emx_ctx with the same seed, target and initial state.  Philox mode only.
 // Host side of the handle and the batched instantiations of the kernel (emx_small_launch.hpp).  With the caller's batched
 // log-prob (emx_set_batch_target_callback) a run is k_batch_cb launches and calls of that function instead (emx_batch_cb.hip).
+// With a fused user target (emx_set_batch_target_fused) the launch is the caller's own instantiation of k_small_run around their
+// device function (emx_fused_target.hpp), through the launcher their translation unit exports; everything else is shared.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,6 +18,7 @@
 
 #include "../../include/emx.h"
 #include "emx_batch_cb.hpp"
+#include "emx_fused_target.hpp"
 #include "emx_internal.hpp"
 #include "emx_pt.hpp"
 #include "emx_rng.hpp"
@@ -66,6 +69,9 @@ struct emx_batch {
     double *cb_q = nullptr, *cb_lp = nullptr, *cb_fac = nullptr, *cb_logu = nullptr;
     int32_t *cb_wi = nullptr, *cb_nrows = nullptr;
     size_t cb_rows = 0;       // B R rows allocated
+    // EMX_TARGET_FUSED_USER: the caller's launcher of k_small_run around their device function, and their device pointer
+    emx_fused_batch_fn fused_fn = nullptr;
+    const void* fused_user = nullptr;
     // emx_autocorr_batch (emx_batch_acf.hip): its hipFFT plans and scratch; tuning "batch_acf_series" (0: auto)
     BatchAcf* acf = nullptr;
     int64_t tune_acf_series = 0;
@@ -111,6 +117,16 @@ int fail(emx_batch* b, int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(b, -2, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// splits of a move (a Gaussian move is one split of the whole ensemble)
+int move_splits(const emx_move_desc& mv) { return mv.kind == EMX_MOVE_GAUSS ? 1 : (int)mv.nsplits; }
+
+// rows of a fused user target's staging area: the largest split of the schedule
+int64_t fused_stage_rows(int64_t N, int32_t nmoves, const emx_move_desc* moves) {
+    int smin = 1 << 30;
+    for (int m = 0; m < nmoves; ++m) smin = std::min(smin, std::max(1, move_splits(moves[m])));
+    return nmoves > 0 ? (N + smin - 1) / smin : N;
+}
+
 // small_eligible's rules (emx.hip) applied to one member's shape; nullptr when the kernel takes it, else why not
 const char* shape_refusal(int64_t N, int32_t D, int32_t target, int32_t nmoves, const emx_move_desc* moves, char* buf, size_t n) {
     if (N < 2 || D < 1) return "nwalkers must be >= 2 and ndim >= 1";
@@ -119,10 +135,11 @@ const char* shape_refusal(int64_t N, int32_t D, int32_t target, int32_t nmoves, 
         return buf;
     }
     const bool callback = target == EMX_TARGET_DEVICE_CALLBACK;      // the caller's batched log-prob (k_batch_cb)
-    if (!callback && target != EMX_TARGET_ISO_GAUSS && target != EMX_TARGET_DIAG_GAUSS && target != EMX_TARGET_DENSE_GAUSS &&
+    const bool fused_user = target == EMX_TARGET_FUSED_USER;         // the caller's device function inside k_small_run
+    if (!callback && !fused_user && target != EMX_TARGET_ISO_GAUSS && target != EMX_TARGET_DIAG_GAUSS && target != EMX_TARGET_DENSE_GAUSS &&
         target != EMX_TARGET_ROSENBROCK && target != EMX_TARGET_BOX)
         return "the batch runs the fused device targets only (IsoGaussian, DiagGaussian, DenseGaussian, Rosenbrock, UniformBox) "
-               "or a batched callback (emx_set_batch_target_callback)";
+               "or a batched callback (emx_set_batch_target_callback) or a fused user target (emx_set_batch_target_fused)";
     if (nmoves < 1 || nmoves > SMALL_MAX_MOVES) {
         snprintf(buf, n, "the batch takes 1 ... %d moves; got %d", SMALL_MAX_MOVES, nmoves);
         return buf;
@@ -140,6 +157,15 @@ const char* shape_refusal(int64_t N, int32_t D, int32_t target, int32_t nmoves, 
             return "with a batched callback target a GaussianMove runs only as the one move of the schedule";
     }
     if (callback) return nullptr;         // k_batch_cb keeps no member in LDS
+    if (fused_user) {                     // the member, at least one step's plans and the staging rows of the largest split
+        const size_t need = small_lds_bytes(N, D, 0, 0, 1) + small_fused_stage_bytes(fused_stage_rows(N, nmoves, moves), D);
+        if (need > SMALL_LDS_MAX) {
+            snprintf(buf, n, "nwalkers x ndim = %lld x %d with a fused user target does not fit one workgroup's LDS (%zu bytes > %zu)",
+                     (long long)N, D, need, SMALL_LDS_MAX);
+            return buf;
+        }
+        return nullptr;
+    }
     if (target == EMX_TARGET_DENSE_GAUSS) {
         const int Dp = (D + 15) / 16 * 16;
         if (Dp > DENSE_FUSED_MAX_DP || N * (int64_t)Dp * Dp > 65536 || small_lds_bytes(N, D, Dp, 1) > SMALL_LDS_MAX) {
@@ -170,7 +196,8 @@ int grow(emx_batch* b, T*& p, size_t& cap, size_t n) {
 // has no more members than the device has CUs, each member has a CU of its own and the single-ensemble (latency) shape
 // is kept; beyond, the workgroup is cut to one half-step's lanes (>= one wave) with plan steps for one entry a thread, so
 // that several members share a CU (32 waves, 160 KB of LDS).  Neither changes a bit: plans do not depend on the state.
-void launch_shape(const emx_batch* b, int num_cu, const Shape& sh, int minsplits, bool dense, int* threads, int* plan_steps) {
+// extra_lds: a fused user target's staging area, on top of small_lds_bytes.
+void launch_shape(const emx_batch* b, int num_cu, const Shape& sh, int minsplits, bool dense, size_t extra_lds, int* threads, int* plan_steps) {
     int t = small_threads(b->N, b->D, b->Dp, sh.G, minsplits, dense), ps = small_batch(b->N);
     if (b->B > num_cu) {
         const int64_t nsmax = (b->N + minsplits - 1) / minsplits;
@@ -182,9 +209,25 @@ void launch_shape(const emx_batch* b, int num_cu, const Shape& sh, int minsplits
     if (b->tune_plan_steps > 0) ps = (int)b->tune_plan_steps;
     if (dense)      // one LDS tile per wave
         while (t > 64 && small_lds_bytes(b->N, b->D, b->Dp, t / 64, ps) > SMALL_LDS_MAX) t = (t / 64 + 1) / 2 * 64;
-    while (ps > 1 && small_lds_bytes(b->N, b->D, dense ? b->Dp : 0, t / 64, ps) > SMALL_LDS_MAX) ps = (ps + 1) / 2;
+    while (ps > 1 && small_lds_bytes(b->N, b->D, dense ? b->Dp : 0, t / 64, ps) + extra_lds > SMALL_LDS_MAX) ps = (ps + 1) / 2;
     *threads = t;
     *plan_steps = ps;
+}
+
+// what a fused user target's launcher answered (include/emx.h: emx_fused_batch_fn), as the handle's error; 0: it launched (or probed)
+int fused_refusal(emx_batch* b, int rc, int movesel) {
+    if (rc == 0) return 0;
+    if (rc == 1)
+        return fail(b, -8, "the fused user target's launcher was built against another version of emx_fused_target.hpp (the library has "
+                           "EMX_FUSED_ABI %u and %zu bytes of kernel arguments): rebuild it with this library's headers",
+                    (unsigned)EMX_FUSED_ABI, sizeof(SmallRunArgs));
+    if (rc == 2) return fail(b, -1, "the fused user target's launcher was compiled for another ndim than the batch's %d", b->D);
+    if (rc == 3)
+        return fail(b, -1, "the fused user target's launcher does not carry the kernel of this schedule (move selector %d): compile it with "
+                           "EMX_FUSED_MOVES_ANY", movesel);
+    if (rc >= 100)
+        return fail(b, -2, "k_small_run fused user target launch failed (ndim=%d): %s", b->D, hipGetErrorString((hipError_t)(rc - 100)));
+    return fail(b, -7, "the fused user target's launcher failed (returned %d)", rc);
 }
 
 // one launch: `nsteps` steps (nsteps 0 with eval0: the initial log-probs only)
@@ -273,16 +316,40 @@ int launch(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t st
     hipDeviceProp_t prop;
     int num_cu = 256;
     if (hipGetDeviceProperties(&prop, b->device) == hipSuccess) num_cu = prop.multiProcessorCount;
+    const bool fused_user = b->target == EMX_TARGET_FUSED_USER;
+    if (fused_user) {
+        BNEED(b, b->fused_fn != nullptr, "fused user target without a launcher (emx_set_batch_target_fused)");
+        a.target = TGT_USER;
+        a.user = b->fused_user;
+        a.stage_rows = (int32_t)fused_stage_rows(b->N, nm, b->moves.data());
+    }
+    const size_t extra_lds = fused_user ? small_fused_stage_bytes(a.stage_rows, b->D) : 0;
     int threads = 0, plan_steps = 0;
-    launch_shape(b, num_cu, sh, minsplits, dense, &threads, &plan_steps);
+    launch_shape(b, num_cu, sh, minsplits, dense, extra_lds, &threads, &plan_steps);
     a.batch = plan_steps;
-    const size_t lds = small_lds_bytes(b->N, b->D, dense ? b->Dp : 0, threads / 64, plan_steps);
+    const size_t lds = small_lds_bytes(b->N, b->D, dense ? b->Dp : 0, threads / 64, plan_steps) + extra_lds;
     BNEED(b, lds <= SMALL_LDS_MAX && threads >= 64 && threads <= 1024 && threads % 64 == 0,
           "batch launch shape: %d threads and %d plan steps need %zu bytes of LDS", threads, plan_steps, lds);
-    const int movesel = (nm == 1 && (!dense || b->moves[0].kind == EMX_MOVE_STRETCH)) ? (int)b->moves[0].kind : SMALL_ANY_MOVE;
-    const hipError_t e = small_dispatch<true>(sh.G, sh.V, sh.CH, dense ? b->Dp / 16 : 0, movesel, b->B, threads, lds, b->stream, a);
-    if (e != hipSuccess)
-        return fail(b, -2, "k_small_run batch launch failed (G=%d V=%d CH=%d ndim=%d): %s", sh.G, sh.V, sh.CH, b->D, hipGetErrorString(e));
+    // (a fused user target's translation unit carries the single-StretchMove selector and the any-schedule one)
+    const int movesel = (nm == 1 && ((!dense && !fused_user) || b->moves[0].kind == EMX_MOVE_STRETCH)) ? (int)b->moves[0].kind : SMALL_ANY_MOVE;
+    if (fused_user) {
+        emx_fused_launch fl{};
+        fl.abi = EMX_FUSED_ABI;
+        fl.args_bytes = (uint32_t)sizeof(SmallRunArgs);
+        fl.ndim = b->D;
+        fl.movesel = movesel;
+        fl.grid = b->B;
+        fl.threads = threads;
+        fl.lds_bytes = lds;
+        fl.hip_stream = (void*)b->stream;
+        fl.args = &a;
+        fl.user = b->fused_user;
+        if (int rc = fused_refusal(b, b->fused_fn(&fl), movesel)) return rc;
+    } else {
+        const hipError_t e = small_dispatch<true>(sh.G, sh.V, sh.CH, dense ? b->Dp / 16 : 0, movesel, b->B, threads, lds, b->stream, a);
+        if (e != hipSuccess)
+            return fail(b, -2, "k_small_run batch launch failed (G=%d V=%d CH=%d ndim=%d): %s", sh.G, sh.V, sh.CH, b->D, hipGetErrorString(e));
+    }
     b->last_threads = threads;
     b->last_plan_steps = plan_steps;
     ++b->launches;
@@ -298,9 +365,6 @@ int launch(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t st
 }
 
 // ---- the caller's batched log-prob (EMX_TARGET_DEVICE_CALLBACK) ----
-
-// splits of a move (a Gaussian move is one split of the whole ensemble)
-int move_splits(const emx_move_desc& mv) { return mv.kind == EMX_MOVE_GAUSS ? 1 : (int)mv.nsplits; }
 
 // the caller's function on `rows` rows of every member: coords (B, rows, D) -> log_prob (B, rows), enqueued on the stream
 int call_back(emx_batch* b, const double* coords, int64_t rows, double* out) {
@@ -719,6 +783,38 @@ int emx_set_batch_target_callback(emx_batch* b, emx_batch_log_prob_fn fn, void* 
     return 0;
 }
 
+int emx_set_batch_target_fused(emx_batch* b, emx_fused_batch_fn fn, int32_t ndim_compiled, const void* user_dev) {
+    BNEED(b, fn != nullptr, "emx_set_batch_target_fused: no launcher");
+    BNEED(b, ndim_compiled == b->D, "the fused user target was compiled for ndim %d; the batch has ndim %d", ndim_compiled, b->D);
+    BNEED(b, b->pt_T == 0, "a tempered batch does not take a fused user target: the tempered commit and the swap pass belong to the "
+                           "batched callback path (emx_set_batch_target_callback)");
+    if (!b->moves.empty()) {
+        char buf[256];
+        const char* why = shape_refusal(b->N, b->D, EMX_TARGET_FUSED_USER, (int32_t)b->moves.size(), b->moves.data(), buf, sizeof buf);
+        BNEED(b, !why, "%s", why);
+    }
+    // the probe: abi, args_bytes and ndim against what the launcher was compiled with; nothing is launched
+    emx_fused_launch fl{};
+    fl.abi = EMX_FUSED_ABI;
+    fl.args_bytes = (uint32_t)sizeof(SmallRunArgs);
+    fl.ndim = b->D;
+    fl.movesel = MOVE_STRETCH;
+    if (int rc = fused_refusal(b, fn(&fl), fl.movesel)) return rc;
+    BHIP(b, hipSetDevice(b->device));
+    BHIP(b, hipStreamSynchronize(b->stream));
+    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
+        if (*p) {
+            hipFree(*p);
+            *p = nullptr;
+        }
+    b->tp0_stride = b->tp1_stride = 0;
+    b->fused_fn = fn;
+    b->fused_user = user_dev;
+    b->target = EMX_TARGET_FUSED_USER;
+    b->Dp = b->D;
+    return 0;
+}
+
 int emx_batch_set_moves(emx_batch* b, int32_t nmoves, const emx_move_desc* moves, const double* cdf) {
     BNEED(b, moves && cdf && nmoves >= 1, "need at least one move and its cdf");
     char buf[256];
@@ -907,6 +1003,8 @@ int emx_batch_launch_info(emx_batch* b, int32_t* threads, int32_t* plan_steps, i
 // ---- parallel tempering (emx_pt.hip) ----
 
 int emx_pt_set_tempering(emx_batch* b, int32_t ntemps, const double* betas, const double* box_lo, const double* box_hi) {
+    BNEED(b, b->target != EMX_TARGET_FUSED_USER, "tempering does not run a fused user target (emx_set_batch_target_fused): the tempered "
+                                                 "commit and the swap pass belong to the batched callback path (emx_set_batch_target_callback)");
     BNEED(b, b->target == EMX_TARGET_DEVICE_CALLBACK, "tempering needs a batched callback target (emx_set_batch_target_callback)");
     BNEED(b, ntemps >= 1 && b->B % ntemps == 0, "ntemps = %d does not divide the batch of %d members", ntemps, b->B);
     BNEED(b, !b->pt_adapt || ntemps <= PT_ADAPT_MAX_T, "an adaptive ladder has at most %d rungs; ntemps = %d", PT_ADAPT_MAX_T, ntemps);

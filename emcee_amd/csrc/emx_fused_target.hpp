@@ -1,0 +1,92 @@
+// Fused user targets of a batch of small ensembles (include/emx.h: emx_set_batch_target_fused; emcee_amd.targets.BatchFused /
+// compile_fused).  PUBLIC: this is the header a user's translation unit includes to compile their own per-row log-probability
+// into the one-workgroup kernel k_small_run (emx_kernels.hpp), and the library includes it for the version constants.
+//
+//     #include <emx_fused_target.hpp>             // hipcc --offload-arch=gfx950 -std=c++17 -ffp-contract=off -I include -I emcee_amd/csrc
+//     struct MyModel {                            // stateless; `user`: the device pointer given to BatchFused, `member`: the index in the batch
+//         __device__ double operator()(const double* x, int ndim, int member, const void* user) const;
+//     };
+//     EMX_FUSED_BATCH_TARGET(my_model, MyModel, /*ndim=*/5)       // emits: extern "C" int my_model(const emx_fused_launch*)
+//
+// `x` points at `ndim` doubles in LDS.  The call is made once per live row by ONE lane and must depend on nothing but its arguments
+// and memory reachable from `user`: no LDS of its own, no barrier, no cross-lane operation (its neighbours hold other rows, or are
+// idle).  -inf is legal, NaN raises the reference's error naming the member; a row with a non-finite coordinate is rejected
+// without being handed over.  `ndim` is fixed at compile time so that the translation unit carries ONE row layout's kernels:
+// by default the single-StretchMove selector and the any-schedule one (every schedule a batch accepts runs under one of them);
+// EMX_FUSED_BATCH_TARGET_MOVES takes a mask that narrows that to one.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#if __has_include(<emx.h>)
+#include <emx.h>
+#else
+#include "../../include/emx.h"
+#endif
+#include "emx_small_launch.hpp"
+
+// bumped with ANY change of SmallRunArgs or of k_small_run's LDS layout: a launcher and a library of different values refuse each other
+#ifndef EMX_FUSED_ABI
+#define EMX_FUSED_ABI 1u
+#endif
+
+#define EMX_FUSED_MOVES_STRETCH 1      // the schedule is one StretchMove
+#define EMX_FUSED_MOVES_ANY 2          // any schedule (stretch, DE, snooker, Gaussian moves; a single StretchMove too)
+
+namespace emx {
+
+// pick_shape (emx_small_host.hpp) of an element-wise target, as a constant expression
+constexpr int fused_v(int D) { return D % 2 == 0 ? 2 : 1; }
+constexpr int fused_g(int D) { return shape_g((D + fused_v(D) - 1) / fused_v(D)); }
+constexpr int fused_ch(int D) { return shape_ch((D + fused_v(D) - 1) / fused_v(D)); }
+
+template <typename USER, int NDIM, int MOVESEL>
+hipError_t launch_fused_move(int grid, int threads, size_t lds, hipStream_t st, const SmallRunArgs& a) {
+    constexpr int G = fused_g(NDIM), V = fused_v(NDIM), CH = fused_ch(NDIM);
+    auto kern = k_small_run<G, V, CH, MOVESEL, false, 0, true, USER>;
+    static size_t lds_granted[MAX_DEVICES] = {};      // as launch_small_move: function attributes are per device
+    int dev = 0;
+    if (lds > 48 * 1024 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MAX_DEVICES && lds > lds_granted[dev]) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        lds_granted[dev] = lds;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, a);
+    return hipGetLastError();
+}
+
+// the launcher behind EMX_FUSED_BATCH_TARGET: the checks, then one launch of the batch (include/emx.h: emx_fused_launch)
+template <typename USER, int NDIM, int MOVES>
+int fused_batch_launch(const emx_fused_launch* L) {
+    static_assert(NDIM >= 1 && NDIM <= 256, "a fused user target has 1 <= ndim <= 256");
+    static_assert((MOVES & (EMX_FUSED_MOVES_STRETCH | EMX_FUSED_MOVES_ANY)) != 0, "no move selector compiled in");
+    if (!L || L->abi != EMX_FUSED_ABI || L->args_bytes != (uint32_t)sizeof(SmallRunArgs)) return 1;
+    if (L->ndim != NDIM) return 2;
+    const bool stretch = L->movesel == MOVE_STRETCH;
+    if (!stretch && L->movesel != SMALL_ANY_MOVE) return 3;
+    if (!stretch && !(MOVES & EMX_FUSED_MOVES_ANY)) return 3;
+    if (L->grid == 0) return 0;                       // the probe of emx_set_batch_target_fused
+    if (!L->args || L->grid < 0 || L->threads < 64 || L->threads > 1024 || L->threads % 64 != 0) return 3;
+    SmallRunArgs a = *static_cast<const SmallRunArgs*>(L->args);
+    if (a.D != NDIM) return 2;
+    a.user = L->user;
+    hipError_t e = hipErrorInvalidValue;
+    if constexpr ((MOVES & EMX_FUSED_MOVES_STRETCH) != 0) {
+        if (stretch) e = launch_fused_move<USER, NDIM, MOVE_STRETCH>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
+    }
+    if constexpr ((MOVES & EMX_FUSED_MOVES_ANY) != 0) {
+        if (!stretch || !(MOVES & EMX_FUSED_MOVES_STRETCH))      // the any-schedule kernel runs a single StretchMove to the same bits
+            e = launch_fused_move<USER, NDIM, SMALL_ANY_MOVE>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
+    }
+    return e == hipSuccess ? 0 : 100 + (int)e;
+}
+
+}  // namespace emx
+
+#define EMX_FUSED_BATCH_TARGET_MOVES(name, Functor, ndim, moves)                                   \
+    extern "C" __attribute__((visibility("default"))) int name(const emx_fused_launch* launch) {  \
+        return emx::fused_batch_launch<Functor, (ndim), (moves)>(launch);                          \
+    }
+#define EMX_FUSED_BATCH_TARGET(name, Functor, ndim) \
+    EMX_FUSED_BATCH_TARGET_MOVES(name, Functor, ndim, EMX_FUSED_MOVES_STRETCH | EMX_FUSED_MOVES_ANY)

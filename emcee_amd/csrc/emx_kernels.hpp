@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "emx_planlog.hpp"
 #include "emx_rng.hpp"
@@ -67,7 +68,7 @@ enum : int { MOVE_STRETCH = 0, MOVE_DE = 1, MOVE_SNOOKER = 2, MOVE_GAUSS = 3, MO
              MOVE_MIX = 8 /* k_persist_mix: DE and snooker steps in one launch */ };
 enum : int { GAUSS_VECTOR = 0, GAUSS_RANDOM = 1, GAUSS_SEQUENTIAL = 2 };
 enum : int { TGT_NONE = 0, TGT_ISO = 1, TGT_DIAG = 2, TGT_DENSE = 3, TGT_ROSEN = 4, TGT_BOX = 5,
-             TGT_REPLAY = 7 };      // (6 is EMX_TARGET_DEVICE_CALLBACK, a host-side three-pass target: never a kernel's)     // replay exchange: no target, no decision -- the slot is a peer's ACCEPTED update, its new log-prob comes with the plan
+             TGT_REPLAY = 7, TGT_USER = 8 };      // (6 is EMX_TARGET_DEVICE_CALLBACK, a host-side three-pass target: never a kernel's)     // replay exchange: no target, no decision -- the slot is a peer's ACCEPTED update, its new log-prob comes with the plan
 enum : uint32_t { ST_NAN_LOGP = 1u, ST_BAD_COORD = 2u, ST_EXCHANGE_OVERFLOW = 4u, ST_EXCHANGE_TIMEOUT = 8u,
                   ST_PLAN_PRODUCER = 16u,
                   ST_SINGULAR_COV = 32u };      // bit 5: KDEMove's complement covariance is not positive definite (emx_walkkde.hip)     // bit 4: the device producer of exact-mode plans stalled or under-ran (emx_mtdev_kernels.hpp)
@@ -2012,6 +2013,10 @@ struct SmallRunArgs {
     const double* tscales;
     long long tp0_stride, tp1_stride, cap;
     int32_t eval0;
+    // fused user targets (k_small_run<..., USER>, emx_fused_target.hpp): the caller's device pointer, handed to the functor with
+    // every row, and the rows of the LDS staging area (the largest split of the schedule)
+    const void* user;
+    int32_t stage_rows;
 };
 
 constexpr int SMALL_STATUS_WORDS = 8;      // a member's status flags (raise_status: one word per bit)
@@ -2101,6 +2106,16 @@ __device__ __forceinline__ void small_update(const SmallRunArgs& A, const Member
     if (live && gl == 0) accs[i] = accept ? 1 : 0;
 }
 
+// a fused user target's functor on one row (void: no such target; never called)
+template <typename USER>
+__device__ __forceinline__ double fused_call(const double* x, int ndim, int member, const void* user) {
+    if constexpr (std::is_void<USER>::value) {
+        return 0.0;
+    } else {
+        return USER{}(x, ndim, member, user);
+    }
+}
+
 // the dense target's quadratic form of the 16 tile rows a wave holds, through the f64 MFMA against the LDS image (k_halfstep's
 // instructions in k_halfstep's order); the value of tile row (lane >> 4) + 4 (lane & 3) lands in lanes with (lane & 15) < 4
 template <int DPB, int KK, int RT>
@@ -2133,11 +2148,19 @@ __device__ __forceinline__ double small_dense_qf(const double* tile, const doubl
     return qf;
 }
 
-template <int G, int V, int CH, int MOVESEL, bool PLANNED, int DPB = 0, bool BATCH = false>
+// One workgroup runs a whole launch of a small ensemble (BATCH: member blockIdx.x of a batch): ensemble, plans and log-probs in LDS.
+// USER (a functor type, emx_fused_target.hpp; void: none): the caller's per-row log-probability compiled into the kernel.  A
+// half-step is then two passes with a barrier between them, k_batch_cb's structure with barriers for kernel boundaries: every
+// proposal of the split goes to an LDS staging row (small_propose, G lanes a row), then ONE lane a row calls the functor on its
+// staged row, decides and commits.  The functor's time is the model's, so it gets every lane of the workgroup rather than the
+// 1 / G of them a per-wave tile would leave busy.  A row with a non-finite coordinate is rejected without reaching the functor.
+template <int G, int V, int CH, int MOVESEL, bool PLANNED, int DPB = 0, bool BATCH = false, typename USER = void>
 static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int WPW = 64 / G;
     constexpr bool DENSE = DPB > 0;
+    constexpr bool FUSED = !std::is_void<USER>::value;
+    static_assert(!FUSED || (BATCH && !PLANNED && !DENSE), "a fused user target runs in batched Philox launches");
     constexpr int Dp = DENSE ? DPB * 16 : 16, KK = Dp / 4, RT = Dp + 2, PPT = 16 / WPW;
     const int N = A.N, D = A.D, T = blockDim.x, tid = threadIdx.x, B = A.batch;
     const int lane = tid & 63, wv = tid >> 6, nwave = T >> 6, sub = lane / G, gl = lane % G;
@@ -2157,6 +2180,10 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
     double* muS = Sfrag + dense_img_doubles(Dp);
     double* tile = muS + Dp + (size_t)wv * (16 * RT + 16);
     double* facS = tile + 16 * RT;
+    // fused user target: one split's proposals, a row every DS doubles (odd: lanes a row apart meet no bank twice), and their factors
+    const int DS = D | 1;
+    double* stage = Sfrag;
+    double* sfac = stage + (size_t)(FUSED ? A.stage_rows : 0) * DS;
     const SmallMember<BATCH> M{A};
     if constexpr (DENSE)
         for (int e = tid; e < dense_img_doubles(Dp) + Dp; e += T) Sfrag[e] = M.tp1()[e];
@@ -2181,7 +2208,13 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
         // proposal's -- eval_valu_target, or the dense tile and MFMA contraction -- which is eval_rows' arithmetic
         if (A.eval0) {
             __syncthreads();
-            if constexpr (DENSE) {
+            if constexpr (FUSED) {
+                for (int t = tid; t < N; t += T) {                                // the functor on the walker's own row
+                    const double lpn = fused_call<USER>(Xs + (size_t)t * D, D, (int)blockIdx.x, A.user);
+                    if (lpn != lpn) raise_status(M.status(), ST_NAN_LOGP);
+                    lps[t] = lpn;
+                }
+            } else if constexpr (DENSE) {
                 for (int base = wv * 16; base < N; base += nwave * 16) {          // wave-uniform
                     const int nslot = min(16, N - base);
 #pragma unroll
@@ -2299,7 +2332,56 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
             int pos0 = b * N;
             for (int split = 0; split < S; ++split) {
                 const int ns = (N - split + S - 1) / S;
-                if constexpr (DENSE) {
+                if constexpr (FUSED) {
+                    // fused user target, pass 1: the split's proposals into the staging rows (slot t -> row t < stage_rows)
+                    for (int base = wv * WPW; base < ns; base += nwave * WPW) {      // wave-uniform
+                        const int t = base + sub;
+                        const bool live = t < ns;
+                        const int pos = pos0 + (live ? t : 0);
+                        Row<G, V, CH> q;
+                        double factor = 0.0;
+                        bool badq = false;
+                        const int i = orders[pos], j0 = p0s[pos], j1 = p1s[pos], j2 = p2s[pos];
+                        if (MOVESEL == MOVE_GAUSS || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_GAUSS))
+                            small_propose<G, V, CH, MOVE_GAUSS>(M, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq, &gg);
+                        else if (MOVESEL == MOVE_STRETCH || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_STRETCH))
+                            small_propose<G, V, CH, MOVE_STRETCH>(M, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq);
+                        else if (MOVESEL == MOVE_DE || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_DE))
+                            small_propose<G, V, CH, MOVE_DE>(M, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq);
+                        else
+                            small_propose<G, V, CH, MOVE_SNOOKER>(M, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq);
+                        if (live && t < A.stage_rows) {
+#pragma unroll
+                            for (int c = 0; c < CH; ++c)
+#pragma unroll
+                                for (int v = 0; v < V; ++v) {
+                                    const int d = (c * G + gl) * V + v;
+                                    if (d < D) stage[(size_t)t * DS + d] = q.x[c][v];
+                                }
+                            if (gl == 0) sfac[t] = badq ? -__builtin_inf() : factor;
+                        }
+                    }
+                    __syncthreads();
+                    // pass 2: one lane a row -- the functor, small_update's decision, the commit
+                    for (int t = tid; t < ns && t < A.stage_rows; t += T) {
+                        const int pos = pos0 + t;
+                        const int i = orders[pos];
+                        const double* qrow = stage + (size_t)t * DS;
+                        const double fac = sfac[t];
+                        bool accept = false;
+                        if (fac != -__builtin_inf()) {                               // (-inf: a non-finite proposal, or a factor that rejects whatever the value)
+                            const double lp_new = fused_call<USER>(qrow, D, (int)blockIdx.x, A.user);
+                            if (lp_new != lp_new) raise_status(M.status(), ST_NAN_LOGP);
+                            const double lnpdiff = fac + lp_new - lps[i];            // red_blue.py:99
+                            accept = lnpdiff > logus[pos];                           // red_blue.py:100
+                            if (accept) {
+                                for (int d = 0; d < D; ++d) Xs[(size_t)i * D + d] = qrow[d];
+                                lps[i] = lp_new;
+                            }
+                        }
+                        accs[i] = accept ? 1 : 0;
+                    }
+                } else if constexpr (DENSE) {
                     // dense Gaussian target: a wave takes 16 slots at a time -- proposals into its LDS tile, the f64 MFMA
                     // contraction and the decisions exactly as k_halfstep does them (same instructions, same order)
                     for (int base = wv * 16; base < ns; base += nwave * 16) {       // wave-uniform

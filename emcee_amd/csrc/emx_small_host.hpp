@@ -46,6 +46,10 @@ inline size_t small_lds_bytes(int64_t N, int D, int dense_dp = 0, int waves = 0,
     return b;
 }
 
+// a fused user target's LDS staging area behind the rest (k_small_run<..., USER>): `rows` proposals (the largest split of the
+// schedule) at D | 1 doubles a row, a factor each, and the 16-byte alignment
+constexpr size_t small_fused_stage_bytes(int64_t rows, int D) { return 16 + (size_t)rows * ((size_t)(D | 1) * 8 + 8); }
+
 // widest padded ndim of a dense Gaussian target whose image the fused kernels and k_small_run keep in LDS
 constexpr int DENSE_FUSED_MAX_DP = 128;
 

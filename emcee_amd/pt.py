@@ -47,7 +47,7 @@ from . import _lib
 from .batch import EnsembleBatch, _trampoline
 from .ensemble import _refuse_extended_precision, walkers_independent
 from .state import State
-from .targets import BatchCallable, BatchKernel, BatchTarget, DeviceTarget
+from .targets import BatchCallable, BatchFused, BatchKernel, BatchTarget, DeviceTarget
 
 __all__ = ["PTSampler", "default_betas", "thermodynamic_integration_log_evidence"]
 
@@ -146,6 +146,9 @@ class PTSampler(object):
         self.ntemps, self.nwalkers, self.ndim, self.nbatch = int(ntemps), int(nwalkers), int(ndim), int(nbatch)
         if min(self.ntemps, self.nwalkers, self.ndim, self.nbatch) < 1:
             raise ValueError("ntemps, nwalkers, ndim and nbatch must be positive")
+        if isinstance(log_likelihood, BatchFused):
+            raise TypeError("PTSampler's log_likelihood is a targets.BatchCallable or targets.BatchKernel; a BatchFused is not: the "
+                            "tempered commit and the swap pass run on the batched callback path (a fused tempered kernel does not exist)")
         if not isinstance(log_likelihood, BatchTarget):
             kind = "fused device target" if isinstance(log_likelihood, DeviceTarget) else type(log_likelihood).__name__
             raise TypeError("PTSampler's log_likelihood is a targets.BatchCallable or targets.BatchKernel; a %s is not (wrap the "
@@ -155,6 +158,8 @@ class PTSampler(object):
             raise ValueError("betas holds %d rungs for ntemps = %d" % (len(self.betas), self.ntemps))
         self._box, self._prior = None, None
         if log_prior is not None:
+            if isinstance(log_prior, BatchFused):
+                raise TypeError("log_prior is None, (lo, hi) or a targets.BatchCallable / BatchKernel; a BatchFused is not")
             if isinstance(log_prior, BatchTarget):
                 self._prior = log_prior
             elif isinstance(log_prior, DeviceTarget) or callable(log_prior):

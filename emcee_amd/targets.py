@@ -10,13 +10,18 @@ no NumPy twin in the product.  The formulas are restated for the parity tests in
 ``oracle/sampler_oracle.py`` only.
 """
 import ctypes
+import hashlib
+import os
+import re
+import shutil
+import subprocess
 
 import numpy as np
 
 from . import _lib
 
 __all__ = ["DeviceTarget", "IsoGaussian", "DiagGaussian", "DenseGaussian", "Rosenbrock", "UniformBox", "DeviceCallable", "DeviceKernel",
-           "BatchCallable", "BatchKernel"]
+           "BatchCallable", "BatchKernel", "BatchFused", "BatchFusedLibrary", "compile_fused", "get_include"]
 
 
 class DeviceTarget(object):
@@ -200,3 +205,110 @@ class BatchKernel(BatchTarget):
             if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
                 raise TypeError("BatchKernel needs an emx_batch_log_prob_fn: a ctypes function or a non-null address")
         self.fn_ptr, self.user_ptr = fn_ptr, user_ptr
+
+
+class BatchFused(BatchTarget):
+    """The user's per-row ``__device__`` log-probability compiled INTO the batch kernel: ``fn_ptr`` is the launcher that
+    ``EMX_FUSED_BATCH_TARGET(name, Functor, ndim)`` of ``emx_fused_target.hpp`` emits in the user's own translation unit (an
+    ``emx_fused_batch_fn`` of ``include/emx.h``: a ctypes function or a non-null address), ``ndim`` the dimension it was compiled
+    for, ``user`` the device pointer the functor receives with every row -- an integer, a ``ctypes.c_void_p``, or a torch CUDA
+    tensor (kept alive; its ``data_ptr()`` is passed) -- holding the per-member data the functor indexes by ``member``.
+
+    :class:`~emcee_amd.EnsembleBatch` then runs as it does for a built-in target: one launch per ``run_mcmc`` chunk, no callback,
+    no proposal block in global memory, bit for bit the :class:`BatchKernel` run of the same function.
+    :func:`compile_fused` builds such a launcher from source.  Not a likelihood of :class:`~emcee_amd.PTSampler`."""
+    kind = _lib.TARGET_FUSED_USER
+
+    def __init__(self, fn_ptr, ndim, user=None):
+        if not isinstance(fn_ptr, ctypes._CFuncPtr):
+            addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
+            if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
+                raise TypeError("BatchFused needs an emx_fused_batch_fn: a ctypes function or a non-null address")
+        if isinstance(ndim, bool) or not isinstance(ndim, (int, np.integer)) or ndim < 1:
+            raise TypeError("BatchFused needs the ndim its launcher was compiled for, an integer >= 1; got %r" % (ndim,))
+        if not (user is None or isinstance(user, (int, np.integer, ctypes.c_void_p)) or hasattr(user, "data_ptr")) or isinstance(user, bool):
+            raise TypeError("BatchFused's user is a device pointer: None, an integer, a ctypes.c_void_p or a torch CUDA tensor")
+        if hasattr(user, "data_ptr") and not getattr(user, "is_cuda", False):
+            raise TypeError("BatchFused's user tensor must live on the GPU (the functor reads it on the device)")
+        self.fn_ptr, self.ndim, self.user = fn_ptr, int(ndim), user
+
+    def user_address(self):
+        """-> the device address handed to the functor (None: a null pointer)"""
+        u = self.user
+        if u is None:
+            return None
+        if hasattr(u, "data_ptr"):
+            return int(u.data_ptr())
+        return u.value if isinstance(u, ctypes.c_void_p) else int(u)
+
+
+def get_include():
+    """-> [``include/``, ``emcee_amd/csrc/``]: the directories a build of the user's own fused target needs on its include path
+    (``emx.h`` and ``emx_fused_target.hpp``)."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    return [os.path.join(os.path.dirname(here), "include"), os.path.join(here, "csrc")]
+
+
+class BatchFusedLibrary(object):
+    """What :func:`compile_fused` built: ``path`` of the shared library, ``lib`` (its ``ctypes.CDLL``: the user's own ``extern
+    "C"`` setup functions of ``source`` are there), ``name`` of the launcher, ``ndim``, and :meth:`target`."""
+
+    def __init__(self, path, name, ndim):
+        self.path, self.name, self.ndim = path, name, int(ndim)
+        _lib.load()                       # one HIP runtime per process: the library's (torch's) first
+        self.lib = ctypes.CDLL(path)
+        self.launcher = getattr(self.lib, name)
+
+    def target(self, user=None):
+        """-> :class:`BatchFused` of the compiled functor with the device pointer ``user``"""
+        t = BatchFused(self.launcher, self.ndim, user)
+        t._library = self                 # the launcher's code lives as long as the target
+        return t
+
+
+FUSED_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC"]
+
+
+def compile_fused(source, functor, ndim, name=None, flags=(), cache_dir=None):
+    """Compile the user's model into the batch kernel -> :class:`BatchFusedLibrary`.
+
+    ``source``: HIP C++ that defines the functor type ``functor`` -- ``__device__ double operator()(const double* x, int ndim,
+    int member, const void* user) const`` -- and whatever ``extern "C"`` helpers the user wants in the same library.  The
+    translation unit is ``#include <emx_fused_target.hpp>``, ``source`` and ``EMX_FUSED_BATCH_TARGET(name, functor, ndim)``,
+    compiled with ``hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -shared -fPIC`` (+ ``flags``) and
+    :func:`get_include`.  The output is cached in ``cache_dir`` (default ``$EMCEE_AMD_CACHE`` or ``~/.cache/emcee_amd``) under
+    the hash of source, functor, ndim, name, flags and every header of the library: a second call with the same inputs compiles
+    nothing.  A compiler failure raises ``RuntimeError`` with the compiler's last lines."""
+    from . import _build
+    ndim = int(ndim)
+    if ndim < 1 or ndim > 256:
+        raise ValueError("compile_fused: 1 <= ndim <= 256; got %d" % ndim)
+    for what, ident in (("functor", functor), ("name", name)):
+        if ident is not None and not re.match(r"^[A-Za-z_][A-Za-z0-9_:]*$", ident):
+            raise ValueError("compile_fused: %s must be a C++ identifier; got %r" % (what, ident))
+    name = name or "emx_fused_%s_%d" % (functor.replace(":", "_"), ndim)
+    flags = [str(f) for f in flags]
+    h = hashlib.sha256(repr((source, functor, ndim, name, FUSED_FLAGS + flags)).encode())
+    for d in _build.DEPS:
+        if d.endswith((".hpp", ".h")):
+            with open(d, "rb") as f:
+                h.update(f.read())
+    key = h.hexdigest()[:24]
+    cache_dir = cache_dir or os.environ.get("EMCEE_AMD_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "emcee_amd")
+    work = os.path.join(str(cache_dir), key)
+    so = os.path.join(work, "lib%s.so" % name)
+    if not os.path.exists(so):
+        os.makedirs(work, exist_ok=True)
+        src = os.path.join(work, "%s.hip" % name)
+        with open(src, "w") as f:
+            f.write("#include <emx_fused_target.hpp>\n\n%s\n\nEMX_FUSED_BATCH_TARGET(%s, %s, %d)\n" % (source, name, functor, ndim))
+        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+        tmp = "%s.%d.tmp" % (so, os.getpid())
+        cmd = [hipcc] + FUSED_FLAGS + flags + ["-I" + d for d in get_include()] + [src, "-o", tmp]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+            raise RuntimeError("compile_fused: hipcc failed (%s):\n%s" % (src, (r.stderr or r.stdout)[-4000:]))
+        os.replace(tmp, so)
+    return BatchFusedLibrary(so, name, ndim)

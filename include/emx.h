@@ -30,7 +30,9 @@ enum emx_target_kind {
     EMX_TARGET_DENSE_GAUSS = 3,/* -0.5 (x-mu)^T icov (x-mu)  docs/tutorials/quickstart.ipynb:76 */
     EMX_TARGET_ROSENBROCK = 4, /* -sum[100 (x_{i+1}-x_i^2)^2 + (1-x_i)^2] / scale (BASELINE C3) */
     EMX_TARGET_BOX = 5,        /* 0 inside [0,1]^D else -inf   test_proposal.py:25-28           */
-    EMX_TARGET_DEVICE_CALLBACK = 6 /* the caller's batched log-prob on device buffers (emx_set_target_callback) */
+    EMX_TARGET_DEVICE_CALLBACK = 6,/* the caller's batched log-prob on device buffers (emx_set_target_callback) */
+    EMX_TARGET_FUSED_USER = 8      /* batches only: the caller's per-row device function compiled into the one-workgroup kernel
+                                      (emx_set_batch_target_fused; 7 is taken inside the kernels) */
 };
 
 enum emx_move_kind {
@@ -503,7 +505,8 @@ int64_t emx_host_pull_capacity(int64_t nwalkers, int32_t world, int32_t nsplits,
  * ONE launch of the one-workgroup kernel k_small_run per chunk of up to 4 096 steps: workgroup b runs member b exactly as an
  * emx_ctx in Philox mode runs that ensemble (same bits).  Shapes: small_kernel's rules per member (nwalkers <= 4 096, ndim <= 256,
  * the LDS bound, the dense contraction bound, <= 8 stretch / DE / snooker / Gaussian moves, DE with >= 2 walkers a complement);
- * fused device targets, or the caller's batched log-prob (emx_set_batch_target_callback below; not EMX_TARGET_HOST).  Arrays are
+ * fused device targets, the caller's batched log-prob (emx_set_batch_target_callback below) or the caller's device function compiled
+ * into the kernel (emx_set_batch_target_fused below); not EMX_TARGET_HOST.  Arrays are
  * member-major: coordinates
  * (B, nwalkers, ndim), log-probs and accept counts (B, nwalkers), the chain (B, capacity, nwalkers, ndim).
  * Tuning keys (emx_batch_set_tuning; neither changes a bit, plans do not depend on the state):
@@ -541,6 +544,31 @@ int emx_batch_set_target(emx_batch* b, int32_t kind, const double* p0, const dou
 typedef int (*emx_batch_log_prob_fn)(void* user, const double* coords_dev, int32_t nbatch, int64_t rows, int32_t ndim,
                                      double* log_prob_dev, void* hip_stream);
 int emx_set_batch_target_callback(emx_batch* b, emx_batch_log_prob_fn fn, void* user);
+/* Fused user targets (EMX_TARGET_FUSED_USER; emcee_amd.targets.BatchFused / compile_fused): the caller's per-row __device__
+ * log-probability compiled INTO k_small_run, so that the batch runs as it does for a built-in target -- one launch per chunk of up
+ * to 4 096 steps, no callback, no proposal block in global memory.  The caller's translation unit includes
+ * emcee_amd/csrc/emx_fused_target.hpp and emits a launcher with EMX_FUSED_BATCH_TARGET(name, Functor, ndim); the library fills the
+ * descriptor below and calls the launcher where it launches its own instantiations.  `args` is the library's internal SmallRunArgs:
+ * `abi` (EMX_FUSED_ABI of that header, bumped with any change of the struct or of the kernel's LDS layout) and `args_bytes`
+ * (its sizeof) are checked by the launcher against the values it was compiled with, so a launcher built against another version
+ * of the header is refused, never run.  grid == 0 is a probe: check abi, args_bytes and ndim, launch nothing.  Returns 0, or
+ * non-zero and nothing launched (1: another version of the header, 2: another ndim, 3: the move selector was not compiled in,
+ * 100 + a hipError_t: the launch failed).  emx_set_batch_target_fused probes once, so a mismatch surfaces at bind time (-8 and
+ * "built against another version of emx_fused_target.hpp").  `user_dev`: a device pointer handed to the functor with every row
+ * (per-member data, indexed by the functor's `member`); the caller keeps it alive.  The one-workgroup rules apply with the
+ * staging area's LDS on top (emx_batch_check with EMX_TARGET_FUSED_USER); "batch_threads" and "batch_plan_steps" apply and
+ * change no bit.  Not a target of tempered batches (emx_pt_set_tempering refuses it). */
+typedef struct emx_fused_launch {
+    uint32_t abi;            /* EMX_FUSED_ABI the library was built with */
+    uint32_t args_bytes;     /* sizeof(SmallRunArgs) of the library */
+    int32_t ndim, movesel, grid, threads;      /* movesel: EMX_MOVE_STRETCH (the schedule is one StretchMove) or 7 (any schedule) */
+    uint64_t lds_bytes;      /* dynamic LDS of a workgroup (> 48 KB: the launcher raises the function's limit) */
+    void* hip_stream;
+    const void* args;        /* SmallRunArgs */
+    const void* user;        /* user_dev */
+} emx_fused_launch;
+typedef int (*emx_fused_batch_fn)(const emx_fused_launch*);     /* 0, or non-zero and nothing launched */
+int emx_set_batch_target_fused(emx_batch* b, emx_fused_batch_fn fn, int32_t ndim_compiled, const void* user_dev);
 /* the move schedule (as emx_set_moves); a sequential GaussianMove only as the one move */
 int emx_batch_set_moves(emx_batch* b, int32_t nmoves, const emx_move_desc* moves, const double* cdf);
 int emx_batch_set_move_scale(emx_batch* b, int32_t move, const double* scale, int32_t n);
