@@ -9,6 +9,7 @@ LIB_PATH = os.path.join(HERE, "libemx.so")
 
 TARGET_HOST, TARGET_ISO, TARGET_DIAG, TARGET_DENSE, TARGET_ROSENBROCK, TARGET_BOX, TARGET_CALLBACK = range(7)
 TARGET_FUSED_USER = 8               # batches only (emx_set_batch_target_fused); 7 is taken inside the kernels
+TARGET_FUSED_PT = 9                 # tempered batches only (emx_pt_set_target_fused)
 MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER, MOVE_GAUSS = range(4)
 MOVE_WALK, MOVE_KDE = 5, 6          # native (Philox) mode only; 4 is not a public kind
 KDE_BW_SCOTT, KDE_BW_SILVERMAN, KDE_BW_SCALAR = range(3)
@@ -34,6 +35,8 @@ DEVICE_LOG_PROB_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c
 BATCH_LOG_PROB_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p)
 # emx_fused_batch_fn: (const emx_fused_launch*) -> int
 FUSED_BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
+# emx_pt_fused_fn: (emx_pt_fused_launch*) -> int
+PT_FUSED_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 
 _P = C.c_void_p
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -187,6 +190,8 @@ SIGNATURES = {
     "emx_pt_get_ladder": (C.c_int, [_P, _P, C.POINTER(C.c_int64)]),
     "emx_pt_set_ladder": (C.c_int, [_P, _dp, C.POINTER(C.c_int64)]),
     "emx_host_pt_adapt_ladder": (C.c_int, [_dp, _i64p, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_int64, _dp]),
+    "emx_pt_set_target_fused": (C.c_int, [_P, PT_FUSED_FN, C.c_int32, _P]),
+    "emx_pt_fused_check": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(MoveDesc), C.c_char_p, C.c_int32]),
     "emx_autocorr_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double, _dp, _ip, C.POINTER(C.c_int64)]),
     "emx_summary_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int32, _P, _P, _P, _P,
                                     C.POINTER(C.c_int64)]),

@@ -34,7 +34,7 @@ from . import summary as _summary
 from .autocorr import integrated_time
 from .ensemble import _native_desc, _parse_move_schedule, _refuse_extended_precision, philox_seed, walkers_independent
 from .state import State
-from .targets import (BatchFused, BatchKernel, BatchTarget, DenseGaussian, DeviceCallable, DeviceKernel, DeviceTarget, DiagGaussian, IsoGaussian,
+from .targets import (BatchFused, BatchKernel, BatchTarget, PTFused, DenseGaussian, DeviceCallable, DeviceKernel, DeviceTarget, DiagGaussian, IsoGaussian,
                       Rosenbrock, UniformBox)
 
 __all__ = ["EnsembleBatch"]
@@ -58,7 +58,7 @@ class EnsembleBatch(object):
     DESnookerMove and GaussianMove.  ``seeds``: B integers; member b draws as a sampler whose generator was seeded with
     ``np.random.RandomState(seeds[b])``.  ``None`` draws them from NumPy's global state."""
 
-    def __init__(self, nbatch, nwalkers, ndim, target, moves=None, seeds=None, device=None, rng="philox"):
+    def __init__(self, nbatch, nwalkers, ndim, target, moves=None, seeds=None, device=None, rng="philox", _tempered=False):
         if rng != "philox":
             raise ValueError("EnsembleBatch runs rng='philox' only (the MT19937 stream is made by one host generator a "
                              "sampler; use EnsembleSampler for rng=%r)" % (rng,))
@@ -67,6 +67,7 @@ class EnsembleBatch(object):
             raise ValueError("nbatch, nwalkers and ndim must be positive")
         self.rng = rng
         self.device = 0 if device is None else int(device)
+        self._tempered = bool(_tempered)      # PTSampler's handle: the only one that takes a PTFused
         self._targets, self._per_member = self._parse_targets(target)
         self._moves, self._weights = _parse_move_schedule(moves)
         self._descs = []
@@ -101,6 +102,12 @@ class EnsembleBatch(object):
     def _parse_targets(self, target):
         if isinstance(target, BatchFused) and target.ndim != self.ndim:
             raise ValueError("the BatchFused target was compiled for ndim %d; the batch has ndim %d" % (target.ndim, self.ndim))
+        if isinstance(target, PTFused):
+            if not self._tempered:
+                raise TypeError("a PTFused is a likelihood of PTSampler: its launcher carries the tempered kernel (for an EnsembleBatch "
+                                "compile the model as a BatchFused)")
+            if target.ndim != self.ndim:
+                raise ValueError("the PTFused target was compiled for ndim %d; the sampler has ndim %d" % (target.ndim, self.ndim))
         if isinstance(target, BatchTarget):
             return [target], False
         if isinstance(target, DeviceTarget) or callable(target):
@@ -160,6 +167,8 @@ class EnsembleBatch(object):
         self._h = h
         if isinstance(self._targets[0], BatchFused):
             self._bind_user_fused(h)
+        elif isinstance(self._targets[0], PTFused):
+            self._bind_pt_fused(h)
         elif isinstance(self._targets[0], BatchTarget):
             self._bind_callback(h)
         else:
@@ -205,6 +214,12 @@ class EnsembleBatch(object):
         fn = t.fn_ptr if isinstance(t.fn_ptr, _lib.FUSED_BATCH_FN) else C.cast(t.fn_ptr, _lib.FUSED_BATCH_FN)
         self._cb_keep = (fn, t)           # the library holds the launcher and the user's device pointer: keep both alive
         self._ck(self._lib().emx_set_batch_target_fused(h, fn, t.ndim, C.c_void_p(t.user_address())))
+
+    def _bind_pt_fused(self, h):
+        t = self._targets[0]
+        fn = t.fn_ptr if isinstance(t.fn_ptr, _lib.PT_FUSED_FN) else C.cast(t.fn_ptr, _lib.PT_FUSED_FN)
+        self._cb_keep = (fn, t)
+        self._ck(self._lib().emx_pt_set_target_fused(h, fn, t.ndim, C.c_void_p(t.user_address())))
 
     def set_tuning(self, key, value):
         """``"batch_threads"`` / ``"batch_plan_steps"`` (include/emx.h): the launch shape; ``"batch_acf_series"``: series per

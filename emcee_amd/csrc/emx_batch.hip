@@ -6,6 +6,8 @@
 // log-prob (emx_set_batch_target_callback) a run is k_batch_cb launches and calls of that function instead (emx_batch_cb.hip).
 // With a fused user target (emx_set_batch_target_fused) the launch is the caller's own instantiation of k_small_run around their
 // device function (emx_fused_target.hpp), through the launcher their translation unit exports; everything else is shared.
+// With a fused tempered target (emx_pt_set_target_fused) a run is launches of the caller's instantiation of k_pt_run
+// (emx_pt_fused.hpp), one workgroup an object, one launch a chunk of steps (launch_pt below).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +23,7 @@
 #include "emx_fused_target.hpp"
 #include "emx_internal.hpp"
 #include "emx_pt.hpp"
+#include "emx_pt_fused.hpp"
 #include "emx_rng.hpp"
 #include "emx_small_host.hpp"
 #include "emx_small_launch.hpp"
@@ -93,6 +96,11 @@ struct emx_batch {
     int32_t pt_adapt = 0;
     double pt_lag = 10000.0, pt_time = 100.0;
     int64_t pt_updates = 0;
+    // EMX_TARGET_FUSED_PT: the caller's launcher of k_pt_run around their likelihood (and prior), their device pointer, and
+    // whether the launcher carries a prior functor (its answer to the probe)
+    emx_pt_fused_fn ptf_fn = nullptr;
+    const void* ptf_user = nullptr;
+    int32_t ptf_has_prior = 0;
 };
 
 namespace {
@@ -134,7 +142,9 @@ const char* shape_refusal(int64_t N, int32_t D, int32_t target, int32_t nmoves, 
         snprintf(buf, n, "nwalkers x ndim = %lld x %d is outside the one-workgroup kernel (nwalkers <= 4096, ndim <= 256)", (long long)N, D);
         return buf;
     }
-    const bool callback = target == EMX_TARGET_DEVICE_CALLBACK;      // the caller's batched log-prob (k_batch_cb)
+    // the caller's batched log-prob (k_batch_cb); a fused tempered target takes the same schedules, and its LDS bound depends on
+    // ntemps (pt_fused_refusal)
+    const bool callback = target == EMX_TARGET_DEVICE_CALLBACK || target == EMX_TARGET_FUSED_PT;
     const bool fused_user = target == EMX_TARGET_FUSED_USER;         // the caller's device function inside k_small_run
     if (!callback && !fused_user && target != EMX_TARGET_ISO_GAUSS && target != EMX_TARGET_DIAG_GAUSS && target != EMX_TARGET_DENSE_GAUSS &&
         target != EMX_TARGET_ROSENBROCK && target != EMX_TARGET_BOX)
@@ -357,6 +367,186 @@ int launch(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t st
         int64_t nstored = 0;
         if (store)
             for (int64_t s2 = 0; s2 < nsteps; ++s2) nstored += ((i0 + s2 + 1) % thin_by == 0) ? 1 : 0;
+        b->stored += nstored;
+        b->proposals += nsteps;
+        b->step += (uint64_t)nsteps;
+    }
+    return 0;
+}
+
+// ---- fused tempered targets (EMX_TARGET_FUSED_PT; emx_pt_fused.hpp) ----
+
+// staging rows a rung: the largest split, halved until the object fits with one plan step (k_pt_run then runs a half-step in chunks)
+int64_t pt_stage_rows(int32_t T, int64_t N, int32_t D, int32_t nmoves, const emx_move_desc* moves) {
+    int64_t R = fused_stage_rows(N, nmoves, moves);
+    while (R > 1 && pt_lds_layout(T, N, D, 1, R).total > SMALL_LDS_MAX) R = (R + 1) / 2;
+    return R;
+}
+
+// one workgroup's LDS for an object of T rungs with `plan_steps` plan steps; the staging rows a rung: the largest split
+size_t pt_fused_lds(int32_t T, int64_t N, int32_t D, int32_t nmoves, const emx_move_desc* moves, int plan_steps) {
+    return pt_lds_layout(T, N, D, plan_steps, pt_stage_rows(T, N, D, nmoves, moves)).total;
+}
+
+// nullptr when one workgroup holds the object with at least one plan step, else why not (the bytes needed)
+const char* pt_fused_refusal(int32_t T, int64_t N, int32_t D, int32_t nmoves, const emx_move_desc* moves, char* buf, size_t n) {
+    if (T < 1) return "ntemps must be >= 1";
+    if (const char* why = shape_refusal(N, D, EMX_TARGET_FUSED_PT, nmoves, moves, buf, n)) return why;
+    // (the coordinates alone bound T N D: the products below stay far inside 64 bits)
+    const double coords = (double)T * (double)N * (double)D * 8.0;
+    const size_t need = coords > 1e12 ? (size_t)1 << 40 : pt_fused_lds(T, N, D, nmoves, moves, 1);
+    if (need > SMALL_LDS_MAX) {
+        snprintf(buf, n, "ntemps x nwalkers x ndim = %d x %lld x %d with a fused tempered target does not fit one workgroup's LDS (%zu "
+                         "bytes > %zu): an object is not split across workgroups; run it on the callback path (targets.BatchKernel)",
+                 T, (long long)N, D, need, SMALL_LDS_MAX);
+        return buf;
+    }
+    return nullptr;
+}
+
+// what a fused tempered target's launcher answered, as the handle's error; 0: it launched (or probed)
+int pt_fused_launcher_refusal(emx_batch* b, int rc, int movesel) {
+    if (rc == 0) return 0;
+    if (rc == 1)
+        return fail(b, -8, "the fused tempered target's launcher was built against another version of emx_pt_fused.hpp (the library has "
+                           "EMX_FUSED_PT_ABI %u and %zu bytes of kernel arguments): rebuild it with this library's headers",
+                    (unsigned)EMX_FUSED_PT_ABI, sizeof(PtRunArgs));
+    if (rc == 2) return fail(b, -1, "the fused tempered target's launcher was compiled for another ndim than the batch's %d", b->D);
+    if (rc == 3)
+        return fail(b, -1, "the fused tempered target's launcher does not carry the kernel of this schedule (move selector %d): compile it "
+                           "with EMX_FUSED_MOVES_ANY", movesel);
+    if (rc >= 100) return fail(b, -2, "k_pt_run launch failed (ndim=%d): %s", b->D, hipGetErrorString((hipError_t)(rc - 100)));
+    return fail(b, -7, "the fused tempered target's launcher failed (returned %d)", rc);
+}
+
+// one launch of k_pt_run: `nsteps` steps of every object (nsteps 0 with eval0: the initial P, L and lp only).  The launch shape
+// follows launch_shape's rule for the rows of one half-step of ALL rungs, plan steps for one entry a thread, shrunk to fit.
+int launch_pt(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t store, bool eval0) {
+    BNEED(b, b->ptf_fn != nullptr, "fused tempered target without a launcher (emx_pt_set_target_fused)");
+    BNEED(b, b->pt_T > 0, "a fused tempered target runs on a tempered handle (emx_pt_set_tempering)");
+    const int nm = (int)b->moves.size();
+    const int32_t T = b->pt_T;
+    PtRunArgs a{};
+    int smin = 1 << 30, smax = 0;
+    bool any_gauss = false;
+    for (int m = 0; m < nm; ++m) {
+        const emx_move_desc& mv = b->moves[m];
+        smin = std::min(smin, move_splits(mv));
+        smax = std::max(smax, move_splits(mv));
+        any_gauss = any_gauss || mv.kind == EMX_MOVE_GAUSS;
+        a.kind[m] = mv.kind;
+        a.nsplits[m] = mv.nsplits;
+        a.a[m] = mv.a;
+        a.sigma[m] = mv.sigma;
+        a.g0[m] = mv.g0;
+        a.gammas[m] = mv.gammas;
+        a.cdf[m] = b->cdf[m];
+        a.gmode[m] = mv.reserved;
+        a.gsigma[m] = mv.sigma;
+        a.gscale[m] = b->mscale[m];
+    }
+    a.nmoves = nm;
+    a.smax = smax;
+    a.X = b->X;
+    a.lp = b->lp;
+    a.L = b->pt_L;
+    a.P = b->pt_P;
+    a.beta = b->pt_beta;
+    a.acc = b->acc;
+    a.acc_count = b->acc_count;
+    a.status = b->status;
+    a.seeds = b->seeds;
+    a.attempts = b->sw_att;
+    a.accepts = b->sw_acc;
+    a.chain = b->chain;
+    a.chain_lp = b->chain_lp;
+    a.chain_L = b->chain_L;
+    a.chain_beta = b->chain_beta;
+    a.cap = b->cap;
+    a.row0 = b->stored;
+    a.box_lo = b->pt_lo;
+    a.box_hi = b->pt_hi;
+    a.step0 = b->step;
+    a.i0 = i0;
+    a.T = T;
+    a.N = (int32_t)b->N;
+    a.D = b->D;
+    a.nsteps = (int32_t)nsteps;
+    a.thin_by = thin_by;
+    a.store = (store && nsteps > 0) ? 1 : 0;
+    a.eval0 = eval0 ? 1 : 0;
+    a.stage_rows = (int32_t)pt_stage_rows(T, b->N, b->D, nm, b->moves.data());
+    a.max_rows = (int32_t)fused_stage_rows(b->N, nm, b->moves.data());
+    a.swap_every = b->swap_every;
+    a.adapt = b->pt_adapt ? 1 : 0;
+    a.lag = b->pt_lag;
+    a.time = b->pt_time;
+    a.adapt_t0 = (long long)b->pt_updates;
+    a.user = b->ptf_user;
+    if (any_gauss && nsteps > 0) {
+        // the step-size factors and the sequential column: launch's host arithmetic
+        std::vector<double> facs((size_t)b->B * nsteps, 1.0);
+        std::vector<int32_t> cols((size_t)nsteps, 0);
+        for (int64_t s2 = 0; s2 < nsteps; ++s2) {
+            const uint64_t step = b->step + (uint64_t)s2;
+            for (int32_t mb = 0; mb < b->B; ++mb) {
+                const uint64_t seed = b->seeds_host[mb];
+                const int mi = nm == 1 ? 0 : native_move_choice(seed, step, b->cdf.data(), nm);
+                const emx_move_desc& mv = b->moves[mi];
+                if (mv.kind != EMX_MOVE_GAUSS || mv.a == 0.0) continue;
+                const Philox4 r = philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), 0x46414354u /*'FACT'*/, 0, (uint32_t)seed,
+                                                (uint32_t)(seed >> 32));
+                facs[(size_t)mb * nsteps + s2] = std::exp(-mv.g0 + 2.0 * mv.g0 * u53(r.v[0], r.v[1]));
+            }
+            emx_move_desc& mv = b->moves[0];
+            if (mv.kind == EMX_MOVE_GAUSS && mv.reserved == EMX_GAUSS_SEQUENTIAL) {
+                cols[s2] = (int32_t)((int64_t)mv.gammas % b->D);
+                mv.gammas = (double)(((int64_t)mv.gammas + 1) % b->D);
+            }
+        }
+        BHIP(b, hipStreamSynchronize(b->stream));        // the previous launch no longer reads the buffers
+        if (grow(b, b->fac_dev, b->fac_cap, facs.size())) return -2;
+        if (grow(b, b->col_dev, b->col_cap, cols.size())) return -2;
+        BHIP(b, hipMemcpy(b->fac_dev, facs.data(), facs.size() * 8, hipMemcpyHostToDevice));
+        BHIP(b, hipMemcpy(b->col_dev, cols.data(), cols.size() * 4, hipMemcpyHostToDevice));
+        a.step_fac = b->fac_dev;
+        a.step_col = b->col_dev;
+    }
+    const Shape sh = pick_shape(b->D, b->D);
+    const int64_t rows = (int64_t)T * a.stage_rows;
+    int threads = (int)std::min<int64_t>(PT_RUN_MAX_THREADS, std::max<int64_t>(64, (rows * sh.G + 63) / 64 * 64));
+    int plan_steps = (int)std::max<int64_t>(1, std::min<int64_t>(64, threads / ((int64_t)T * b->N)));
+    if (b->tune_threads > 0) threads = (int)b->tune_threads;
+    if (b->tune_plan_steps > 0) plan_steps = (int)b->tune_plan_steps;
+    while (plan_steps > 1 && pt_fused_lds(T, b->N, b->D, nm, b->moves.data(), plan_steps) > SMALL_LDS_MAX) plan_steps = (plan_steps + 1) / 2;
+    a.plan_steps = plan_steps;
+    const size_t lds = pt_fused_lds(T, b->N, b->D, nm, b->moves.data(), plan_steps);
+    BNEED(b, threads <= PT_RUN_MAX_THREADS, "batch_threads: at most %d with a fused tempered target", PT_RUN_MAX_THREADS);
+    BNEED(b, lds <= SMALL_LDS_MAX && threads >= 64 && threads % 64 == 0,
+          "fused tempered launch shape: %d threads and %d plan steps need %zu bytes of LDS", threads, plan_steps, lds);
+    const int movesel = (nm == 1 && b->moves[0].kind == EMX_MOVE_STRETCH) ? (int)EMX_MOVE_STRETCH : SMALL_ANY_MOVE;
+    emx_pt_fused_launch fl{};
+    fl.abi = EMX_FUSED_PT_ABI;
+    fl.args_bytes = (uint32_t)sizeof(PtRunArgs);
+    fl.ndim = b->D;
+    fl.movesel = movesel;
+    fl.grid = b->B / T;
+    fl.threads = threads;
+    fl.lds_bytes = lds;
+    fl.hip_stream = (void*)b->stream;
+    fl.args = &a;
+    fl.user = b->ptf_user;
+    if (int rc = pt_fused_launcher_refusal(b, b->ptf_fn(&fl), movesel)) return rc;
+    b->last_threads = threads;
+    b->last_plan_steps = plan_steps;
+    ++b->launches;
+    if (nsteps > 0) {
+        int64_t nstored = 0, npass = 0;
+        for (int64_t s2 = 0; s2 < nsteps; ++s2) {
+            if (store && (i0 + s2 + 1) % thin_by == 0) ++nstored;
+            if (b->swap_every > 0 && (b->step + (uint64_t)s2 + 1) % (uint64_t)b->swap_every == 0) ++npass;
+        }
+        if (b->pt_adapt) b->pt_updates += npass;      // one update a pass, as swap_pass counts them
         b->stored += nstored;
         b->proposals += nsteps;
         b->step += (uint64_t)nsteps;
@@ -815,6 +1005,47 @@ int emx_set_batch_target_fused(emx_batch* b, emx_fused_batch_fn fn, int32_t ndim
     return 0;
 }
 
+int emx_pt_set_target_fused(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compiled, const void* user_dev) {
+    BNEED(b, fn != nullptr, "emx_pt_set_target_fused: no launcher");
+    BNEED(b, ndim_compiled == b->D, "the fused tempered target was compiled for ndim %d; the batch has ndim %d", ndim_compiled, b->D);
+    BNEED(b, b->pt_T == 0, "emx_pt_set_target_fused comes before emx_pt_set_tempering");
+    if (!b->moves.empty()) {
+        char buf[256];
+        const char* why = shape_refusal(b->N, b->D, EMX_TARGET_FUSED_PT, (int32_t)b->moves.size(), b->moves.data(), buf, sizeof buf);
+        BNEED(b, !why, "%s", why);
+    }
+    // the probe: abi, args_bytes and ndim against what the launcher was compiled with; nothing is launched
+    emx_pt_fused_launch fl{};
+    fl.abi = EMX_FUSED_PT_ABI;
+    fl.args_bytes = (uint32_t)sizeof(PtRunArgs);
+    fl.ndim = b->D;
+    fl.movesel = MOVE_STRETCH;
+    if (int rc = pt_fused_launcher_refusal(b, fn(&fl), fl.movesel)) return rc;
+    BHIP(b, hipSetDevice(b->device));
+    BHIP(b, hipStreamSynchronize(b->stream));
+    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
+        if (*p) {
+            hipFree(*p);
+            *p = nullptr;
+        }
+    b->tp0_stride = b->tp1_stride = 0;
+    b->ptf_fn = fn;
+    b->ptf_user = user_dev;
+    b->ptf_has_prior = fl.has_prior ? 1 : 0;
+    b->target = EMX_TARGET_FUSED_PT;
+    b->Dp = b->D;
+    return 0;
+}
+
+int emx_pt_fused_check(int32_t ntemps, int64_t nwalkers, int32_t ndim, int32_t nmoves, const emx_move_desc* moves, char* msg,
+                       int32_t msglen) {
+    char buf[320];
+    const char* why = (nmoves < 1 || !moves) ? "no moves" : pt_fused_refusal(ntemps, nwalkers, ndim, nmoves, moves, buf, sizeof buf);
+    if (!why) return 0;
+    if (msg && msglen > 0) snprintf(msg, (size_t)msglen, "%s", why);
+    return -1;
+}
+
 int emx_batch_set_moves(emx_batch* b, int32_t nmoves, const emx_move_desc* moves, const double* cdf) {
     BNEED(b, moves && cdf && nmoves >= 1, "need at least one move and its cdf");
     char buf[256];
@@ -884,6 +1115,7 @@ int emx_batch_eval_state_log_prob(emx_batch* b) {
     BNEED(b, !b->moves.empty(), "no moves set");
     BHIP(b, hipSetDevice(b->device));
     if (b->target == EMX_TARGET_DEVICE_CALLBACK) return eval_callback(b);
+    if (b->target == EMX_TARGET_FUSED_PT) return launch_pt(b, 0, 0, 1, 0, true);
     return launch(b, 0, 0, 1, 0, true);
 }
 
@@ -938,9 +1170,10 @@ int emx_batch_run(emx_batch* b, int64_t nsteps, int32_t thin_by, int32_t store) 
     // up to 4 096 steps a launch (as a single ensemble's); with Gaussian moves the per-member factors stay <= 32 MB a launch
     const int64_t total = nsteps * thin_by;
     const int64_t most = any_gauss ? std::max<int64_t>(1, std::min<int64_t>(4096, (4 << 20) / b->B)) : 4096;
+    const bool ptf = b->target == EMX_TARGET_FUSED_PT;
     for (int64_t i = 0; i < total;) {
         const int64_t chunk = std::min<int64_t>(total - i, most);
-        const int rc = launch(b, i, chunk, thin_by, store, false);
+        const int rc = ptf ? launch_pt(b, i, chunk, thin_by, store, false) : launch(b, i, chunk, thin_by, store, false);
         if (rc) return rc;
         i += chunk;
     }
@@ -1005,7 +1238,16 @@ int emx_batch_launch_info(emx_batch* b, int32_t* threads, int32_t* plan_steps, i
 int emx_pt_set_tempering(emx_batch* b, int32_t ntemps, const double* betas, const double* box_lo, const double* box_hi) {
     BNEED(b, b->target != EMX_TARGET_FUSED_USER, "tempering does not run a fused user target (emx_set_batch_target_fused): the tempered "
                                                  "commit and the swap pass belong to the batched callback path (emx_set_batch_target_callback)");
-    BNEED(b, b->target == EMX_TARGET_DEVICE_CALLBACK, "tempering needs a batched callback target (emx_set_batch_target_callback)");
+    BNEED(b, b->target == EMX_TARGET_DEVICE_CALLBACK || b->target == EMX_TARGET_FUSED_PT,
+          "tempering needs a batched callback target (emx_set_batch_target_callback)");
+    if (b->target == EMX_TARGET_FUSED_PT) {
+        BNEED(b, !(b->ptf_has_prior && box_lo), "the fused tempered target's launcher carries a prior functor: a box prior on top is refused");
+        if (!b->moves.empty()) {
+            char buf[320];
+            const char* why = pt_fused_refusal(ntemps, b->N, b->D, (int32_t)b->moves.size(), b->moves.data(), buf, sizeof buf);
+            BNEED(b, !why, "%s", why);
+        }
+    }
     BNEED(b, ntemps >= 1 && b->B % ntemps == 0, "ntemps = %d does not divide the batch of %d members", ntemps, b->B);
     BNEED(b, !b->pt_adapt || ntemps <= PT_ADAPT_MAX_T, "an adaptive ladder has at most %d rungs; ntemps = %d", PT_ADAPT_MAX_T, ntemps);
     BNEED(b, betas != nullptr, "no betas");
@@ -1061,6 +1303,8 @@ int emx_pt_set_tempering(emx_batch* b, int32_t ntemps, const double* betas, cons
 int emx_set_batch_prior_callback(emx_batch* b, emx_batch_log_prob_fn fn, void* user) {
     BNEED(b, b->pt_T > 0, "a prior callback needs tempering (emx_pt_set_tempering)");
     BNEED(b, b->pt_lo == nullptr || fn == nullptr, "the batch has a box prior already");
+    BNEED(b, b->target != EMX_TARGET_FUSED_PT || fn == nullptr, "a fused tempered target takes its prior as a functor of its launcher (or a box), "
+                                                                "not as a callback");
     BHIP(b, hipStreamSynchronize(b->stream));
     b->pr_fn = fn;
     b->pr_user = user;

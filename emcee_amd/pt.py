@@ -5,6 +5,13 @@
 as the members of one :class:`~emcee_amd.EnsembleBatch` handle, member ``g * ntemps + t`` being rung t of group g, with the
 user's :class:`~emcee_amd.targets.BatchCallable` / :class:`~emcee_amd.targets.BatchKernel` as the untempered likelihood.
 
+Fused form.  A :class:`~emcee_amd.targets.PTFused` likelihood -- the user's per-row ``__device__`` likelihood and, optionally,
+prior compiled into the tempered kernel ``k_pt_run`` (:func:`~emcee_amd.targets.compile_fused_pt`) -- runs one workgroup an
+object: all its rungs in LDS, the half-steps of every rung side by side, the swap pass and the ladder update between workgroup
+barriers, ONE launch per ``run_mcmc`` chunk of up to 4 096 steps.  Everything below holds unchanged, and the run is bit for bit the
+``BatchKernel`` run of the same functions (while no proposal has a non-finite coordinate: the fused form rejects such a row without
+calling a functor).  An object must fit one workgroup's LDS (``emx_pt_fused_check``); larger ones keep the callback path.
+
 Tempered log-probability.  ``lp = beta * L + P`` as two separate IEEE operations (no contraction).  At ``beta == 0``,
 ``lp = P``, so ``0 * -inf`` never occurs.  Where ``P == -inf`` the row's ``L`` is ignored (NaN included) and kept as ``-inf``.
 The commit is :class:`~emcee_amd.EnsembleBatch`'s Metropolis rule on the tempered ``lp``; ``L`` and ``lp`` are kept per walker.
@@ -47,7 +54,7 @@ from . import _lib
 from .batch import EnsembleBatch, _trampoline
 from .ensemble import _refuse_extended_precision, walkers_independent
 from .state import State
-from .targets import BatchCallable, BatchFused, BatchKernel, BatchTarget, DeviceTarget
+from .targets import BatchCallable, BatchFused, BatchKernel, BatchTarget, DeviceTarget, PTFused
 
 __all__ = ["PTSampler", "default_betas", "thermodynamic_integration_log_evidence"]
 
@@ -133,6 +140,8 @@ class PTSampler(object):
     proposal block and returns ``(nbatch, ntemps, R)``) or a :class:`~emcee_amd.targets.BatchKernel` (``nbatch * ntemps`` members
     in (object, rung) order), evaluated untempered.  ``log_prior``: None (flat, improper), ``(lo, hi)`` (a box the kernel
     evaluates: 0 inside, -inf outside), or a BatchCallable / BatchKernel called on the same block before the likelihood.
+    A :class:`~emcee_amd.targets.PTFused` likelihood (module docstring) takes ``log_prior`` None or ``(lo, hi)`` only, and neither
+    when its launcher carries a prior functor.
     ``betas``: strictly decreasing from 1 to >= 0, else :func:`default_betas` ``(ntemps, ndim, Tmax)``; every object starts on
     it.  ``moves``: the schedule forms of :class:`~emcee_amd.EnsembleBatch`'s callback path.  ``adaptive``: adapt each object's
     ladder after every swap pass (module docstring; ptemcee's ``adaptation_lag`` and ``adaptation_time``, both > 0).
@@ -153,6 +162,9 @@ class PTSampler(object):
             kind = "fused device target" if isinstance(log_likelihood, DeviceTarget) else type(log_likelihood).__name__
             raise TypeError("PTSampler's log_likelihood is a targets.BatchCallable or targets.BatchKernel; a %s is not (wrap the "
                             "model in BatchCallable)" % kind)
+        fused = isinstance(log_likelihood, PTFused)
+        if fused and log_likelihood.ndim != self.ndim:
+            raise ValueError("the PTFused target was compiled for ndim %d; the sampler has ndim %d" % (log_likelihood.ndim, self.ndim))
         self.betas = _check_betas(betas) if betas is not None else default_betas(self.ntemps, self.ndim, Tmax)
         if len(self.betas) != self.ntemps:
             raise ValueError("betas holds %d rungs for ntemps = %d" % (len(self.betas), self.ntemps))
@@ -160,6 +172,11 @@ class PTSampler(object):
         if log_prior is not None:
             if isinstance(log_prior, BatchFused):
                 raise TypeError("log_prior is None, (lo, hi) or a targets.BatchCallable / BatchKernel; a BatchFused is not")
+            if fused and log_likelihood.has_prior:
+                raise ValueError("the PTFused launcher carries a prior functor: log_prior must be None")
+            if fused and isinstance(log_prior, BatchTarget):
+                raise TypeError("with a PTFused likelihood log_prior is None or (lo, hi): a BatchCallable / BatchKernel prior would need "
+                                "the callback path (compile the prior into the launcher: compile_fused_pt(..., prior=...))")
             if isinstance(log_prior, BatchTarget):
                 self._prior = log_prior
             elif isinstance(log_prior, DeviceTarget) or callable(log_prior):
@@ -190,7 +207,14 @@ class PTSampler(object):
         self.member_seeds = np.stack([np.random.RandomState(s).randint(0, 2 ** 32, size=self.ntemps, dtype=np.uint64)
                                       for s in seeds])
         self._b = EnsembleBatch(self.nbatch * self.ntemps, self.nwalkers, self.ndim, self._wrap(log_likelihood), moves=moves,
-                                seeds=self.member_seeds.reshape(-1), device=device)
+                                seeds=self.member_seeds.reshape(-1), device=device, _tempered=True)
+        self._fused = log_likelihood if fused else None
+        if fused:           # an object must fit one workgroup's LDS: refused here, before any device is touched
+            msg = C.create_string_buffer(512)
+            d = self._b._descs
+            arr = (_lib.MoveDesc * len(d))(*d)
+            if _lib.load().emx_pt_fused_check(self.ntemps, self.nwalkers, self.ndim, len(d), arr, msg, 512) != 0:
+                raise ValueError("PTSampler: %s" % msg.value.decode())
         self.device = self._b.device
         self._h = None
         self._prior_keep = None
@@ -203,7 +227,7 @@ class PTSampler(object):
 
     def _wrap(self, t):
         """a BatchCallable's fn sees (nbatch, ntemps, R, ndim); a BatchKernel the handle's members as they are"""
-        if isinstance(t, BatchKernel):
+        if isinstance(t, (BatchKernel, PTFused)):
             return t
         fn, G, T, D = t.fn, self.nbatch, self.ntemps, self.ndim
         return BatchCallable(lambda q: fn(q.view(G, T, q.shape[1], D)))
@@ -218,7 +242,10 @@ class PTSampler(object):
             h = self._b._handle()
             ptr = (lambda a: None if a is None else a.ctypes.data_as(C.c_void_p))
             lo, hi = self._box if self._box is not None else (None, None)
-            self._ck(lib.emx_pt_set_tempering(h, self.ntemps, self.betas, ptr(lo), ptr(hi)))
+            rc = lib.emx_pt_set_tempering(h, self.ntemps, self.betas, ptr(lo), ptr(hi))
+            if rc != 0 and self._fused is not None and b"carries a prior functor" in lib.emx_batch_last_error(h):
+                raise ValueError("the PTFused launcher carries a prior functor: log_prior must be None")
+            self._ck(rc)
             if self._prior is not None:
                 p = self._wrap(self._prior)
                 if isinstance(p, BatchKernel):
@@ -435,7 +462,7 @@ class PTSampler(object):
         """-> ``(logZ, dlogZ)``, each ``(nbatch,)``: thermodynamic integration over each object's ladder of the mean ``L`` of the
         stored steps after ``int(fburnin * iteration)``.  Needs a normalised prior (a box, or a prior callable), and a ladder
         that did not change over those steps."""
-        if self._box is None and self._prior is None:
+        if self._box is None and self._prior is None and not (self._fused is not None and self._fused.has_prior):
             raise ValueError("the evidence needs a normalised prior: with log_prior=None the prior is flat and improper")
         discard = int(fburnin * self.iteration)
         means = self.mean_log_likelihood(discard)

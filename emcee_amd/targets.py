@@ -21,7 +21,8 @@ import numpy as np
 from . import _lib
 
 __all__ = ["DeviceTarget", "IsoGaussian", "DiagGaussian", "DenseGaussian", "Rosenbrock", "UniformBox", "DeviceCallable", "DeviceKernel",
-           "BatchCallable", "BatchKernel", "BatchFused", "BatchFusedLibrary", "compile_fused", "get_include"]
+           "BatchCallable", "BatchKernel", "BatchFused", "BatchFusedLibrary", "compile_fused", "get_include", "PTFused", "PTFusedLibrary",
+           "compile_fused_pt"]
 
 
 class DeviceTarget(object):
@@ -216,7 +217,8 @@ class BatchFused(BatchTarget):
 
     :class:`~emcee_amd.EnsembleBatch` then runs as it does for a built-in target: one launch per ``run_mcmc`` chunk, no callback,
     no proposal block in global memory, bit for bit the :class:`BatchKernel` run of the same function.
-    :func:`compile_fused` builds such a launcher from source.  Not a likelihood of :class:`~emcee_amd.PTSampler`."""
+    :func:`compile_fused` builds such a launcher from source.  Not a likelihood of :class:`~emcee_amd.PTSampler` (its launcher
+    carries the untempered kernel): the tempered form is :class:`PTFused`."""
     kind = _lib.TARGET_FUSED_USER
 
     def __init__(self, fn_ptr, ndim, user=None):
@@ -240,6 +242,35 @@ class BatchFused(BatchTarget):
         if hasattr(u, "data_ptr"):
             return int(u.data_ptr())
         return u.value if isinstance(u, ctypes.c_void_p) else int(u)
+
+
+class PTFused(BatchTarget):
+    """The user's per-row ``__device__`` log-likelihood (and, optionally, log-prior) compiled INTO the tempered kernel of
+    :class:`~emcee_amd.PTSampler`: ``fn_ptr`` is the launcher that ``EMX_FUSED_PT_TARGET(name, LikeFunctor, PriorFunctor, ndim)`` of
+    ``emx_pt_fused.hpp`` emits in the user's own translation unit (an ``emx_pt_fused_fn`` of ``include/emx.h``), ``ndim`` the
+    dimension it was compiled for, ``user`` the device pointer both functors receive with every row (as :class:`BatchFused`'s); the
+    functors' ``member`` is ``object * ntemps + rung``.  ``has_prior``: whether the launcher carries a prior functor (None: not
+    known before the launcher is probed at the first run).
+
+    One workgroup then runs one object -- all its rungs, the swap pass and the ladder adaptation -- in LDS: one launch per
+    ``run_mcmc`` chunk, bit for bit the :class:`BatchKernel` run of the same functions.  :func:`compile_fused_pt` builds such a
+    launcher from source.  A likelihood of :class:`~emcee_amd.PTSampler` only."""
+
+    def __init__(self, fn_ptr, ndim, user=None, has_prior=None):
+        if not isinstance(fn_ptr, ctypes._CFuncPtr):
+            addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
+            if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
+                raise TypeError("PTFused needs an emx_pt_fused_fn: a ctypes function or a non-null address")
+        if isinstance(ndim, bool) or not isinstance(ndim, (int, np.integer)) or ndim < 1:
+            raise TypeError("PTFused needs the ndim its launcher was compiled for, an integer >= 1; got %r" % (ndim,))
+        if not (user is None or isinstance(user, (int, np.integer, ctypes.c_void_p)) or hasattr(user, "data_ptr")) or isinstance(user, bool):
+            raise TypeError("PTFused's user is a device pointer: None, an integer, a ctypes.c_void_p or a torch CUDA tensor")
+        if hasattr(user, "data_ptr") and not getattr(user, "is_cuda", False):
+            raise TypeError("PTFused's user tensor must live on the GPU (the functors read it on the device)")
+        self.fn_ptr, self.ndim, self.user = fn_ptr, int(ndim), user
+        self.has_prior = None if has_prior is None else bool(has_prior)
+
+    user_address = BatchFused.user_address
 
 
 def get_include():
@@ -267,6 +298,74 @@ class BatchFusedLibrary(object):
 
 
 FUSED_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC"]
+
+
+def _compile_cached(what, header, source, tail, key_parts, name, flags, cache_dir):
+    """the shared build of compile_fused / compile_fused_pt: cache key, translation unit, hipcc, diagnostics -> path of the library"""
+    from . import _build
+    h = hashlib.sha256(repr(key_parts + (FUSED_FLAGS + flags,)).encode())
+    for d in _build.DEPS:
+        if d.endswith((".hpp", ".h")):
+            with open(d, "rb") as f:
+                h.update(f.read())
+    key = h.hexdigest()[:24]
+    cache_dir = cache_dir or os.environ.get("EMCEE_AMD_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "emcee_amd")
+    work = os.path.join(str(cache_dir), key)
+    so = os.path.join(work, "lib%s.so" % name)
+    if not os.path.exists(so):
+        os.makedirs(work, exist_ok=True)
+        src = os.path.join(work, "%s.hip" % name)
+        with open(src, "w") as f:
+            f.write("#include <%s>\n\n%s\n\n%s\n" % (header, source, tail))
+        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+        tmp = "%s.%d.tmp" % (so, os.getpid())
+        cmd = [hipcc] + FUSED_FLAGS + flags + ["-I" + d for d in get_include()] + [src, "-o", tmp]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+            raise RuntimeError("%s: hipcc failed (%s):\n%s" % (what, src, (r.stderr or r.stdout)[-4000:]))
+        os.replace(tmp, so)
+    return so
+
+
+class PTFusedLibrary(object):
+    """What :func:`compile_fused_pt` built: ``path``, ``lib`` (its ``ctypes.CDLL``), ``name`` of the launcher, ``ndim``,
+    ``has_prior``, and :meth:`target`."""
+
+    def __init__(self, path, name, ndim, has_prior):
+        self.path, self.name, self.ndim, self.has_prior = path, name, int(ndim), bool(has_prior)
+        _lib.load()                       # one HIP runtime per process: the library's (torch's) first
+        self.lib = ctypes.CDLL(path)
+        self.launcher = getattr(self.lib, name)
+
+    def target(self, user=None):
+        """-> :class:`PTFused` of the compiled functors with the device pointer ``user``"""
+        t = PTFused(self.launcher, self.ndim, user, has_prior=self.has_prior)
+        t._library = self                 # the launcher's code lives as long as the target
+        return t
+
+
+def compile_fused_pt(source, likelihood, ndim, prior=None, name=None, flags=(), cache_dir=None):
+    """Compile the user's model into the tempered kernel -> :class:`PTFusedLibrary`.
+
+    ``source``: HIP C++ that defines the functor type ``likelihood`` and, unless ``prior`` is None, the functor type ``prior`` (both
+    ``__device__ double operator()(const double* x, int ndim, int member, const void* user) const``).  The translation unit is
+    ``#include <emx_pt_fused.hpp>``, ``source`` and ``EMX_FUSED_PT_TARGET(name, likelihood, prior or emx::NoFusedPrior, ndim)``,
+    compiled and cached as :func:`compile_fused` does (the same flags; the key is the hash of source, both names, ndim, name, flags
+    and every header of the library); a compiler failure raises ``RuntimeError`` with the compiler's last lines."""
+    ndim = int(ndim)
+    if ndim < 1 or ndim > 256:
+        raise ValueError("compile_fused_pt: 1 <= ndim <= 256; got %d" % ndim)
+    for what, ident in (("likelihood", likelihood), ("prior", prior), ("name", name)):
+        if (ident is not None or what == "likelihood") and not (isinstance(ident, str) and re.match(r"^[A-Za-z_][A-Za-z0-9_:]*$", ident)):
+            raise ValueError("compile_fused_pt: %s must be a C++ identifier; got %r" % (what, ident))
+    name = name or "emx_pt_fused_%s_%d" % (likelihood.replace(":", "_"), ndim)
+    flags = [str(f) for f in flags]
+    tail = "EMX_FUSED_PT_TARGET(%s, %s, %s, %d)" % (name, likelihood, prior or "emx::NoFusedPrior", ndim)
+    so = _compile_cached("compile_fused_pt", "emx_pt_fused.hpp", source, tail, ("pt", source, likelihood, prior, ndim, name), name, flags,
+                         cache_dir)
+    return PTFusedLibrary(so, name, ndim, prior is not None)
 
 
 def compile_fused(source, functor, ndim, name=None, flags=(), cache_dir=None):

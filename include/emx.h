@@ -31,8 +31,10 @@ enum emx_target_kind {
     EMX_TARGET_ROSENBROCK = 4, /* -sum[100 (x_{i+1}-x_i^2)^2 + (1-x_i)^2] / scale (BASELINE C3) */
     EMX_TARGET_BOX = 5,        /* 0 inside [0,1]^D else -inf   test_proposal.py:25-28           */
     EMX_TARGET_DEVICE_CALLBACK = 6,/* the caller's batched log-prob on device buffers (emx_set_target_callback) */
-    EMX_TARGET_FUSED_USER = 8      /* batches only: the caller's per-row device function compiled into the one-workgroup kernel
+    EMX_TARGET_FUSED_USER = 8,     /* batches only: the caller's per-row device function compiled into the one-workgroup kernel
                                       (emx_set_batch_target_fused; 7 is taken inside the kernels) */
+    EMX_TARGET_FUSED_PT = 9        /* tempered batches only: the caller's likelihood (and prior) compiled into the tempered
+                                      one-workgroup kernel k_pt_run (emx_pt_set_target_fused) */
 };
 
 enum emx_move_kind {
@@ -557,7 +559,8 @@ int emx_set_batch_target_callback(emx_batch* b, emx_batch_log_prob_fn fn, void* 
  * "built against another version of emx_fused_target.hpp").  `user_dev`: a device pointer handed to the functor with every row
  * (per-member data, indexed by the functor's `member`); the caller keeps it alive.  The one-workgroup rules apply with the
  * staging area's LDS on top (emx_batch_check with EMX_TARGET_FUSED_USER); "batch_threads" and "batch_plan_steps" apply and
- * change no bit.  Not a target of tempered batches (emx_pt_set_tempering refuses it). */
+ * change no bit.  Not a target of tempered batches (emx_pt_set_tempering refuses it: this launcher carries k_small_run; the
+ * tempered kernel has its own launcher type, emx_pt_set_target_fused below). */
 typedef struct emx_fused_launch {
     uint32_t abi;            /* EMX_FUSED_ABI the library was built with */
     uint32_t args_bytes;     /* sizeof(SmallRunArgs) of the library */
@@ -681,6 +684,37 @@ int emx_pt_set_ladder(emx_batch* b, const double* betas, const int64_t* updates)
  * after t earlier updates.  0, or -1 for bad arguments. */
 int emx_host_pt_adapt_ladder(const double* betas, const int64_t* accepts, int32_t ntemps, int64_t nwalkers, double lag, double time,
                              int64_t t, double* out);
+/* Fused tempered targets (EMX_TARGET_FUSED_PT; emcee_amd.targets.PTFused / compile_fused_pt): the caller's per-row __device__
+ * log-likelihood and, optionally, log-prior compiled INTO the tempered one-workgroup kernel k_pt_run.  One workgroup owns one object:
+ * all its ntemps rungs live in LDS, every rung's half-step rows run side by side, the swap pass and the ladder update run on LDS
+ * between workgroup barriers, and a run is ONE launch per chunk of up to 4 096 steps -- no callback, no proposal block, no k_pt_swap
+ * launch.  Bit for bit the tempered callback run of the same functions (while no proposal has a non-finite coordinate: such a row
+ * is rejected here without reaching a functor).  The caller's translation unit includes emcee_amd/csrc/emx_pt_fused.hpp and emits a
+ * launcher with EMX_FUSED_PT_TARGET(name, LikeFunctor, PriorFunctor, ndim) (emx::NoFusedPrior: no prior functor -- the handle's
+ * box, or a flat prior); the functors' `member` is object * ntemps + rung.  The descriptor is emx_fused_launch's with the library's
+ * PtRunArgs behind `args` and EMX_FUSED_PT_ABI in `abi`; the launcher's answers are emx_fused_batch_fn's (1: another version of
+ * the header, 2: another ndim, 3: the move selector was not compiled in, 100 + a hipError_t), and it writes `has_prior` (grid == 0:
+ * the probe, nothing launched).  emx_pt_set_target_fused probes once and makes the launcher the handle's likelihood;
+ * emx_pt_set_tempering then accepts the handle (with box_lo / box_hi only when the launcher has no prior functor, and only when
+ * emx_pt_fused_check takes the shape).  emx_set_batch_prior_callback does not apply.  "batch_threads" and "batch_plan_steps" apply
+ * and change no bit.  Everything that reads the handle's state or chain (emx_pt_get_state, emx_pt_swap, emx_pt_get_ladder,
+ * emx_pt_set_ladder, emx_pt_swap_counts, emx_batch_chain_read, ...) works unchanged. */
+typedef struct emx_pt_fused_launch {
+    uint32_t abi;            /* EMX_FUSED_PT_ABI the library was built with */
+    uint32_t args_bytes;     /* sizeof(PtRunArgs) of the library */
+    int32_t ndim, movesel, grid, threads;      /* grid: objects (workgroups); movesel as emx_fused_launch's */
+    uint64_t lds_bytes;
+    void* hip_stream;
+    const void* args;        /* PtRunArgs */
+    const void* user;        /* user_dev */
+    int32_t has_prior;       /* out: 1 when the launcher carries a prior functor */
+} emx_pt_fused_launch;
+typedef int (*emx_pt_fused_fn)(emx_pt_fused_launch*);     /* 0, or non-zero and nothing launched */
+int emx_pt_set_target_fused(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compiled, const void* user_dev);
+/* host only (no device touched): 0 when one workgroup's LDS holds an object of ntemps rungs of (nwalkers, ndim) under this
+ * schedule with at least one plan step, else -1 and the reason (with the bytes needed) in msg */
+int emx_pt_fused_check(int32_t ntemps, int64_t nwalkers, int32_t ndim, int32_t nmoves, const emx_move_desc* moves, char* msg,
+                       int32_t msglen);
 
 #ifdef __cplusplus
 }
