@@ -33,6 +33,19 @@ _lib = None
 DEVICE_LOG_PROB_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p)
 # emx_batch_log_prob_fn: (user, coords_dev, nbatch, rows, ndim, log_prob_dev, hip_stream) -> int
 BATCH_LOG_PROB_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p)
+# emx_batch_log_prob_blobs_fn: (user, coords_dev, nbatch, rows, ndim, log_prob_dev, nblobs, blobs_dev, hip_stream) -> int
+BATCH_LOG_PROB_BLOBS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                      C.c_void_p)
+MAX_BLOBS = 32                      # blobs a sample of a batch target (BATCH_MAX_BLOBS)
+
+
+class FusedLaunch(C.Structure):
+    """emx_fused_launch of include/emx.h: the descriptor a fused user target's launcher is handed"""
+    _fields_ = [("abi", C.c_uint32), ("args_bytes", C.c_uint32), ("ndim", C.c_int32), ("movesel", C.c_int32), ("grid", C.c_int32),
+                ("threads", C.c_int32), ("lds_bytes", C.c_uint64), ("hip_stream", C.c_void_p), ("args", C.c_void_p),
+                ("user", C.c_void_p), ("nblobs", C.c_int32), ("reserved", C.c_int32)]
+
+
 # emx_fused_batch_fn: (const emx_fused_launch*) -> int
 FUSED_BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 # emx_pt_fused_fn: (emx_pt_fused_launch*) -> int
@@ -196,6 +209,12 @@ SIGNATURES = {
     "emx_summary_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int32, _P, _P, _P, _P,
                                     C.POINTER(C.c_int64)]),
     "emx_host_order_stats": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int32, _i64p, _dp]),
+    "emx_set_batch_target_fused_blobs": (C.c_int, [_P, FUSED_BATCH_FN, C.c_int32, _P, C.c_int32]),
+    "emx_set_batch_target_callback_blobs": (C.c_int, [_P, BATCH_LOG_PROB_BLOBS_FN, _P, C.c_int32]),
+    "emx_check_batch_blobs": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MoveDesc), C.c_int32, C.c_char_p, C.c_int32]),
+    "emx_get_blobs_batch": (C.c_int, [_P, _P, C.POINTER(C.c_int32)]),
+    "emx_summary_batch_plane": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int32, _P, _P,
+                                          _P, _P, C.POINTER(C.c_int64)]),
 }
 
 

@@ -23,6 +23,12 @@ proposals) and ``S_max`` calls of that function, whatever B; member b is bit for
 schedule (a GaussianMove, one split, only as the sole move); ``R = ceil(nwalkers / S_min)``, and rows of ``q[b]`` past the
 member's current split are padding -- copies of its walkers, their values ignored.  The LDS bound does not apply there.
 Host callables, ``DeviceCallable`` and ``DeviceKernel`` targets run through :class:`~emcee_amd.EnsembleSampler`.
+
+Blobs.  A ``BatchFused`` / ``BatchCallable`` / ``BatchKernel`` with ``nblobs = K > 0`` produces K float64 derived quantities with
+every log-probability (the reference's ``log_prob_fn`` returning ``(lp, blobs...)``).  They stay on the device: committed exactly
+when the log-probability is (a rejected proposal keeps the walker's previous ones), stored in a blob plane next to the chain,
+read with :meth:`EnsembleBatch.get_blobs` / ``get_last_sample().blobs`` and summarised with :meth:`EnsembleBatch.get_blob_summary`.
+Coordinates, log-probs and accept counts are bit for bit those of the same function without blobs.
 """
 import ctypes as C
 
@@ -82,7 +88,10 @@ class EnsembleBatch(object):
         lib = _lib.load()
         msg = C.create_string_buffer(256)
         arr = (_lib.MoveDesc * len(self._descs))(*self._descs)
-        if lib.emx_batch_check(self.nwalkers, self.ndim, self._targets[0].kind, len(self._descs), arr, msg, 256) != 0:
+        self.nblobs = int(getattr(self._targets[0], "nblobs", 0)) if isinstance(self._targets[0], BatchTarget) else 0
+        if self.nblobs and self._tempered:
+            raise TypeError("a tempered batch records no blobs (nblobs = %d)" % self.nblobs)
+        if lib.emx_check_batch_blobs(self.nwalkers, self.ndim, self._targets[0].kind, len(self._descs), arr, self.nblobs, msg, 256) != 0:
             raise ValueError("EnsembleBatch: %s" % msg.value.decode())
         if seeds is None:
             seeds = np.random.randint(0, 2 ** 32, size=self.nbatch, dtype=np.uint64)
@@ -201,19 +210,26 @@ class EnsembleBatch(object):
 
     def _bind_callback(self, h):
         t = self._targets[0]
+        ftype = _lib.BATCH_LOG_PROB_BLOBS_FN if self.nblobs else _lib.BATCH_LOG_PROB_FN
         if isinstance(t, BatchKernel):
-            fn = t.fn_ptr if isinstance(t.fn_ptr, _lib.BATCH_LOG_PROB_FN) else C.cast(t.fn_ptr, _lib.BATCH_LOG_PROB_FN)
+            fn = t.fn_ptr if isinstance(t.fn_ptr, ftype) else C.cast(t.fn_ptr, ftype)
             user = t.user_ptr if isinstance(t.user_ptr, C.c_void_p) else C.c_void_p(t.user_ptr)
         else:
-            fn, user = _lib.BATCH_LOG_PROB_FN(_trampoline(t.fn, self.device, self._cb_box)), None
+            fn, user = ftype(_trampoline(t.fn, self.device, self._cb_box, self.nblobs)), None
         self._cb_keep = fn                # the library holds the pointer: keep the object alive
-        self._ck(self._lib().emx_set_batch_target_callback(h, fn, user))
+        if self.nblobs:
+            self._ck(self._lib().emx_set_batch_target_callback_blobs(h, fn, user, self.nblobs))
+        else:
+            self._ck(self._lib().emx_set_batch_target_callback(h, fn, user))
 
     def _bind_user_fused(self, h):
         t = self._targets[0]
         fn = t.fn_ptr if isinstance(t.fn_ptr, _lib.FUSED_BATCH_FN) else C.cast(t.fn_ptr, _lib.FUSED_BATCH_FN)
         self._cb_keep = (fn, t)           # the library holds the launcher and the user's device pointer: keep both alive
-        self._ck(self._lib().emx_set_batch_target_fused(h, fn, t.ndim, C.c_void_p(t.user_address())))
+        if self.nblobs:
+            self._ck(self._lib().emx_set_batch_target_fused_blobs(h, fn, t.ndim, C.c_void_p(t.user_address()), self.nblobs))
+        else:
+            self._ck(self._lib().emx_set_batch_target_fused(h, fn, t.ndim, C.c_void_p(t.user_address())))
 
     def _bind_pt_fused(self, h):
         t = self._targets[0]
@@ -323,7 +339,7 @@ class EnsembleBatch(object):
         thin, discard = int(thin), int(discard)
         start = min(discard + thin - 1, it)                 # reference backend.py:53
         nsel = len(range(start, it, thin))
-        shape = (hi - lo, nsel, self.nwalkers) + ((self.ndim,) if what == 0 else ())
+        shape = (hi - lo, nsel, self.nwalkers) + ((self.ndim,) if what == 0 else (self.nblobs,) if what == 4 else ())
         out = np.empty(shape)
         if nsel and hi > lo:
             self._ck(self._lib().emx_batch_chain_read(self._h, what, lo, hi, start, it, thin, out))
@@ -338,6 +354,13 @@ class EnsembleBatch(object):
     def get_log_prob(self, discard=0, thin=1, flat=False):
         """``(B, nsteps, nwalkers)``; ``flat`` -> ``(B, nsteps * nwalkers)``."""
         return self._read(1, 0, self.nbatch, discard, thin, flat)
+
+    def get_blobs(self, discard=0, thin=1, flat=False):
+        """``(B, nsteps, nwalkers, nblobs)``; ``flat`` -> ``(B, nsteps * nwalkers, nblobs)``: the blobs stored with every sample
+        of the chain.  None when the target has no blobs (as the reference's)."""
+        if not self.nblobs:
+            return None
+        return self._read(4, 0, self.nbatch, discard, thin, flat)
 
     def _accepted(self):
         out = np.zeros((self.nbatch, self.nwalkers))
@@ -395,11 +418,20 @@ class EnsembleBatch(object):
         host.  A device failure raises :class:`emcee_amd._lib.EmxError` (no fallback)."""
         return self._summary(discard, thin, quantiles, cov, 0, self.nbatch)
 
-    def _summary(self, discard, thin, quantiles, cov, lo, hi):
+    def get_blob_summary(self, discard=0, thin=1, quantiles=(0.16, 0.5, 0.84), cov=True):
+        """-> :class:`~emcee_amd.summary.BatchSummary` of every member's BLOBS: what :meth:`get_summary` returns, computed over the
+        blob plane on the device by the same kernels, with ``nblobs`` in ``ndim``'s place -- ``mean`` ``(B, nblobs)``, ``cov``
+        ``(B, nblobs, nblobs)``, ``quantiles`` ``(B, nq, nblobs)``; ``map_coords`` ``(B, nblobs)`` holds the blobs of the stored
+        sample with the largest stored log-prob (``map_log_prob``).  Raises ``ValueError`` when the target has no blobs."""
+        return self._summary(discard, thin, quantiles, cov, 0, self.nbatch, plane=4)
+
+    def _summary(self, discard, thin, quantiles, cov, lo, hi, plane=0):
+        if plane == 4 and not self.nblobs:
+            raise ValueError("the target has no blobs (nblobs = 0): there is no blob plane to summarise")
         q = _summary.check_quantiles(quantiles)
         _, _, nt = self._summary_rows(discard, thin)
         ranks, ilo, ihi, g = _summary.plan_ranks(nt * self.nwalkers, q)
-        n, mean, c, order, mx, mlp = self._summary_device(discard, thin, ranks, cov, lo, hi)
+        n, mean, c, order, mx, mlp = self._summary_device(discard, thin, ranks, cov, lo, hi, plane)
         return _summary.BatchSummary(n, mean, c, _summary.interpolate(order, ilo, ihi, g), mx, mlp)
 
     def _summary_rows(self, discard, thin):
@@ -417,7 +449,7 @@ class EnsembleBatch(object):
             raise ValueError("discard = %d, thin = %d select none of the %d stored steps" % (discard, thin, it))
         return start, it, nt
 
-    def _summary_device(self, discard=0, thin=1, ranks=(), cov=True, lo=0, hi=None):
+    def _summary_device(self, discard=0, thin=1, ranks=(), cov=True, lo=0, hi=None, plane=0):
         """-> (n, mean (hi - lo, ndim), cov (hi - lo, ndim, ndim) or None, order statistics (hi - lo, len(ranks), ndim), MAP
         coordinates (hi - lo, ndim), MAP log-probs (hi - lo)): ``emx_summary_batch`` on members [lo, hi), ``order[:, r, d]``
         being the ``ranks[r]``-th smallest (0-based) of the ``n`` selected samples of parameter d.  Arguments are checked
@@ -433,14 +465,18 @@ class EnsembleBatch(object):
         thin, n = int(thin), nt * self.nwalkers
         if len(ranks) and not (0 <= ranks.min() and ranks.max() < n):
             raise ValueError("ranks must lie in [0, %d)" % n)
-        M, D = hi - lo, self.ndim
+        M, D = hi - lo, (self.nblobs if plane == 4 else self.ndim)
         mean, mx, mlp = np.empty((M, D)), np.empty((M, D)), np.empty(M)
         c = np.empty((M, D, D)) if cov else None
         order = np.empty((M, len(ranks), D))
         ptr = (lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p))
         ns = C.c_int64(0)
-        self._ck(self._lib().emx_summary_batch(self._h, lo, hi, start, it, thin, ptr(mean), ptr(c), len(ranks), ptr(ranks), ptr(order),
-                                               ptr(mx), ptr(mlp), C.byref(ns)))
+        if plane == 0:
+            self._ck(self._lib().emx_summary_batch(self._h, lo, hi, start, it, thin, ptr(mean), ptr(c), len(ranks), ptr(ranks), ptr(order),
+                                                   ptr(mx), ptr(mlp), C.byref(ns)))
+        else:
+            self._ck(self._lib().emx_summary_batch_plane(self._h, plane, lo, hi, start, it, thin, ptr(mean), ptr(c), len(ranks), ptr(ranks),
+                                                         ptr(order), ptr(mx), ptr(mlp), C.byref(ns)))
         assert ns.value == n
         return n, mean, c, order, mx, mlp
 
@@ -451,7 +487,11 @@ class EnsembleBatch(object):
         coords = np.empty((self.nbatch, self.nwalkers, self.ndim))
         lp = np.empty((self.nbatch, self.nwalkers))
         self._ck(self._lib().emx_batch_get_state(self._h, coords.ctypes.data_as(C.c_void_p), lp.ctypes.data_as(C.c_void_p)))
-        return State(coords, log_prob=lp)
+        blobs = None
+        if self.nblobs:
+            blobs = np.empty((self.nbatch, self.nwalkers, self.nblobs))
+            self._ck(self._lib().emx_get_blobs_batch(self._h, blobs.ctypes.data_as(C.c_void_p), None))
+        return State(coords, log_prob=lp, blobs=blobs)
 
     def __len__(self):
         return self.nbatch
@@ -484,7 +524,25 @@ def _check_tol(tau, nt, tol, quiet, members, err_tau):
     autocorr.logger.warning(msg)
 
 
-def _trampoline(fn, device, box):
+def _split_result(res, nb, rows, nblobs):
+    """what a BatchCallable's ``fn`` returned for ``nb`` members x ``rows`` rows -> (log_prob, blobs or None), after the shape
+    checks: ``nb * rows`` log-probs and, with ``nblobs > 0``, a pair whose second entry has shape ``(nb, rows, nblobs)``."""
+    bl = None
+    if nblobs:
+        if not (isinstance(res, (tuple, list)) and len(res) == 2):
+            raise ValueError("with nblobs = %d the batched log_prob_fn returns (log_prob, blobs); got %s" % (nblobs, type(res).__name__))
+        res, bl = res
+        got = tuple(bl.shape) if hasattr(bl, "shape") else np.shape(bl)
+        if got != (nb, rows, nblobs):
+            raise ValueError("the batched log_prob_fn returned blobs of shape %s; expected (members, rows, nblobs) = %s"
+                             % (got, (nb, rows, nblobs)))
+    got = tuple(res.shape) if hasattr(res, "shape") else np.shape(res)
+    if int(np.prod(got, dtype=np.int64)) != nb * rows:
+        raise ValueError("the batched log_prob_fn returned %d values for %d members x %d rows" % (int(np.prod(got, dtype=np.int64)), nb, rows))
+    return res, bl
+
+
+def _trampoline(fn, device, box, nblobs=0):
     """emx_batch_log_prob_fn over a BatchCallable's ``fn`` (DeviceEnsemble.set_target_callback's eager form): ``fn`` sees the
     library's block as a ``(B, rows, ndim)`` tensor and runs on the handle's stream; an exception is kept in ``box[0]``."""
     import torch
@@ -492,7 +550,8 @@ def _trampoline(fn, device, box):
     streams = {}
     dev = torch.device("cuda", device)
 
-    def tramp(user, q_ptr, nb, rows, ndim, lp_ptr, stream):
+    def tramp(user, q_ptr, nb, rows, ndim, lp_ptr, *rest):
+        stream = rest[-1]                 # (emx_batch_log_prob_blobs_fn: nblobs and blobs_dev come before it)
         try:
             s = streams.get(stream)
             if s is None:
@@ -501,10 +560,12 @@ def _trampoline(fn, device, box):
             with torch.cuda.stream(s):
                 q = torch.as_tensor(_DevView(q_ptr, n * ndim), device=dev).view(nb, rows, ndim)
                 out = torch.as_tensor(_DevView(lp_ptr, n), device=dev)
-                res = torch.as_tensor(fn(q), dtype=torch.float64, device=dev).reshape(-1)
-                if res.numel() != n:
-                    raise ValueError("the batched log_prob_fn returned %d values for %d members x %d rows" % (res.numel(), nb, rows))
+                res, bl = _split_result(fn(q), nb, rows, nblobs)
+                res = torch.as_tensor(res, dtype=torch.float64, device=dev).reshape(-1)
                 out.copy_(res)
+                if nblobs:
+                    bl = torch.as_tensor(bl, dtype=torch.float64, device=dev).reshape(-1)
+                    torch.as_tensor(_DevView(rest[1], n * nblobs), device=dev).copy_(bl)
             return 0
         except BaseException as e:  # noqa: BLE001  (handed to the caller by EnsembleBatch._ck)
             box[0] = e
@@ -530,6 +591,16 @@ class _Member(object):
     def get_log_prob(self, discard=0, thin=1, flat=False):
         return self._batch._read(1, self.index, self.index + 1, discard, thin, flat)[0]
 
+    def get_blobs(self, discard=0, thin=1, flat=False):
+        if not self._batch.nblobs:
+            return None
+        return self._batch._read(4, self.index, self.index + 1, discard, thin, flat)[0]
+
+    def get_blob_summary(self, discard=0, thin=1, quantiles=(0.16, 0.5, 0.84), cov=True):
+        """:meth:`EnsembleBatch.get_blob_summary` of this member alone, without the leading axis."""
+        r = self._batch._summary(discard, thin, quantiles, cov, self.index, self.index + 1, plane=4)
+        return _summary.BatchSummary(r.nsamples, *[None if a is None else a[0] for a in r[1:]])
+
     @property
     def acceptance_fraction(self):
         return self._batch.acceptance_fraction[self.index]
@@ -549,4 +620,4 @@ class _Member(object):
 
     def get_last_sample(self):
         s = self._batch.get_last_sample()
-        return State(s.coords[self.index], log_prob=s.log_prob[self.index])
+        return State(s.coords[self.index], log_prob=s.log_prob[self.index], blobs=None if s.blobs is None else s.blobs[self.index])

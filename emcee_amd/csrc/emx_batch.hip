@@ -75,6 +75,11 @@ struct emx_batch {
     // EMX_TARGET_FUSED_USER: the caller's launcher of k_small_run around their device function, and their device pointer
     emx_fused_batch_fn fused_fn = nullptr;
     const void* fused_user = nullptr;
+    // blobs (emx_set_batch_target_fused_blobs / emx_set_batch_target_callback_blobs; 0: none): the walkers' current ones (B, N,
+    // nblobs), the blob plane (B, cap, N, nblobs) next to the chain, the callback's function and its (B, R, nblobs) block
+    int32_t nblobs = 0;
+    double *blobs = nullptr, *chain_blobs = nullptr, *cb_bq = nullptr;
+    emx_batch_log_prob_blobs_fn cbb_fn = nullptr;
     // emx_autocorr_batch (emx_batch_acf.hip): its hipFFT plans and scratch; tuning "batch_acf_series" (0: auto)
     BatchAcf* acf = nullptr;
     int64_t tune_acf_series = 0;
@@ -136,8 +141,16 @@ int64_t fused_stage_rows(int64_t N, int32_t nmoves, const emx_move_desc* moves) 
 }
 
 // small_eligible's rules (emx.hip) applied to one member's shape; nullptr when the kernel takes it, else why not
-const char* shape_refusal(int64_t N, int32_t D, int32_t target, int32_t nmoves, const emx_move_desc* moves, char* buf, size_t n) {
+const char* shape_refusal(int64_t N, int32_t D, int32_t target, int32_t nmoves, const emx_move_desc* moves, char* buf, size_t n,
+                          int32_t nblobs = 0) {
     if (N < 2 || D < 1) return "nwalkers must be >= 2 and ndim >= 1";
+    if (nblobs < 0 || nblobs > BATCH_MAX_BLOBS) {
+        snprintf(buf, n, "a batch target carries 1 ... %d blobs a sample; got %d", BATCH_MAX_BLOBS, nblobs);
+        return buf;
+    }
+    if (nblobs > 0 && target != EMX_TARGET_DEVICE_CALLBACK && target != EMX_TARGET_FUSED_USER)
+        return "blobs come from a batched callback (emx_set_batch_target_callback_blobs) or a fused user target "
+               "(emx_set_batch_target_fused_blobs): the built-in and the tempered targets have none";
     if (N > 4096 || D > 256) {
         snprintf(buf, n, "nwalkers x ndim = %lld x %d is outside the one-workgroup kernel (nwalkers <= 4096, ndim <= 256)", (long long)N, D);
         return buf;
@@ -172,6 +185,12 @@ const char* shape_refusal(int64_t N, int32_t D, int32_t target, int32_t nmoves, 
         if (need > SMALL_LDS_MAX) {
             snprintf(buf, n, "nwalkers x ndim = %lld x %d with a fused user target does not fit one workgroup's LDS (%zu bytes > %zu)",
                      (long long)N, D, need, SMALL_LDS_MAX);
+            return buf;
+        }
+        if (need + small_blob_bytes(N, nblobs) > SMALL_LDS_MAX) {
+            snprintf(buf, n, "nwalkers x ndim = %lld x %d with a fused user target and %d blobs a walker does not fit one workgroup's LDS "
+                             "(%zu bytes > %zu; %zu without the blobs)", (long long)N, D, nblobs, need + small_blob_bytes(N, nblobs),
+                     SMALL_LDS_MAX, need);
             return buf;
         }
         return nullptr;
@@ -232,6 +251,9 @@ int fused_refusal(emx_batch* b, int rc, int movesel) {
                            "EMX_FUSED_ABI %u and %zu bytes of kernel arguments): rebuild it with this library's headers",
                     (unsigned)EMX_FUSED_ABI, sizeof(SmallRunArgs));
     if (rc == 2) return fail(b, -1, "the fused user target's launcher was compiled for another ndim than the batch's %d", b->D);
+    if (rc == 4)
+        return fail(b, -1, "the fused user target's launcher was compiled for another number of blobs than the %d asked for "
+                           "(EMX_FUSED_BATCH_TARGET_BLOBS's nblobs; EMX_FUSED_BATCH_TARGET has none)", b ? b->nblobs : 0);
     if (rc == 3)
         return fail(b, -1, "the fused user target's launcher does not carry the kernel of this schedule (move selector %d): compile it with "
                            "EMX_FUSED_MOVES_ANY", movesel);
@@ -332,8 +354,16 @@ int launch(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t st
         a.target = TGT_USER;
         a.user = b->fused_user;
         a.stage_rows = (int32_t)fused_stage_rows(b->N, nm, b->moves.data());
+        if (b->nblobs > 0) {
+            a.nblobs = b->nblobs;
+            a.blobs = b->blobs;
+            if (store && nsteps > 0) {
+                BNEED(b, b->chain_blobs != nullptr, "no blob plane (emx_batch_chain_config)");
+                a.chain_blobs = b->chain_blobs + (size_t)b->stored * b->N * b->nblobs;
+            }
+        }
     }
-    const size_t extra_lds = fused_user ? small_fused_stage_bytes(a.stage_rows, b->D) : 0;
+    const size_t extra_lds = fused_user ? small_fused_stage_bytes(a.stage_rows, b->D) + small_blob_bytes(b->N, b->nblobs) : 0;
     int threads = 0, plan_steps = 0;
     launch_shape(b, num_cu, sh, minsplits, dense, extra_lds, &threads, &plan_steps);
     a.batch = plan_steps;
@@ -354,6 +384,7 @@ int launch(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t st
         fl.hip_stream = (void*)b->stream;
         fl.args = &a;
         fl.user = b->fused_user;
+        fl.nblobs = b->nblobs;
         if (int rc = fused_refusal(b, b->fused_fn(&fl), movesel)) return rc;
     } else {
         const hipError_t e = small_dispatch<true>(sh.G, sh.V, sh.CH, dense ? b->Dp / 16 : 0, movesel, b->B, threads, lds, b->stream, a);
@@ -557,8 +588,10 @@ int launch_pt(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t
 // ---- the caller's batched log-prob (EMX_TARGET_DEVICE_CALLBACK) ----
 
 // the caller's function on `rows` rows of every member: coords (B, rows, D) -> log_prob (B, rows), enqueued on the stream
-int call_back(emx_batch* b, const double* coords, int64_t rows, double* out) {
-    const int rc = b->cb_fn(b->cb_user, coords, b->B, rows, b->D, out, (void*)b->stream);
+// (a target with blobs: and their blobs (B, rows, nblobs) -> blobs_out)
+int call_back(emx_batch* b, const double* coords, int64_t rows, double* out, double* blobs_out = nullptr) {
+    const int rc = b->nblobs > 0 ? b->cbb_fn(b->cb_user, coords, b->B, rows, b->D, out, b->nblobs, blobs_out, (void*)b->stream)
+                                 : b->cb_fn(b->cb_user, coords, b->B, rows, b->D, out, (void*)b->stream);
     if (rc != 0) return fail(b, -7, "the batched device log-prob callback failed (returned %d)", rc);
     return 0;
 }
@@ -616,7 +649,7 @@ int swap_pass(emx_batch* b, uint64_t step, int64_t row, bool swap) {
 
 // the initial log-probs: one call on the whole state, then the per-member NaN check
 int eval_callback(emx_batch* b) {
-    BNEED(b, b->cb_fn != nullptr, "device callback target without a callback (emx_set_batch_target_callback)");
+    BNEED(b, b->cb_fn != nullptr || b->cbb_fn != nullptr, "device callback target without a callback (emx_set_batch_target_callback)");
     if (b->pt_T > 0) {       // tempered: P (the caller's prior, the box or 0), L, then lp and the NaN check in one launch
         if (b->pr_fn) {
             if (int rc = call_prior(b, b->X, b->N, b->pt_P)) return rc;
@@ -629,7 +662,7 @@ int eval_callback(emx_batch* b) {
         ++b->launches;
         return 0;
     }
-    if (int rc = call_back(b, b->X, b->N, b->lp)) return rc;
+    if (int rc = call_back(b, b->X, b->N, b->lp, b->blobs)) return rc;      // the state's blobs by the same call
     BHIP(b, batch_lp_check(b->lp, b->status, b->B, (int32_t)b->N, b->stream));
     ++b->launches;
     return 0;
@@ -639,7 +672,7 @@ int eval_callback(emx_batch* b) {
 // the caller's function on the (B, R, D) block; one commit-only launch at the end.  Nothing is synchronised inside the loop
 // except, with Gaussian moves, the upload of the step-size factors once per chunk of steps (as the fused path does).
 int run_callback(emx_batch* b, int64_t total, int32_t thin_by, int32_t store) {
-    BNEED(b, b->cb_fn != nullptr, "device callback target without a callback (emx_set_batch_target_callback)");
+    BNEED(b, b->cb_fn != nullptr || b->cbb_fn != nullptr, "device callback target without a callback (emx_set_batch_target_callback)");
     if (total == 0) return 0;
     const int nm = (int)b->moves.size();
     int smin = 1 << 30, smax = 0;
@@ -665,9 +698,9 @@ int run_callback(emx_batch* b, int64_t total, int32_t thin_by, int32_t store) {
     const size_t rows = (size_t)b->B * R;
     if (rows > b->cb_rows) {
         BHIP(b, hipStreamSynchronize(b->stream));
-        for (void* p : {(void*)b->cb_q, (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi, (void*)b->cb_pr})
+        for (void* p : {(void*)b->cb_q, (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi, (void*)b->cb_pr, (void*)b->cb_bq})
             if (p) hipFree(p);
-        b->cb_q = b->cb_lp = b->cb_fac = b->cb_logu = b->cb_pr = nullptr;
+        b->cb_q = b->cb_lp = b->cb_fac = b->cb_logu = b->cb_pr = b->cb_bq = nullptr;
         b->cb_wi = nullptr;
         b->cb_rows = 0;
         BHIP(b, hipMalloc((void**)&b->cb_q, rows * b->D * 8));
@@ -678,6 +711,14 @@ int run_callback(emx_batch* b, int64_t total, int32_t thin_by, int32_t store) {
         b->cb_rows = rows;
     }
     if (!b->cb_nrows) BHIP(b, hipMalloc((void**)&b->cb_nrows, (size_t)b->B * 4));
+    if (b->nblobs > 0) {
+        if (!b->cb_bq) BHIP(b, hipMalloc((void**)&b->cb_bq, b->cb_rows * b->nblobs * 8));
+        BNEED(b, !store || b->chain_blobs != nullptr, "no blob plane (emx_batch_chain_config)");
+        a.nblobs = b->nblobs;
+        a.bq = b->cb_bq;
+        a.blobs = b->blobs;
+        a.chain_blobs = b->chain_blobs;
+    }
     a.nmoves = nm;
     a.X = b->X;
     a.lp = b->lp;
@@ -771,7 +812,7 @@ int run_callback(emx_batch* b, int64_t total, int32_t thin_by, int32_t store) {
                 if (int rc = launch_cb(true, k, step)) return rc;
                 if (pt && b->pr_fn)                  // the prior first, on the same block
                     if (int rc = call_prior(b, b->cb_q, R, b->cb_pr)) return rc;
-                if (int rc = call_back(b, b->cb_q, R, b->cb_lp)) return rc;
+                if (int rc = call_back(b, b->cb_q, R, b->cb_lp, b->cb_bq)) return rc;
                 pending = true;
                 pending_swap = swap;
                 stored_row = row;
@@ -793,6 +834,30 @@ int run_callback(emx_batch* b, int64_t total, int32_t thin_by, int32_t store) {
     return 0;
 }
 
+// the handle's blob count becomes K (0: none): the walkers' blobs and, where a chain is configured, the blob plane.  The cb
+// block is dropped (its width changes); nothing may be stored yet when K > 0 (the plane would miss those rows)
+int set_blobs(emx_batch* b, int32_t K) {
+    BNEED(b, K >= 0 && K <= BATCH_MAX_BLOBS, "a batch target carries 1 ... %d blobs a sample; got %d", BATCH_MAX_BLOBS, K);
+    BNEED(b, K == 0 || b->pt_T == 0, "a tempered batch does not take blobs");
+    BNEED(b, K == 0 || b->stored == 0, "a target with blobs is set before the first stored step");
+    if (K == b->nblobs && (K == 0 || b->blobs)) return 0;
+    BHIP(b, hipStreamSynchronize(b->stream));
+    for (double** p : {&b->blobs, &b->chain_blobs, &b->cb_bq})
+        if (*p) {
+            hipFree(*p);
+            *p = nullptr;
+        }
+    b->nblobs = 0;
+    if (K > 0) {
+        const size_t BNK = (size_t)b->B * b->N * K;
+        BHIP(b, hipMalloc((void**)&b->blobs, BNK * 8));
+        BHIP(b, hipMemsetAsync(b->blobs, 0, BNK * 8, b->stream));
+        if (b->cap > 0) BHIP(b, hipMalloc((void**)&b->chain_blobs, (size_t)b->cap * BNK * 8));
+        b->nblobs = K;
+    }
+    return 0;
+}
+
 }  // namespace
 
 int emx_internal_batch_view(emx_batch* b, EmxBatchView* v) {
@@ -810,6 +875,8 @@ int emx_internal_batch_view(emx_batch* b, EmxBatchView* v) {
     v->acf = &b->acf;
     v->summary_members = b->tune_summary_members;
     v->summary = &b->summary;
+    v->chain_blobs = b->chain_blobs;
+    v->nblobs = b->nblobs;
     return 0;
 }
 
@@ -824,6 +891,15 @@ int emx_batch_check(int64_t nwalkers, int32_t ndim, int32_t target, int32_t nmov
                     int32_t msglen) {
     char buf[256];
     const char* why = (nmoves > 0 && !moves) ? "no moves" : shape_refusal(nwalkers, ndim, target, nmoves, moves, buf, sizeof buf);
+    if (!why) return 0;
+    if (msg && msglen > 0) snprintf(msg, (size_t)msglen, "%s", why);
+    return -1;
+}
+
+int emx_check_batch_blobs(int64_t nwalkers, int32_t ndim, int32_t target, int32_t nmoves, const emx_move_desc* moves, int32_t nblobs,
+                          char* msg, int32_t msglen) {
+    char buf[320];
+    const char* why = (nmoves > 0 && !moves) ? "no moves" : shape_refusal(nwalkers, ndim, target, nmoves, moves, buf, sizeof buf, nblobs);
     if (!why) return 0;
     if (msg && msglen > 0) snprintf(msg, (size_t)msglen, "%s", why);
     return -1;
@@ -870,7 +946,7 @@ int emx_batch_destroy(emx_batch* b) {
                     (void*)b->tscales, (void*)b->chain, (void*)b->chain_lp, (void*)b->fac_dev, (void*)b->col_dev, (void*)b->cb_q,
                     (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi, (void*)b->cb_nrows, (void*)b->pt_beta,
                     (void*)b->pt_lo, (void*)b->pt_hi, (void*)b->pt_L, (void*)b->pt_P, (void*)b->chain_L, (void*)b->cb_pr, (void*)b->sw_att,
-                    (void*)b->sw_acc, (void*)b->chain_beta})
+                    (void*)b->sw_acc, (void*)b->chain_beta, (void*)b->blobs, (void*)b->chain_blobs, (void*)b->cb_bq})
         if (p) hipFree(p);
     for (double* p : b->mscale)
         if (p) hipFree(p);
@@ -935,6 +1011,7 @@ int emx_batch_set_target(emx_batch* b, int32_t kind, const double* p0, const dou
             const double v = scales ? scales[per_member ? m : 0] : 0.0;
             sc[m] = v != 0.0 ? v : 20.0;
         }
+    if (int rc = set_blobs(b, 0)) return rc;       // the built-in targets have none
     BHIP(b, hipStreamSynchronize(b->stream));      // no kernel still reads the old parameters
     for (double** p : {&b->tp0, &b->tp1, &b->tscales})
         if (*p) {
@@ -956,9 +1033,32 @@ int emx_batch_set_target(emx_batch* b, int32_t kind, const double* p0, const dou
     return 0;
 }
 
+int emx_set_batch_target_callback_blobs(emx_batch* b, emx_batch_log_prob_blobs_fn fn, void* user, int32_t nblobs) {
+    BNEED(b, fn != nullptr, "emx_set_batch_target_callback_blobs: no function");
+    BNEED(b, nblobs >= 1 && nblobs <= BATCH_MAX_BLOBS, "emx_set_batch_target_callback_blobs: 1 <= nblobs <= %d; got %d", BATCH_MAX_BLOBS, nblobs);
+    BNEED(b, b->pt_T == 0, "a tempered batch does not take blobs");
+    BHIP(b, hipSetDevice(b->device));
+    if (int rc = set_blobs(b, nblobs)) return rc;
+    BHIP(b, hipStreamSynchronize(b->stream));
+    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
+        if (*p) {
+            hipFree(*p);
+            *p = nullptr;
+        }
+    b->tp0_stride = b->tp1_stride = 0;
+    b->cb_fn = nullptr;
+    b->cbb_fn = fn;
+    b->cb_user = user;
+    b->target = EMX_TARGET_DEVICE_CALLBACK;
+    b->Dp = b->D;
+    return 0;
+}
+
 int emx_set_batch_target_callback(emx_batch* b, emx_batch_log_prob_fn fn, void* user) {
     BNEED(b, fn != nullptr, "emx_set_batch_target_callback: no function");
     BHIP(b, hipSetDevice(b->device));
+    if (int rc = set_blobs(b, 0)) return rc;
+    b->cbb_fn = nullptr;
     BHIP(b, hipStreamSynchronize(b->stream));
     for (double** p : {&b->tp0, &b->tp1, &b->tscales})
         if (*p) {
@@ -974,23 +1074,40 @@ int emx_set_batch_target_callback(emx_batch* b, emx_batch_log_prob_fn fn, void* 
 }
 
 int emx_set_batch_target_fused(emx_batch* b, emx_fused_batch_fn fn, int32_t ndim_compiled, const void* user_dev) {
+    return emx_set_batch_target_fused_blobs(b, fn, ndim_compiled, user_dev, 0);
+}
+
+int emx_set_batch_target_fused_blobs(emx_batch* b, emx_fused_batch_fn fn, int32_t ndim_compiled, const void* user_dev, int32_t nblobs) {
     BNEED(b, fn != nullptr, "emx_set_batch_target_fused: no launcher");
+    BNEED(b, nblobs >= 0 && nblobs <= BATCH_MAX_BLOBS, "emx_set_batch_target_fused_blobs: 0 <= nblobs <= %d; got %d", BATCH_MAX_BLOBS, nblobs);
     BNEED(b, ndim_compiled == b->D, "the fused user target was compiled for ndim %d; the batch has ndim %d", ndim_compiled, b->D);
     BNEED(b, b->pt_T == 0, "a tempered batch does not take a fused user target: the tempered commit and the swap pass belong to the "
                            "batched callback path (emx_set_batch_target_callback)");
     if (!b->moves.empty()) {
         char buf[256];
-        const char* why = shape_refusal(b->N, b->D, EMX_TARGET_FUSED_USER, (int32_t)b->moves.size(), b->moves.data(), buf, sizeof buf);
+        const char* why = shape_refusal(b->N, b->D, EMX_TARGET_FUSED_USER, (int32_t)b->moves.size(), b->moves.data(), buf, sizeof buf, nblobs);
         BNEED(b, !why, "%s", why);
     }
-    // the probe: abi, args_bytes and ndim against what the launcher was compiled with; nothing is launched
+    // the probe: abi, args_bytes, ndim and nblobs against what the launcher was compiled with; nothing is launched
     emx_fused_launch fl{};
+    SmallRunArgs probe_args{};
+    probe_args.D = b->D;
+    probe_args.nblobs = nblobs;
     fl.abi = EMX_FUSED_ABI;
     fl.args_bytes = (uint32_t)sizeof(SmallRunArgs);
     fl.ndim = b->D;
     fl.movesel = MOVE_STRETCH;
-    if (int rc = fused_refusal(b, fn(&fl), fl.movesel)) return rc;
+    fl.args = &probe_args;
+    fl.nblobs = nblobs;
+    if (int rc = fn(&fl)) {
+        const int32_t had = b->nblobs;
+        b->nblobs = nblobs;               // (the count the message names)
+        rc = fused_refusal(b, rc, fl.movesel);
+        b->nblobs = had;
+        return rc;
+    }
     BHIP(b, hipSetDevice(b->device));
+    if (int rc = set_blobs(b, nblobs)) return rc;
     BHIP(b, hipStreamSynchronize(b->stream));
     for (double** p : {&b->tp0, &b->tp1, &b->tscales})
         if (*p) {
@@ -1022,6 +1139,7 @@ int emx_pt_set_target_fused(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compi
     fl.movesel = MOVE_STRETCH;
     if (int rc = pt_fused_launcher_refusal(b, fn(&fl), fl.movesel)) return rc;
     BHIP(b, hipSetDevice(b->device));
+    if (int rc = set_blobs(b, 0)) return rc;
     BHIP(b, hipStreamSynchronize(b->stream));
     for (double** p : {&b->tp0, &b->tp1, &b->tscales})
         if (*p) {
@@ -1049,7 +1167,7 @@ int emx_pt_fused_check(int32_t ntemps, int64_t nwalkers, int32_t ndim, int32_t n
 int emx_batch_set_moves(emx_batch* b, int32_t nmoves, const emx_move_desc* moves, const double* cdf) {
     BNEED(b, moves && cdf && nmoves >= 1, "need at least one move and its cdf");
     char buf[256];
-    const char* why = shape_refusal(b->N, b->D, b->target >= 0 ? b->target : EMX_TARGET_ISO_GAUSS, nmoves, moves, buf, sizeof buf);
+    const char* why = shape_refusal(b->N, b->D, b->target >= 0 ? b->target : EMX_TARGET_ISO_GAUSS, nmoves, moves, buf, sizeof buf, b->nblobs);
     BNEED(b, !why, "%s", why);
     for (int m = 0; m < nmoves; ++m)
         BNEED(b, !(moves[m].kind == EMX_MOVE_GAUSS && moves[m].reserved == EMX_GAUSS_SEQUENTIAL && nmoves > 1),
@@ -1110,6 +1228,16 @@ int emx_batch_get_state(emx_batch* b, double* coords, double* log_prob) {
     return 0;
 }
 
+int emx_get_blobs_batch(emx_batch* b, double* out, int32_t* nblobs_out) {
+    if (nblobs_out) *nblobs_out = b->nblobs;
+    BNEED(b, b->nblobs > 0 && b->blobs, "the handle's target has no blobs");
+    if (out) {
+        BHIP(b, hipMemcpyAsync(out, b->blobs, (size_t)b->B * b->N * b->nblobs * 8, hipMemcpyDeviceToHost, b->stream));
+        BHIP(b, hipStreamSynchronize(b->stream));
+    }
+    return 0;
+}
+
 int emx_batch_eval_state_log_prob(emx_batch* b) {
     BNEED(b, b->target >= 0, "no target set");
     BNEED(b, !b->moves.empty(), "no moves set");
@@ -1123,11 +1251,17 @@ int emx_batch_chain_config(emx_batch* b, int64_t capacity) {
     BNEED(b, capacity >= 0, "negative capacity");
     if (capacity <= b->cap) return 0;
     BHIP(b, hipSetDevice(b->device));
-    const size_t ND = (size_t)b->N * b->D, N = (size_t)b->N;
+    const size_t ND = (size_t)b->N * b->D, N = (size_t)b->N, NK = (size_t)b->N * b->nblobs;
+    double* nB = nullptr;                 // the blob plane, only for a target with blobs
+    if (NK > 0) BHIP(b, hipMalloc((void**)&nB, (size_t)b->B * capacity * NK * 8));
     double *nc = nullptr, *nl = nullptr;
-    BHIP(b, hipMalloc((void**)&nc, (size_t)b->B * capacity * ND * 8));
+    if (hipMalloc((void**)&nc, (size_t)b->B * capacity * ND * 8) != hipSuccess) {
+        if (nB) hipFree(nB);
+        return fail(b, -2, "chain allocation failed");
+    }
     if (hipMalloc((void**)&nl, (size_t)b->B * capacity * N * 8) != hipSuccess) {
         hipFree(nc);
+        if (nB) hipFree(nB);
         return fail(b, -2, "chain allocation failed");
     }
     double *nL = nullptr, *nb = nullptr;
@@ -1136,6 +1270,7 @@ int emx_batch_chain_config(emx_batch* b, int64_t capacity) {
         hipFree(nc);
         hipFree(nl);
         if (nL) hipFree(nL);
+        if (nB) hipFree(nB);
         return fail(b, -2, "chain allocation failed");
     }
     if (b->stored > 0) {      // what is stored stays: member by member, into the longer rows
@@ -1143,8 +1278,12 @@ int emx_batch_chain_config(emx_batch* b, int64_t capacity) {
         BHIP(b, hipMemcpy2DAsync(nl, capacity * N * 8, b->chain_lp, b->cap * N * 8, b->stored * N * 8, b->B, hipMemcpyDeviceToDevice, b->stream));
         if (nL) BHIP(b, hipMemcpy2DAsync(nL, capacity * N * 8, b->chain_L, b->cap * N * 8, b->stored * N * 8, b->B, hipMemcpyDeviceToDevice, b->stream));
         if (nb) BHIP(b, hipMemcpy2DAsync(nb, capacity * 8, b->chain_beta, b->cap * 8, b->stored * 8, b->B, hipMemcpyDeviceToDevice, b->stream));
+        if (nB && b->chain_blobs)
+            BHIP(b, hipMemcpy2DAsync(nB, capacity * NK * 8, b->chain_blobs, b->cap * NK * 8, b->stored * NK * 8, b->B, hipMemcpyDeviceToDevice, b->stream));
     }
     BHIP(b, hipStreamSynchronize(b->stream));
+    if (b->chain_blobs) hipFree(b->chain_blobs);
+    b->chain_blobs = nB;
     if (b->chain_L) hipFree(b->chain_L);
     b->chain_L = nL;
     if (b->chain_beta) hipFree(b->chain_beta);
@@ -1188,8 +1327,8 @@ int emx_batch_iteration(emx_batch* b, int64_t* stored, int64_t* proposals) {
 
 int emx_batch_chain_read(emx_batch* b, int32_t what, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop,
                          int64_t stride, double* out) {
-    BNEED(b, what == 0 || what == 1 || ((what == 2 || what == 3) && b->chain_L),
-          "what: 0 coordinates, 1 log-probs, 2 log-likelihoods, 3 betas (the last two tempered)");
+    BNEED(b, what == 0 || what == 1 || ((what == 2 || what == 3) && b->chain_L) || (what == 4 && b->chain_blobs),
+          "what: 0 coordinates, 1 log-probs, 2 log-likelihoods, 3 betas (the last two tempered), 4 blobs (a target with blobs)");
     BNEED(b, 0 <= member_lo && member_lo <= member_hi && member_hi <= b->B, "members [%d, %d) outside [0, %d)", member_lo, member_hi, b->B);
     BNEED(b, stride >= 1 && 0 <= start && start <= stop && stop <= b->stored, "rows [%lld, %lld) outside the %lld stored",
           (long long)start, (long long)stop, (long long)b->stored);
@@ -1197,8 +1336,8 @@ int emx_batch_chain_read(emx_batch* b, int32_t what, int32_t member_lo, int32_t 
     const int64_t nsel = (stop - start + stride - 1) / stride;
     if (nsel == 0 || member_hi == member_lo) return 0;
     BHIP(b, hipSetDevice(b->device));
-    const size_t row = what == 3 ? 1 : (size_t)b->N * (what == 0 ? b->D : 1);
-    const double* base = what == 0 ? b->chain : what == 1 ? b->chain_lp : what == 2 ? b->chain_L : b->chain_beta;
+    const size_t row = what == 3 ? 1 : (size_t)b->N * (what == 0 ? b->D : what == 4 ? b->nblobs : 1);
+    const double* base = what == 0 ? b->chain : what == 1 ? b->chain_lp : what == 2 ? b->chain_L : what == 3 ? b->chain_beta : b->chain_blobs;
     for (int32_t m = member_lo; m < member_hi; ++m)
         BHIP(b, hipMemcpy2DAsync(out + (size_t)(m - member_lo) * nsel * row, row * 8, base + ((size_t)m * b->cap + start) * row, stride * row * 8,
                                  row * 8, nsel, hipMemcpyDeviceToHost, b->stream));
@@ -1240,6 +1379,8 @@ int emx_pt_set_tempering(emx_batch* b, int32_t ntemps, const double* betas, cons
                                                  "commit and the swap pass belong to the batched callback path (emx_set_batch_target_callback)");
     BNEED(b, b->target == EMX_TARGET_DEVICE_CALLBACK || b->target == EMX_TARGET_FUSED_PT,
           "tempering needs a batched callback target (emx_set_batch_target_callback)");
+    BNEED(b, b->nblobs == 0, "tempering does not run a target with blobs (emx_set_batch_target_callback_blobs): the tempered commit "
+                             "and the swap pass carry none");
     if (b->target == EMX_TARGET_FUSED_PT) {
         BNEED(b, !(b->ptf_has_prior && box_lo), "the fused tempered target's launcher carries a prior functor: a box prior on top is refused");
         if (!b->moves.empty()) {

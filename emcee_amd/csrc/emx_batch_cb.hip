@@ -42,8 +42,8 @@ __device__ __forceinline__ double box_prior(const double* q, const double* lo, c
 }
 
 // TEMPERED: the commit of parallel tempering (BatchCbArgs' tempering fields); the untempered instantiation is the kernel as it
-// was, bit for bit and instruction for instruction
-template <int G, int V, int CH, bool TEMPERED>
+// was, bit for bit and instruction for instruction.  BLOBS (untempered only): the commit carries the caller's blobs with the row
+template <int G, int V, int CH, bool TEMPERED, bool BLOBS = false>
 __global__ __launch_bounds__(CB_MAX_THREADS) void k_batch_cb(const BatchCbArgs A) {
     constexpr int WPW = 64 / G;
     const int N = A.N, D = A.D, R = A.R, T = blockDim.x, tid = threadIdx.x;
@@ -123,6 +123,16 @@ __global__ __launch_bounds__(CB_MAX_THREADS) void k_batch_cb(const BatchCbArgs A
                 if (accept || stored) load_row<G, V, CH>(x, accept ? A.q + r * D : X + (size_t)i * D, D, gl);
                 if (accept) store_row<G, V, CH>(x, X + (size_t)i * D, D, gl);
                 if (stored) store_row_stream<G, V, CH>(x, cr + (size_t)i * D, D, gl);
+                if constexpr (BLOBS) {                                               // move.py:29-45: the blobs follow the accepted row
+                    const int K = A.nblobs;
+                    double* bw = A.blobs + (b * (size_t)N + i) * K;
+                    double* bc = stored ? A.chain_blobs + (((size_t)b * A.cap + A.chain_row) * (size_t)N + i) * K : nullptr;
+                    for (int k = gl; k < K; k += G) {
+                        const double v = accept ? A.bq[r * K + k] : bw[k];
+                        if (accept) bw[k] = v;
+                        if (stored) bc[k] = v;
+                    }
+                }
                 if (gl == 0) {
                     if (accept) lp[i] = lpn;
                     acc[i] = accept ? 1 : 0;
@@ -216,7 +226,8 @@ __global__ __launch_bounds__(64) void k_batch_lp_check(const double* lp, uint32_
 
 template <int G, int V, int CH>
 hipError_t launch_cb(int grid, int threads, hipStream_t st, const BatchCbArgs& a) {
-    auto kern = a.beta ? k_batch_cb<G, V, CH, true> : k_batch_cb<G, V, CH, false>;
+    if (a.nblobs > 0 && a.beta) return hipErrorInvalidValue;      // tempered handles carry no blobs
+    auto kern = a.beta ? k_batch_cb<G, V, CH, true> : a.nblobs > 0 ? k_batch_cb<G, V, CH, false, true> : k_batch_cb<G, V, CH, false>;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, st, a);
     return hipGetLastError();
 }

@@ -55,6 +55,12 @@ struct BatchCbArgs {
     double* chain_L;           // (B, cap, N)
     int32_t rows_in_commit;    // the commit writes the stored step's rows (0: the swap pass writes them after the step)
     double* chain_beta;        // (B, cap): the stored step's beta of each member, written with its rows
+    // blobs (emx_set_batch_target_callback_blobs; nblobs 0: none, the kernel above bit for bit; untempered only): the caller's
+    // blobs of q, row for row with lpq; an accepted row's replace the walker's, and a stored step writes the walker's to the plane
+    const double* bq;          // (B, R, nblobs)
+    double* blobs;             // (B, N, nblobs)
+    double* chain_blobs;       // (B, cap, N, nblobs)
+    int32_t nblobs;
 };
 
 // threads of a k_batch_cb workgroup: at most 512, for 256 VGPRs a lane (with 1 024 threads' 128, 12 to 46 of them spilled)

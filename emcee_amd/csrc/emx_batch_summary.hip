@@ -468,8 +468,22 @@ extern "C" {
 int emx_summary_batch(emx_batch* b, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop, int64_t stride, double* mean_out,
                       double* cov_out, int32_t nranks, const int64_t* ranks, double* order_out, double* map_coords_out,
                       double* map_log_prob_out, int64_t* nsamples_out) {
+    return emx_summary_batch_plane(b, 0, member_lo, member_hi, start, stop, stride, mean_out, cov_out, nranks, ranks, order_out,
+                                   map_coords_out, map_log_prob_out, nsamples_out);
+}
+
+// plane 4: the blob plane in the chain's place -- the same (rows, N, width) layout with width nblobs, so the kernels run unchanged
+int emx_summary_batch_plane(emx_batch* b, int32_t plane, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop, int64_t stride,
+                            double* mean_out, double* cov_out, int32_t nranks, const int64_t* ranks, double* order_out,
+                            double* map_coords_out, double* map_log_prob_out, int64_t* nsamples_out) {
     EmxBatchView v;
     if (emx_internal_batch_view(b, &v)) return -1;
+    if (plane != 0 && plane != 4) return sfail(b, -1, "emx_summary_batch_plane: plane 0 (coordinates) or 4 (blobs); got %d", plane);
+    if (plane == 4) {
+        if (v.nblobs < 1) return sfail(b, -1, "emx_summary_batch_plane: the handle's target has no blobs");
+        v.chain = v.chain_blobs;
+        v.D = v.nblobs;
+    }
     if (!(0 <= member_lo && member_lo < member_hi && member_hi <= v.B))
         return sfail(b, -1, "emx_summary_batch: members [%d, %d) outside [0, %d) or empty", member_lo, member_hi, v.B);
     if (!v.chain || !v.chain_lp || v.stored <= 0) return sfail(b, -1, "emx_summary_batch: no stored chain (emx_batch_chain_config + a stored run)");

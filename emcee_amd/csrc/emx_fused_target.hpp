@@ -14,6 +14,17 @@
 // without being handed over.  `ndim` is fixed at compile time so that the translation unit carries ONE row layout's kernels:
 // by default the single-StretchMove selector and the any-schedule one (every schedule a batch accepts runs under one of them);
 // EMX_FUSED_BATCH_TARGET_MOVES takes a mask that narrows that to one.
+//
+// Blobs -- derived quantities recorded with every sample (EnsembleBatch.get_blobs) -- come from the five-argument form:
+//
+//     struct MyModel {
+//         __device__ double operator()(const double* x, int ndim, int member, const void* user, double* blobs) const;
+//     };
+//     EMX_FUSED_BATCH_TARGET_BLOBS(my_model, MyModel, /*ndim=*/5, /*nblobs=*/2)
+//
+// The call writes blobs[0 ... nblobs) (lane-private, zero on entry; 1 <= nblobs <= 32, any value is legal, NaN included) and
+// returns the log-probability as before.  The kernel keeps every walker's blobs in LDS, replaces them exactly when it accepts
+// the row, and stores them next to the chain.  Coordinates, log-probs and accept counts are those of the same function without blobs.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,7 +39,7 @@
 
 // bumped with ANY change of SmallRunArgs or of k_small_run's LDS layout: a launcher and a library of different values refuse each other
 #ifndef EMX_FUSED_ABI
-#define EMX_FUSED_ABI 1u
+#define EMX_FUSED_ABI 2u
 #endif
 
 #define EMX_FUSED_MOVES_STRETCH 1      // the schedule is one StretchMove
@@ -41,10 +52,10 @@ constexpr int fused_v(int D) { return D % 2 == 0 ? 2 : 1; }
 constexpr int fused_g(int D) { return shape_g((D + fused_v(D) - 1) / fused_v(D)); }
 constexpr int fused_ch(int D) { return shape_ch((D + fused_v(D) - 1) / fused_v(D)); }
 
-template <typename USER, int NDIM, int MOVESEL>
+template <typename USER, int NDIM, int MOVESEL, int NBLOBS = 0>
 hipError_t launch_fused_move(int grid, int threads, size_t lds, hipStream_t st, const SmallRunArgs& a) {
     constexpr int G = fused_g(NDIM), V = fused_v(NDIM), CH = fused_ch(NDIM);
-    auto kern = k_small_run<G, V, CH, MOVESEL, false, 0, true, USER>;
+    auto kern = k_small_run<G, V, CH, MOVESEL, false, 0, true, USER, NBLOBS>;
     static size_t lds_granted[MAX_DEVICES] = {};      // as launch_small_move: function attributes are per device
     int dev = 0;
     if (lds > 48 * 1024 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MAX_DEVICES && lds > lds_granted[dev]) {
@@ -57,27 +68,32 @@ hipError_t launch_fused_move(int grid, int threads, size_t lds, hipStream_t st, 
 }
 
 // the launcher behind EMX_FUSED_BATCH_TARGET: the checks, then one launch of the batch (include/emx.h: emx_fused_launch)
-template <typename USER, int NDIM, int MOVES>
+template <typename USER, int NDIM, int MOVES, int NBLOBS = 0>
 int fused_batch_launch(const emx_fused_launch* L) {
     static_assert(NDIM >= 1 && NDIM <= 256, "a fused user target has 1 <= ndim <= 256");
+    static_assert(NBLOBS >= 0 && NBLOBS <= 32, "a fused user target has 0 <= nblobs <= 32");
     static_assert((MOVES & (EMX_FUSED_MOVES_STRETCH | EMX_FUSED_MOVES_ANY)) != 0, "no move selector compiled in");
     if (!L || L->abi != EMX_FUSED_ABI || L->args_bytes != (uint32_t)sizeof(SmallRunArgs)) return 1;
     if (L->ndim != NDIM) return 2;
     const bool stretch = L->movesel == MOVE_STRETCH;
     if (!stretch && L->movesel != SMALL_ANY_MOVE) return 3;
     if (!stretch && !(MOVES & EMX_FUSED_MOVES_ANY)) return 3;
+    // the blob count against the one compiled in.  (A blob-free launcher reads the field only of a descriptor that carries `args`,
+    // as the library's always does: a bare probe of the four fields above is answered from them alone.)
+    if ((NBLOBS > 0 || L->args) && L->nblobs != NBLOBS) return 4;
     if (L->grid == 0) return 0;                       // the probe of emx_set_batch_target_fused
     if (!L->args || L->grid < 0 || L->threads < 64 || L->threads > 1024 || L->threads % 64 != 0) return 3;
     SmallRunArgs a = *static_cast<const SmallRunArgs*>(L->args);
     if (a.D != NDIM) return 2;
+    if (a.nblobs != NBLOBS || (NBLOBS > 0 && !a.blobs)) return 4;
     a.user = L->user;
     hipError_t e = hipErrorInvalidValue;
     if constexpr ((MOVES & EMX_FUSED_MOVES_STRETCH) != 0) {
-        if (stretch) e = launch_fused_move<USER, NDIM, MOVE_STRETCH>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
+        if (stretch) e = launch_fused_move<USER, NDIM, MOVE_STRETCH, NBLOBS>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
     }
     if constexpr ((MOVES & EMX_FUSED_MOVES_ANY) != 0) {
         if (!stretch || !(MOVES & EMX_FUSED_MOVES_STRETCH))      // the any-schedule kernel runs a single StretchMove to the same bits
-            e = launch_fused_move<USER, NDIM, SMALL_ANY_MOVE>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
+            e = launch_fused_move<USER, NDIM, SMALL_ANY_MOVE, NBLOBS>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
     }
     return e == hipSuccess ? 0 : 100 + (int)e;
 }
@@ -90,3 +106,9 @@ int fused_batch_launch(const emx_fused_launch* L) {
     }
 #define EMX_FUSED_BATCH_TARGET(name, Functor, ndim) \
     EMX_FUSED_BATCH_TARGET_MOVES(name, Functor, ndim, EMX_FUSED_MOVES_STRETCH | EMX_FUSED_MOVES_ANY)
+// the five-argument functor (..., double* blobs) with `nblobs` doubles a sample; both move selectors
+#define EMX_FUSED_BATCH_TARGET_BLOBS(name, Functor, ndim, nblobs)                                                        \
+    extern "C" __attribute__((visibility("default"))) int name(const emx_fused_launch* launch) {                        \
+        static_assert((nblobs) >= 1, "EMX_FUSED_BATCH_TARGET_BLOBS: 1 <= nblobs <= 32 (none: EMX_FUSED_BATCH_TARGET)");  \
+        return emx::fused_batch_launch<Functor, (ndim), EMX_FUSED_MOVES_STRETCH | EMX_FUSED_MOVES_ANY, (nblobs)>(launch); \
+    }

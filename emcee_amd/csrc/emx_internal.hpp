@@ -50,6 +50,8 @@ struct EmxBatchView {
     BatchAcf** acf;          // the handle's slot (nullptr until the first call)
     int64_t summary_members; // tuning "batch_summary_members" (0: auto)
     BatchSummary** summary;  // the handle's slot (nullptr until the first call)
+    const double* chain_blobs;   // (B, cap, N, nblobs) member-major, or nullptr
+    int32_t nblobs;
 };
 // implemented in emx_batch.hip
 int emx_internal_batch_view(emx_batch* b, EmxBatchView* v);

@@ -2017,6 +2017,12 @@ struct SmallRunArgs {
     // every row, and the rows of the LDS staging area (the largest split of the schedule)
     const void* user;
     int32_t stage_rows;
+    // blobs of a fused user target (k_small_run<..., USER, NBLOBS>): nblobs doubles a walker that the functor writes with every
+    // log-probability and that are committed with it.  blobs is member-strided (N nblobs), chain_blobs the first row of the blob
+    // plane this launch may append to, member-major with `cap` rows a member like the chain (nullptr: nothing stored)
+    double* blobs;
+    double* chain_blobs;
+    int32_t nblobs;
 };
 
 constexpr int SMALL_STATUS_WORDS = 8;      // a member's status flags (raise_status: one word per bit)
@@ -2034,6 +2040,8 @@ struct SmallMember {
     __device__ __forceinline__ uint32_t* status() const { return A.status + m() * SMALL_STATUS_WORDS; }
     __device__ __forceinline__ double* chain() const { return A.chain + m() * (size_t)A.cap * A.N * A.D; }
     __device__ __forceinline__ double* chain_lp() const { return A.chain_lp + m() * (size_t)A.cap * A.N; }
+    __device__ __forceinline__ double* blobs() const { return A.blobs + m() * (size_t)A.N * A.nblobs; }
+    __device__ __forceinline__ double* chain_blobs() const { return A.chain_blobs + m() * (size_t)A.cap * A.N * A.nblobs; }
     __device__ __forceinline__ const double* tp0() const { return BATCH && A.tp0 ? A.tp0 + m() * (size_t)A.tp0_stride : A.tp0; }
     __device__ __forceinline__ const double* tp1() const { return BATCH && A.tp1 ? A.tp1 + m() * (size_t)A.tp1_stride : A.tp1; }
     __device__ __forceinline__ const double* step_fac() const { return BATCH && A.step_fac ? A.step_fac + m() * (size_t)A.nsteps : A.step_fac; }
@@ -2116,6 +2124,16 @@ __device__ __forceinline__ double fused_call(const double* x, int ndim, int memb
     }
 }
 
+// the same with blobs: the functor's five-argument form writes the row's NBLOBS derived quantities to `blobs` (lane-private)
+template <typename USER>
+__device__ __forceinline__ double fused_call_blobs(const double* x, int ndim, int member, const void* user, double* blobs) {
+    if constexpr (std::is_void<USER>::value) {
+        return 0.0;
+    } else {
+        return USER{}(x, ndim, member, user, blobs);
+    }
+}
+
 // the dense target's quadratic form of the 16 tile rows a wave holds, through the f64 MFMA against the LDS image (k_halfstep's
 // instructions in k_halfstep's order); the value of tile row (lane >> 4) + 4 (lane & 3) lands in lanes with (lane & 15) < 4
 template <int DPB, int KK, int RT>
@@ -2154,13 +2172,16 @@ __device__ __forceinline__ double small_dense_qf(const double* tile, const doubl
 // proposal of the split goes to an LDS staging row (small_propose, G lanes a row), then ONE lane a row calls the functor on its
 // staged row, decides and commits.  The functor's time is the model's, so it gets every lane of the workgroup rather than the
 // 1 / G of them a per-wave tile would leave busy.  A row with a non-finite coordinate is rejected without reaching the functor.
-template <int G, int V, int CH, int MOVESEL, bool PLANNED, int DPB = 0, bool BATCH = false, typename USER = void>
+// NBLOBS > 0 (fused user targets only): every walker carries NBLOBS doubles in LDS behind the staging area, written by the
+// functor with the walker's log-probability, committed exactly when that log-probability is, and stored with the chain rows.
+template <int G, int V, int CH, int MOVESEL, bool PLANNED, int DPB = 0, bool BATCH = false, typename USER = void, int NBLOBS = 0>
 static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int WPW = 64 / G;
     constexpr bool DENSE = DPB > 0;
     constexpr bool FUSED = !std::is_void<USER>::value;
     static_assert(!FUSED || (BATCH && !PLANNED && !DENSE), "a fused user target runs in batched Philox launches");
+    static_assert(NBLOBS == 0 || FUSED, "blobs are a fused user target's");
     constexpr int Dp = DENSE ? DPB * 16 : 16, KK = Dp / 4, RT = Dp + 2, PPT = 16 / WPW;
     const int N = A.N, D = A.D, T = blockDim.x, tid = threadIdx.x, B = A.batch;
     const int lane = tid & 63, wv = tid >> 6, nwave = T >> 6, sub = lane / G, gl = lane % G;
@@ -2184,6 +2205,7 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
     const int DS = D | 1;
     double* stage = Sfrag;
     double* sfac = stage + (size_t)(FUSED ? A.stage_rows : 0) * DS;
+    double* bls = sfac + (FUSED ? A.stage_rows : 0);     // NBLOBS > 0: the walkers' blobs, NBLOBS doubles each
     const SmallMember<BATCH> M{A};
     if constexpr (DENSE)
         for (int e = tid; e < dense_img_doubles(Dp) + Dp; e += T) Sfrag[e] = M.tp1()[e];
@@ -2194,6 +2216,8 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
         acnt[e] = 0u;
         accs[e] = 0;
     }
+    if constexpr (NBLOBS > 0)
+        for (int e = tid; e < N * NBLOBS; e += T) bls[e] = M.blobs()[e];
     Row<G, V, CH> mu, iv;
 #pragma unroll
     for (int c = 0; c < CH; ++c)
@@ -2210,7 +2234,15 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
             __syncthreads();
             if constexpr (FUSED) {
                 for (int t = tid; t < N; t += T) {                                // the functor on the walker's own row
-                    const double lpn = fused_call<USER>(Xs + (size_t)t * D, D, (int)blockIdx.x, A.user);
+                    double lpn;
+                    if constexpr (NBLOBS > 0) {
+                        double bl[NBLOBS] = {};
+                        lpn = fused_call_blobs<USER>(Xs + (size_t)t * D, D, (int)blockIdx.x, A.user, bl);
+#pragma unroll
+                        for (int k = 0; k < NBLOBS; ++k) bls[(size_t)t * NBLOBS + k] = bl[k];
+                    } else {
+                        lpn = fused_call<USER>(Xs + (size_t)t * D, D, (int)blockIdx.x, A.user);
+                    }
                     if (lpn != lpn) raise_status(M.status(), ST_NAN_LOGP);
                     lps[t] = lpn;
                 }
@@ -2370,13 +2402,25 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                         const double fac = sfac[t];
                         bool accept = false;
                         if (fac != -__builtin_inf()) {                               // (-inf: a non-finite proposal, or a factor that rejects whatever the value)
-                            const double lp_new = fused_call<USER>(qrow, D, (int)blockIdx.x, A.user);
+                            double lp_new;
+                            [[maybe_unused]] double bl[NBLOBS > 0 ? NBLOBS : 1];
+                            if constexpr (NBLOBS > 0) {
+#pragma unroll
+                                for (int k = 0; k < NBLOBS; ++k) bl[k] = 0.0;
+                                lp_new = fused_call_blobs<USER>(qrow, D, (int)blockIdx.x, A.user, bl);
+                            } else {
+                                lp_new = fused_call<USER>(qrow, D, (int)blockIdx.x, A.user);
+                            }
                             if (lp_new != lp_new) raise_status(M.status(), ST_NAN_LOGP);
                             const double lnpdiff = fac + lp_new - lps[i];            // red_blue.py:99
                             accept = lnpdiff > logus[pos];                           // red_blue.py:100
                             if (accept) {
                                 for (int d = 0; d < D; ++d) Xs[(size_t)i * D + d] = qrow[d];
                                 lps[i] = lp_new;
+                                if constexpr (NBLOBS > 0) {                          // move.py:29-45: the blobs follow the accepted row
+#pragma unroll
+                                    for (int k = 0; k < NBLOBS; ++k) bls[(size_t)i * NBLOBS + k] = bl[k];
+                                }
                             }
                         }
                         accs[i] = accept ? 1 : 0;
@@ -2473,6 +2517,10 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                     cl[e] = lps[e];
                     acnt[e] += accs[e];
                 }
+                if constexpr (NBLOBS > 0) {
+                    double* cb = M.chain_blobs() + (size_t)row * N * NBLOBS;
+                    for (int e = tid; e < N * NBLOBS; e += T) cb[e] = bls[e];
+                }
                 ++row;
                 __syncthreads();                     // the next half-step overwrites what was just copied
             }
@@ -2485,6 +2533,8 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
         M.acc()[e] = accs[e];
         M.acc_count()[e] += acnt[e];
     }
+    if constexpr (NBLOBS > 0)
+        for (int e = tid; e < N * NBLOBS; e += T) M.blobs()[e] = bls[e];
 }
 
 // logs of a host-supplied plan (exact / inputs modes), full width: logu = ln(uacc),

@@ -50,6 +50,12 @@ inline size_t small_lds_bytes(int64_t N, int D, int dense_dp = 0, int waves = 0,
 // schedule) at D | 1 doubles a row, a factor each, and the 16-byte alignment
 constexpr size_t small_fused_stage_bytes(int64_t rows, int D) { return 16 + (size_t)rows * ((size_t)(D | 1) * 8 + 8); }
 
+// a fused user target's blobs in LDS behind the staging area (k_small_run<..., USER, NBLOBS>): nblobs doubles a walker
+constexpr size_t small_blob_bytes(int64_t N, int nblobs) { return (size_t)N * (size_t)nblobs * 8; }
+
+// blobs a sample of a batch target may carry
+constexpr int BATCH_MAX_BLOBS = 32;
+
 // widest padded ndim of a dense Gaussian target whose image the fused kernels and k_small_run keep in LDS
 constexpr int DENSE_FUSED_MAX_DP = 128;
 

@@ -158,6 +158,9 @@ class PTSampler(object):
         if isinstance(log_likelihood, BatchFused):
             raise TypeError("PTSampler's log_likelihood is a targets.BatchCallable or targets.BatchKernel; a BatchFused is not: the "
                             "tempered commit and the swap pass run on the batched callback path (a fused tempered kernel does not exist)")
+        if isinstance(log_likelihood, BatchTarget) and getattr(log_likelihood, "nblobs", 0) > 0:
+            raise TypeError("PTSampler does not record blobs: its log_likelihood is a target with nblobs = 0 (the tempered commit and "
+                            "the swap pass carry none; got nblobs = %d)" % log_likelihood.nblobs)
         if not isinstance(log_likelihood, BatchTarget):
             kind = "fused device target" if isinstance(log_likelihood, DeviceTarget) else type(log_likelihood).__name__
             raise TypeError("PTSampler's log_likelihood is a targets.BatchCallable or targets.BatchKernel; a %s is not (wrap the "

@@ -160,10 +160,17 @@ class DeviceKernel(DeviceTarget):
             ens._cb_owner = self
 
 
+def _check_nblobs(who, nblobs):
+    if isinstance(nblobs, bool) or not isinstance(nblobs, (int, np.integer)) or not 0 <= nblobs <= _lib.MAX_BLOBS:
+        raise ValueError("%s: nblobs is an integer in [0, %d] (float64 blobs a sample); got %r" % (who, _lib.MAX_BLOBS, nblobs))
+    return int(nblobs)
+
+
 class BatchTarget(DeviceTarget):
     """Base of the batched callback targets of :class:`~emcee_amd.EnsembleBatch` (``emx_set_batch_target_callback``): one call
     evaluates the proposals of every member of a batch.  They are not targets of a single ensemble."""
     kind = _lib.TARGET_CALLBACK
+    nblobs = 0                            # blobs a sample (EnsembleBatch.get_blobs); the built-in targets have none
 
     def bind(self, ens):
         raise TypeError("%s is a target of EnsembleBatch, not of a single ensemble (use DeviceCallable with EnsembleSampler)"
@@ -187,25 +194,29 @@ class BatchCallable(BatchTarget):
             d = q - mu_t
             return -0.5 * (ivar_t * d * d).sum(-1)
         batch = EnsembleBatch(B, nwalkers, ndim, BatchCallable(log_prob), seeds=seeds)
+
+    ``nblobs = K > 0``: ``fn(q)`` returns ``(lp, blobs)`` with ``blobs`` of shape ``(B, n, K)``, K float64 derived quantities
+    a row, kept with every sample (``EnsembleBatch.get_blobs``).
     """
 
-    def __init__(self, fn):
+    def __init__(self, fn, nblobs=0):
         if not callable(fn):
             raise TypeError("BatchCallable needs a callable")
-        self.fn = fn
+        self.fn, self.nblobs = fn, _check_nblobs("BatchCallable", nblobs)
 
 
 class BatchKernel(BatchTarget):
     """A native batched log-probability: a C function with the signature ``emx_batch_log_prob_fn`` of ``include/emx.h``
     (typically one that launches the user's own HIP kernel on the stream it is handed) and its opaque ``user`` pointer.  A
-    proposal step is then library launches and calls of that function alone, with no Python in between."""
+    proposal step is then library launches and calls of that function alone, with no Python in between.  With ``nblobs = K > 0``
+    the function has the signature ``emx_batch_log_prob_blobs_fn`` and also writes a ``(nbatch, rows, K)`` block of blobs."""
 
-    def __init__(self, fn_ptr, user_ptr=None):
+    def __init__(self, fn_ptr, user_ptr=None, nblobs=0):
         if not isinstance(fn_ptr, ctypes._CFuncPtr):
             addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
             if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
                 raise TypeError("BatchKernel needs an emx_batch_log_prob_fn: a ctypes function or a non-null address")
-        self.fn_ptr, self.user_ptr = fn_ptr, user_ptr
+        self.fn_ptr, self.user_ptr, self.nblobs = fn_ptr, user_ptr, _check_nblobs("BatchKernel", nblobs)
 
 
 class BatchFused(BatchTarget):
@@ -218,10 +229,14 @@ class BatchFused(BatchTarget):
     :class:`~emcee_amd.EnsembleBatch` then runs as it does for a built-in target: one launch per ``run_mcmc`` chunk, no callback,
     no proposal block in global memory, bit for bit the :class:`BatchKernel` run of the same function.
     :func:`compile_fused` builds such a launcher from source.  Not a likelihood of :class:`~emcee_amd.PTSampler` (its launcher
-    carries the untempered kernel): the tempered form is :class:`PTFused`."""
+    carries the untempered kernel): the tempered form is :class:`PTFused`.
+
+    ``nblobs = K > 0``: the launcher was emitted by ``EMX_FUSED_BATCH_TARGET_BLOBS(name, Functor, ndim, K)`` around the functor's
+    five-argument form, which writes K doubles a row (``EnsembleBatch.get_blobs``); a launcher compiled for another count is
+    refused when the target is bound."""
     kind = _lib.TARGET_FUSED_USER
 
-    def __init__(self, fn_ptr, ndim, user=None):
+    def __init__(self, fn_ptr, ndim, user=None, nblobs=0):
         if not isinstance(fn_ptr, ctypes._CFuncPtr):
             addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
             if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
@@ -233,6 +248,7 @@ class BatchFused(BatchTarget):
         if hasattr(user, "data_ptr") and not getattr(user, "is_cuda", False):
             raise TypeError("BatchFused's user tensor must live on the GPU (the functor reads it on the device)")
         self.fn_ptr, self.ndim, self.user = fn_ptr, int(ndim), user
+        self.nblobs = _check_nblobs("BatchFused", nblobs)
 
     def user_address(self):
         """-> the device address handed to the functor (None: a null pointer)"""
@@ -282,17 +298,17 @@ def get_include():
 
 class BatchFusedLibrary(object):
     """What :func:`compile_fused` built: ``path`` of the shared library, ``lib`` (its ``ctypes.CDLL``: the user's own ``extern
-    "C"`` setup functions of ``source`` are there), ``name`` of the launcher, ``ndim``, and :meth:`target`."""
+    "C"`` setup functions of ``source`` are there), ``name`` of the launcher, ``ndim``, ``nblobs``, and :meth:`target`."""
 
-    def __init__(self, path, name, ndim):
-        self.path, self.name, self.ndim = path, name, int(ndim)
+    def __init__(self, path, name, ndim, nblobs=0):
+        self.path, self.name, self.ndim, self.nblobs = path, name, int(ndim), int(nblobs)
         _lib.load()                       # one HIP runtime per process: the library's (torch's) first
         self.lib = ctypes.CDLL(path)
         self.launcher = getattr(self.lib, name)
 
     def target(self, user=None):
         """-> :class:`BatchFused` of the compiled functor with the device pointer ``user``"""
-        t = BatchFused(self.launcher, self.ndim, user)
+        t = BatchFused(self.launcher, self.ndim, user, nblobs=self.nblobs)
         t._library = self                 # the launcher's code lives as long as the target
         return t
 
@@ -368,7 +384,7 @@ def compile_fused_pt(source, likelihood, ndim, prior=None, name=None, flags=(), 
     return PTFusedLibrary(so, name, ndim, prior is not None)
 
 
-def compile_fused(source, functor, ndim, name=None, flags=(), cache_dir=None):
+def compile_fused(source, functor, ndim, nblobs=0, name=None, flags=(), cache_dir=None):
     """Compile the user's model into the batch kernel -> :class:`BatchFusedLibrary`.
 
     ``source``: HIP C++ that defines the functor type ``functor`` -- ``__device__ double operator()(const double* x, int ndim,
@@ -377,17 +393,23 @@ def compile_fused(source, functor, ndim, name=None, flags=(), cache_dir=None):
     compiled with ``hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -shared -fPIC`` (+ ``flags``) and
     :func:`get_include`.  The output is cached in ``cache_dir`` (default ``$EMCEE_AMD_CACHE`` or ``~/.cache/emcee_amd``) under
     the hash of source, functor, ndim, name, flags and every header of the library: a second call with the same inputs compiles
-    nothing.  A compiler failure raises ``RuntimeError`` with the compiler's last lines."""
+    nothing.  A compiler failure raises ``RuntimeError`` with the compiler's last lines.
+
+    ``nblobs = K > 0``: the functor has the five-argument form ``(const double* x, int ndim, int member, const void* user, double*
+    blobs)`` and writes ``blobs[0 ... K)``; the translation unit ends with ``EMX_FUSED_BATCH_TARGET_BLOBS(name, functor, ndim, K)``
+    and K is part of the cache key."""
     from . import _build
     ndim = int(ndim)
     if ndim < 1 or ndim > 256:
         raise ValueError("compile_fused: 1 <= ndim <= 256; got %d" % ndim)
+    nblobs = _check_nblobs("compile_fused", nblobs)
     for what, ident in (("functor", functor), ("name", name)):
         if ident is not None and not re.match(r"^[A-Za-z_][A-Za-z0-9_:]*$", ident):
             raise ValueError("compile_fused: %s must be a C++ identifier; got %r" % (what, ident))
     name = name or "emx_fused_%s_%d" % (functor.replace(":", "_"), ndim)
     flags = [str(f) for f in flags]
-    h = hashlib.sha256(repr((source, functor, ndim, name, FUSED_FLAGS + flags)).encode())
+    # (nblobs joins the key only when there are blobs: the keys of blob-free builds stay what they were)
+    h = hashlib.sha256(repr((source, functor, ndim, name, FUSED_FLAGS + flags) + ((nblobs,) if nblobs else ())).encode())
     for d in _build.DEPS:
         if d.endswith((".hpp", ".h")):
             with open(d, "rb") as f:
@@ -400,7 +422,9 @@ def compile_fused(source, functor, ndim, name=None, flags=(), cache_dir=None):
         os.makedirs(work, exist_ok=True)
         src = os.path.join(work, "%s.hip" % name)
         with open(src, "w") as f:
-            f.write("#include <emx_fused_target.hpp>\n\n%s\n\nEMX_FUSED_BATCH_TARGET(%s, %s, %d)\n" % (source, name, functor, ndim))
+            tail = ("EMX_FUSED_BATCH_TARGET_BLOBS(%s, %s, %d, %d)" % (name, functor, ndim, nblobs) if nblobs else
+                    "EMX_FUSED_BATCH_TARGET(%s, %s, %d)" % (name, functor, ndim))
+            f.write("#include <emx_fused_target.hpp>\n\n%s\n\n%s\n" % (source, tail))
         hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
         tmp = "%s.%d.tmp" % (so, os.getpid())
         cmd = [hipcc] + FUSED_FLAGS + flags + ["-I" + d for d in get_include()] + [src, "-o", tmp]
@@ -410,4 +434,4 @@ def compile_fused(source, functor, ndim, name=None, flags=(), cache_dir=None):
                 os.remove(tmp)
             raise RuntimeError("compile_fused: hipcc failed (%s):\n%s" % (src, (r.stderr or r.stdout)[-4000:]))
         os.replace(tmp, so)
-    return BatchFusedLibrary(so, name, ndim)
+    return BatchFusedLibrary(so, name, ndim, nblobs)

@@ -555,7 +555,7 @@ int emx_set_batch_target_callback(emx_batch* b, emx_batch_log_prob_fn fn, void* 
  * (its sizeof) are checked by the launcher against the values it was compiled with, so a launcher built against another version
  * of the header is refused, never run.  grid == 0 is a probe: check abi, args_bytes and ndim, launch nothing.  Returns 0, or
  * non-zero and nothing launched (1: another version of the header, 2: another ndim, 3: the move selector was not compiled in,
- * 100 + a hipError_t: the launch failed).  emx_set_batch_target_fused probes once, so a mismatch surfaces at bind time (-8 and
+ * 4: another number of blobs, 100 + a hipError_t: the launch failed).  emx_set_batch_target_fused probes once, so a mismatch surfaces at bind time (-8 and
  * "built against another version of emx_fused_target.hpp").  `user_dev`: a device pointer handed to the functor with every row
  * (per-member data, indexed by the functor's `member`); the caller keeps it alive.  The one-workgroup rules apply with the
  * staging area's LDS on top (emx_batch_check with EMX_TARGET_FUSED_USER); "batch_threads" and "batch_plan_steps" apply and
@@ -569,9 +569,42 @@ typedef struct emx_fused_launch {
     void* hip_stream;
     const void* args;        /* SmallRunArgs */
     const void* user;        /* user_dev */
+    int32_t nblobs;          /* blobs a sample of the handle's target (0: none); the launcher answers 4 when it was compiled for another count */
+    int32_t reserved;        /* 0 */
 } emx_fused_launch;
 typedef int (*emx_fused_batch_fn)(const emx_fused_launch*);     /* 0, or non-zero and nothing launched */
 int emx_set_batch_target_fused(emx_batch* b, emx_fused_batch_fn fn, int32_t ndim_compiled, const void* user_dev);
+/* ---- blobs of a batch: derived quantities recorded with every sample (the reference's log_prob_fn returning (lp, blobs...);
+ * emcee_amd.EnsembleBatch.get_blobs) ----
+ * A batch target may produce nblobs (1 ... 32) doubles with every log-probability, by the same call.  The handle keeps each
+ * walker's current blobs (B, nwalkers, nblobs) and a blob plane (B, capacity, nwalkers, nblobs) next to the chain.  A proposal's
+ * blobs replace the walker's exactly when its log-probability does (moves/move.py:29-45): a rejected proposal, and a row rejected
+ * without reaching the target (a non-finite coordinate, a -inf factor), keep the previous ones.  Values are not validated (NaN is
+ * legal).  emx_batch_eval_state_log_prob fills the blobs of the state, emx_batch_chain_read reads the plane (what 4) and
+ * emx_summary_batch_plane summarises it.  Coordinates, log-probs and accept counts are bit for bit those of the same function
+ * without blobs.  Untempered handles only (emx_pt_set_tempering refuses a handle with blobs); the built-in targets have none.
+ * Set before the first stored step.
+ *
+ * emx_set_batch_target_fused_blobs: emx_set_batch_target_fused for a launcher emitted by EMX_FUSED_BATCH_TARGET_BLOBS(name,
+ * Functor, ndim, nblobs) -- the functor's five-argument form (..., double* blobs).  The walkers' blobs live in LDS behind the
+ * staging area (nwalkers nblobs doubles on top of emx_batch_check's bound: emx_check_batch_blobs).  The probe hands the count to
+ * the launcher, which answers 4 when it was compiled for another one (-1 and "another number of blobs" at bind time);
+ * nblobs 0 is emx_set_batch_target_fused.
+ *
+ * emx_set_batch_target_callback_blobs: emx_set_batch_target_callback for a function that also writes blobs_dev, a (nbatch, rows,
+ * nblobs) block, row for row with log_prob_dev (padding rows' blobs are ignored like their log-probs).
+ *
+ * (emx_check_batch_blobs and emx_get_blobs_batch are named like emx_summary_batch: the emx_batch_ prefix is the handle's closed
+ * set of entry points.) */
+int emx_set_batch_target_fused_blobs(emx_batch* b, emx_fused_batch_fn fn, int32_t ndim_compiled, const void* user_dev, int32_t nblobs);
+typedef int (*emx_batch_log_prob_blobs_fn)(void* user, const double* coords_dev, int32_t nbatch, int64_t rows, int32_t ndim,
+                                           double* log_prob_dev, int32_t nblobs, double* blobs_dev, void* hip_stream);
+int emx_set_batch_target_callback_blobs(emx_batch* b, emx_batch_log_prob_blobs_fn fn, void* user, int32_t nblobs);
+/* emx_batch_check for a target with nblobs blobs a sample (host only): 0, or -1 and the reason in msg */
+int emx_check_batch_blobs(int64_t nwalkers, int32_t ndim, int32_t target, int32_t nmoves, const emx_move_desc* moves, int32_t nblobs,
+                          char* msg, int32_t msglen);
+/* the current state's blobs -> out (B, nwalkers, nblobs); -1 when the target has none; *nblobs_out (may be NULL): the count */
+int emx_get_blobs_batch(emx_batch* b, double* out, int32_t* nblobs_out);
 /* the move schedule (as emx_set_moves); a sequential GaussianMove only as the one move */
 int emx_batch_set_moves(emx_batch* b, int32_t nmoves, const emx_move_desc* moves, const double* cdf);
 int emx_batch_set_move_scale(emx_batch* b, int32_t move, const double* scale, int32_t n);
@@ -582,14 +615,15 @@ int emx_batch_get_philox(emx_batch* b, uint64_t* seeds, uint64_t* step);
 int emx_batch_set_state(emx_batch* b, const double* coords, const double* log_prob);     /* log_prob may be NULL */
 int emx_batch_get_state(emx_batch* b, double* coords, double* log_prob);                 /* either may be NULL */
 /* every member's log-probs of its coordinates in one launch, with emx_eval_state_log_prob's arithmetic (a batched callback: one
- * call and one NaN-check launch) */
+ * call and one NaN-check launch); a target with blobs fills the state's blobs by the same call */
 int emx_batch_eval_state_log_prob(emx_batch* b);
 /* capacity: stored steps a member can hold; growing keeps what is stored */
 int emx_batch_chain_config(emx_batch* b, int64_t capacity);
 int emx_batch_run(emx_batch* b, int64_t nsteps, int32_t thin_by, int32_t store);
 int emx_batch_iteration(emx_batch* b, int64_t* stored, int64_t* proposals);
 /* rows start, start + stride, ... < stop of members [member_lo, member_hi): what 0 -> (members, rows, nwalkers, ndim), 1 -> log-probs;
- * tempered handles also 2 -> log-likelihoods (members, rows, nwalkers) and 3 -> betas (members, rows) */
+ * tempered handles also 2 -> log-likelihoods (members, rows, nwalkers) and 3 -> betas (members, rows); a target with blobs also
+ * 4 -> the blob plane (members, rows, nwalkers, nblobs) */
 int emx_batch_chain_read(emx_batch* b, int32_t what, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop,
                          int64_t stride, double* out);
 /* Integrated autocorrelation time of members [member_lo, member_hi) per parameter (autocorr.py:20-123 on
@@ -615,6 +649,14 @@ int emx_autocorr_batch(emx_batch* b, int32_t member_lo, int32_t member_hi, int64
 int emx_summary_batch(emx_batch* b, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop, int64_t stride,
                       double* mean_out, double* cov_out, int32_t nranks, const int64_t* ranks, double* order_out,
                       double* map_coords_out, double* map_log_prob_out, int64_t* nsamples_out);
+/* emx_summary_batch over one plane of the stored samples: plane 0 the coordinates (emx_summary_batch itself), plane 4 the blobs
+ * (emx_batch_chain_read's `what`), the same (rows, nwalkers, width) layout with width nblobs in ndim's place: mean_out (members,
+ * nblobs), cov_out (members, nblobs, nblobs), order_out (members, nranks, nblobs), map_coords_out (members, nblobs) the blobs
+ * of the sample of the largest stored log-prob.  The same kernels and the same fixed summation order.  -1 for plane 4 of a
+ * handle without blobs. */
+int emx_summary_batch_plane(emx_batch* b, int32_t plane, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop,
+                            int64_t stride, double* mean_out, double* cov_out, int32_t nranks, const int64_t* ranks,
+                            double* order_out, double* map_coords_out, double* map_log_prob_out, int64_t* nsamples_out);
 /* host twin of the selection (no device): the ranks[r]-th smallest of x[0], x[stride], ..., n values, with the same key
  * transform and digit search as the kernels.  0, or -1 for bad arguments (n < 1, stride < 1, nranks outside [0, 32], a rank
  * outside [0, n)). */
