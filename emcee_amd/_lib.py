@@ -10,6 +10,7 @@ LIB_PATH = os.path.join(HERE, "libemx.so")
 TARGET_HOST, TARGET_ISO, TARGET_DIAG, TARGET_DENSE, TARGET_ROSENBROCK, TARGET_BOX, TARGET_CALLBACK = range(7)
 TARGET_FUSED_USER = 8               # batches only (emx_set_batch_target_fused); 7 is taken inside the kernels
 TARGET_FUSED_PT = 9                 # tempered batches only (emx_pt_set_target_fused)
+TARGET_FUSED_ENSEMBLE = 10          # a single ensemble: the user's device function compiled into the half-step (emx_set_target_fused)
 MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER, MOVE_GAUSS = range(4)
 MOVE_WALK, MOVE_KDE = 5, 6          # native (Philox) mode only; 4 is not a public kind
 KDE_BW_SCOTT, KDE_BW_SILVERMAN, KDE_BW_SCALAR = range(3)
@@ -46,6 +47,15 @@ class FusedLaunch(C.Structure):
                 ("user", C.c_void_p), ("nblobs", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FusedEnsembleLaunch(C.Structure):
+    """emx_fused_ensemble_launch of include/emx.h: the descriptor the launcher of a single sampler's fused user target is handed"""
+    _fields_ = [("abi", C.c_uint32), ("args_bytes", C.c_uint32), ("ndim", C.c_int32), ("move", C.c_int32), ("grid", C.c_int32),
+                ("threads", C.c_int32), ("lds_bytes", C.c_uint64), ("hip_stream", C.c_void_p), ("args", C.c_void_p),
+                ("user", C.c_void_p)]
+
+
+# emx_fused_ensemble_fn: (const emx_fused_ensemble_launch*) -> int
+FUSED_ENSEMBLE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 # emx_fused_batch_fn: (const emx_fused_launch*) -> int
 FUSED_BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 # emx_pt_fused_fn: (emx_pt_fused_launch*) -> int
@@ -80,6 +90,7 @@ SIGNATURES = {
     "emx_snapshot_free": (C.c_int, [_P, C.c_int32]),
     "emx_set_target": (C.c_int, [_P, C.c_int32, _P, _P, C.c_double]),
     "emx_set_target_callback": (C.c_int, [_P, DEVICE_LOG_PROB_FN, _P]),
+    "emx_set_target_fused": (C.c_int, [_P, FUSED_ENSEMBLE_FN, _P]),
     "emx_eval_state_log_prob": (C.c_int, [_P]),
     "emx_eval_log_prob": (C.c_int, [_P, _dp, C.c_int64, _dp]),
     "emx_set_moves": (C.c_int, [_P, C.c_int32, C.POINTER(MoveDesc), _dp]),

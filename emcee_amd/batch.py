@@ -40,7 +40,7 @@ from . import summary as _summary
 from .autocorr import integrated_time
 from .ensemble import _native_desc, _parse_move_schedule, _refuse_extended_precision, philox_seed, walkers_independent
 from .state import State
-from .targets import (BatchFused, BatchKernel, BatchTarget, PTFused, DenseGaussian, DeviceCallable, DeviceKernel, DeviceTarget, DiagGaussian, IsoGaussian,
+from .targets import (BatchFused, BatchKernel, BatchTarget, DeviceFused, PTFused, DenseGaussian, DeviceCallable, DeviceKernel, DeviceTarget, DiagGaussian, IsoGaussian,
                       Rosenbrock, UniformBox)
 
 __all__ = ["EnsembleBatch"]
@@ -119,6 +119,9 @@ class EnsembleBatch(object):
                 raise ValueError("the PTFused target was compiled for ndim %d; the sampler has ndim %d" % (target.ndim, self.ndim))
         if isinstance(target, BatchTarget):
             return [target], False
+        if isinstance(target, DeviceFused):
+            raise TypeError("a DeviceFused is a target of EnsembleSampler: its launcher carries the single sampler's half-step kernel "
+                            "(for an EnsembleBatch compile the model as a BatchFused: the functor is the same)")
         if isinstance(target, DeviceTarget) or callable(target):
             targets, per_member = [target], False
         else:

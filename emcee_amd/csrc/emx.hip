@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/emx.h"
+#include "emx_fused_ensemble.hpp"
 #include "emx_internal.hpp"
 #include "emx_kernels.hpp"
 #include "emx_launch.hpp"
@@ -291,6 +292,8 @@ struct emx_ctx {
     double* snap[NSNAPSHOT] = {};
     // target
     emx_device_log_prob_fn cb_fn = nullptr;   // EMX_TARGET_DEVICE_CALLBACK: the caller's batched log-prob, run on device buffers
+    emx_fused_ensemble_fn fused_fn = nullptr; // EMX_TARGET_FUSED_ENSEMBLE: the launcher of the caller's translation unit (k_halfstep_user) ...
+    const void* fused_user = nullptr;         // ... and the device pointer its functor receives
     void* cb_user = nullptr;
     int target = EMX_TARGET_HOST;
     double *tp0 = nullptr, *tp1 = nullptr;
@@ -820,6 +823,26 @@ int launch_split(emx_ctx* c, int move, int target, int S, int split, int pos0, i
     }
     const bool dense = target == EMX_TARGET_DENSE_GAUSS;
     const bool callback = target == EMX_TARGET_DEVICE_CALLBACK;
+    const bool fused = target == EMX_TARGET_FUSED_ENSEMBLE;
+    if (fused) {
+        // the caller's function compiled into the half-step (emx_fused_ensemble.hpp): one launch, one replica, no replay
+        if (!c->fused_fn) {
+            c->err = "fused user target without a launcher (emx_set_target_fused)";
+            return -1;
+        }
+        if (step_desc) {
+            c->err = "fused user target: not replayable from a step graph";
+            return -1;
+        }
+        if (c->world != 1 || c->comm || sendbuf || t_hi_dev || c->launch_declp || c->persist_cap) {
+            c->err = "fused user target: one replica, one launch per half-step (no exchange, no sharding, no persistent kernel)";
+            return -1;
+        }
+        if (move != MOVE_EVAL && !ps) {
+            c->err = "fused user target: half-step without a plan";
+            return -1;
+        }
+    }
     if ((dense && dense_is_wide(c)) || callback) {
         // Three passes on the stream -- the reference's compute_log_prob between get_proposal and the accept loop
         // (red_blue.py:90-101): propose -> log-prob of the proposal block -> decision + commit.  The log-prob pass is
@@ -1075,7 +1098,30 @@ int launch_split(emx_ctx* c, int move, int target, int S, int split, int pos0, i
     // has eight waves a CU and the two are level -- profiles/r04/slab_ab.txt; tuning "slab" = 2 takes it from padded 80 on)
     const bool slab = dense && c->tune_slab && c->Dp >= (c->tune_slab == 2 ? 80 : 112) && sh.G == 16 && sh.V == 2 && sh.CH == 4 &&
                       (move == MOVE_STRETCH || move == MOVE_DE) && lean_kind(a, 16, 2, 4, move, true) == 1;
-    if (slab) {
+    if (fused) {
+        emx_fused_ensemble_launch fl{};
+        fl.abi = EMX_FUSED_ENSEMBLE_ABI;
+        fl.args_bytes = (uint32_t)sizeof(HalfStepArgs);
+        fl.ndim = D;
+        fl.move = move;
+        fl.grid = (int32_t)std::min<int64_t>((nown + fused_ens_tile_rule(D) - 1) / fused_ens_tile_rule(D), (int64_t)c->num_cu * 64);
+        fl.threads = FUSED_ENS_THREADS;
+        fl.lds_bytes = fused_ens_lds_bytes(D);
+        fl.hip_stream = (void*)c->stream;
+        fl.args = &a;
+        fl.user = c->fused_user;
+        const int rcf = c->fused_fn(&fl);
+        if (rcf) {
+            char b[256];
+            snprintf(b, sizeof(b), "fused user target: the launcher refused the half-step (move %d, ndim %d): %s", move, D,
+                     rcf == 1 ? "built against another version of emx_fused_ensemble.hpp" : rcf == 2 ? "compiled for another ndim" :
+                     rcf == 3 ? "move or launch shape not compiled in" : rcf == 5 ? "the launch carries an exchange" :
+                     rcf >= 100 ? hipGetErrorString((hipError_t)(rcf - 100)) : "unknown answer");
+            c->err = b;
+            return rcf >= 100 ? -2 : -8;
+        }
+        e = hipSuccess;
+    } else if (slab) {
         const int wpb = 8;
         const int64_t ntile = (nown + 15) / 16;
         const int64_t nb = std::min<int64_t>((ntile + wpb - 1) / wpb, (int64_t)c->num_cu * c->tune_bpc);
@@ -1743,6 +1789,41 @@ int emx_set_target_callback(emx_ctx* c, emx_device_log_prob_fn fn, void* user) {
     graph_invalidate(c);
     c->graph_warm = false;
     c->target = EMX_TARGET_DEVICE_CALLBACK;
+    c->tscale = 1.0;
+    return 0;
+}
+
+// The caller's per-row device function compiled into the half-step (include/emx.h; emx_fused_ensemble.hpp): launch_split hands the
+// element-wise half-step, and every evaluation of rows, to the caller's launcher.
+int emx_set_target_fused(emx_ctx* c, emx_fused_ensemble_fn launcher, const void* user) {
+    { const int rcs_ = persist_settle(c); if (rcs_) return rcs_; }
+    NEED(c, launcher != nullptr, "emx_set_target_fused: no launcher");
+    NEED(c, c->D >= 1 && c->D <= FUSED_ENS_MAX_NDIM, "emx_set_target_fused: a fused user target has 1 <= ndim <= %d; the ensemble has ndim %d",
+         FUSED_ENS_MAX_NDIM, c->D);
+    NEED(c, c->world == 1 && !c->comm && !c->sendbuf && !c->peers_ready,
+         "emx_set_target_fused: a fused user target runs on one replica (no sharding, no exchange)");
+    // the probe: abi, args_bytes and ndim against what the launcher was compiled with; nothing is launched.  (A launcher of the
+    // batch targets reads the same two leading fields, finds another constant and answers 1.)
+    emx_fused_ensemble_launch fl{};
+    fl.abi = EMX_FUSED_ENSEMBLE_ABI;
+    fl.args_bytes = (uint32_t)sizeof(HalfStepArgs);
+    fl.ndim = c->D;
+    fl.move = MOVE_EVAL;
+    const int rcp = launcher(&fl);
+    if (rcp == 2) FAIL(c, -1, "emx_set_target_fused: the fused user target was compiled for another ndim; the ensemble has ndim %d", c->D);
+    if (rcp)
+        FAIL(c, -8, "emx_set_target_fused: the launcher was built against another version of emx_fused_ensemble.hpp, or is not an "
+                    "EMX_FUSED_ENSEMBLE_TARGET launcher (it answered %d); rebuild it against this library's headers", rcp);
+    HIPOK(c, hipSetDevice(c->device));
+    PIPE_STOP(c);
+    drop_prepared(c);          // plans made ahead were shaped (lean or full) for the previous target
+    HIPOK(c, hipStreamSynchronize(c->stream));
+    c->fused_fn = launcher;
+    c->fused_user = user;
+    c->Dp = 0;
+    graph_invalidate(c);
+    c->graph_warm = false;
+    c->target = EMX_TARGET_FUSED_ENSEMBLE;
     c->tscale = 1.0;
     return 0;
 }
@@ -3022,6 +3103,7 @@ static emx_ctx::GraphSlot* graph_ready(emx_ctx* c, int store) {
     if (c->graph_disabled || !c->tune_graph || !c->graph_warm) return nullptr;
     if (c->rng_mode != EMX_RNG_PHILOX || c->moves.size() != 1 || c->world != 1 || c->comm || c->sendbuf) return nullptr;
     if (c->prof_max > 0 || c->tune_ablate || c->cur.active || !c->prepared.empty()) return nullptr;
+    if (c->target == EMX_TARGET_FUSED_ENSEMBLE) return nullptr;      // a fused user target: one launch per half-step, never a graph
     if (store && c->stored + NB > c->cap) return nullptr;
     auto& g = c->gslot[store ? 1 : 0];
     const emx_move_desc& mv = c->moves[0];
@@ -4426,6 +4508,7 @@ int emx_set_shard(emx_ctx* c, int32_t rank, int32_t world) {
     HIPOK(c, hipSetDevice(c->device));
     NEED(c, world >= 1 && rank >= 0 && rank < world, "bad (rank, world)");
     NEED(c, world <= c->N, "more ranks than walkers");
+    NEED(c, world == 1 || c->target != EMX_TARGET_FUSED_ENSEMBLE, "a fused user target (emx_set_target_fused) runs on one replica: world = %d refused", world);
     HIPOK(c, hipStreamSynchronize(c->stream));
     drop_prepared(c);          // plans made ahead were shaped (lean or full) for the previous sharding
     c->rank = rank;

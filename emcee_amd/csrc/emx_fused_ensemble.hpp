@@ -1,0 +1,251 @@
+// Fused user targets of the single sampler (include/emx.h: emx_set_target_fused; emcee_amd.targets.DeviceFused /
+// compile_fused_ensemble).  PUBLIC: this is the header a user's translation unit includes to compile their own per-row
+// log-probability into the half-step of a large ensemble, and the library includes it for the version constants and the launch rules.
+//
+//     #include <emx_fused_ensemble.hpp>           // hipcc --offload-arch=gfx950 -std=c++17 -ffp-contract=off -I include -I emcee_amd/csrc
+//     struct MyModel {                            // stateless; `user`: the device pointer given to DeviceFused; `member` is always 0
+//         __device__ double operator()(const double* x, int ndim, int member, const void* user) const;
+//     };
+//     EMX_FUSED_ENSEMBLE_TARGET(my_model, MyModel, /*ndim=*/5)    // emits: extern "C" int my_model(const emx_fused_ensemble_launch*)
+//
+// The functor contract is the batch one (emx_fused_target.hpp), so one model source serves both: `x` points at `ndim` doubles in
+// LDS, the call is made once per live row by ONE lane and depends on nothing but its arguments and memory reachable from `user`
+// (no LDS of its own, no barrier, no cross-lane operation).  -inf is legal, NaN raises the reference's error; a row with a
+// non-finite coordinate is rejected without being handed over.
+//
+// k_halfstep_user is ONE launch per half-step where a DeviceKernel target takes three (propose -> the caller's kernel -> commit,
+// the proposal block going through HBM twice): a workgroup takes tiles of TILE slots of the split,
+//   1. G lanes a row make the proposal -- k_halfstep's arithmetic in pick_shape's row layout (load_row / make_proposal /
+//      gauss_disp_row: the same bits, group reductions included) -- and stage it in LDS, rows D | 1 doubles apart;
+//   2. one lane a row calls the functor on its staged row and takes the decision (k_wide_commit's rule): lp, acc, acc_count,
+//      chain_lp, the NaN status bit;
+//   3. G lanes a row commit the accepted rows from LDS to X and append the chain row of a stored step (streaming stores).
+// The MOVE_EVAL instantiation is phases 1 and 2 over rows of X (initial log-probs; the log-prob pass of WalkMove / KDEMove).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#if __has_include(<emx.h>)
+#include <emx.h>
+#else
+#include "../../include/emx.h"
+#endif
+#include "emx_kernels.hpp"
+#include "emx_small_host.hpp"
+
+// bumped with ANY change of HalfStepArgs or of k_halfstep_user's launch rules: a launcher and a library of different values refuse
+// each other
+#ifndef EMX_FUSED_ENSEMBLE_ABI
+#define EMX_FUSED_ENSEMBLE_ABI 0x454e5301u
+#endif
+
+namespace emx {
+
+constexpr int FUSED_ENS_MAX_NDIM = 256;
+constexpr int FUSED_ENS_THREADS = 256;      // four waves: (256 / G) rows a pass
+
+// pick_shape(D, D) (emx_small_host.hpp) -- the layout of the element-wise k_halfstep -- as a constant expression
+constexpr int fused_ens_v(int D) { return D % 2 == 0 ? 2 : 1; }
+constexpr int fused_ens_g(int D) { return shape_g((D + fused_ens_v(D) - 1) / fused_ens_v(D)); }
+constexpr int fused_ens_ch(int D) { return shape_ch((D + fused_ens_v(D) - 1) / fused_ens_v(D)); }
+
+// Slots a workgroup stages at once (profiles/ensemble_fused.md): as many as keep the staging area near 33 KB, so that four
+// workgroups share a CU's 160 KB; never fewer than one pass of the workgroup's groups.
+constexpr int fused_ens_tile_rule(int D) { return D <= 64 ? 64 : D <= 128 ? 32 : 16; }
+// dynamic LDS of a workgroup: the staged rows, a factor a row, a flag a row (1: non-finite proposal, 2: accepted)
+constexpr size_t fused_ens_lds_of(int D, int tile) { return ((size_t)tile * ((size_t)(D | 1) * 8 + 8 + 4) + 15) / 16 * 16; }
+constexpr size_t fused_ens_lds_bytes(int D) { return fused_ens_lds_of(D, fused_ens_tile_rule(D)); }
+
+template <int G, int V, int CH, int MOVE, typename USER, int TILE>
+static __global__ __launch_bounds__(FUSED_ENS_THREADS) void k_halfstep_user(const HalfStepArgs A, const void* user) {
+    static_assert(G >= 4 && G <= 64 && (64 % G) == 0, "G lanes per walker");
+    constexpr int T = FUSED_ENS_THREADS;
+    constexpr int WPW = 64 / G;                 // rows a wave and pass
+    constexpr int GPB = (T / 64) * WPW;         // rows a workgroup and pass
+    static_assert(TILE >= GPB && TILE % GPB == 0 && TILE <= T, "the tile is whole passes of the workgroup, a lane a row in the decision");
+    constexpr int NPASS = TILE / GPB;
+    constexpr int NR = rows_per_pass<MOVE>();
+    constexpr bool EVAL = MOVE == MOVE_EVAL;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int D = A.D, DS = D | 1;              // odd row stride: the decision lanes' reads of column d hit distinct banks
+    double* const stage = smem;
+    double* const sfac = stage + (size_t)TILE * DS;
+    int* const sflag = reinterpret_cast<int*>(sfac + TILE);
+    const int tid = threadIdx.x, lane = tid & 63, wib = tid >> 6;
+    const int sub = lane / G, gl = lane % G;
+
+    for (int t0 = A.t_lo + (int)blockIdx.x * TILE; t0 < A.t_hi; t0 += (int)gridDim.x * TILE) {      // workgroup-uniform
+        const int nrow = min(TILE, A.t_hi - t0);
+        // the decision lane's scalars: independent of the proposals, in flight while they are made
+        int my_i = 0;
+        double my_lpo = 0.0, my_logu = 0.0;
+        if (tid < nrow) {
+            const int pos = A.pos0 + t0 + tid;
+            my_i = A.order[pos];
+            if constexpr (!EVAL) {
+                my_lpo = A.lp[my_i];
+                my_logu = A.logu[pos];
+            }
+        }
+        // -------- 1. proposals, G lanes a row --------
+        int wi[NPASS], ja[NPASS], jb[NR >= 3 ? NPASS : 1], jc[NR >= 4 ? NPASS : 1];
+#pragma unroll
+        for (int p = 0; p < NPASS; ++p) {
+            const int r = p * GPB + wib * WPW + sub;
+            const int pos = A.pos0 + t0 + (r < nrow ? r : 0);
+            wi[p] = A.order[pos];
+            ja[p] = NR >= 2 ? A.p0[pos] : -1;
+            if constexpr (NR >= 3) jb[p] = A.p1[pos];
+            if constexpr (NR >= 4) jc[p] = A.p2[pos];
+        }
+        Row<G, V, CH> xi[NPASS];
+#pragma unroll
+        for (int p = 0; p < NPASS; ++p) {
+            const int r = p * GPB + wib * WPW + sub;
+            const bool live = r < nrow;
+            const int pos = A.pos0 + t0 + (live ? r : 0);
+            const int i = wi[p];
+            Row<G, V, CH> xa, xb, xc, q;
+            load_row<G, V, CH>(xi[p], A.X + (size_t)i * D, D, gl);
+            if constexpr (MOVE == MOVE_GAUSS) {
+                if (A.disp) load_row<G, V, CH>(xa, A.disp + (size_t)i * D, D, gl);
+                else gauss_disp_row<G, V, CH>(xa, A, i, ja[p], D, gl);
+            } else if constexpr (NR >= 2) {
+                load_row<G, V, CH>(xa, A.X + (size_t)ja[p] * D, D, gl);
+            }
+            if constexpr (NR >= 3) load_row<G, V, CH>(xb, A.X + (size_t)jb[p] * D, D, gl);
+            if constexpr (NR >= 4) load_row<G, V, CH>(xc, A.X + (size_t)jc[p] * D, D, gl);
+            double s0 = 0.0, factor = 0.0;
+            if constexpr (!EVAL) {
+                s0 = (MOVE == MOVE_SNOOKER) ? 0.0 : A.s0[pos];
+                factor = A.fac[pos];
+            }
+            make_proposal<G, V, CH, MOVE>(xi[p], NR >= 2 ? xa : xi[p], NR >= 3 ? xb : xi[p], NR >= 4 ? xc : xi[p], s0, A.gammas, D, gl, q,
+                                          factor, ja[p]);
+            // a non-finite proposal: the sticky error (ensemble.py:476-479), rejected, never handed to the functor
+            bool bl = false;
+#pragma unroll
+            for (int c = 0; c < CH; ++c)
+#pragma unroll
+                for (int v = 0; v < V; ++v) bl |= !(fabs(q.x[c][v]) <= 1.79769313486231570815e308);
+            const bool badq = group_any<G>(bl, sub);
+            if (live) {
+                if (!EVAL && badq && gl == 0) raise_status(A.status, ST_BAD_COORD);      // (an evaluated block's was raised by the kernel that proposed it)
+#pragma unroll
+                for (int c = 0; c < CH; ++c)
+#pragma unroll
+                    for (int v = 0; v < V; ++v) {
+                        const int d = (c * G + gl) * V + v;
+                        if (d < D) stage[(size_t)r * DS + d] = q.x[c][v];
+                    }
+                if (gl == 0) {
+                    sfac[r] = factor;
+                    sflag[r] = badq ? 1 : 0;
+                }
+            }
+        }
+        __syncthreads();
+        // -------- 2. the functor and the decision, one lane a row (red_blue.py:96-101, as k_wide_commit) --------
+        if (tid < nrow) {
+            const bool bad = sflag[tid] != 0;
+            if constexpr (EVAL) {
+                double lpn = -__builtin_inf();      // a non-finite row: rejected by whoever compares against it
+                if (!bad) {
+                    lpn = USER{}(stage + (size_t)tid * DS, D, 0, user);
+                    if (lpn != lpn) raise_status(A.status, ST_NAN_LOGP);
+                }
+                A.lp[my_i] = lpn;
+            } else {
+                bool accept = false;
+                double lpn = my_lpo;
+                if (!bad) {
+                    lpn = USER{}(stage + (size_t)tid * DS, D, 0, user);
+                    if (lpn != lpn) raise_status(A.status, ST_NAN_LOGP);                 // ensemble.py:550-551
+                    const double lnpdiff = sfac[tid] + lpn - my_lpo;                     // red_blue.py:99
+                    accept = lnpdiff > my_logu;                                          // red_blue.py:100
+                }
+                if (accept) A.lp[my_i] = lpn;                                            // move.py:34
+                A.acc[my_i] = accept ? 1 : 0;
+                if (A.chain_lp) {
+                    A.chain_lp[my_i] = accept ? lpn : my_lpo;
+                    if (accept) A.acc_count[my_i] += 1u;
+                }
+                sflag[tid] = accept ? 2 : 0;
+            }
+        }
+        __syncthreads();
+        // -------- 3. commit, G lanes a row: accepted rows from LDS (move.py:33), the chain row of a stored step --------
+        if constexpr (!EVAL) {
+#pragma unroll
+            for (int p = 0; p < NPASS; ++p) {
+                const int r = p * GPB + wib * WPW + sub;
+                if (r >= nrow) continue;
+                const bool accept = sflag[r] == 2;
+                if (!accept && !A.chain) continue;
+                Row<G, V, CH> rr = xi[p];
+                if (accept) {
+#pragma unroll
+                    for (int c = 0; c < CH; ++c)
+#pragma unroll
+                        for (int v = 0; v < V; ++v) {
+                            const int d = (c * G + gl) * V + v;
+                            rr.x[c][v] = d < D ? stage[(size_t)r * DS + d] : 0.0;
+                        }
+                    store_row<G, V, CH>(rr, A.X + (size_t)wi[p] * D, D, gl);
+                }
+                if (A.chain) store_row_stream<G, V, CH>(rr, A.chain + (size_t)wi[p] * D, D, gl);
+            }
+            __syncthreads();                        // the staged rows are consumed before the next tile overwrites them
+        }
+    }
+}
+
+template <typename USER, int NDIM, int MOVE>
+hipError_t launch_fused_ens_move(int grid, hipStream_t st, const HalfStepArgs& a, const void* user) {
+    constexpr int G = fused_ens_g(NDIM), V = fused_ens_v(NDIM), CH = fused_ens_ch(NDIM), TILE = fused_ens_tile_rule(NDIM);
+    static_assert(G * V * CH >= NDIM, "the row layout covers the row");
+    constexpr size_t lds = fused_ens_lds_of(NDIM, TILE);
+    static_assert(lds <= 48 * 1024, "the staging area stays below the LDS a kernel gets without asking");
+    hipLaunchKernelGGL((k_halfstep_user<G, V, CH, MOVE, USER, TILE>), dim3(grid), dim3(FUSED_ENS_THREADS), lds, st, a, user);
+    return hipGetLastError();
+}
+
+// the launcher behind EMX_FUSED_ENSEMBLE_TARGET: the checks, then one launch of the half-step (include/emx.h:
+// emx_fused_ensemble_launch).  0, or non-zero and nothing launched: 1 another version of the header (or another launcher type's
+// descriptor), 2 another ndim, 3 a move or launch shape that was not compiled in, 5 a HalfStepArgs that carries an exchange, a graph
+// descriptor or a device-side slot count, 100 + a hipError_t.
+template <typename USER, int NDIM>
+int fused_ensemble_launch(const emx_fused_ensemble_launch* L) {
+    static_assert(NDIM >= 1 && NDIM <= FUSED_ENS_MAX_NDIM, "a fused user target has 1 <= ndim <= 256");
+    if (!L || L->abi != EMX_FUSED_ENSEMBLE_ABI || L->args_bytes != (uint32_t)sizeof(HalfStepArgs)) return 1;
+    if (L->ndim != NDIM) return 2;
+    if (L->move != MOVE_STRETCH && L->move != MOVE_DE && L->move != MOVE_SNOOKER && L->move != MOVE_GAUSS && L->move != MOVE_EVAL) return 3;
+    if (L->grid == 0) return 0;                       // the probe of emx_set_target_fused
+    constexpr int TILE = fused_ens_tile_rule(NDIM);
+    if (!L->args || L->grid < 0 || L->threads != FUSED_ENS_THREADS || L->lds_bytes < fused_ens_lds_of(NDIM, TILE)) return 3;
+    const HalfStepArgs& a = *static_cast<const HalfStepArgs*>(L->args);
+    if (a.D != NDIM) return 2;
+    if (a.sendbuf || a.desc || a.t_hi_dev || a.peers || a.npeer || a.declp || a.push_peers || a.npush) return 5;
+    if (a.t_hi <= a.t_lo) return 0;
+    // `grid` is the most workgroups the library allows; a tile a workgroup until then
+    const long long tiles = ((long long)a.t_hi - a.t_lo + TILE - 1) / TILE;
+    const int grid = (int)(tiles < L->grid ? tiles : L->grid);
+    const hipStream_t st = (hipStream_t)L->hip_stream;
+    hipError_t e = hipErrorInvalidValue;
+    switch (L->move) {
+        case MOVE_STRETCH: e = launch_fused_ens_move<USER, NDIM, MOVE_STRETCH>(grid, st, a, L->user); break;
+        case MOVE_DE: e = launch_fused_ens_move<USER, NDIM, MOVE_DE>(grid, st, a, L->user); break;
+        case MOVE_SNOOKER: e = launch_fused_ens_move<USER, NDIM, MOVE_SNOOKER>(grid, st, a, L->user); break;
+        case MOVE_GAUSS: e = launch_fused_ens_move<USER, NDIM, MOVE_GAUSS>(grid, st, a, L->user); break;
+        case MOVE_EVAL: e = launch_fused_ens_move<USER, NDIM, MOVE_EVAL>(grid, st, a, L->user); break;
+    }
+    return e == hipSuccess ? 0 : 100 + (int)e;
+}
+
+}  // namespace emx
+
+#define EMX_FUSED_ENSEMBLE_TARGET(name, Functor, ndim)                                                      \
+    extern "C" __attribute__((visibility("default"))) int name(const emx_fused_ensemble_launch* launch) {  \
+        return emx::fused_ensemble_launch<Functor, (ndim)>(launch);                                         \
+    }

@@ -247,6 +247,17 @@ class DeviceEnsemble:
         self._ck(self.lib.emx_set_target_callback(self.ctx, fn, C.c_void_p(user_ptr) if not isinstance(user_ptr, C.c_void_p) else user_ptr))
         self._target_kind = _lib.TARGET_CALLBACK
 
+    def set_target_fused(self, fn_ptr, user_address=None):
+        """A launcher emitted by ``EMX_FUSED_ENSEMBLE_TARGET`` (``emx_fused_ensemble.hpp``) as the target: the user's per-row device
+        function runs inside the half-step kernel.  ``fn_ptr``: a ctypes function or an address; ``user_address``: the device
+        address its functor receives (None: null).  The library probes the launcher and refuses another header version or ndim."""
+        if isinstance(fn_ptr, (int, np.integer)):
+            fn_ptr = C.c_void_p(int(fn_ptr))
+        fn = fn_ptr if isinstance(fn_ptr, _lib.FUSED_ENSEMBLE_FN) else C.cast(fn_ptr, _lib.FUSED_ENSEMBLE_FN)
+        self._touch_target = fn                                 # the library holds the pointer: keep the object alive
+        self._ck(self.lib.emx_set_target_fused(self.ctx, fn, C.c_void_p(user_address)))
+        self._target_kind = _lib.TARGET_FUSED_ENSEMBLE
+
     def walkers_independent(self):
         """The reference's initial-state check (ensemble.py:653-663) on the ensemble this context holds: nothing crosses PCIe."""
         verdict = C.c_int32(0)

@@ -32,7 +32,7 @@ from .moves.kde import kde_desc
 from .moves.walk import walk_desc
 from .pbar import get_progress_bar
 from .state import DeviceState, ResidentState, State
-from .targets import BatchTarget, DeviceTarget
+from .targets import BatchTarget, DeviceFused, DeviceTarget
 from .utils import deprecation_warning
 
 __all__ = ["EnsembleSampler", "walkers_independent"]
@@ -109,6 +109,12 @@ class EnsembleSampler(object):
         if isinstance(log_prob_fn, BatchTarget):
             raise TypeError("%s evaluates every member of a batch at once: run it with EnsembleBatch (a single ensemble takes a "
                             "DeviceCallable or DeviceKernel)" % type(log_prob_fn).__name__)
+        if isinstance(log_prob_fn, DeviceFused):
+            if distributed:
+                raise ValueError("a DeviceFused target runs on one GPU: distributed=True is refused (shard a DeviceKernel or "
+                                 "DeviceCallable, or a built-in target)")
+            if log_prob_fn.ndim != ndim:
+                raise ValueError("the DeviceFused target was compiled for ndim %d; the sampler has ndim %d" % (log_prob_fn.ndim, ndim))
         for value, text in ((a, "The 'a' argument is deprecated, use 'moves' instead"),
                             (threads, "The 'threads' argument is deprecated"),
                             (runtime_sortingfn, "The 'runtime_sortingfn' argument is deprecated"),

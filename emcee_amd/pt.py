@@ -54,7 +54,7 @@ from . import _lib
 from .batch import EnsembleBatch, _trampoline
 from .ensemble import _refuse_extended_precision, walkers_independent
 from .state import State
-from .targets import BatchCallable, BatchFused, BatchKernel, BatchTarget, DeviceTarget, PTFused
+from .targets import BatchCallable, BatchFused, BatchKernel, BatchTarget, DeviceFused, DeviceTarget, PTFused
 
 __all__ = ["PTSampler", "default_betas", "thermodynamic_integration_log_evidence"]
 
@@ -158,6 +158,9 @@ class PTSampler(object):
         if isinstance(log_likelihood, BatchFused):
             raise TypeError("PTSampler's log_likelihood is a targets.BatchCallable or targets.BatchKernel; a BatchFused is not: the "
                             "tempered commit and the swap pass run on the batched callback path (a fused tempered kernel does not exist)")
+        if isinstance(log_likelihood, DeviceFused):
+            raise TypeError("PTSampler's log_likelihood is a targets.BatchCallable, targets.BatchKernel or targets.PTFused; a DeviceFused "
+                            "is not: its launcher carries the single sampler's half-step kernel (compile the model as a PTFused)")
         if isinstance(log_likelihood, BatchTarget) and getattr(log_likelihood, "nblobs", 0) > 0:
             raise TypeError("PTSampler does not record blobs: its log_likelihood is a target with nblobs = 0 (the tempered commit and "
                             "the swap pass carry none; got nblobs = %d)" % log_likelihood.nblobs)

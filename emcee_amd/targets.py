@@ -22,7 +22,7 @@ from . import _lib
 
 __all__ = ["DeviceTarget", "IsoGaussian", "DiagGaussian", "DenseGaussian", "Rosenbrock", "UniformBox", "DeviceCallable", "DeviceKernel",
            "BatchCallable", "BatchKernel", "BatchFused", "BatchFusedLibrary", "compile_fused", "get_include", "PTFused", "PTFusedLibrary",
-           "compile_fused_pt"]
+           "compile_fused_pt", "DeviceFused", "DeviceFusedLibrary", "compile_fused_ensemble"]
 
 
 class DeviceTarget(object):
@@ -158,6 +158,54 @@ class DeviceKernel(DeviceTarget):
         if getattr(ens, "_cb_owner", None) is not self:
             ens.set_target_callback_c(self.fn_ptr, self.user_ptr)
             ens._cb_owner = self
+
+
+class DeviceFused(DeviceTarget):
+    """The user's per-row ``__device__`` log-probability compiled INTO the half-step kernel of :class:`~emcee_amd.EnsembleSampler`:
+    ``fn_ptr`` is the launcher that ``EMX_FUSED_ENSEMBLE_TARGET(name, Functor, ndim)`` of ``emx_fused_ensemble.hpp`` emits in the
+    user's own translation unit (an ``emx_fused_ensemble_fn`` of ``include/emx.h``: a ctypes function or a non-null address),
+    ``ndim`` the dimension it was compiled for (1 ... 256), ``user`` the device pointer the functor receives with every row -- None,
+    an integer, a ``ctypes.c_void_p``, or a torch CUDA tensor (kept alive; its ``data_ptr()`` is passed).
+
+    A half-step is then ONE kernel launch -- proposal, the user's function on the row staged in LDS, accept / commit -- where a
+    :class:`DeviceKernel` takes three and sends the proposal block through memory; the run is bit for bit the :class:`DeviceKernel`
+    run of the same function, with every move that path runs, in both rng modes.  The functor contract is :class:`BatchFused`'s
+    (``member`` is always 0), so one model source serves both; :func:`compile_fused_ensemble` builds the launcher from source.
+    One GPU only (``distributed=True`` is refused); no blobs.  Not a target of :class:`~emcee_amd.EnsembleBatch` or
+    :class:`~emcee_amd.PTSampler`, and not callable outside a sampler."""
+    kind = _lib.TARGET_FUSED_ENSEMBLE
+
+    def __init__(self, fn_ptr, ndim, user=None):
+        if not isinstance(fn_ptr, ctypes._CFuncPtr):
+            addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
+            if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
+                raise TypeError("DeviceFused needs an emx_fused_ensemble_fn: a ctypes function or a non-null address")
+        if isinstance(ndim, bool) or not isinstance(ndim, (int, np.integer)) or not 1 <= ndim <= 256:
+            raise TypeError("DeviceFused needs the ndim its launcher was compiled for, an integer in [1, 256]; got %r" % (ndim,))
+        if not (user is None or isinstance(user, (int, np.integer, ctypes.c_void_p)) or hasattr(user, "data_ptr")) or isinstance(user, bool):
+            raise TypeError("DeviceFused's user is a device pointer: None, an integer, a ctypes.c_void_p or a torch CUDA tensor")
+        if hasattr(user, "data_ptr") and not getattr(user, "is_cuda", False):
+            raise TypeError("DeviceFused's user tensor must live on the GPU (the functor reads it on the device)")
+        self.fn_ptr, self.ndim, self.user = fn_ptr, int(ndim), user
+
+    def user_address(self):
+        """-> the device address handed to the functor (None: a null pointer)"""
+        u = self.user
+        if u is None:
+            return None
+        if hasattr(u, "data_ptr"):
+            return int(u.data_ptr())
+        return u.value if isinstance(u, ctypes.c_void_p) else int(u)
+
+    def bind(self, ens):
+        if ens.ndim != self.ndim:
+            raise ValueError("the DeviceFused target was compiled for ndim %d; the sampler has ndim %d" % (self.ndim, ens.ndim))
+        if getattr(ens, "_cb_owner", None) is not self or ens._target_kind != self.kind:
+            ens.set_target_fused(self.fn_ptr, self.user_address())
+            ens._cb_owner = self
+
+    def __call__(self, x):
+        raise TypeError("DeviceFused is evaluated inside EnsembleSampler's kernels on the device (sampler.compute_log_prob(x) evaluates rows)")
 
 
 def _check_nblobs(who, nblobs):
@@ -343,6 +391,46 @@ def _compile_cached(what, header, source, tail, key_parts, name, flags, cache_di
             raise RuntimeError("%s: hipcc failed (%s):\n%s" % (what, src, (r.stderr or r.stdout)[-4000:]))
         os.replace(tmp, so)
     return so
+
+
+class DeviceFusedLibrary(object):
+    """What :func:`compile_fused_ensemble` built: ``path`` of the shared library, ``lib`` (its ``ctypes.CDLL``: the user's own
+    ``extern "C"`` setup functions of ``source`` are there), ``name`` of the launcher, ``ndim``, and :meth:`target`."""
+
+    def __init__(self, path, name, ndim):
+        self.path, self.name, self.ndim = path, name, int(ndim)
+        _lib.load()                       # one HIP runtime per process: the library's (torch's) first
+        self.lib = ctypes.CDLL(path)
+        self.launcher = getattr(self.lib, name)
+
+    def target(self, user=None):
+        """-> :class:`DeviceFused` of the compiled functor with the device pointer ``user``"""
+        t = DeviceFused(self.launcher, self.ndim, user)
+        t._library = self                 # the launcher's code lives as long as the target
+        return t
+
+
+def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir=None):
+    """Compile the user's model into the single sampler's half-step kernel -> :class:`DeviceFusedLibrary`.
+
+    ``source``: HIP C++ that defines the functor type ``functor`` -- ``__device__ double operator()(const double* x, int ndim, int
+    member, const void* user) const``, the contract of :func:`compile_fused` (``member`` is 0 here) -- and whatever ``extern "C"``
+    helpers the user wants in the same library.  The translation unit is ``#include <emx_fused_ensemble.hpp>``, ``source`` and
+    ``EMX_FUSED_ENSEMBLE_TARGET(name, functor, ndim)``, compiled and cached as :func:`compile_fused` does (the same flags; the key is
+    the hash of source, functor, ndim, name, flags and every header of the library, ``emx_fused_ensemble.hpp`` among them); a
+    compiler failure raises ``RuntimeError`` with the compiler's last lines."""
+    ndim = int(ndim)
+    if ndim < 1 or ndim > 256:
+        raise ValueError("compile_fused_ensemble: 1 <= ndim <= 256; got %d" % ndim)
+    for what, ident in (("functor", functor), ("name", name)):
+        if (ident is not None or what == "functor") and not (isinstance(ident, str) and re.match(r"^[A-Za-z_][A-Za-z0-9_:]*$", ident)):
+            raise ValueError("compile_fused_ensemble: %s must be a C++ identifier; got %r" % (what, ident))
+    name = name or "emx_fused_ensemble_%s_%d" % (functor.replace(":", "_"), ndim)
+    flags = [str(f) for f in flags]
+    tail = "EMX_FUSED_ENSEMBLE_TARGET(%s, %s, %d)" % (name, functor, ndim)
+    so = _compile_cached("compile_fused_ensemble", "emx_fused_ensemble.hpp", source, tail, ("ensemble", source, functor, ndim, name), name,
+                         flags, cache_dir)
+    return DeviceFusedLibrary(so, name, ndim)
 
 
 class PTFusedLibrary(object):

@@ -33,8 +33,10 @@ enum emx_target_kind {
     EMX_TARGET_DEVICE_CALLBACK = 6,/* the caller's batched log-prob on device buffers (emx_set_target_callback) */
     EMX_TARGET_FUSED_USER = 8,     /* batches only: the caller's per-row device function compiled into the one-workgroup kernel
                                       (emx_set_batch_target_fused; 7 is taken inside the kernels) */
-    EMX_TARGET_FUSED_PT = 9        /* tempered batches only: the caller's likelihood (and prior) compiled into the tempered
+    EMX_TARGET_FUSED_PT = 9,       /* tempered batches only: the caller's likelihood (and prior) compiled into the tempered
                                       one-workgroup kernel k_pt_run (emx_pt_set_target_fused) */
+    EMX_TARGET_FUSED_ENSEMBLE = 10 /* a single ensemble: the caller's per-row device function compiled into the half-step kernel
+                                      k_halfstep_user (emx_set_target_fused) */
 };
 
 enum emx_move_kind {
@@ -178,6 +180,36 @@ int emx_snapshot_free(emx_ctx* ctx, int32_t slot);
 typedef int (*emx_device_log_prob_fn)(void* user, const double* coords_dev, int64_t n, int32_t ndim, double* log_prob_dev,
                                       void* hip_stream);
 int emx_set_target_callback(emx_ctx* ctx, emx_device_log_prob_fn fn, void* user);
+/* Fused user targets of a single ensemble (EMX_TARGET_FUSED_ENSEMBLE; emcee_amd.targets.DeviceFused / compile_fused_ensemble):
+ * the caller's per-row __device__ log-probability compiled INTO the half-step kernel, so that a half-step is ONE launch --
+ * proposal, the caller's function on the row staged in LDS, decision, commit -- where the callback target above takes three and
+ * sends the proposal block through memory.  The caller's translation unit includes emcee_amd/csrc/emx_fused_ensemble.hpp and emits
+ * a launcher with EMX_FUSED_ENSEMBLE_TARGET(name, Functor, ndim), 1 <= ndim <= 256; the library fills the descriptor below and calls
+ * the launcher where it launches its own element-wise half-step, and for every evaluation of rows (the initial log-probs, the
+ * log-prob pass of WalkMove / KDEMove).  `args` is the library's internal HalfStepArgs: `abi` (EMX_FUSED_ENSEMBLE_ABI of that
+ * header, bumped with any change of the struct or of the launch rules) and `args_bytes` (its sizeof) are checked by the launcher
+ * against the values it was compiled with, so a launcher built against another version of the header -- or a launcher of the batch
+ * targets, whose descriptors start with the same two fields and carry other constants -- is refused, never run.  grid == 0 is a
+ * probe: check abi, args_bytes, ndim and move, launch nothing.  Otherwise `grid` is the most workgroups the launch may use,
+ * `threads` and `lds_bytes` the workgroup size and the dynamic LDS the header's rules give for ndim (the launcher refuses others).
+ * Returns 0, or non-zero and nothing launched (1: another version of the header, 2: another ndim, 3: a move or launch shape that
+ * was not compiled in, 5: args that carry an exchange, a graph descriptor or a device-side slot count, 100 + a hipError_t: the
+ * launch failed).  emx_set_target_fused probes once, so a mismatch surfaces at bind time (-8 and "built against another version of
+ * emx_fused_ensemble.hpp").  `user_dev`: a device pointer handed to the functor with every row; the caller keeps it alive.
+ * Such a context always runs one launch per half-step (never the one-workgroup kernel, the persistent kernels or a step graph),
+ * in either rng mode; results are bit for bit those of emx_set_target_callback with the same function.  One replica only:
+ * emx_set_shard / emx_comm_init on such a context, and this call on a sharded one, are refused. */
+typedef struct emx_fused_ensemble_launch {
+    uint32_t abi;            /* EMX_FUSED_ENSEMBLE_ABI the library was built with */
+    uint32_t args_bytes;     /* sizeof(HalfStepArgs) of the library */
+    int32_t ndim, move, grid, threads;      /* move: EMX_MOVE_STRETCH / DE / SNOOKER / GAUSS, or 4: evaluate rows */
+    uint64_t lds_bytes;
+    void* hip_stream;
+    const void* args;        /* HalfStepArgs */
+    const void* user;        /* user_dev */
+} emx_fused_ensemble_launch;
+typedef int (*emx_fused_ensemble_fn)(const emx_fused_ensemble_launch*);     /* 0, or non-zero and nothing launched */
+int emx_set_target_fused(emx_ctx* ctx, emx_fused_ensemble_fn launcher, const void* user);
 
 /* ---- target: the batched log-prob (ensemble.py:458-553, vectorised) -------------------- */
 /* p0/p1: DIAG (mu, ivar); DENSE (mu, icov[D*D], symmetric positive definite: factored once as
