@@ -54,8 +54,16 @@ class FusedEnsembleLaunch(C.Structure):
                 ("user", C.c_void_p)]
 
 
+class FusedEnsembleBlobsLaunch(C.Structure):
+    """emx_fused_ensemble_blobs_launch of include/emx.h: FusedEnsembleLaunch's fields, then the blob count and pointers"""
+    _fields_ = FusedEnsembleLaunch._fields_ + [("nblobs", C.c_int32), ("reserved", C.c_int32), ("blobs_cur", C.c_void_p),
+                                               ("blobs_row", C.c_void_p)]
+
+
 # emx_fused_ensemble_fn: (const emx_fused_ensemble_launch*) -> int
 FUSED_ENSEMBLE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
+# emx_fused_ensemble_blobs_fn: (const emx_fused_ensemble_blobs_launch*) -> int
+FUSED_ENSEMBLE_BLOBS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 # emx_fused_batch_fn: (const emx_fused_launch*) -> int
 FUSED_BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 # emx_pt_fused_fn: (emx_pt_fused_launch*) -> int
@@ -91,6 +99,11 @@ SIGNATURES = {
     "emx_set_target": (C.c_int, [_P, C.c_int32, _P, _P, C.c_double]),
     "emx_set_target_callback": (C.c_int, [_P, DEVICE_LOG_PROB_FN, _P]),
     "emx_set_target_fused": (C.c_int, [_P, FUSED_ENSEMBLE_FN, _P]),
+    "emx_set_target_fused_blobs": (C.c_int, [_P, FUSED_ENSEMBLE_BLOBS_FN, _P, C.c_int32]),
+    "emx_get_blobs": (C.c_int, [_P, _P, C.POINTER(C.c_int32)]),
+    "emx_set_blobs": (C.c_int, [_P, _dp]),
+    "emx_eval_log_prob_blobs": (C.c_int, [_P, _dp, C.c_int64, _dp, _dp]),
+    "emx_snapshot_read_blobs": (C.c_int, [_P, C.c_int32, _dp]),
     "emx_eval_state_log_prob": (C.c_int, [_P]),
     "emx_eval_log_prob": (C.c_int, [_P, _dp, C.c_int64, _dp]),
     "emx_set_moves": (C.c_int, [_P, C.c_int32, C.POINTER(MoveDesc), _dp]),

@@ -31,7 +31,7 @@ class Backend(object):
         self._accepted = np.zeros(self.nwalkers, dtype=self.dtype)
         self._chain = np.empty((0, self.nwalkers, self.ndim), dtype=self.dtype)
         self._log_prob = np.empty((0, self.nwalkers), dtype=self.dtype)
-        self.blobs = None
+        self._blobs = None
         self.random_state = None
         self.initialized = True
         if self._dev is not None:
@@ -55,6 +55,8 @@ class Backend(object):
         it = self.iteration
         self._chain = self._dev.chain_read(0, 0, it)
         self._log_prob = self._dev.chain_read(1, 0, it)
+        if self._dev_nblobs():
+            self._blobs = self._dev.chain_read(2, 0, it)
         self._accepted = self._dev.accepted_counts().astype(self.dtype)
         self._iteration = it
         self._dev = None
@@ -100,9 +102,23 @@ class Backend(object):
     def log_prob(self, v):
         self._log_prob = v
 
+    def _dev_nblobs(self):
+        """blobs a sample that the attached device keeps next to its chain (a DeviceFused target with nblobs); 0: none there"""
+        return self._dev.nblobs() if self._dev is not None else 0
+
+    @property
+    def blobs(self):
+        if self._dev_nblobs():
+            return self._dev.chain_read(2, 0, self.iteration)
+        return self._blobs
+
+    @blobs.setter
+    def blobs(self, v):
+        self._blobs = v
+
     def has_blobs(self):
         """Whether blob storage has been set up (the log-prob function returns metadata)."""
-        return self.blobs is not None
+        return self._blobs is not None or self._dev_nblobs() > 0
 
     def get_value(self, name, flat=False, thin=1, discard=0):
         it = self.iteration
@@ -111,8 +127,8 @@ class Backend(object):
         if name == "blobs" and not self.has_blobs():
             return None
         start = discard + thin - 1                     # reference backend.py:53
-        if self._dev is not None and name in ("chain", "log_prob"):
-            v = self._dev.chain_read(0 if name == "chain" else 1, min(start, it), it, thin)
+        if self._dev is not None and (name in ("chain", "log_prob") or (name == "blobs" and self._dev_nblobs())):
+            v = self._dev.chain_read({"chain": 0, "log_prob": 1, "blobs": 2}[name], min(start, it), it, thin)
         else:
             v = getattr(self, name)[start:it:thin]
         if flat:
@@ -184,6 +200,8 @@ class Backend(object):
 
     # ---- growth / saving ----
     def _check_blobs(self, blobs):
+        if self._dev_nblobs():
+            return                  # the device appends its own blob plane: nothing of the host's to keep consistent
         has_blobs = self.has_blobs()
         if has_blobs and blobs is None:
             raise ValueError("inconsistent use of blobs")
@@ -197,7 +215,7 @@ class Backend(object):
         it = self.iteration
         if self._dev is not None:
             self._dev.chain_config(it + ngrow)
-            have = 0 if self.blobs is None else len(self.blobs)
+            have = 0 if self._blobs is None else len(self._blobs)
         else:
             i = ngrow - (len(self._chain) - it)
             a = np.empty((i, self.nwalkers, self.ndim), dtype=self.dtype)
@@ -206,10 +224,10 @@ class Backend(object):
             self._log_prob = np.concatenate((self._log_prob, a), axis=0)
             have = len(self._chain) - i
         if blobs is not None:
-            i = it + ngrow - (0 if self.blobs is None else len(self.blobs))
+            i = it + ngrow - (0 if self._blobs is None else len(self._blobs))
             dt = np.dtype((blobs.dtype, blobs.shape[1:]))
             a = np.empty((max(i, 0), self.nwalkers), dtype=dt)
-            self.blobs = a if self.blobs is None else np.concatenate((self.blobs, a), axis=0)
+            self._blobs = a if self._blobs is None else np.concatenate((self._blobs, a), axis=0)
         del have
 
     def _check(self, state, accepted):
@@ -237,7 +255,7 @@ class Backend(object):
         self._chain[self._iteration, :, :] = state.coords
         self._log_prob[self._iteration, :] = state.log_prob
         if state.blobs is not None:
-            self.blobs[self._iteration, :] = state.blobs
+            self._blobs[self._iteration, :] = state.blobs
         self._accepted = self._accepted + accepted
         self.random_state = state.random_state
         self._iteration += 1
@@ -256,7 +274,7 @@ class Backend(object):
     def _device_step_saved(self, state_blobs, random_state):
         """Book-keeping after the kernel appended a step to the device chain."""
         if state_blobs is not None:
-            self.blobs[self.iteration - 1, :] = state_blobs
+            self._blobs[self.iteration - 1, :] = state_blobs
         self.random_state = random_state
 
     def __getstate__(self):
@@ -267,10 +285,18 @@ class Backend(object):
             it = self.iteration
             d["_chain"] = self._dev.chain_read(0, 0, it)
             d["_log_prob"] = self._dev.chain_read(1, 0, it)
+            if self._dev_nblobs():
+                d["_blobs"] = self._dev.chain_read(2, 0, it)
             d["_accepted"] = self._dev.accepted_counts().astype(self.dtype)
             d["_iteration"] = it
             d["_dev"] = None
         return d
+
+    def __setstate__(self, d):
+        d = dict(d)
+        if "blobs" in d:            # pickled before `blobs` became a property over `_blobs`
+            d["_blobs"] = d.pop("blobs")
+        self.__dict__.update(d)
 
     def __enter__(self):
         return self

@@ -294,6 +294,14 @@ struct emx_ctx {
     emx_device_log_prob_fn cb_fn = nullptr;   // EMX_TARGET_DEVICE_CALLBACK: the caller's batched log-prob, run on device buffers
     emx_fused_ensemble_fn fused_fn = nullptr; // EMX_TARGET_FUSED_ENSEMBLE: the launcher of the caller's translation unit (k_halfstep_user) ...
     const void* fused_user = nullptr;         // ... and the device pointer its functor receives
+    // blobs of a fused user target (emx_set_target_fused_blobs; k_halfstep_user_blobs): nblobs doubles a sample
+    emx_fused_ensemble_blobs_fn fused_blobs_fn = nullptr;
+    int nblobs = 0;
+    double* blobs = nullptr;                  // (N, nblobs): the walkers' current blobs, committed where lp is
+    double* evalblobs = nullptr;              // (N, nblobs): the rows of emx_eval_log_prob_blobs
+    double* blob_plane = nullptr;             // (cap, N, nblobs): next to chain / chain_lp
+    double* snap_blobs[NSNAPSHOT] = {};       // a snapshot slot's blobs ...
+    int snap_nb[NSNAPSHOT] = {};              // ... and how many a sample it holds
     void* cb_user = nullptr;
     int target = EMX_TARGET_HOST;
     double *tp0 = nullptr, *tp1 = nullptr;
@@ -741,6 +749,12 @@ int prefetch_depth_host(int G, int V, int CH, int move, bool dense) {
 // (36 blocks = 72 KB + 4 waves x 16.6 KB; round 3 -- 112 with 8- and 4-wave groups before)
 inline bool dense_is_wide(const emx_ctx* c) { return c->Dp > DENSE_FUSED_MAX_DP || c->tune_dense_wide; }
 
+// k_wide_commit, which ends a WalkMove / KDEMove half-step, commits no blobs
+static std::string blobs_walk_kde_refusal(int kind) {
+    return std::string(kind == EMX_MOVE_WALK ? "WalkMove" : "KDEMove") +
+           ": not available with a fused user target that carries blobs (its evaluate-then-commit path has no blob commit)";
+}
+
 // launch one fused (or propose-only) half-step over the slots [t_lo, t_hi) of `split`
 int launch_split(emx_ctx* c, int move, int target, int S, int split, int pos0, int ns, int t_lo, int t_hi,
                  const emx_move_desc* mv, const emx_ctx::PlanSlot* ps, const int32_t* order,
@@ -751,6 +765,10 @@ int launch_split(emx_ctx* c, int move, int target, int S, int split, int pos0, i
     if (is_walk_kde(move)) {
         // WalkMove / KDEMove (emx_walkkde.hip): their proposal kernels write qout / fout, then -- a device target -- the three-pass
         // path's evaluation of the proposal block and k_wide_commit; a host target stops at the proposals (emx_propose / emx_accept)
+        if (target == EMX_TARGET_FUSED_ENSEMBLE && c->nblobs > 0) {
+            c->err = blobs_walk_kde_refusal(move);
+            return -1;
+        }
         if (!c->cur.active || !c->cur.native || !ps || !mv) {
             c->err = "WalkMove / KDEMove steps run on the device in the Philox rng mode only";
             return -1;
@@ -826,7 +844,7 @@ int launch_split(emx_ctx* c, int move, int target, int S, int split, int pos0, i
     const bool fused = target == EMX_TARGET_FUSED_ENSEMBLE;
     if (fused) {
         // the caller's function compiled into the half-step (emx_fused_ensemble.hpp): one launch, one replica, no replay
-        if (!c->fused_fn) {
+        if (c->nblobs > 0 ? !c->fused_blobs_fn : !c->fused_fn) {
             c->err = "fused user target without a launcher (emx_set_target_fused)";
             return -1;
         }
@@ -1099,23 +1117,50 @@ int launch_split(emx_ctx* c, int move, int target, int S, int split, int pos0, i
     const bool slab = dense && c->tune_slab && c->Dp >= (c->tune_slab == 2 ? 80 : 112) && sh.G == 16 && sh.V == 2 && sh.CH == 4 &&
                       (move == MOVE_STRETCH || move == MOVE_DE) && lean_kind(a, 16, 2, 4, move, true) == 1;
     if (fused) {
-        emx_fused_ensemble_launch fl{};
-        fl.abi = EMX_FUSED_ENSEMBLE_ABI;
-        fl.args_bytes = (uint32_t)sizeof(HalfStepArgs);
-        fl.ndim = D;
-        fl.move = move;
-        fl.grid = (int32_t)std::min<int64_t>((nown + fused_ens_tile_rule(D) - 1) / fused_ens_tile_rule(D), (int64_t)c->num_cu * 64);
-        fl.threads = FUSED_ENS_THREADS;
-        fl.lds_bytes = fused_ens_lds_bytes(D);
-        fl.hip_stream = (void*)c->stream;
-        fl.args = &a;
-        fl.user = c->fused_user;
-        const int rcf = c->fused_fn(&fl);
+        int rcf;
+        if (c->nblobs > 0) {
+            // the blobs go where lp and chain_lp go: the walkers' array (an evaluation of other rows: the evaluation buffer), and the
+            // plane's row of the stored step chain_lp points into
+            const int K = c->nblobs, tile = fused_ens_blobs_tile_rule(D, K);
+            emx_fused_ensemble_blobs_launch fl{};
+            fl.abi = EMX_FUSED_ENSEMBLE_BLOBS_ABI;
+            fl.args_bytes = (uint32_t)sizeof(HalfStepArgs);
+            fl.ndim = D;
+            fl.move = move;
+            fl.grid = (int32_t)std::min<int64_t>((nown + tile - 1) / tile, (int64_t)c->num_cu * 64);
+            fl.threads = FUSED_ENS_THREADS;
+            fl.lds_bytes = fused_ens_blobs_lds_bytes(D, K);
+            fl.hip_stream = (void*)c->stream;
+            fl.args = &a;
+            fl.user = c->fused_user;
+            fl.nblobs = K;
+            fl.blobs_cur = lp == c->lp ? c->blobs : c->evalblobs;
+            fl.blobs_row = chain_lp ? c->blob_plane + (size_t)((chain_lp - c->chain_lp) / c->N) * c->N * K : nullptr;
+            if (!c->fused_blobs_fn || !fl.blobs_cur || (chain_lp && !c->blob_plane) || (lp != c->lp && lp != c->evallp)) {
+                c->err = "fused user target with blobs: no launcher or no blob storage for this launch";
+                return -1;
+            }
+            rcf = c->fused_blobs_fn(&fl);
+        } else {
+            emx_fused_ensemble_launch fl{};
+            fl.abi = EMX_FUSED_ENSEMBLE_ABI;
+            fl.args_bytes = (uint32_t)sizeof(HalfStepArgs);
+            fl.ndim = D;
+            fl.move = move;
+            fl.grid = (int32_t)std::min<int64_t>((nown + fused_ens_tile_rule(D) - 1) / fused_ens_tile_rule(D), (int64_t)c->num_cu * 64);
+            fl.threads = FUSED_ENS_THREADS;
+            fl.lds_bytes = fused_ens_lds_bytes(D);
+            fl.hip_stream = (void*)c->stream;
+            fl.args = &a;
+            fl.user = c->fused_user;
+            rcf = c->fused_fn(&fl);
+        }
         if (rcf) {
             char b[256];
             snprintf(b, sizeof(b), "fused user target: the launcher refused the half-step (move %d, ndim %d): %s", move, D,
                      rcf == 1 ? "built against another version of emx_fused_ensemble.hpp" : rcf == 2 ? "compiled for another ndim" :
                      rcf == 3 ? "move or launch shape not compiled in" : rcf == 5 ? "the launch carries an exchange" :
+                     rcf == 4 ? "compiled for another number of blobs" :
                      rcf >= 100 ? hipGetErrorString((hipError_t)(rcf - 100)) : "unknown answer");
             c->err = b;
             return rcf >= 100 ? -2 : -8;
@@ -1343,6 +1388,10 @@ int emx_destroy(emx_ctx* c) {
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (double* s : c->snap)
+        if (s) hipFree(s);
+    for (double* s : c->snap_blobs)
+        if (s) hipFree(s);
+    for (double* s : {c->blobs, c->evalblobs, c->blob_plane})
         if (s) hipFree(s);
 
     for (auto& s : c->ring) {
@@ -1793,6 +1842,12 @@ int emx_set_target_callback(emx_ctx* c, emx_device_log_prob_fn fn, void* user) {
     return 0;
 }
 
+static void blob_storage_free(emx_ctx* c) {
+    for (double** p : {&c->blobs, &c->evalblobs, &c->blob_plane})
+        if (*p) hipFree(*p), *p = nullptr;
+    c->nblobs = 0;
+}
+
 // The caller's per-row device function compiled into the half-step (include/emx.h; emx_fused_ensemble.hpp): launch_split hands the
 // element-wise half-step, and every evaluation of rows, to the caller's launcher.
 int emx_set_target_fused(emx_ctx* c, emx_fused_ensemble_fn launcher, const void* user) {
@@ -1814,17 +1869,101 @@ int emx_set_target_fused(emx_ctx* c, emx_fused_ensemble_fn launcher, const void*
     if (rcp)
         FAIL(c, -8, "emx_set_target_fused: the launcher was built against another version of emx_fused_ensemble.hpp, or is not an "
                     "EMX_FUSED_ENSEMBLE_TARGET launcher (it answered %d); rebuild it against this library's headers", rcp);
+    NEED(c, c->nblobs == 0 || c->stored == 0, "emx_set_target_fused: the context holds %lld stored steps with %d blobs a sample; "
+         "reset the chain before the blob count changes", (long long)c->stored, c->nblobs);
     HIPOK(c, hipSetDevice(c->device));
     PIPE_STOP(c);
     drop_prepared(c);          // plans made ahead were shaped (lean or full) for the previous target
     HIPOK(c, hipStreamSynchronize(c->stream));
+    blob_storage_free(c);
     c->fused_fn = launcher;
+    c->fused_blobs_fn = nullptr;
     c->fused_user = user;
     c->Dp = 0;
     graph_invalidate(c);
     c->graph_warm = false;
     c->target = EMX_TARGET_FUSED_ENSEMBLE;
     c->tscale = 1.0;
+    return 0;
+}
+
+// The same with nblobs derived quantities a sample (include/emx.h): the walkers' blobs, an evaluation buffer and -- sized like the
+// chain -- the blob plane are the context's; the launcher is probed for the count.
+int emx_set_target_fused_blobs(emx_ctx* c, emx_fused_ensemble_blobs_fn launcher, const void* user, int32_t nblobs) {
+    NEED(c, nblobs >= 0 && nblobs <= FUSED_ENS_MAX_BLOBS, "emx_set_target_fused_blobs: 0 <= nblobs <= %d; got %d", FUSED_ENS_MAX_BLOBS, nblobs);
+    if (nblobs == 0) return emx_set_target_fused(c, reinterpret_cast<emx_fused_ensemble_fn>(launcher), user);
+    { const int rcs_ = persist_settle(c); if (rcs_) return rcs_; }
+    NEED(c, launcher != nullptr, "emx_set_target_fused_blobs: no launcher");
+    NEED(c, c->D >= 1 && c->D <= FUSED_ENS_MAX_NDIM, "emx_set_target_fused_blobs: a fused user target has 1 <= ndim <= %d; the ensemble has ndim %d",
+         FUSED_ENS_MAX_NDIM, c->D);
+    NEED(c, c->world == 1 && !c->comm && !c->sendbuf && !c->peers_ready,
+         "emx_set_target_fused_blobs: a fused user target runs on one replica (no sharding, no exchange)");
+    NEED(c, c->nblobs == nblobs || c->stored == 0, "emx_set_target_fused_blobs: the context holds %lld stored steps with %d blobs a "
+         "sample; reset the chain before the blob count changes to %d", (long long)c->stored, c->nblobs, nblobs);
+    for (const auto& mv : c->moves)
+        if (is_walk_kde(mv.kind)) FAIL(c, -1, "%s", blobs_walk_kde_refusal(mv.kind).c_str());
+    emx_fused_ensemble_blobs_launch fl{};          // the probe: nothing is launched
+    fl.abi = EMX_FUSED_ENSEMBLE_BLOBS_ABI;
+    fl.args_bytes = (uint32_t)sizeof(HalfStepArgs);
+    fl.ndim = c->D;
+    fl.move = MOVE_EVAL;
+    fl.nblobs = nblobs;
+    const int rcp = launcher(&fl);
+    if (rcp == 2) FAIL(c, -1, "emx_set_target_fused_blobs: the fused user target was compiled for another ndim; the ensemble has ndim %d", c->D);
+    if (rcp == 4) FAIL(c, -1, "emx_set_target_fused_blobs: the fused user target was compiled for another number of blobs; %d were asked for", nblobs);
+    if (rcp)
+        FAIL(c, -8, "emx_set_target_fused_blobs: the launcher was built against another version of emx_fused_ensemble.hpp, or is not an "
+                    "EMX_FUSED_ENSEMBLE_TARGET_BLOBS launcher (it answered %d); rebuild it against this library's headers", rcp);
+    HIPOK(c, hipSetDevice(c->device));
+    PIPE_STOP(c);
+    drop_prepared(c);
+    HIPOK(c, hipStreamSynchronize(c->stream));
+    if (c->nblobs != nblobs) {
+        blob_storage_free(c);
+        const size_t nb = (size_t)c->N * nblobs * 8;
+        double *cur = nullptr, *ev = nullptr, *plane = nullptr;
+        hipError_t e = hipMalloc((void**)&cur, nb);
+        if (e == hipSuccess) e = hipMalloc((void**)&ev, nb);
+        if (e == hipSuccess && c->cap > 0) e = hipMalloc((void**)&plane, nb * c->cap);
+        if (e == hipSuccess) e = hipMemsetAsync(cur, 0, nb, c->stream);
+        if (e != hipSuccess) {
+            for (double* p : {cur, ev, plane})
+                if (p) hipFree(p);
+            FAIL(c, -4, "emx_set_target_fused_blobs: blob storage allocation failed: %s", hipGetErrorString(e));
+        }
+        c->blobs = cur;
+        c->evalblobs = ev;
+        c->blob_plane = plane;
+        c->nblobs = nblobs;
+    }
+    c->fused_blobs_fn = launcher;
+    c->fused_fn = nullptr;
+    c->fused_user = user;
+    c->Dp = 0;
+    graph_invalidate(c);
+    c->graph_warm = false;
+    c->target = EMX_TARGET_FUSED_ENSEMBLE;
+    c->tscale = 1.0;
+    return 0;
+}
+
+int emx_get_blobs(emx_ctx* c, double* out, int32_t* nblobs_out) {
+    if (nblobs_out) *nblobs_out = c->nblobs;
+    if (!out) return 0;
+    { const int rcs_ = persist_settle(c); if (rcs_) return rcs_; }
+    NEED(c, c->nblobs > 0, "emx_get_blobs: the context's target carries no blobs");
+    HIPOK(c, hipSetDevice(c->device));
+    HIPOK(c, hipMemcpyAsync(out, c->blobs, (size_t)c->N * c->nblobs * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int emx_set_blobs(emx_ctx* c, const double* in) {
+    { const int rcs_ = persist_settle(c); if (rcs_) return rcs_; }
+    NEED(c, c->nblobs > 0 && in, "emx_set_blobs: the context's target carries no blobs");
+    HIPOK(c, hipSetDevice(c->device));
+    HIPOK(c, hipMemcpyAsync(c->blobs, in, (size_t)c->N * c->nblobs * 8, hipMemcpyHostToDevice, c->stream));
+    HIPOK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -1840,6 +1979,26 @@ int emx_snapshot_save(emx_ctx* c, int32_t slot) {
     if (!c->snap[slot]) HIPOK(c, hipMalloc((void**)&c->snap[slot], (nx + nl) * 8));
     HIPOK(c, hipMemcpyAsync(c->snap[slot], c->X, nx * 8, hipMemcpyDeviceToDevice, c->stream));
     HIPOK(c, hipMemcpyAsync(c->snap[slot] + nx, c->lp, nl * 8, hipMemcpyDeviceToDevice, c->stream));
+    if (c->nblobs > 0) {
+        if (c->snap_blobs[slot] && c->snap_nb[slot] != c->nblobs) {
+            HIPOK(c, hipStreamSynchronize(c->stream));
+            HIPOK(c, hipFree(c->snap_blobs[slot]));
+            c->snap_blobs[slot] = nullptr;
+        }
+        if (!c->snap_blobs[slot]) HIPOK(c, hipMalloc((void**)&c->snap_blobs[slot], nl * c->nblobs * 8));
+        HIPOK(c, hipMemcpyAsync(c->snap_blobs[slot], c->blobs, nl * c->nblobs * 8, hipMemcpyDeviceToDevice, c->stream));
+    }
+    c->snap_nb[slot] = c->nblobs;
+    return 0;
+}
+
+int emx_snapshot_read_blobs(emx_ctx* c, int32_t slot, double* blobs) {
+    { const int rcs_ = persist_settle(c); if (rcs_) return rcs_; }
+    HIPOK(c, hipSetDevice(c->device));
+    NEED(c, slot >= 0 && slot < emx_ctx::NSNAPSHOT && c->snap[slot], "no snapshot in slot %d", slot);
+    NEED(c, c->snap_nb[slot] > 0 && c->snap_blobs[slot] && blobs, "the snapshot in slot %d carries no blobs", slot);
+    HIPOK(c, hipMemcpyAsync(blobs, c->snap_blobs[slot], (size_t)c->N * c->snap_nb[slot] * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -1864,6 +2023,10 @@ int emx_snapshot_restore(emx_ctx* c, int32_t slot) {
     const size_t nx = (size_t)c->N * c->D;
     HIPOK(c, hipMemcpyAsync(c->X, c->snap[slot], nx * 8, hipMemcpyDeviceToDevice, c->stream));
     HIPOK(c, hipMemcpyAsync(c->lp, c->snap[slot] + nx, (size_t)c->N * 8, hipMemcpyDeviceToDevice, c->stream));
+    if (c->nblobs > 0) {
+        NEED(c, c->snap_nb[slot] == c->nblobs, "the snapshot in slot %d holds %d blobs a sample; the context has %d", slot, c->snap_nb[slot], c->nblobs);
+        HIPOK(c, hipMemcpyAsync(c->blobs, c->snap_blobs[slot], (size_t)c->N * c->nblobs * 8, hipMemcpyDeviceToDevice, c->stream));
+    }
     return 0;
 }
 
@@ -1965,21 +2128,28 @@ int emx_eval_state_log_prob(emx_ctx* c) {
     return eval_rows(c, c->X, c->lp, c->N);
 }
 
-int emx_eval_log_prob(emx_ctx* c, const double* coords, int64_t n, double* out) {
+int emx_eval_log_prob_blobs(emx_ctx* c, const double* coords, int64_t n, double* out, double* blobs_out) {
     HIPOK(c, hipSetDevice(c->device));
     NEED(c, n >= 0 && n <= c->N, "emx_eval_log_prob: n must be <= nwalkers");
+    NEED(c, !blobs_out || (c->nblobs > 0 && c->target == EMX_TARGET_FUSED_ENSEMBLE), "emx_eval_log_prob_blobs: the context's target carries no blobs");
     if (n == 0) return 0;
     HIPOK(c, hipMemcpyAsync(c->evalX, coords, (size_t)n * c->D * 8, hipMemcpyHostToDevice, c->stream));
     int rc = eval_rows(c, c->evalX, c->evallp, n);
     if (rc) return rc;
     HIPOK(c, hipMemcpyAsync(out, c->evallp, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (blobs_out) HIPOK(c, hipMemcpyAsync(blobs_out, c->evalblobs, (size_t)n * c->nblobs * 8, hipMemcpyDeviceToHost, c->stream));
     HIPOK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
+int emx_eval_log_prob(emx_ctx* c, const double* coords, int64_t n, double* out) { return emx_eval_log_prob_blobs(c, coords, n, out, nullptr); }
+
 int emx_set_moves(emx_ctx* c, int32_t nmoves, const emx_move_desc* moves, const double* cdf) {
     { const int rcs_ = persist_settle(c); if (rcs_) return rcs_; }
     NEED(c, nmoves >= 1, "need at least one move");
+    if (c->target == EMX_TARGET_FUSED_ENSEMBLE && c->nblobs > 0)
+        for (int i = 0; i < nmoves; ++i)
+            if (is_walk_kde(moves[i].kind)) FAIL(c, -1, "%s", blobs_walk_kde_refusal(moves[i].kind).c_str());
     PIPE_STOP(c);
     for (int i = 0; i < nmoves; ++i) {
         NEED(c, (moves[i].kind >= 0 && moves[i].kind <= EMX_MOVE_GAUSS) || is_walk_kde(moves[i].kind), "unknown move kind");
@@ -2095,8 +2265,8 @@ int emx_chain_config(emx_ctx* c, int64_t cap) {
     HIPOK(c, hipSetDevice(c->device));
     NEED(c, cap >= c->stored, "capacity below the number of stored steps");
     if (cap == c->cap) return 0;
-    double *nc = nullptr, *nl = nullptr;
-    const size_t row = (size_t)c->N * c->D * 8, lrow = (size_t)c->N * 8;
+    double *nc = nullptr, *nl = nullptr, *nbp = nullptr;
+    const size_t row = (size_t)c->N * c->D * 8, lrow = (size_t)c->N * 8, brow = lrow * c->nblobs;
     if (cap > 0) {
         hipError_t e = hipMalloc((void**)&nc, row * cap);
         if (e != hipSuccess) FAIL(c, -4, "chain allocation of %.2f GB failed: %s", row * cap / 1e9, hipGetErrorString(e));
@@ -2105,17 +2275,28 @@ int emx_chain_config(emx_ctx* c, int64_t cap) {
             hipFree(nc);
             FAIL(c, -4, "chain log_prob allocation failed: %s", hipGetErrorString(e));
         }
+        if (brow) {
+            e = hipMalloc((void**)&nbp, brow * cap);
+            if (e != hipSuccess) {
+                hipFree(nc);
+                hipFree(nl);
+                FAIL(c, -4, "blob plane allocation of %.2f GB failed: %s", brow * cap / 1e9, hipGetErrorString(e));
+            }
+        }
         if (c->stored > 0) {
             HIPOK(c, hipMemcpyAsync(nc, c->chain, row * c->stored, hipMemcpyDeviceToDevice, c->stream));
             HIPOK(c, hipMemcpyAsync(nl, c->chain_lp, lrow * c->stored, hipMemcpyDeviceToDevice, c->stream));
+            if (brow) HIPOK(c, hipMemcpyAsync(nbp, c->blob_plane, brow * c->stored, hipMemcpyDeviceToDevice, c->stream));
         }
     }
     HIPOK(c, hipStreamSynchronize(c->stream));
     graph_invalidate(c);   // captured kernels hold the chain base pointers
     if (c->chain) hipFree(c->chain);
     if (c->chain_lp) hipFree(c->chain_lp);
+    if (c->blob_plane) hipFree(c->blob_plane);
     c->chain = nc;
     c->chain_lp = nl;
+    c->blob_plane = nbp;
     c->cap = cap;
     return 0;
 }
@@ -2146,8 +2327,10 @@ int emx_chain_read(emx_ctx* c, int32_t what, int64_t start, int64_t stop, int64_
     { const int rcs_ = persist_settle(c); if (rcs_) return rcs_; }
     HIPOK(c, hipSetDevice(c->device));
     NEED(c, stride >= 1 && start >= 0 && stop <= c->stored, "chain slice out of range");
-    const size_t row = what == 0 ? (size_t)c->N * c->D * 8 : (size_t)c->N * 8;
-    const char* base = what == 0 ? (const char*)c->chain : (const char*)c->chain_lp;
+    NEED(c, what >= 0 && what <= 2, "emx_chain_read: what is 0 (chain), 1 (log_prob) or 2 (blobs)");
+    NEED(c, what != 2 || (c->nblobs > 0 && (c->blob_plane || c->stored == 0)), "emx_chain_read: the context's target carries no blobs");
+    const size_t row = what == 0 ? (size_t)c->N * c->D * 8 : what == 2 ? (size_t)c->N * c->nblobs * 8 : (size_t)c->N * 8;
+    const char* base = what == 0 ? (const char*)c->chain : what == 2 ? (const char*)c->blob_plane : (const char*)c->chain_lp;
     char* o = (char*)out;
     if (stride == 1) {
         if (stop > start) {

@@ -21,6 +21,11 @@ _STATUS_PLAN_PRODUCER = 16
 _STATUS_SINGULAR_COV = 32
 
 
+def _blob_shape(b):
+    """(..., K) as the reference shapes blobs: a single blob a walker is not wrapped (ensemble.py:541-545)"""
+    return b[..., 0] if b.shape[-1] == 1 else b
+
+
 def _as_f64(a, shape=None):
     a = np.ascontiguousarray(a, dtype=np.float64)
     if shape is not None and a.shape != shape:
@@ -107,6 +112,33 @@ class DeviceEnsemble:
         x, lp = np.empty((self.nwalkers, self.ndim)), np.empty(self.nwalkers)
         self._ck(self.lib.emx_snapshot_read(self.ctx, slot, x.ctypes.data, lp.ctypes.data))
         return x, lp
+
+    def snapshot_read_blobs(self, slot, nblobs):
+        """-> the blobs the snapshot carries, shaped as :meth:`get_blobs` shapes them"""
+        out = np.empty((self.nwalkers, nblobs))
+        self._ck(self.lib.emx_snapshot_read_blobs(self.ctx, slot, out))
+        return _blob_shape(out)
+
+    # ---- blobs of a fused user target (emx_set_target_fused_blobs) ----
+    def nblobs(self):
+        """blobs a sample the context's target carries (0: none)"""
+        k = C.c_int32(0)
+        self._ck(self.lib.emx_get_blobs(self.ctx, None, C.byref(k)))
+        return k.value
+
+    def get_blobs(self):
+        """-> the walkers' current blobs ``(nwalkers, K)``; ``(nwalkers,)`` for K == 1 (a single blob is not wrapped)"""
+        out = np.empty((self.nwalkers, self.nblobs()))
+        self._ck(self.lib.emx_get_blobs(self.ctx, out.ctypes.data, None))
+        return _blob_shape(out)
+
+    def set_blobs(self, blobs):
+        self._touch()
+        k = self.nblobs()
+        b = np.asarray(blobs, dtype=np.float64)
+        if b.shape not in ((self.nwalkers, k),) + (((self.nwalkers,),) if k == 1 else ()):
+            raise ValueError("invalid blobs size; the target carries %d blobs a walker, expected %s" % (k, (self.nwalkers, k)))
+        self._ck(self.lib.emx_set_blobs(self.ctx, np.ascontiguousarray(b.reshape(self.nwalkers, k))))
 
     def snapshot_restore(self, slot):
         self._touch()
@@ -247,12 +279,19 @@ class DeviceEnsemble:
         self._ck(self.lib.emx_set_target_callback(self.ctx, fn, C.c_void_p(user_ptr) if not isinstance(user_ptr, C.c_void_p) else user_ptr))
         self._target_kind = _lib.TARGET_CALLBACK
 
-    def set_target_fused(self, fn_ptr, user_address=None):
+    def set_target_fused(self, fn_ptr, user_address=None, nblobs=0):
         """A launcher emitted by ``EMX_FUSED_ENSEMBLE_TARGET`` (``emx_fused_ensemble.hpp``) as the target: the user's per-row device
         function runs inside the half-step kernel.  ``fn_ptr``: a ctypes function or an address; ``user_address``: the device
-        address its functor receives (None: null).  The library probes the launcher and refuses another header version or ndim."""
+        address its functor receives (None: null).  The library probes the launcher and refuses another header version or ndim.
+        ``nblobs`` > 0: a launcher of ``EMX_FUSED_ENSEMBLE_TARGET_BLOBS`` with that many blobs a sample (another count is refused)."""
         if isinstance(fn_ptr, (int, np.integer)):
             fn_ptr = C.c_void_p(int(fn_ptr))
+        if nblobs:
+            fn = fn_ptr if isinstance(fn_ptr, _lib.FUSED_ENSEMBLE_BLOBS_FN) else C.cast(fn_ptr, _lib.FUSED_ENSEMBLE_BLOBS_FN)
+            self._touch_target = fn
+            self._ck(self.lib.emx_set_target_fused_blobs(self.ctx, fn, C.c_void_p(user_address), int(nblobs)))
+            self._target_kind = _lib.TARGET_FUSED_ENSEMBLE
+            return
         fn = fn_ptr if isinstance(fn_ptr, _lib.FUSED_ENSEMBLE_FN) else C.cast(fn_ptr, _lib.FUSED_ENSEMBLE_FN)
         self._touch_target = fn                                 # the library holds the pointer: keep the object alive
         self._ck(self.lib.emx_set_target_fused(self.ctx, fn, C.c_void_p(user_address)))
@@ -268,17 +307,24 @@ class DeviceEnsemble:
         self._touch()
         self._ck(self.lib.emx_eval_state_log_prob(self.ctx))
 
-    def eval_log_prob(self, coords):
+    def eval_log_prob(self, coords, nblobs=0):
+        """-> the rows' log-probs; with ``nblobs`` (the target's count) ``(log_prob, blobs)``, the blobs shaped as :meth:`get_blobs`'"""
         coords = _as_f64(coords)
         if coords.ndim != 2 or coords.shape[1] != self.ndim:
             raise ValueError("coords must be (n, ndim)")
         out = np.empty(coords.shape[0])
+        blobs = np.empty((coords.shape[0], nblobs)) if nblobs else None
         for lo in range(0, coords.shape[0], self.nwalkers):
             blk = np.ascontiguousarray(coords[lo:lo + self.nwalkers])
             o = np.empty(blk.shape[0])
-            self._ck(self.lib.emx_eval_log_prob(self.ctx, blk, blk.shape[0], o))
+            if nblobs:
+                ob = np.empty((blk.shape[0], nblobs))
+                self._ck(self.lib.emx_eval_log_prob_blobs(self.ctx, blk, blk.shape[0], o, ob))
+                blobs[lo:lo + blk.shape[0]] = ob
+            else:
+                self._ck(self.lib.emx_eval_log_prob(self.ctx, blk, blk.shape[0], o))
             out[lo:lo + blk.shape[0]] = o
-        return out
+        return (out, _blob_shape(blobs)) if nblobs else out
 
     # ---- moves / rng ----
     def set_moves(self, descs, cdf):
@@ -347,11 +393,11 @@ class DeviceEnsemble:
 
     def chain_read(self, what, start, stop, stride=1):
         nsel = len(range(start, stop, stride))
-        shape = (nsel, self.nwalkers, self.ndim) if what == 0 else (nsel, self.nwalkers)
+        shape = (nsel, self.nwalkers, self.ndim) if what == 0 else (nsel, self.nwalkers, self.nblobs()) if what == 2 else (nsel, self.nwalkers)
         out = np.empty(shape)
         if nsel:
             self._ck(self.lib.emx_chain_read(self.ctx, what, start, stop, stride, out))
-        return out
+        return _blob_shape(out) if what == 2 else out
 
     def accepted_counts(self):
         out = np.empty(self.nwalkers)

@@ -115,6 +115,8 @@ class EnsembleSampler(object):
                                  "DeviceCallable, or a built-in target)")
             if log_prob_fn.ndim != ndim:
                 raise ValueError("the DeviceFused target was compiled for ndim %d; the sampler has ndim %d" % (log_prob_fn.ndim, ndim))
+            if log_prob_fn.nblobs and blobs_dtype is not None and np.dtype(blobs_dtype) != np.float64:
+                raise ValueError("a DeviceFused target keeps its blobs on the device as float64: blobs_dtype=%r is refused" % (blobs_dtype,))
         for value, text in ((a, "The 'a' argument is deprecated, use 'moves' instead"),
                             (threads, "The 'threads' argument is deprecated"),
                             (runtime_sortingfn, "The 'runtime_sortingfn' argument is deprecated"),
@@ -180,6 +182,8 @@ class EnsembleSampler(object):
             self._random.set_state(self._replicate(self._random.get_state()))
 
         self._device_target = log_prob_fn if isinstance(log_prob_fn, DeviceTarget) else None
+        # blobs a sample that the target keeps on the device next to the chain (DeviceFused(nblobs=K)); 0: blobs, if any, are the host's
+        self._device_nblobs = int(getattr(log_prob_fn, "nblobs", 0)) if isinstance(log_prob_fn, DeviceFused) else 0
         self.log_prob_fn = _FunctionWrapper(log_prob_fn, args, kwargs)
 
         self.params_are_named = parameter_names is not None
@@ -374,8 +378,12 @@ class EnsembleSampler(object):
         if np.any(np.isnan(state.log_prob)):
             raise ValueError("The initial log_prob was NaN")
 
-        # which execution path
-        can_fuse = self._device_target is not None and state.blobs is None
+        # which execution path (blobs a DeviceFused target keeps on the device do not leave the fused path: "no host blobs")
+        dev_nb = self._device_nblobs
+        if dev_nb and state.blobs is None:
+            raise ValueError("If you start sampling with a given log_prob, you also need to provide the "
+                             "current list of blobs at that position.")
+        can_fuse = self._device_target is not None and (state.blobs is None or dev_nb > 0)
         descs = [_native_desc(m, self.ndim, can_fuse, self._philox_moves()) for m in self._moves]
         native = all(d is not None for d in descs)
         fused = native and can_fuse
@@ -396,7 +404,10 @@ class EnsembleSampler(object):
         if native:
             ens = self._configure_device(descs, fused)
             ens.set_state(state.coords, np.asarray(state.log_prob, dtype=np.float64))
-            if state.blobs is None:
+            if dev_nb and fused:
+                ens.set_blobs(state.blobs)
+                state = DeviceState(ens, random_state=state.random_state, nblobs=dev_nb)
+            elif state.blobs is None:
                 # from here on the state lives in HBM; the yielded object copies it back lazily
                 state = DeviceState(ens, random_state=state.random_state)
             if own_backend and store:
@@ -408,8 +419,9 @@ class EnsembleSampler(object):
         elif own_backend:
             self.backend._detach()
         dev_store = native and store and own_backend and self.backend._dev is ens
+        dev_blobs = dev_nb > 0 and fused and dev_store         # the kernel appends the blob plane itself
         if store:
-            self.backend.grow(nsaves, state.blobs)
+            self.backend.grow(nsaves, None if dev_blobs else state.blobs)
 
         map_fn = self.pool.map if self.pool is not None else map
         self._flush_rng()
@@ -459,8 +471,8 @@ class EnsembleSampler(object):
                         move.tune(state, accepted)
                     if save:
                         if dev_store:
-                            self.backend._device_step_saved(state.blobs, lazy_rs if isinstance(state, DeviceState)
-                                                            else state.random_state)
+                            self.backend._device_step_saved(None if dev_blobs else state.blobs,
+                                                            lazy_rs if isinstance(state, DeviceState) else state.random_state)
                         else:
                             if native and not isinstance(state, DeviceState):
                                 state.coords, state.log_prob = ens.get_state()
@@ -563,7 +575,7 @@ class EnsembleSampler(object):
             state = State(initial_state, copy=True)
             if self._dist is not None:
                 state = self._replicate(state)
-            if state.blobs is not None:
+            if state.blobs is not None and not self._device_nblobs:
                 return None
             if np.shape(state.coords) != (self.nwalkers, self.ndim):
                 raise ValueError(f"incompatible input dimensions {np.shape(state.coords)}")
@@ -601,7 +613,12 @@ class EnsembleSampler(object):
                 lp0 = np.asarray(state.log_prob, dtype=np.float64)
                 if np.shape(lp0) != (self.nwalkers,):
                     raise ValueError("incompatible input dimensions")
+                if self._device_nblobs and state.blobs is None:
+                    raise ValueError("If you start sampling with a given log_prob, you also need to provide the "
+                                     "current list of blobs at that position.")
                 ens.set_state(state.coords, lp0)
+                if self._device_nblobs:
+                    ens.set_blobs(state.blobs)
         if lp0 is not None and np.any(np.isnan(lp0)):
             raise ValueError("The initial log_prob was NaN")
         if store:
@@ -614,7 +631,7 @@ class EnsembleSampler(object):
         self._sync_rng_from_device(ens)
         self._raise_on_device_status(ens, store)
         if self._dist is None:
-            out = ResidentState(ens, random_state=self.random_state)      # the arrays cross PCIe when (if) they are read
+            out = ResidentState(ens, random_state=self.random_state, nblobs=self._device_nblobs)      # the arrays cross PCIe when (if) they are read
         else:
             coords, lp = ens.get_state()
             out = State(coords, log_prob=lp, random_state=self.random_state)
@@ -637,11 +654,15 @@ class EnsembleSampler(object):
         if self._device_target is not None:
             ens = self._device_ensemble()
             self._device_target.bind(ens) if ens._target_kind != self._device_target.kind else None
-            log_prob = ens.eval_log_prob(np.atleast_2d(p))
+            blobs = None
+            if self._device_nblobs:
+                log_prob, blobs = ens.eval_log_prob(np.atleast_2d(p), self._device_nblobs)
+            else:
+                log_prob = ens.eval_log_prob(np.atleast_2d(p))
             ens.status()
             if np.any(np.isnan(log_prob)):
                 raise ValueError("Probability function returned NaN")
-            return log_prob, None
+            return log_prob, blobs
 
         if self._dist is not None and self._exchange == "logprob":
             log_prob, blob = self._shared_log_prob(np.atleast_2d(p))

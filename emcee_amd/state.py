@@ -61,9 +61,10 @@ class DeviceState(State):
     device: like the reference -- which mutates and re-yields one ``State`` object
     (``ensemble.py:409-424``) -- the object always reflects the sampler's *current* position, but a
     loop that never looks at the coordinates never pays the (nwalkers x ndim) PCIe copy.
-    Assigning to ``coords`` / ``log_prob`` detaches that field from the device."""
+    Assigning to ``coords`` / ``log_prob`` detaches that field from the device.  ``nblobs`` > 0: the
+    target keeps that many blobs a walker on the device, and ``blobs`` is read from there as lazily."""
 
-    __slots__ = ("_ens", "_c", "_lp", "_rs")
+    __slots__ = ("_ens", "_c", "_lp", "_rs", "_b", "_nb")
 
     @property
     def random_state(self):
@@ -75,17 +76,30 @@ class DeviceState(State):
     def random_state(self, value):
         self._rs = value
 
-    def __init__(self, ens, blobs=None, random_state=None):
+    def __init__(self, ens, blobs=None, random_state=None, nblobs=0):
         self._ens = ens
         self._c = None
         self._lp = None
-        self.blobs = blobs
+        self._b = blobs
+        self._nb = int(nblobs)
         self.random_state = random_state
 
     def _invalidate(self):
         """Called by the sampler after every device step."""
         self._c = None
         self._lp = None
+        if self._nb:
+            self._b = None
+
+    @property
+    def blobs(self):
+        if self._b is None and self._nb and self._ens is not None:
+            self._b = self._ens.get_blobs()
+        return self._b
+
+    @blobs.setter
+    def blobs(self, v):
+        self._b = v
 
     def _fetch(self):
         if self._ens is not None and (self._c is None or self._lp is None):
@@ -123,18 +137,20 @@ class ResidentState(State):
     the device state the continuation uploads nothing; when a later call is about to change the ensemble and the object is
     still alive and unread, its values are kept by a device-to-device copy (``emx_snapshot_save``) and read from there on
     demand.  Reading ``coords`` / ``log_prob`` materialises plain NumPy arrays (from then on it behaves like any State: the
-    caller may edit them, so the next run uploads them)."""
+    caller may edit them, so the next run uploads them).  The blobs of a target that keeps ``nblobs`` of them a walker on the
+    device travel the same way: with the snapshot, and to the host with the other arrays."""
 
-    __slots__ = ("_ens", "_gen", "_slot", "_c", "_lp", "__weakref__")
+    __slots__ = ("_ens", "_gen", "_slot", "_c", "_lp", "_b", "_nb", "__weakref__")
 
-    def __init__(self, ens, random_state=None):
+    def __init__(self, ens, random_state=None, nblobs=0):
         import weakref
         self._ens = ens
         self._gen = ens._gen
         self._slot = None
         self._c = None
         self._lp = None
-        self.blobs = None
+        self._b = None
+        self._nb = int(nblobs)
         self.random_state = random_state
         ens._resident = weakref.ref(self)
 
@@ -166,18 +182,25 @@ class ResidentState(State):
         if self._c is not None and self._lp is not None:
             return
         ens = self._ens
+        b = None
         if self._slot is not None:
             c, lp = ens.snapshot_read(self._slot)
+            if self._nb:
+                b = ens.snapshot_read_blobs(self._slot, self._nb)
             ens.snapshot_release(self._slot)
             self._slot = None
         elif live or ens._gen == self._gen:
             c, lp = ens.get_state()
+            if self._nb:
+                b = ens.get_blobs()
         else:
             raise RuntimeError("ResidentState lost its device copy")      # cannot happen: _touch snapshots first
         if self._c is None:
             self._c = c
         if self._lp is None:
             self._lp = lp
+        if self._b is None:
+            self._b = b
 
     def _peek_coords(self):
         """coordinates for a read-only internal check (the initial-state conditioning): a private copy, the object stays
@@ -217,3 +240,15 @@ class ResidentState(State):
     def log_prob(self, v):
         self._materialise()
         self._lp = v
+
+    @property
+    def blobs(self):
+        if self._nb:
+            self._materialise()
+        return self._b
+
+    @blobs.setter
+    def blobs(self, v):
+        if self._nb:
+            self._materialise()
+        self._b = v

@@ -171,11 +171,18 @@ class DeviceFused(DeviceTarget):
     :class:`DeviceKernel` takes three and sends the proposal block through memory; the run is bit for bit the :class:`DeviceKernel`
     run of the same function, with every move that path runs, in both rng modes.  The functor contract is :class:`BatchFused`'s
     (``member`` is always 0), so one model source serves both; :func:`compile_fused_ensemble` builds the launcher from source.
-    One GPU only (``distributed=True`` is refused); no blobs.  Not a target of :class:`~emcee_amd.EnsembleBatch` or
-    :class:`~emcee_amd.PTSampler`, and not callable outside a sampler."""
+    One GPU only (``distributed=True`` is refused).  Not a target of :class:`~emcee_amd.EnsembleBatch` or
+    :class:`~emcee_amd.PTSampler`, and not callable outside a sampler.
+
+    ``nblobs = K > 0``: the launcher was emitted by ``EMX_FUSED_ENSEMBLE_TARGET_BLOBS(name, Functor, ndim, K)`` around the functor's
+    five-argument form ``(x, ndim, member, user, double* blobs)``, which writes K float64 derived quantities a row in the call
+    that returns the log-probability.  They stay on the device next to the chain -- ``get_blobs``, ``get_last_sample().blobs``,
+    ``compute_log_prob(x)[1]`` and the returned state's ``.blobs`` read them from there, ``(nsteps, nwalkers, K)``, or ``(nsteps,
+    nwalkers)`` for ``K == 1`` -- and the run stays one launch per half-step, the samples those of the blob-free functor.  A
+    launcher compiled for another count is refused when the target is bound; ``WalkMove`` / ``KDEMove`` are refused with blobs."""
     kind = _lib.TARGET_FUSED_ENSEMBLE
 
-    def __init__(self, fn_ptr, ndim, user=None):
+    def __init__(self, fn_ptr, ndim, user=None, nblobs=0):
         if not isinstance(fn_ptr, ctypes._CFuncPtr):
             addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
             if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
@@ -187,6 +194,7 @@ class DeviceFused(DeviceTarget):
         if hasattr(user, "data_ptr") and not getattr(user, "is_cuda", False):
             raise TypeError("DeviceFused's user tensor must live on the GPU (the functor reads it on the device)")
         self.fn_ptr, self.ndim, self.user = fn_ptr, int(ndim), user
+        self.nblobs = _check_nblobs("DeviceFused", nblobs)
 
     def user_address(self):
         """-> the device address handed to the functor (None: a null pointer)"""
@@ -201,7 +209,7 @@ class DeviceFused(DeviceTarget):
         if ens.ndim != self.ndim:
             raise ValueError("the DeviceFused target was compiled for ndim %d; the sampler has ndim %d" % (self.ndim, ens.ndim))
         if getattr(ens, "_cb_owner", None) is not self or ens._target_kind != self.kind:
-            ens.set_target_fused(self.fn_ptr, self.user_address())
+            ens.set_target_fused(self.fn_ptr, self.user_address(), self.nblobs)
             ens._cb_owner = self
 
     def __call__(self, x):
@@ -395,22 +403,22 @@ def _compile_cached(what, header, source, tail, key_parts, name, flags, cache_di
 
 class DeviceFusedLibrary(object):
     """What :func:`compile_fused_ensemble` built: ``path`` of the shared library, ``lib`` (its ``ctypes.CDLL``: the user's own
-    ``extern "C"`` setup functions of ``source`` are there), ``name`` of the launcher, ``ndim``, and :meth:`target`."""
+    ``extern "C"`` setup functions of ``source`` are there), ``name`` of the launcher, ``ndim``, ``nblobs``, and :meth:`target`."""
 
-    def __init__(self, path, name, ndim):
-        self.path, self.name, self.ndim = path, name, int(ndim)
+    def __init__(self, path, name, ndim, nblobs=0):
+        self.path, self.name, self.ndim, self.nblobs = path, name, int(ndim), _check_nblobs("DeviceFusedLibrary", nblobs)
         _lib.load()                       # one HIP runtime per process: the library's (torch's) first
         self.lib = ctypes.CDLL(path)
         self.launcher = getattr(self.lib, name)
 
     def target(self, user=None):
         """-> :class:`DeviceFused` of the compiled functor with the device pointer ``user``"""
-        t = DeviceFused(self.launcher, self.ndim, user)
+        t = DeviceFused(self.launcher, self.ndim, user, nblobs=self.nblobs)
         t._library = self                 # the launcher's code lives as long as the target
         return t
 
 
-def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir=None):
+def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir=None, nblobs=0):
     """Compile the user's model into the single sampler's half-step kernel -> :class:`DeviceFusedLibrary`.
 
     ``source``: HIP C++ that defines the functor type ``functor`` -- ``__device__ double operator()(const double* x, int ndim, int
@@ -418,7 +426,11 @@ def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir
     helpers the user wants in the same library.  The translation unit is ``#include <emx_fused_ensemble.hpp>``, ``source`` and
     ``EMX_FUSED_ENSEMBLE_TARGET(name, functor, ndim)``, compiled and cached as :func:`compile_fused` does (the same flags; the key is
     the hash of source, functor, ndim, name, flags and every header of the library, ``emx_fused_ensemble.hpp`` among them); a
-    compiler failure raises ``RuntimeError`` with the compiler's last lines."""
+    compiler failure raises ``RuntimeError`` with the compiler's last lines.
+
+    ``nblobs = K > 0``: the functor has the five-argument form ``(x, ndim, member, user, double* blobs)`` and the translation unit
+    ends in ``EMX_FUSED_ENSEMBLE_TARGET_BLOBS(name, functor, ndim, K)`` -- the source :func:`compile_fused` takes with ``nblobs``."""
+    nblobs = _check_nblobs("compile_fused_ensemble", nblobs)
     ndim = int(ndim)
     if ndim < 1 or ndim > 256:
         raise ValueError("compile_fused_ensemble: 1 <= ndim <= 256; got %d" % ndim)
@@ -428,9 +440,12 @@ def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir
     name = name or "emx_fused_ensemble_%s_%d" % (functor.replace(":", "_"), ndim)
     flags = [str(f) for f in flags]
     tail = "EMX_FUSED_ENSEMBLE_TARGET(%s, %s, %d)" % (name, functor, ndim)
-    so = _compile_cached("compile_fused_ensemble", "emx_fused_ensemble.hpp", source, tail, ("ensemble", source, functor, ndim, name), name,
-                         flags, cache_dir)
-    return DeviceFusedLibrary(so, name, ndim)
+    key = ("ensemble", source, functor, ndim, name)
+    if nblobs:                            # (a blob-free build keeps the key, and with it the cached library, it always had)
+        tail = "EMX_FUSED_ENSEMBLE_TARGET_BLOBS(%s, %s, %d, %d)" % (name, functor, ndim, nblobs)
+        key += ("nblobs", nblobs)
+    so = _compile_cached("compile_fused_ensemble", "emx_fused_ensemble.hpp", source, tail, key, name, flags, cache_dir)
+    return DeviceFusedLibrary(so, name, ndim, nblobs)
 
 
 class PTFusedLibrary(object):

@@ -210,6 +210,38 @@ typedef struct emx_fused_ensemble_launch {
 } emx_fused_ensemble_launch;
 typedef int (*emx_fused_ensemble_fn)(const emx_fused_ensemble_launch*);     /* 0, or non-zero and nothing launched */
 int emx_set_target_fused(emx_ctx* ctx, emx_fused_ensemble_fn launcher, const void* user);
+/* The same target with blobs: nblobs (1 ... 32) float64 derived quantities a sample, written by the functor's five-argument form
+ * (x, ndim, member, user, double* blobs) in the call that returns the log-probability, committed where the log-probability is
+ * committed and appended to a blob plane (capacity, N, nblobs) next to the chain.  The caller's translation unit emits the launcher
+ * with EMX_FUSED_ENSEMBLE_TARGET_BLOBS(name, Functor, ndim, nblobs).  The descriptor's leading fields are those of
+ * emx_fused_ensemble_launch; `abi` is EMX_FUSED_ENSEMBLE_BLOBS_ABI, a constant of its own, so each launcher answers 1 to the other's
+ * descriptor.  blobs_cur: the walkers' current blobs (N, nblobs) -- or, for an evaluation of rows, the block's; blobs_row: the
+ * plane's row of a stored step, NULL on an unstored one.  Answers as above, and 4: another number of blobs.
+ * emx_set_target_fused_blobs probes once (-1 and "another number of blobs" on answer 4); nblobs == 0 is emx_set_target_fused with
+ * a launcher of that type.  A sharded context is refused, and so is a change of the blob count while stored steps exist.  Blob
+ * values are not validated.  A WalkMove / KDEMove in the schedule of a context with blobs is refused (emx_set_moves, emx_run). */
+typedef struct emx_fused_ensemble_blobs_launch {
+    uint32_t abi;            /* EMX_FUSED_ENSEMBLE_BLOBS_ABI the library was built with */
+    uint32_t args_bytes;     /* sizeof(HalfStepArgs) of the library */
+    int32_t ndim, move, grid, threads;
+    uint64_t lds_bytes;
+    void* hip_stream;
+    const void* args;        /* HalfStepArgs */
+    const void* user;        /* user_dev */
+    int32_t nblobs, reserved;
+    double* blobs_cur;
+    double* blobs_row;
+} emx_fused_ensemble_blobs_launch;
+typedef int (*emx_fused_ensemble_blobs_fn)(const emx_fused_ensemble_blobs_launch*);
+int emx_set_target_fused_blobs(emx_ctx* ctx, emx_fused_ensemble_blobs_fn launcher, const void* user, int32_t nblobs);
+/* the walkers' current blobs (N, nblobs) of such a context: nblobs_out (may be NULL) receives the count, 0 without blobs; out may
+ * be NULL to ask for the count alone */
+int emx_get_blobs(emx_ctx* ctx, double* out, int32_t* nblobs_out);
+int emx_set_blobs(emx_ctx* ctx, const double* in);
+/* emx_eval_log_prob, and the rows' blobs (n, nblobs) */
+int emx_eval_log_prob_blobs(emx_ctx* ctx, const double* coords, int64_t n, double* lp_out, double* blobs_out);
+/* the blobs (N, nblobs) a snapshot slot carries (emx_snapshot_save / _restore copy them with coords and log_prob) */
+int emx_snapshot_read_blobs(emx_ctx* ctx, int32_t slot, double* blobs);
 
 /* ---- target: the batched log-prob (ensemble.py:458-553, vectorised) -------------------- */
 /* p0/p1: DIAG (mu, ivar); DENSE (mu, icov[D*D], symmetric positive definite: factored once as
@@ -217,7 +249,7 @@ int emx_set_target_fused(emx_ctx* ctx, emx_fused_ensemble_fn launcher, const voi
  * ndim 112, as a log-prob kernel of its own between propose and commit up to ndim 2048); others NULL.
  * scale: Rosenbrock divisor. */
 int emx_set_target(emx_ctx* ctx, int32_t kind, const double* p0, const double* p1, double scale);
-/* log-prob of the current state, stored as the state's log_prob (ensemble.py:350-351) */
+/* log-prob of the current state, stored as the state's log_prob (ensemble.py:350-351); a target with blobs fills the state's blobs */
 int emx_eval_state_log_prob(emx_ctx* ctx);
 /* EnsembleSampler.compute_log_prob(coords) for n host rows (n <= nwalkers per call) */
 int emx_eval_log_prob(emx_ctx* ctx, const double* coords, int64_t n, double* out);
@@ -247,7 +279,7 @@ int emx_iteration(emx_ctx* ctx, int64_t* stored_steps, int64_t* proposals);
  * the host is the bottleneck (a busy or slow host thread); results are bit-identical either way.  captured: bit0 no-store graph, bit1 store graph. */
 int emx_graph_state(emx_ctx* ctx, int32_t* disabled, int32_t* captured);
 /* Backend.get_value slices (backend.py:42-58): steps start, start+stride, ... < stop.
- * what: 0 chain -> out[(nsel, N, D)], 1 log_prob -> out[(nsel, N)]. */
+ * what: 0 chain -> out[(nsel, N, D)], 1 log_prob -> out[(nsel, N)], 2 blobs -> out[(nsel, N, nblobs)] (a context with blobs). */
 int emx_chain_read(emx_ctx* ctx, int32_t what, int64_t start, int64_t stop, int64_t stride, double* out);
 int emx_accepted_counts(emx_ctx* ctx, double* out /* N, backend.accepted */);
 

@@ -4,11 +4,16 @@
   kernel   targets.DeviceKernel: the same function behind an emx_device_log_prob_fn (three launches a half-step)
   builtin  targets.DiagGaussian: the library's own closed form (the distance left to a built-in target)
 
-    python tools/ensemble_fused_bench.py [--modes fused,kernel,builtin] [--shapes 65536x64,4096x16,1048576x32] [--seconds 1.5]
-                                         [--flags="-IDIR ..."] [--out FILE]
+  fused+K  the same functor in its five-argument form with K blobs a sample (--nblobs 1,4,32 adds one such mode per count)
+  host     the same model with one blob as a vectorised Python callable: the host-callable path, for scale
 
-Philox mode, store=False, blocks of steps timed by a host clock around a device synchronise; the median of at least `--seconds`
-of blocks per mode, the modes of a shape taken in alternation so that drift of the machine hits them alike.  `--modes kernel` needs
+    python tools/ensemble_fused_bench.py [--modes fused,kernel,builtin,host] [--shapes 65536x64,4096x16,1048576x32] [--seconds 1.5]
+                                         [--nblobs 1,4,32] [--store] [--flags="-IDIR ..."] [--out FILE]
+
+Philox mode, blocks of steps timed by a host clock around a device synchronise; the median of at least `--seconds`
+of blocks per mode, the modes of a shape taken in alternation so that drift of the machine hits them alike.  store=False unless
+`--store`: then every step appends chain, log-probs and blobs, the sampler is reset before each block (the chain keeps its
+allocation) and a block is as many steps as fit 4 GB of chain.  `--modes kernel` needs
 nothing of the fused target, so the same file measures a checkout that predates it.  `--flags` are further compiler flags of the
 fused launcher: tuning experiments put an edited copy of emx_fused_ensemble.hpp ahead of the library's with --flags=-IDIR.  Prints
 one JSON line per shape and mode; `steps_total` counts every step the mode's sampler ran (a kernel trace has two half-steps each)."""
@@ -42,8 +47,18 @@ __device__ inline double diag_model(const double* x, int ndim, const void* user)
     }
     return -0.5 * acc;
 }
+#ifndef BENCH_NBLOBS
+#define BENCH_NBLOBS 0
+#endif
 struct DiagModel {
     __device__ double operator()(const double* x, int ndim, int, const void* user) const { return diag_model(x, ndim, user); }
+    __device__ double operator()(const double* x, int ndim, int, const void* user, double* blobs) const {
+        const double lp = diag_model(x, ndim, user);
+        blobs[0] = lp;
+#pragma unroll
+        for (int k = 1; k < BENCH_NBLOBS; ++k) blobs[k] = x[k % ndim] * (double)(k + 1);
+        return lp;
+    }
 };
 """
 
@@ -104,10 +119,12 @@ def main():
     ap.add_argument("--shapes", default="65536x64,4096x16,1048576x32")
     ap.add_argument("--seconds", type=float, default=1.5)
     ap.add_argument("--flags", default="", help="further hipcc flags of the fused launcher, separated by blanks")
+    ap.add_argument("--nblobs", default="", help="blob counts: each adds a mode fused+K (the five-argument functor)")
+    ap.add_argument("--store", action="store_true", help="store the chain (and the blobs): the sampler is reset before every block")
     ap.add_argument("--cache", default=None, help="directory of compiled user libraries (default: a temporary one)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    modes = a.modes.split(",")
+    modes = a.modes.split(",") + ["fused+%d" % int(k) for k in a.nblobs.split(",") if k]
     work = a.cache or tempfile.mkdtemp(prefix="ensemble_fused_bench_")
     os.makedirs(work, exist_ok=True)
     cb = build_callback(work)
@@ -122,40 +139,61 @@ def main():
         assert dev
         samplers = {}
         for mode in modes:
+            kw = {}
             if mode == "fused":
                 lib = targets.compile_fused_ensemble(MODEL, "DiagModel", D, flags=a.flags.split(), cache_dir=work)
                 t = lib.target(user=dev)
+            elif mode.startswith("fused+"):
+                K = int(mode[6:])
+                lib = targets.compile_fused_ensemble(MODEL, "DiagModel", D, flags=a.flags.split() + ["-DBENCH_NBLOBS=%d" % K], cache_dir=work,
+                                                     nblobs=K)
+                t = lib.target(user=dev)
+            elif mode == "host":
+                def t(p, mu=mu, ivar=ivar):
+                    lp = -0.5 * np.sum(ivar * (p - mu) ** 2, axis=1)
+                    return np.column_stack([lp, lp])
+                kw = dict(vectorize=True)
             elif mode == "kernel":
                 t = targets.DeviceKernel(cb.diag_rows, dev)
             else:
                 t = targets.DiagGaussian(mu, ivar)
-            s = emcee_amd.EnsembleSampler(N, D, t, rng="philox")
+            s = emcee_amd.EnsembleSampler(N, D, t, rng="philox", **kw)
             s._random.seed(3)
-            samplers[mode] = [s, s.run_mcmc(p0, 16, store=False, skip_initial_state_check=True), [], 16]
+            samplers[mode] = [s, s.run_mcmc(p0, 16, store=a.store, skip_initial_state_check=True), [], 16]
         block = max(32, min(2000, int(6.4e9 / (N * D)) // 16 * 16))      # some tens of milliseconds a block
+        if a.store:
+            block = max(16, min(block, int(4e9 / (N * D * 8)) // 16 * 16))
+
+        def run(ent, n):
+            if a.store:
+                ent[0].reset()
+            ent[1] = ent[0].run_mcmc(ent[1], n, store=a.store, skip_initial_state_check=True)
         t_end = time.perf_counter() + 0.5                    # clocks up, every mode warm
         while time.perf_counter() < t_end:
             for mode in modes:
                 ent = samplers[mode]
-                ent[1] = ent[0].run_mcmc(ent[1], block, store=False, skip_initial_state_check=True)
+                run(ent, block if mode != "host" else 4)
                 ent[3] += block
         spent = dict((m, 0.0) for m in modes)
         while min(spent.values()) < a.seconds:
             for mode in modes:                               # alternating
                 ent = samplers[mode]
+                nb = block if mode != "host" else 4          # (milliseconds a step: a few steps are a block)
+                if a.store:
+                    ent[0].reset()
                 ent[0]._ens.sync()
                 t0 = time.perf_counter()
-                ent[1] = ent[0].run_mcmc(ent[1], block, store=False, skip_initial_state_check=True)
+                ent[1] = ent[0].run_mcmc(ent[1], nb, store=a.store, skip_initial_state_check=True)
                 ent[0]._ens.sync()
                 dt = time.perf_counter() - t0
-                ent[2].append(dt / block)
-                ent[3] += block
+                ent[2].append(dt / nb)
+                ent[3] += nb
                 spent[mode] += dt
         for mode in modes:
             v = np.sort(np.array(samplers[mode][2])) * 1e6
             acc = float(np.mean(samplers[mode][0]._ens.accepted_mask()))
-            rec = dict(shape=shape, mode=mode, flags=a.flags, us_per_step=float(np.median(v)), p10=float(v[int(0.1 * (len(v) - 1))]),
-                       p90=float(v[int(np.ceil(0.9 * (len(v) - 1)))]), blocks=len(v), steps_per_block=block, steps_total=samplers[mode][3],
+            rec = dict(shape=shape, mode=mode, flags=a.flags, store=bool(a.store), us_per_step=float(np.median(v)), p10=float(v[int(0.1 * (len(v) - 1))]),
+                       p90=float(v[int(np.ceil(0.9 * (len(v) - 1)))]), blocks=len(v), steps_per_block=block if mode != "host" else 4, steps_total=samplers[mode][3],
                        last_accept_fraction=acc)
             lines.append(json.dumps(rec))
             print(lines[-1], flush=True)
