@@ -100,6 +100,10 @@ SIGNATURES = {
     "emx_set_target_callback": (C.c_int, [_P, DEVICE_LOG_PROB_FN, _P]),
     "emx_set_target_fused": (C.c_int, [_P, FUSED_ENSEMBLE_FN, _P]),
     "emx_set_target_fused_blobs": (C.c_int, [_P, FUSED_ENSEMBLE_BLOBS_FN, _P, C.c_int32]),
+    "emx_set_target_fused_small": (C.c_int, [_P, FUSED_BATCH_FN]),
+    "emx_small_fused_check": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(MoveDesc), C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
+    "emx_small_fused_pays": (C.c_int, [C.c_int64, C.c_int32, C.c_int32]),
+    "emx_small_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "emx_get_blobs": (C.c_int, [_P, _P, C.POINTER(C.c_int32)]),
     "emx_set_blobs": (C.c_int, [_P, _dp]),
     "emx_eval_log_prob_blobs": (C.c_int, [_P, _dp, C.c_int64, _dp, _dp]),

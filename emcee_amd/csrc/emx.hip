@@ -296,6 +296,9 @@ struct emx_ctx {
     const void* fused_user = nullptr;         // ... and the device pointer its functor receives
     // blobs of a fused user target (emx_set_target_fused_blobs; k_halfstep_user_blobs): nblobs doubles a sample
     emx_fused_ensemble_blobs_fn fused_blobs_fn = nullptr;
+    // the same target's one-workgroup launcher (emx_set_target_fused_small; k_small_run around the caller's functor), or null
+    emx_fused_batch_fn fused_small_fn = nullptr;
+    int64_t small_launches = 0, small_steps = 0;      // one-workgroup launches and the steps run in them (emx_small_info)
     int nblobs = 0;
     double* blobs = nullptr;                  // (N, nblobs): the walkers' current blobs, committed where lp is
     double* evalblobs = nullptr;              // (N, nblobs): the rows of emx_eval_log_prob_blobs
@@ -1878,6 +1881,7 @@ int emx_set_target_fused(emx_ctx* c, emx_fused_ensemble_fn launcher, const void*
     blob_storage_free(c);
     c->fused_fn = launcher;
     c->fused_blobs_fn = nullptr;
+    c->fused_small_fn = nullptr;
     c->fused_user = user;
     c->Dp = 0;
     graph_invalidate(c);
@@ -1938,12 +1942,42 @@ int emx_set_target_fused_blobs(emx_ctx* c, emx_fused_ensemble_blobs_fn launcher,
     }
     c->fused_blobs_fn = launcher;
     c->fused_fn = nullptr;
+    c->fused_small_fn = nullptr;
     c->fused_user = user;
     c->Dp = 0;
     graph_invalidate(c);
     c->graph_warm = false;
     c->target = EMX_TARGET_FUSED_ENSEMBLE;
     c->tscale = 1.0;
+    return 0;
+}
+
+// The one-workgroup launcher of the bound fused user target (include/emx.h; emx_fused_ensemble.hpp: EMX_FUSED_ENSEMBLE_SMALL_TARGET):
+// probed for version, ndim and blob count; run_small calls it where it launches the library's own k_small_run instantiations.
+int emx_set_target_fused_small(emx_ctx* c, emx_fused_batch_fn small_launcher) {
+    { const int rcs_ = persist_settle(c); if (rcs_) return rcs_; }
+    NEED(c, c->target == EMX_TARGET_FUSED_ENSEMBLE, "emx_set_target_fused_small: the context's target is not a fused user target "
+         "(call emx_set_target_fused or emx_set_target_fused_blobs first)");
+    if (small_launcher) {
+        emx_fused_launch fl{};                     // the probe: nothing is launched
+        fl.abi = EMX_FUSED_ENSEMBLE_SMALL_ABI;
+        fl.args_bytes = (uint32_t)sizeof(SmallRunArgs);
+        fl.ndim = c->D;
+        fl.movesel = MOVE_STRETCH;
+        fl.nblobs = c->nblobs;
+        const int rcp = small_launcher(&fl);
+        if (rcp == 2) FAIL(c, -1, "emx_set_target_fused_small: the fused user target was compiled for another ndim; the ensemble has ndim %d", c->D);
+        if (rcp == 4)
+            FAIL(c, -1, "emx_set_target_fused_small: the fused user target was compiled for another number of blobs; the context's target has %d",
+                 c->nblobs);
+        if (rcp)
+            FAIL(c, -8, "emx_set_target_fused_small: the launcher was built against another version of emx_fused_ensemble.hpp, or is not an "
+                        "EMX_FUSED_ENSEMBLE_SMALL_TARGET launcher (it answered %d); rebuild it against this library's headers", rcp);
+    }
+    HIPOK(c, hipSetDevice(c->device));
+    PIPE_STOP(c);              // whether the host pipeline feeds this context depends on small_eligible
+    drop_prepared(c);
+    c->fused_small_fn = small_launcher;
     return 0;
 }
 
@@ -3374,16 +3408,75 @@ hipError_t emx_small_dispatch(int G, int V, int CH, int dpb, int movesel, int th
                               const emx::SmallRunArgs& a);
 
 // ---- small ensembles: whole runs inside one workgroup (k_small_run; shape rules in emx_small_host.hpp) -------
-static bool small_eligible(const emx_ctx* c) {
-    if (!c->tune_small || (c->rng_mode != EMX_RNG_PHILOX && c->rng_mode != EMX_RNG_MT19937)) return false;
-    if (c->moves.empty() || (int)c->moves.size() > SMALL_MAX_MOVES) return false;
-    for (const auto& mv : c->moves) {
+// the moves the one-workgroup kernel runs in this rng mode (nullptr), or why not
+static const char* small_moves_refusal(int64_t N, int32_t nmoves, const emx_move_desc* moves, int32_t rng_mode) {
+    if (rng_mode != EMX_RNG_PHILOX && rng_mode != EMX_RNG_MT19937) return "the one-workgroup kernel makes or takes plans: rng mode philox or mt19937";
+    if (nmoves < 1 || nmoves > SMALL_MAX_MOVES || !moves) return "the one-workgroup kernel takes 1 ... 8 moves (SMALL_MAX_MOVES)";
+    for (int m = 0; m < nmoves; ++m) {
+        const emx_move_desc& mv = moves[m];
         if (mv.kind == EMX_MOVE_GAUSS) {
-            if (c->rng_mode != EMX_RNG_PHILOX) return false;      // exact mode: N x D host normals per step, general path
+            if (rng_mode != EMX_RNG_PHILOX) return "a GaussianMove in mt19937 mode takes N x ndim host normals a step: general path";
             continue;
         }
-        if (mv.kind != EMX_MOVE_STRETCH && mv.kind != EMX_MOVE_DE && mv.kind != EMX_MOVE_SNOOKER) return false;
-        if (mv.kind == EMX_MOVE_DE && c->N - (c->N + mv.nsplits - 1) / mv.nsplits < 2) return false;
+        if (mv.kind != EMX_MOVE_STRETCH && mv.kind != EMX_MOVE_DE && mv.kind != EMX_MOVE_SNOOKER)
+            return "the one-workgroup kernel runs StretchMove, DEMove, DESnookerMove and GaussianMove only";
+        if (mv.nsplits < 1 || mv.nsplits > N) return "nsplits must be in [1, nwalkers]";
+        if (mv.kind == EMX_MOVE_DE && N - (N + mv.nsplits - 1) / mv.nsplits < 2) return "DEMove: a complement has fewer than 2 walkers";
+    }
+    return nullptr;
+}
+
+// rows of a fused user target's staging area in k_small_run: the largest split of the schedule (a Gaussian move has one split)
+static int64_t small_fused_stage_rows(int64_t N, int32_t nmoves, const emx_move_desc* moves) {
+    int smin = 1 << 30;
+    for (int m = 0; m < nmoves; ++m) smin = std::min(smin, std::max(1, (int)moves[m].nsplits));
+    return (N + smin - 1) / smin;
+}
+
+// a fused user target's shape in the one-workgroup kernel (emx_small_fused_check; small_eligible asks the same function)
+static const char* small_fused_refusal(int64_t N, int32_t D, int32_t nmoves, const emx_move_desc* moves, int32_t rng_mode, int32_t nblobs,
+                                       char* buf, size_t n) {
+    if (N < 2 || D < 1) return "nwalkers must be >= 2 and ndim >= 1";
+    if (nblobs < 0 || nblobs > FUSED_ENS_MAX_BLOBS) {
+        snprintf(buf, n, "a fused user target carries 0 ... %d blobs a sample; got %d", FUSED_ENS_MAX_BLOBS, nblobs);
+        return buf;
+    }
+    if (N > 4096 || D > FUSED_ENS_MAX_NDIM) {
+        snprintf(buf, n, "nwalkers x ndim = %lld x %d is outside the one-workgroup kernel (nwalkers <= 4096, ndim <= %d)", (long long)N, D,
+                 FUSED_ENS_MAX_NDIM);
+        return buf;
+    }
+    if (const char* why = small_moves_refusal(N, nmoves, moves, rng_mode)) return why;
+    const size_t need = small_lds_bytes(N, D) + small_fused_stage_bytes(small_fused_stage_rows(N, nmoves, moves), D) + small_blob_bytes(N, nblobs);
+    if (need > SMALL_LDS_MAX) {
+        snprintf(buf, n, "nwalkers x ndim = %lld x %d with a fused user target and %d blobs a walker does not fit one workgroup's LDS "
+                         "(%zu bytes > %zu)", (long long)N, D, nblobs, need, SMALL_LDS_MAX);
+        return buf;
+    }
+    return nullptr;
+}
+
+// Where the one-workgroup kernel of a fused user target beats the launch per half-step (profiles/ensemble_fused_small.md).  One
+// lane a row calls the functor and commits the row, so the kernel's step time grows with ndim where the half-step launches' does not:
+//   Philox plans (the general path: 8 ... 16 us a step): ndim <= 10 and nwalkers x ndim <= 1 024 -- measured at 32 x 5, 100 x 10,
+//     128 x 8, 200 x 5, 256 x 4, 512 x 2: 1.2 ... 3.5 times faster; slower at 64 x 32, 606 x 16, 1 000 x 5 and, for a DE + snooker
+//     mixture, from 64 x 16 on;
+//   the host's MT19937 plans (the general path: 25 ... 35 us a step): ndim <= 16, whatever fits -- measured up to 1 000 x 5 and
+//     606 x 16: 1.7 ... 6.9 times faster; wider rows were not measured.
+static bool small_fused_pays(int64_t N, int32_t D, int32_t rng_mode) {
+    if (rng_mode == EMX_RNG_MT19937) return D <= 16;
+    return D <= 10 && N * (int64_t)D <= 1024;
+}
+
+static bool small_eligible(const emx_ctx* c) {
+    if (!c->tune_small) return false;
+    if (small_moves_refusal(c->N, (int32_t)c->moves.size(), c->moves.data(), c->rng_mode)) return false;
+    if (c->target == EMX_TARGET_FUSED_ENSEMBLE) {      // the caller's functor inside k_small_run: with a small launcher bound, where it fits
+        char buf[320];
+        // (an emx_run of ONE step -- sample() driven step by step -- keeps the launch per half-step)
+        // ("small_kernel" 2: wherever it fits, whether it pays or not)
+        return c->fused_small_fn && c->call_steps >= 2 && (c->tune_small >= 2 || small_fused_pays(c->N, c->D, c->rng_mode)) && c->world == 1 && !c->comm && !c->sendbuf && c->prof_max <= 0 && !c->tune_ablate && !c->cur.active &&
+               !small_fused_refusal(c->N, c->D, (int32_t)c->moves.size(), c->moves.data(), c->rng_mode, c->nblobs, buf, sizeof buf);
     }
     if (c->target != EMX_TARGET_ISO_GAUSS && c->target != EMX_TARGET_DIAG_GAUSS && c->target != EMX_TARGET_ROSENBROCK &&
         c->target != EMX_TARGET_BOX && c->target != EMX_TARGET_DENSE_GAUSS)
@@ -3527,12 +3620,62 @@ static int run_small(emx_ctx* c, int64_t i0, int64_t nsteps, int32_t thin_by, in
         gauss_bulk = &bp;
     }
     const int threads = small_threads(c->N, c->D, c->Dp, sh.G, minsplits, dense);
-    const size_t lds = dense ? small_lds_bytes(c->N, c->D, c->Dp, threads / 64) : small_lds_bytes(c->N, c->D);
+    const bool fused = c->target == EMX_TARGET_FUSED_ENSEMBLE;
+    if (fused) {
+        // the caller's functor inside the kernel: the staging rows of the largest split, the walkers' blobs and the plane's first row
+        NEED(c, c->fused_small_fn != nullptr, "fused user target without a one-workgroup launcher (emx_set_target_fused_small)");
+        a.target = TGT_USER;
+        a.user = c->fused_user;
+        a.stage_rows = (int32_t)small_fused_stage_rows(c->N, nm, c->moves.data());
+        if (c->nblobs > 0) {
+            a.nblobs = c->nblobs;
+            a.blobs = c->blobs;
+            if (store) {
+                NEED(c, c->blob_plane != nullptr, "no blob plane (emx_chain_config)");
+                a.chain_blobs = c->blob_plane + (size_t)c->stored * c->N * c->nblobs;
+            }
+        }
+    }
+    const size_t lds = dense   ? small_lds_bytes(c->N, c->D, c->Dp, threads / 64)
+                       : fused ? small_lds_bytes(c->N, c->D) + small_fused_stage_bytes(a.stage_rows, c->D) + small_blob_bytes(c->N, c->nblobs)
+                               : small_lds_bytes(c->N, c->D);
     hipError_t e = hipErrorInvalidValue;
-    const int movesel = (nm == 1 && (!dense || c->moves[0].kind == EMX_MOVE_STRETCH)) ? (int)c->moves[0].kind : SMALL_ANY_MOVE;
+    // (a fused user target's translation unit carries the single-StretchMove selector and the any-schedule one)
+    const int movesel = (nm == 1 && ((!dense && !fused) || c->moves[0].kind == EMX_MOVE_STRETCH)) ? (int)c->moves[0].kind : SMALL_ANY_MOVE;
     // (MOVE_GAUSS == 3 is a valid single selector for the element-wise targets; the dense variant carries it under ANY)
-    e = emx_small_dispatch(sh.G, sh.V, sh.CH, dense ? c->Dp / 16 : 0, movesel, threads, lds, c->stream, a);
-    if (e != hipSuccess) FAIL(c, -2, "k_small_run launch failed (G=%d V=%d CH=%d ndim=%d): %s", sh.G, sh.V, sh.CH, c->D, hipGetErrorString(e));
+    if (fused) {
+        emx_fused_launch fl{};
+        fl.abi = EMX_FUSED_ENSEMBLE_SMALL_ABI;
+        fl.args_bytes = (uint32_t)sizeof(SmallRunArgs);
+        fl.ndim = c->D;
+        fl.movesel = movesel;
+        fl.grid = 1;
+        fl.threads = threads;
+        fl.lds_bytes = lds;
+        fl.hip_stream = (void*)c->stream;
+        fl.args = &a;
+        fl.user = c->fused_user;
+        fl.nblobs = c->nblobs;
+        fl.reserved = a.plans ? 1 : 0;
+        const int rcf = c->fused_small_fn(&fl);
+        if (rcf == 1)
+            FAIL(c, -8, "the fused user target's one-workgroup launcher was built against another version of emx_fused_ensemble.hpp (the "
+                        "library has EMX_FUSED_ENSEMBLE_SMALL_ABI 0x%x and %zu bytes of kernel arguments): rebuild it with this library's headers",
+                 (unsigned)EMX_FUSED_ENSEMBLE_SMALL_ABI, sizeof(SmallRunArgs));
+        if (rcf == 2) FAIL(c, -1, "the fused user target's one-workgroup launcher was compiled for another ndim than the ensemble's %d", c->D);
+        if (rcf == 4)
+            FAIL(c, -1, "the fused user target's one-workgroup launcher was compiled for another number of blobs than the context's %d", c->nblobs);
+        if (rcf == 3)
+            FAIL(c, -1, "the fused user target's one-workgroup launcher does not carry the kernel of this launch (move selector %d, %s plans, "
+                        "%d threads, %zu bytes of LDS)", movesel, a.plans ? "host" : "Philox", threads, lds);
+        if (rcf >= 100) FAIL(c, -2, "k_small_run fused user target launch failed (ndim=%d): %s", c->D, hipGetErrorString((hipError_t)(rcf - 100)));
+        if (rcf) FAIL(c, -7, "the fused user target's one-workgroup launcher failed (returned %d)", rcf);
+    } else {
+        e = emx_small_dispatch(sh.G, sh.V, sh.CH, dense ? c->Dp / 16 : 0, movesel, threads, lds, c->stream, a);
+        if (e != hipSuccess) FAIL(c, -2, "k_small_run launch failed (G=%d V=%d CH=%d ndim=%d): %s", sh.G, sh.V, sh.CH, c->D, hipGetErrorString(e));
+    }
+    ++c->small_launches;
+    c->small_steps += nsteps;
     int64_t nstored = 0;
     if (store)
         for (int64_t s2 = 0; s2 < nsteps; ++s2) nstored += ((i0 + s2 + 1) % thin_by == 0) ? 1 : 0;
@@ -4330,6 +4473,24 @@ int emx_persist_info(emx_ctx* c, int64_t out[4]) {
     out[2] = c->persist_halfsteps;
     out[3] = c->persist_recovered;       // launches that gave up untouched and were redone on the per-half-step path (persist_settle)
     return 0;
+}
+
+int emx_small_info(emx_ctx* c, int64_t out[4]) {
+    out[0] = c->small_launches;
+    out[1] = c->small_steps;
+    out[2] = out[3] = 0;
+    return 0;
+}
+
+int emx_small_fused_pays(int64_t nwalkers, int32_t ndim, int32_t rng_mode) { return small_fused_pays(nwalkers, ndim, rng_mode) ? 1 : 0; }
+
+int emx_small_fused_check(int64_t nwalkers, int32_t ndim, int32_t nmoves, const emx_move_desc* moves, int32_t rng_mode, int32_t nblobs,
+                          char* msg, int32_t msglen) {
+    char buf[320];
+    const char* why = small_fused_refusal(nwalkers, ndim, nmoves, moves, rng_mode, nblobs, buf, sizeof buf);
+    if (!why) return 0;
+    if (msg && msglen > 0) snprintf(msg, (size_t)msglen, "%s", why);
+    return -1;
 }
 
 int emx_persist_local_launches(emx_ctx* c, int64_t* n) {

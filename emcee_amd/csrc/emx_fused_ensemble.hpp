@@ -29,6 +29,15 @@
 // k_halfstep_user_blobs is the same half-step: the decision lane commits the blobs to the walkers' current ones where it commits lp
 // and appends the blob plane's row where it appends chain_lp -- a rejected row keeps its previous blobs -- so the blobs cost no
 // launch and no second pass over the proposal block.  k_halfstep_user itself compiles to what it compiled to before.
+//
+// Small ensembles (opt-in; include/emx.h: emx_set_target_fused_small).  An ensemble that fits one workgroup's LDS runs whole
+// run_mcmc calls inside k_small_run (emx_kernels.hpp) when the translation unit ALSO emits
+//     EMX_FUSED_ENSEMBLE_SMALL_TARGET(my_model_small, MyModel, /*ndim=*/5)              // int my_model_small(const emx_fused_launch*)
+//     EMX_FUSED_ENSEMBLE_SMALL_TARGET_BLOBS(my_model_small, MyModel, /*ndim=*/5, /*nblobs=*/2)
+// next to the half-step launcher above (which keeps the initial log-probs, every evaluation of rows and the ensembles that do not
+// fit).  The launcher carries k_small_run<..., BATCH = false, USER> for the single-StretchMove and the any-schedule selectors, each
+// with Philox plans and with the plans of the host's MT19937 twin: four kernels, which is why the macro is a second one -- a
+// translation unit without it compiles to what it always did.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,12 +61,19 @@
 #ifndef EMX_FUSED_ENSEMBLE_BLOBS_ABI
 #define EMX_FUSED_ENSEMBLE_BLOBS_ABI 0x454e4201u
 #endif
+// the small launcher's descriptor is emx_fused_launch with this constant, bumped -- like EMX_FUSED_ABI of emx_fused_target.hpp -- with
+// ANY change of SmallRunArgs or of k_small_run's LDS layout.  A value of its own, so that a batch launcher (EMX_FUSED_BATCH_TARGET: the
+// BATCH kernel, which reads per-member arrays a single ensemble has none of) and a small launcher answer 1 to each other's descriptor
+#ifndef EMX_FUSED_ENSEMBLE_SMALL_ABI
+#define EMX_FUSED_ENSEMBLE_SMALL_ABI 0x45535301u
+#endif
 
 namespace emx {
 
 constexpr int FUSED_ENS_MAX_NDIM = 256;
 constexpr int FUSED_ENS_THREADS = 256;      // four waves: (256 / G) rows a pass
 constexpr int FUSED_ENS_MAX_BLOBS = 32;     // float64 blobs a sample (emcee_amd._lib.MAX_BLOBS)
+constexpr int FUSED_ENS_MAX_DEVICES = 64;   // devices one process may drive (the one-workgroup kernel's LDS limit is raised per device)
 
 // pick_shape(D, D) (emx_small_host.hpp) -- the layout of the element-wise k_halfstep -- as a constant expression
 constexpr int fused_ens_v(int D) { return D % 2 == 0 ? 2 : 1; }
@@ -487,6 +503,66 @@ int fused_ensemble_blobs_launch(const emx_fused_ensemble_blobs_launch* L) {
     return e == hipSuccess ? 0 : 100 + (int)e;
 }
 
+// ---- small ensembles: the one-workgroup kernel around the same functor ----
+template <typename USER, int NDIM, int MOVESEL, bool PLANNED, int NB>
+hipError_t launch_fused_ens_small(int threads, size_t lds, hipStream_t st, const SmallRunArgs& a) {
+    constexpr int G = fused_ens_g(NDIM), V = fused_ens_v(NDIM), CH = fused_ens_ch(NDIM);
+    static_assert(G * V * CH >= NDIM, "the row layout covers the row");
+    auto kern = k_small_run<G, V, CH, MOVESEL, PLANNED, 0, false, USER, NB>;
+    static size_t lds_granted[FUSED_ENS_MAX_DEVICES] = {};      // as launch_small_move: function attributes are per device
+    int dev = 0;
+    if (lds > 48 * 1024 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < FUSED_ENS_MAX_DEVICES && lds > lds_granted[dev]) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        lds_granted[dev] = lds;
+    }
+    hipLaunchKernelGGL(kern, dim3(1), dim3(threads), lds, st, a);
+    return hipGetLastError();
+}
+
+// the launcher behind EMX_FUSED_ENSEMBLE_SMALL_TARGET[_BLOBS] (include/emx.h: emx_set_target_fused_small).  The descriptor is
+// emx_fused_launch: abi EMX_FUSED_ENSEMBLE_SMALL_ABI, args a SmallRunArgs, grid 1 (0: the probe), reserved 1 when the plans are the
+// host's (exact MT19937 mode: args carries `plans`), else 0.  0, or non-zero and nothing launched: 1 another version of the headers
+// (or another launcher type's descriptor), 2 another ndim, 3 a move selector or a launch shape that was not compiled in -- a
+// workgroup, an LDS size or a staging area that does not hold the ensemble among them --, 4 another number of blobs, 100 + a hipError_t.
+template <typename USER, int NDIM, int NB>
+int fused_ensemble_small_launch(const emx_fused_launch* L) {
+    static_assert(NDIM >= 1 && NDIM <= FUSED_ENS_MAX_NDIM, "a fused user target has 1 <= ndim <= 256");
+    static_assert(NB >= 0 && NB <= FUSED_ENS_MAX_BLOBS, "a fused user target has 0 <= nblobs <= 32");
+    if (!L || L->abi != EMX_FUSED_ENSEMBLE_SMALL_ABI || L->args_bytes != (uint32_t)sizeof(SmallRunArgs)) return 1;
+    if (L->ndim != NDIM) return 2;
+    const bool stretch = L->movesel == MOVE_STRETCH;
+    if ((!stretch && L->movesel != SMALL_ANY_MOVE) || (L->reserved != 0 && L->reserved != 1)) return 3;
+    if (L->nblobs != NB) return 4;
+    if (L->grid == 0) return 0;                       // the probe of emx_set_target_fused_small
+    if (!L->args || L->grid != 1 || L->threads < 64 || L->threads > 1024 || L->threads % 64 != 0) return 3;
+    SmallRunArgs a = *static_cast<const SmallRunArgs*>(L->args);
+    if (a.D != NDIM) return 2;
+    if (a.nblobs != NB || (NB > 0 && !a.blobs)) return 4;
+    const bool planned = L->reserved == 1;
+    if (planned != (a.plans != nullptr) || (planned && a.nmoves > 1 && !a.step_moves)) return 3;
+    // what the kernel keeps in LDS fits what the launch asks for: the ensemble, `batch` steps' plans, a staging row for every slot of
+    // the largest split, the blobs
+    if (a.N < 2 || a.N > 4096 || a.batch < 1 || a.nmoves < 1 || a.nmoves > SMALL_MAX_MOVES || a.stage_rows < 1) return 3;
+    for (int m = 0; m < a.nmoves; ++m) {
+        if (a.nsplits[m] < 1 || (a.N + a.nsplits[m] - 1) / a.nsplits[m] > a.stage_rows) return 3;
+        if ((a.kind[m] == MOVE_GAUSS && planned) || (stretch && a.kind[m] != MOVE_STRETCH)) return 3;      // (exact mode: the normals are the host's)
+    }
+    const size_t need = small_lds_bytes(a.N, NDIM, 0, 0, a.batch) + small_fused_stage_bytes(a.stage_rows, NDIM) + small_blob_bytes(a.N, NB);
+    if (need > (size_t)L->lds_bytes || (size_t)L->lds_bytes > SMALL_LDS_MAX) return 3;
+    a.user = L->user;
+    const hipStream_t st = (hipStream_t)L->hip_stream;
+    const size_t lds = (size_t)L->lds_bytes;
+    hipError_t e;
+    if (stretch)
+        e = planned ? launch_fused_ens_small<USER, NDIM, MOVE_STRETCH, true, NB>(L->threads, lds, st, a)
+                    : launch_fused_ens_small<USER, NDIM, MOVE_STRETCH, false, NB>(L->threads, lds, st, a);
+    else
+        e = planned ? launch_fused_ens_small<USER, NDIM, SMALL_ANY_MOVE, true, NB>(L->threads, lds, st, a)
+                    : launch_fused_ens_small<USER, NDIM, SMALL_ANY_MOVE, false, NB>(L->threads, lds, st, a);
+    return e == hipSuccess ? 0 : 100 + (int)e;
+}
+
 }  // namespace emx
 
 #define EMX_FUSED_ENSEMBLE_TARGET(name, Functor, ndim)                                                      \
@@ -498,4 +574,15 @@ int fused_ensemble_blobs_launch(const emx_fused_ensemble_blobs_launch* L) {
 #define EMX_FUSED_ENSEMBLE_TARGET_BLOBS(name, Functor, ndim, nblobs)                                              \
     extern "C" __attribute__((visibility("default"))) int name(const emx_fused_ensemble_blobs_launch* launch) {  \
         return emx::fused_ensemble_blobs_launch<Functor, (ndim), (nblobs)>(launch);                               \
+    }
+
+// opt-in, next to one of the two above: the one-workgroup kernel of an ensemble that fits one workgroup's LDS
+#define EMX_FUSED_ENSEMBLE_SMALL_TARGET(name, Functor, ndim)                                      \
+    extern "C" __attribute__((visibility("default"))) int name(const emx_fused_launch* launch) { \
+        return emx::fused_ensemble_small_launch<Functor, (ndim), 0>(launch);                      \
+    }
+#define EMX_FUSED_ENSEMBLE_SMALL_TARGET_BLOBS(name, Functor, ndim, nblobs)                                                          \
+    extern "C" __attribute__((visibility("default"))) int name(const emx_fused_launch* launch) {                                   \
+        static_assert((nblobs) >= 1, "EMX_FUSED_ENSEMBLE_SMALL_TARGET_BLOBS: 1 <= nblobs <= 32 (none: EMX_FUSED_ENSEMBLE_SMALL_TARGET)"); \
+        return emx::fused_ensemble_small_launch<Functor, (ndim), (nblobs)>(launch);                                                 \
     }

@@ -2167,7 +2167,9 @@ __device__ __forceinline__ double small_dense_qf(const double* tile, const doubl
 }
 
 // One workgroup runs a whole launch of a small ensemble (BATCH: member blockIdx.x of a batch): ensemble, plans and log-probs in LDS.
-// USER (a functor type, emx_fused_target.hpp; void: none): the caller's per-row log-probability compiled into the kernel.  A
+// USER (a functor type; void: none): the caller's per-row log-probability compiled into the kernel -- of a batch
+// (emx_fused_target.hpp, BATCH) or of a single ensemble in either rng mode (emx_fused_ensemble.hpp: !BATCH, the functor's `member`
+// is 0, the chain and blob-plane pointers are those of the launch's first stored row as for the built-in targets).  A
 // half-step is then two passes with a barrier between them, k_batch_cb's structure with barriers for kernel boundaries: every
 // proposal of the split goes to an LDS staging row (small_propose, G lanes a row), then ONE lane a row calls the functor on its
 // staged row, decides and commits.  The functor's time is the model's, so it gets every lane of the workgroup rather than the
@@ -2180,7 +2182,8 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
     constexpr int WPW = 64 / G;
     constexpr bool DENSE = DPB > 0;
     constexpr bool FUSED = !std::is_void<USER>::value;
-    static_assert(!FUSED || (BATCH && !PLANNED && !DENSE), "a fused user target runs in batched Philox launches");
+    static_assert(!FUSED || !DENSE, "a fused user target has no dense form");
+    static_assert(!FUSED || !(BATCH && PLANNED), "batches run in Philox mode only");
     static_assert(NBLOBS == 0 || FUSED, "blobs are a fused user target's");
     constexpr int Dp = DENSE ? DPB * 16 : 16, KK = Dp / 4, RT = Dp + 2, PPT = 16 / WPW;
     const int N = A.N, D = A.D, T = blockDim.x, tid = threadIdx.x, B = A.batch;
@@ -2237,11 +2240,11 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                     double lpn;
                     if constexpr (NBLOBS > 0) {
                         double bl[NBLOBS] = {};
-                        lpn = fused_call_blobs<USER>(Xs + (size_t)t * D, D, (int)blockIdx.x, A.user, bl);
+                        lpn = fused_call_blobs<USER>(Xs + (size_t)t * D, D, (int)M.m(), A.user, bl);
 #pragma unroll
                         for (int k = 0; k < NBLOBS; ++k) bls[(size_t)t * NBLOBS + k] = bl[k];
                     } else {
-                        lpn = fused_call<USER>(Xs + (size_t)t * D, D, (int)blockIdx.x, A.user);
+                        lpn = fused_call<USER>(Xs + (size_t)t * D, D, (int)M.m(), A.user);
                     }
                     if (lpn != lpn) raise_status(M.status(), ST_NAN_LOGP);
                     lps[t] = lpn;
@@ -2374,7 +2377,7 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                         double factor = 0.0;
                         bool badq = false;
                         const int i = orders[pos], j0 = p0s[pos], j1 = p1s[pos], j2 = p2s[pos];
-                        if (MOVESEL == MOVE_GAUSS || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_GAUSS))
+                        if (!PLANNED && (MOVESEL == MOVE_GAUSS || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_GAUSS)))
                             small_propose<G, V, CH, MOVE_GAUSS>(M, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq, &gg);
                         else if (MOVESEL == MOVE_STRETCH || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_STRETCH))
                             small_propose<G, V, CH, MOVE_STRETCH>(M, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq);
@@ -2407,9 +2410,9 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                             if constexpr (NBLOBS > 0) {
 #pragma unroll
                                 for (int k = 0; k < NBLOBS; ++k) bl[k] = 0.0;
-                                lp_new = fused_call_blobs<USER>(qrow, D, (int)blockIdx.x, A.user, bl);
+                                lp_new = fused_call_blobs<USER>(qrow, D, (int)M.m(), A.user, bl);
                             } else {
-                                lp_new = fused_call<USER>(qrow, D, (int)blockIdx.x, A.user);
+                                lp_new = fused_call<USER>(qrow, D, (int)M.m(), A.user);
                             }
                             if (lp_new != lp_new) raise_status(M.status(), ST_NAN_LOGP);
                             const double lnpdiff = fac + lp_new - lps[i];            // red_blue.py:99

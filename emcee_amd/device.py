@@ -279,23 +279,31 @@ class DeviceEnsemble:
         self._ck(self.lib.emx_set_target_callback(self.ctx, fn, C.c_void_p(user_ptr) if not isinstance(user_ptr, C.c_void_p) else user_ptr))
         self._target_kind = _lib.TARGET_CALLBACK
 
-    def set_target_fused(self, fn_ptr, user_address=None, nblobs=0):
+    def set_target_fused(self, fn_ptr, user_address=None, nblobs=0, small_fn=None):
         """A launcher emitted by ``EMX_FUSED_ENSEMBLE_TARGET`` (``emx_fused_ensemble.hpp``) as the target: the user's per-row device
         function runs inside the half-step kernel.  ``fn_ptr``: a ctypes function or an address; ``user_address``: the device
         address its functor receives (None: null).  The library probes the launcher and refuses another header version or ndim.
-        ``nblobs`` > 0: a launcher of ``EMX_FUSED_ENSEMBLE_TARGET_BLOBS`` with that many blobs a sample (another count is refused)."""
+        ``nblobs`` > 0: a launcher of ``EMX_FUSED_ENSEMBLE_TARGET_BLOBS`` with that many blobs a sample (another count is refused).
+        ``small_fn``: the ``EMX_FUSED_ENSEMBLE_SMALL_TARGET[_BLOBS]`` launcher of the same functor (``emx_set_target_fused_small``): an
+        ensemble that fits one workgroup's LDS then runs ``run`` calls in one workgroup; None: none is bound."""
         if isinstance(fn_ptr, (int, np.integer)):
             fn_ptr = C.c_void_p(int(fn_ptr))
         if nblobs:
             fn = fn_ptr if isinstance(fn_ptr, _lib.FUSED_ENSEMBLE_BLOBS_FN) else C.cast(fn_ptr, _lib.FUSED_ENSEMBLE_BLOBS_FN)
             self._touch_target = fn
             self._ck(self.lib.emx_set_target_fused_blobs(self.ctx, fn, C.c_void_p(user_address), int(nblobs)))
-            self._target_kind = _lib.TARGET_FUSED_ENSEMBLE
-            return
-        fn = fn_ptr if isinstance(fn_ptr, _lib.FUSED_ENSEMBLE_FN) else C.cast(fn_ptr, _lib.FUSED_ENSEMBLE_FN)
-        self._touch_target = fn                                 # the library holds the pointer: keep the object alive
-        self._ck(self.lib.emx_set_target_fused(self.ctx, fn, C.c_void_p(user_address)))
+        else:
+            fn = fn_ptr if isinstance(fn_ptr, _lib.FUSED_ENSEMBLE_FN) else C.cast(fn_ptr, _lib.FUSED_ENSEMBLE_FN)
+            self._touch_target = fn                             # the library holds the pointer: keep the object alive
+            self._ck(self.lib.emx_set_target_fused(self.ctx, fn, C.c_void_p(user_address)))
         self._target_kind = _lib.TARGET_FUSED_ENSEMBLE
+        self._small_keep = None
+        if small_fn is not None:
+            if isinstance(small_fn, (int, np.integer)):
+                small_fn = C.c_void_p(int(small_fn))
+            sfn = small_fn if isinstance(small_fn, _lib.FUSED_BATCH_FN) else C.cast(small_fn, _lib.FUSED_BATCH_FN)
+            self._small_keep = sfn
+            self._ck(self.lib.emx_set_target_fused_small(self.ctx, sfn))
 
     def walkers_independent(self):
         """The reference's initial-state check (ensemble.py:653-663) on the ensemble this context holds: nothing crosses PCIe."""
@@ -649,6 +657,12 @@ class DeviceEnsemble:
         self._ck(self.lib.emx_persist_local_launches(self.ctx, C.byref(loc)))
         return {"qualifies": bool(out[0]), "launches": int(out[1]), "halfsteps": int(out[2]), "recovered": int(out[3]),
                 "local_launches": int(loc.value)}
+
+    def small_info(self):
+        """the one-workgroup kernel (include/emx.h emx_small_info): launches since creation and the steps run in them"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.lib.emx_small_info(self.ctx, out))
+        return {"launches": int(out[0]), "steps": int(out[1])}
 
     def mtdev_info(self):
         """exact-mode plans made on the device (include/emx.h emx_mtdev_info)"""

@@ -179,10 +179,19 @@ class DeviceFused(DeviceTarget):
     that returns the log-probability.  They stay on the device next to the chain -- ``get_blobs``, ``get_last_sample().blobs``,
     ``compute_log_prob(x)[1]`` and the returned state's ``.blobs`` read them from there, ``(nsteps, nwalkers, K)``, or ``(nsteps,
     nwalkers)`` for ``K == 1`` -- and the run stays one launch per half-step, the samples those of the blob-free functor.  A
-    launcher compiled for another count is refused when the target is bound; ``WalkMove`` / ``KDEMove`` are refused with blobs."""
+    launcher compiled for another count is refused when the target is bound; ``WalkMove`` / ``KDEMove`` are refused with blobs.
+
+    ``small_fn``: the launcher that ``EMX_FUSED_ENSEMBLE_SMALL_TARGET(name, Functor, ndim)`` (``..._SMALL_TARGET_BLOBS`` with blobs)
+    emits next to ``fn_ptr`` in the same translation unit (:func:`compile_fused_ensemble` does by default).  An ensemble that fits
+    one workgroup's LDS -- the common 32 to a few hundred walkers at 5 to 20 parameters; ``emx_small_fused_check`` of
+    ``include/emx.h`` has the rule -- then runs whole ``run_mcmc`` calls inside one workgroup, one launch per chunk of steps, in both
+    rng modes, with or without blobs, to the same bits -- where that was measured faster (``emx_small_fused_pays``: ndim <= 16 under
+    ``rng="mt19937"``, ndim <= 10 and nwalkers x ndim <= 1 024 under ``rng="philox"``).  Larger ensembles, ``WalkMove`` / ``KDEMove``
+    schedules, a ``GaussianMove`` under ``rng="mt19937"`` and ``sample()`` driven step by step keep the launch per half-step.  None:
+    always that path."""
     kind = _lib.TARGET_FUSED_ENSEMBLE
 
-    def __init__(self, fn_ptr, ndim, user=None, nblobs=0):
+    def __init__(self, fn_ptr, ndim, user=None, nblobs=0, small_fn=None):
         if not isinstance(fn_ptr, ctypes._CFuncPtr):
             addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
             if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
@@ -193,7 +202,11 @@ class DeviceFused(DeviceTarget):
             raise TypeError("DeviceFused's user is a device pointer: None, an integer, a ctypes.c_void_p or a torch CUDA tensor")
         if hasattr(user, "data_ptr") and not getattr(user, "is_cuda", False):
             raise TypeError("DeviceFused's user tensor must live on the GPU (the functor reads it on the device)")
-        self.fn_ptr, self.ndim, self.user = fn_ptr, int(ndim), user
+        if small_fn is not None and not isinstance(small_fn, ctypes._CFuncPtr):
+            addr = small_fn.value if isinstance(small_fn, ctypes.c_void_p) else small_fn
+            if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
+                raise TypeError("DeviceFused's small_fn is an EMX_FUSED_ENSEMBLE_SMALL_TARGET launcher: a ctypes function, a non-null address or None")
+        self.fn_ptr, self.ndim, self.user, self.small_fn = fn_ptr, int(ndim), user, small_fn
         self.nblobs = _check_nblobs("DeviceFused", nblobs)
 
     def user_address(self):
@@ -209,7 +222,7 @@ class DeviceFused(DeviceTarget):
         if ens.ndim != self.ndim:
             raise ValueError("the DeviceFused target was compiled for ndim %d; the sampler has ndim %d" % (self.ndim, ens.ndim))
         if getattr(ens, "_cb_owner", None) is not self or ens._target_kind != self.kind:
-            ens.set_target_fused(self.fn_ptr, self.user_address(), self.nblobs)
+            ens.set_target_fused(self.fn_ptr, self.user_address(), self.nblobs, small_fn=self.small_fn)
             ens._cb_owner = self
 
     def __call__(self, x):
@@ -403,22 +416,25 @@ def _compile_cached(what, header, source, tail, key_parts, name, flags, cache_di
 
 class DeviceFusedLibrary(object):
     """What :func:`compile_fused_ensemble` built: ``path`` of the shared library, ``lib`` (its ``ctypes.CDLL``: the user's own
-    ``extern "C"`` setup functions of ``source`` are there), ``name`` of the launcher, ``ndim``, ``nblobs``, and :meth:`target`."""
+    ``extern "C"`` setup functions of ``source`` are there), ``name`` of the launcher, ``ndim``, ``nblobs``, ``small_name`` /
+    ``small_launcher`` (the one-workgroup launcher, None when it was built with ``small=False``) and :meth:`target`."""
 
-    def __init__(self, path, name, ndim, nblobs=0):
+    def __init__(self, path, name, ndim, nblobs=0, small_name=None):
         self.path, self.name, self.ndim, self.nblobs = path, name, int(ndim), _check_nblobs("DeviceFusedLibrary", nblobs)
         _lib.load()                       # one HIP runtime per process: the library's (torch's) first
         self.lib = ctypes.CDLL(path)
         self.launcher = getattr(self.lib, name)
+        self.small_name = small_name
+        self.small_launcher = getattr(self.lib, small_name) if small_name else None
 
     def target(self, user=None):
         """-> :class:`DeviceFused` of the compiled functor with the device pointer ``user``"""
-        t = DeviceFused(self.launcher, self.ndim, user, nblobs=self.nblobs)
+        t = DeviceFused(self.launcher, self.ndim, user, nblobs=self.nblobs, small_fn=self.small_launcher)
         t._library = self                 # the launcher's code lives as long as the target
         return t
 
 
-def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir=None, nblobs=0):
+def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir=None, nblobs=0, small=True):
     """Compile the user's model into the single sampler's half-step kernel -> :class:`DeviceFusedLibrary`.
 
     ``source``: HIP C++ that defines the functor type ``functor`` -- ``__device__ double operator()(const double* x, int ndim, int
@@ -429,7 +445,11 @@ def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir
     compiler failure raises ``RuntimeError`` with the compiler's last lines.
 
     ``nblobs = K > 0``: the functor has the five-argument form ``(x, ndim, member, user, double* blobs)`` and the translation unit
-    ends in ``EMX_FUSED_ENSEMBLE_TARGET_BLOBS(name, functor, ndim, K)`` -- the source :func:`compile_fused` takes with ``nblobs``."""
+    ends in ``EMX_FUSED_ENSEMBLE_TARGET_BLOBS(name, functor, ndim, K)`` -- the source :func:`compile_fused` takes with ``nblobs``.
+
+    ``small`` (default True): the translation unit also ends in ``EMX_FUSED_ENSEMBLE_SMALL_TARGET[_BLOBS](name_small, functor, ndim[,
+    K])``, the one-workgroup launcher of ensembles that fit one workgroup's LDS (:class:`DeviceFused`'s ``small_fn``; four more
+    kernels to compile, about 2 s more).  ``small=False`` builds the library without it: the translation unit it always was."""
     nblobs = _check_nblobs("compile_fused_ensemble", nblobs)
     ndim = int(ndim)
     if ndim < 1 or ndim > 256:
@@ -444,8 +464,14 @@ def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir
     if nblobs:                            # (a blob-free build keeps the key, and with it the cached library, it always had)
         tail = "EMX_FUSED_ENSEMBLE_TARGET_BLOBS(%s, %s, %d, %d)" % (name, functor, ndim, nblobs)
         key += ("nblobs", nblobs)
+    small_name = name + "_small" if small else None
+    if not small:                         # (the default build keeps the form of key it always had; the headers are part of its hash)
+        key += ("half-step launcher only",)
+    else:
+        tail += ("\nEMX_FUSED_ENSEMBLE_SMALL_TARGET_BLOBS(%s, %s, %d, %d)" % (small_name, functor, ndim, nblobs) if nblobs else
+                 "\nEMX_FUSED_ENSEMBLE_SMALL_TARGET(%s, %s, %d)" % (small_name, functor, ndim))
     so = _compile_cached("compile_fused_ensemble", "emx_fused_ensemble.hpp", source, tail, key, name, flags, cache_dir)
-    return DeviceFusedLibrary(so, name, ndim, nblobs)
+    return DeviceFusedLibrary(so, name, ndim, nblobs, small_name)
 
 
 class PTFusedLibrary(object):

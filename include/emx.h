@@ -107,7 +107,8 @@ int emx_status(emx_ctx* ctx, uint32_t* bits);
  *   "graph"                    0         1: a 16-step block of Philox launches replayed as a hipGraph
  *   "prep_hint"                1         steps a caller of emx_step_begin will take (Philox plan batch size)
  *   "full_plan"                0         1: Philox plans carry every column (default: the ones the step's fused kernel reads)
- *   "small_kernel"             1         ensembles that fit one workgroup's LDS run whole emx_run calls in one workgroup
+ *   "small_kernel"             1         ensembles that fit one workgroup's LDS run whole emx_run calls in one workgroup (2: a fused
+ *                                        user target's too wherever they fit, not only where that is faster: emx_small_fused_pays)
  *   "gauss_materialize"        0         Gaussian move: 1: proposals through memory (parity tests of the register form)
  *   -- dense targets --
  *   "dense_wide"               0         1: the propose / log-prob / commit path whatever the ndim; 2: ... with the single-role log-prob kernel
@@ -196,8 +197,9 @@ int emx_set_target_callback(emx_ctx* ctx, emx_device_log_prob_fn fn, void* user)
  * was not compiled in, 5: args that carry an exchange, a graph descriptor or a device-side slot count, 100 + a hipError_t: the
  * launch failed).  emx_set_target_fused probes once, so a mismatch surfaces at bind time (-8 and "built against another version of
  * emx_fused_ensemble.hpp").  `user_dev`: a device pointer handed to the functor with every row; the caller keeps it alive.
- * Such a context always runs one launch per half-step (never the one-workgroup kernel, the persistent kernels or a step graph),
- * in either rng mode; results are bit for bit those of emx_set_target_callback with the same function.  One replica only:
+ * Such a context runs one launch per half-step (never the persistent kernels or a step graph) in either rng mode -- or, with a
+ * one-workgroup launcher bound and an ensemble that fits (emx_set_target_fused_small below), one launch per chunk of steps;
+ * results are bit for bit those of emx_set_target_callback with the same function either way.  One replica only:
  * emx_set_shard / emx_comm_init on such a context, and this call on a sharded one, are refused. */
 typedef struct emx_fused_ensemble_launch {
     uint32_t abi;            /* EMX_FUSED_ENSEMBLE_ABI the library was built with */
@@ -234,6 +236,34 @@ typedef struct emx_fused_ensemble_blobs_launch {
 } emx_fused_ensemble_blobs_launch;
 typedef int (*emx_fused_ensemble_blobs_fn)(const emx_fused_ensemble_blobs_launch*);
 int emx_set_target_fused_blobs(emx_ctx* ctx, emx_fused_ensemble_blobs_fn launcher, const void* user, int32_t nblobs);
+/* Small ensembles of a fused user target: whole emx_run calls inside ONE workgroup (k_small_run around the caller's functor:
+ * ensemble, plans, log-probs and blobs in LDS), one launch per chunk of up to 4 096 steps where the half-step launcher takes two
+ * launches a step, in both rng modes, bit for bit the same chain.  Opt-in: the caller's translation unit also emits
+ * EMX_FUSED_ENSEMBLE_SMALL_TARGET(name, Functor, ndim) or ..._SMALL_TARGET_BLOBS(name, Functor, ndim, nblobs) (four more kernels to
+ * compile), and the launcher is bound here AFTER emx_set_target_fused[_blobs], which keeps the initial log-probs, every evaluation
+ * of rows and the ensembles that do not fit (binding a target unbinds the small launcher; NULL unbinds it).  The descriptor is
+ * emx_fused_launch (below, with the batch targets) with `args` the library's SmallRunArgs, `abi` EMX_FUSED_ENSEMBLE_SMALL_ABI of
+ * emx_fused_ensemble.hpp -- a constant of its own, so a batch launcher is refused, never run --, grid 1 (0: the probe)
+ * and `reserved` 1 when the plans are those of the host's MT19937 twin (exact mode), 0 for Philox plans.  Answers: emx_fused_batch_fn's.
+ * The probe checks version, ndim and the context's blob count: -8 / -1 with the wording of the other fused binds.
+ * The one-workgroup path CAN be taken when emx_small_fused_check accepts the shape: "small_kernel" on, one replica, StretchMove / DEMove
+ * (every complement >= 2) / DESnookerMove, a GaussianMove in Philox mode only (WalkMove / KDEMove keep the half-step path), and
+ *   small_lds_bytes(N, ndim) + small_fused_stage_bytes(largest split, ndim) + small_blob_bytes(N, nblobs) <= 150 KB
+ * (emx_small_host.hpp).  It IS taken where it also pays (emx_small_fused_pays: one lane a row calls the functor and commits, so the
+ * kernel's step time grows with ndim -- measured, profiles/ensemble_fused_small.md: with Philox plans ndim <= 10 and nwalkers x ndim
+ * <= 1 024, with the host's MT19937 plans ndim <= 16), or wherever it fits with the tuning key "small_kernel" = 2 (tests,
+ * experiments).  Otherwise, for emx_step_begin steps and for an emx_run of a single step, nothing changes. */
+struct emx_fused_launch;
+typedef int (*emx_fused_small_fn)(const struct emx_fused_launch*);      /* an emx_fused_batch_fn */
+int emx_set_target_fused_small(emx_ctx* ctx, emx_fused_small_fn small_launcher);
+/* the rule above as a host-only predicate (rng_mode: EMX_RNG_*): 0, or -1 and the reason in msg */
+int emx_small_fused_check(int64_t nwalkers, int32_t ndim, int32_t nmoves, const emx_move_desc* moves, int32_t rng_mode, int32_t nblobs,
+                          char* msg, int32_t msglen);
+/* 1 where the one-workgroup kernel of a fused user target is the faster path at this shape and rng mode (host only), else 0 */
+int emx_small_fused_pays(int64_t nwalkers, int32_t ndim, int32_t rng_mode);
+/* the one-workgroup kernel of this context, any target: out[0] launches and out[1] the steps run in them since emx_create;
+ * out[2], out[3]: 0 */
+int emx_small_info(emx_ctx* ctx, int64_t out[4]);
 /* the walkers' current blobs (N, nblobs) of such a context: nblobs_out (may be NULL) receives the count, 0 without blobs; out may
  * be NULL to ask for the count alone */
 int emx_get_blobs(emx_ctx* ctx, double* out, int32_t* nblobs_out);
@@ -634,7 +664,7 @@ typedef struct emx_fused_launch {
     const void* args;        /* SmallRunArgs */
     const void* user;        /* user_dev */
     int32_t nblobs;          /* blobs a sample of the handle's target (0: none); the launcher answers 4 when it was compiled for another count */
-    int32_t reserved;        /* 0 */
+    int32_t reserved;        /* batches: 0.  emx_set_target_fused_small: 1 when args carries the host's plans (exact MT19937 mode) */
 } emx_fused_launch;
 typedef int (*emx_fused_batch_fn)(const emx_fused_launch*);     /* 0, or non-zero and nothing launched */
 int emx_set_batch_target_fused(emx_batch* b, emx_fused_batch_fn fn, int32_t ndim_compiled, const void* user_dev);

@@ -1,6 +1,9 @@
 """us per step of ONE user model -- a diagonal Gaussian with its data behind `user` -- run three ways through EnsembleSampler:
 
-  fused    targets.DeviceFused: the functor compiled into the half-step kernel (one launch a half-step)
+  fused    targets.DeviceFused: the functor compiled into the half-step kernel (one launch a half-step) and, where the ensemble
+           fits one workgroup's LDS and that is the faster path, into the one-workgroup kernel (one launch a chunk of steps)
+  fused_small     the same target with the tuning key small_kernel = 2: the one-workgroup kernel wherever the ensemble fits
+  fused_general   the same target with the tuning key small_kernel = 0: always one launch a half-step
   kernel   targets.DeviceKernel: the same function behind an emx_device_log_prob_fn (three launches a half-step)
   builtin  targets.DiagGaussian: the library's own closed form (the distance left to a built-in target)
 
@@ -9,8 +12,9 @@
 
     python tools/ensemble_fused_bench.py [--modes fused,kernel,builtin,host] [--shapes 65536x64,4096x16,1048576x32] [--seconds 1.5]
                                          [--nblobs 1,4,32] [--store] [--flags="-IDIR ..."] [--out FILE]
+                                         [--rng philox|mt19937] [--moves stretch|de+snooker] [--block STEPS]
 
-Philox mode, blocks of steps timed by a host clock around a device synchronise; the median of at least `--seconds`
+`--rng` picks the plans (default Philox), `--moves` the schedule (default one StretchMove; de+snooker: a 0.6 / 0.4 mixture).  Blocks of steps timed by a host clock around a device synchronise; the median of at least `--seconds`
 of blocks per mode, the modes of a shape taken in alternation so that drift of the machine hits them alike.  store=False unless
 `--store`: then every step appends chain, log-probs and blobs, the sampler is reset before each block (the chain keeps its
 allocation) and a block is as many steps as fit 4 GB of chain.  `--modes kernel` needs
@@ -123,6 +127,9 @@ def main():
     ap.add_argument("--store", action="store_true", help="store the chain (and the blobs): the sampler is reset before every block")
     ap.add_argument("--cache", default=None, help="directory of compiled user libraries (default: a temporary one)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--block", type=int, default=0, help="steps a timed block (default: some tens of milliseconds of the large shapes, 2 000 at most)")
+    ap.add_argument("--rng", default="philox", choices=["philox", "mt19937"])
+    ap.add_argument("--moves", default="stretch", choices=["stretch", "de+snooker"])
     a = ap.parse_args()
     modes = a.modes.split(",") + ["fused+%d" % int(k) for k in a.nblobs.split(",") if k]
     work = a.cache or tempfile.mkdtemp(prefix="ensemble_fused_bench_")
@@ -140,7 +147,7 @@ def main():
         samplers = {}
         for mode in modes:
             kw = {}
-            if mode == "fused":
+            if mode in ("fused", "fused_small", "fused_general"):
                 lib = targets.compile_fused_ensemble(MODEL, "DiagModel", D, flags=a.flags.split(), cache_dir=work)
                 t = lib.target(user=dev)
             elif mode.startswith("fused+"):
@@ -157,10 +164,16 @@ def main():
                 t = targets.DeviceKernel(cb.diag_rows, dev)
             else:
                 t = targets.DiagGaussian(mu, ivar)
-            s = emcee_amd.EnsembleSampler(N, D, t, rng="philox", **kw)
+            if a.moves == "de+snooker":
+                kw["moves"] = [(emcee_amd.moves.DEMove(), 0.6), (emcee_amd.moves.DESnookerMove(), 0.4)]
+            s = emcee_amd.EnsembleSampler(N, D, t, rng=a.rng, **kw)
             s._random.seed(3)
+            if mode in ("fused_small", "fused_general"):
+                s._device_ensemble().set_tuning("small_kernel", 2 if mode == "fused_small" else 0)
             samplers[mode] = [s, s.run_mcmc(p0, 16, store=a.store, skip_initial_state_check=True), [], 16]
         block = max(32, min(2000, int(6.4e9 / (N * D)) // 16 * 16))      # some tens of milliseconds a block
+        if a.block > 0:
+            block = a.block
         if a.store:
             block = max(16, min(block, int(4e9 / (N * D * 8)) // 16 * 16))
 
@@ -192,7 +205,9 @@ def main():
         for mode in modes:
             v = np.sort(np.array(samplers[mode][2])) * 1e6
             acc = float(np.mean(samplers[mode][0]._ens.accepted_mask()))
-            rec = dict(shape=shape, mode=mode, flags=a.flags, store=bool(a.store), us_per_step=float(np.median(v)), p10=float(v[int(0.1 * (len(v) - 1))]),
+            ens = samplers[mode][0]._ens
+            small = ens.small_info()["launches"] if hasattr(ens, "small_info") else None
+            rec = dict(shape=shape, mode=mode, rng=a.rng, moves=a.moves, small_launches=small, flags=a.flags, store=bool(a.store), us_per_step=float(np.median(v)), p10=float(v[int(0.1 * (len(v) - 1))]),
                        p90=float(v[int(np.ceil(0.9 * (len(v) - 1)))]), blocks=len(v), steps_per_block=block if mode != "host" else 4, steps_total=samplers[mode][3],
                        last_accept_fraction=acc)
             lines.append(json.dumps(rec))
