@@ -236,6 +236,8 @@ SIGNATURES = {
     "emx_autocorr_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double, _dp, _ip, C.POINTER(C.c_int64)]),
     "emx_summary_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int32, _P, _P, _P, _P,
                                     C.POINTER(C.c_int64)]),
+    "emx_summary": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "emx_summary_info": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "emx_host_order_stats": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int32, _i64p, _dp]),
     "emx_set_batch_target_fused_blobs": (C.c_int, [_P, FUSED_BATCH_FN, C.c_int32, _P, C.c_int32]),
     "emx_set_batch_target_callback_blobs": (C.c_int, [_P, BATCH_LOG_PROB_BLOBS_FN, _P, C.c_int32]),

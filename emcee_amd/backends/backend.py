@@ -8,6 +8,7 @@ through ``Move.propose``) it is a plain in-memory store with the reference's ``s
 import numpy as np
 
 from .. import autocorr
+from .. import summary as _summary
 from .._lib import EmxError
 from ..state import State
 
@@ -192,6 +193,72 @@ class Backend(object):
                 return thin * tau_est
         x = self.get_chain(discard=discard, thin=thin)
         return thin * autocorr.integrated_time(x, **kwargs)
+
+    COV_MAX_DEVICE = 256        # columns of emx_summary's covariance
+
+    def get_summary(self, discard=0, thin=1, quantiles=(0.16, 0.5, 0.84), cov=True):
+        """-> :class:`~emcee_amd.summary.BatchSummary` of the stored samples over the steps of ``get_chain(discard=discard,
+        thin=thin)`` and all walkers: ``nsamples``, ``mean`` ``(ndim,)``, ``cov`` ``(ndim, ndim)`` (``np.cov(flat.T)``, exactly
+        symmetric; None with ``cov=False``), ``quantiles`` ``(nq, ndim)`` (``np.quantile``'s default rule, at most 16),
+        ``map_coords`` ``(ndim,)`` / ``map_log_prob``: the stored sample with the largest stored log-prob, the earliest step and
+        then the lowest walker among equals.
+
+        A device-resident chain is reduced where it lives (``emx_summary``): only these numbers cross to the host.  A chain on
+        the host (user-written moves, Python blobs) is reduced with NumPy into the same tuple, and so is a device chain whose
+        call fails (no room for the scratch next to a long chain).  On the device ``cov=True`` needs ``ndim <= 256``."""
+        return self._summary("chain", discard, thin, quantiles, cov)
+
+    def get_blob_summary(self, discard=0, thin=1, quantiles=(0.16, 0.5, 0.84), cov=True):
+        """-> :class:`~emcee_amd.summary.BatchSummary` of the stored BLOBS: what :meth:`get_summary` returns with the blobs of
+        a sample in its coordinates' place (``map_coords``: the blobs of the sample with the largest stored log-prob).  The blob
+        plane of a ``DeviceFused`` target is reduced on the device; blobs kept on the host must be plain floats of shape
+        ``(nsteps, nwalkers)`` or ``(nsteps, nwalkers, K)`` (``TypeError`` otherwise).  ``ValueError`` when there are no blobs."""
+        return self._summary("blobs", discard, thin, quantiles, cov)
+
+    def _summary(self, name, discard, thin, quantiles, cov):
+        if int(thin) != thin or thin < 1:
+            raise ValueError("thin must be an integer >= 1; got %r" % (thin,))
+        if int(discard) != discard or discard < 0:
+            raise ValueError("discard must be an integer >= 0; got %r" % (discard,))
+        q = _summary.check_quantiles(quantiles)
+        thin, discard = int(thin), int(discard)
+        it = self.iteration if self.initialized else 0
+        if it <= 0:
+            raise AttributeError("you must run the sampler with 'store == True' before accessing the results")
+        if name == "blobs" and not self.has_blobs():
+            raise ValueError("the target has no blobs (nblobs = 0): there is no blob plane to summarise")
+        start = min(discard + thin - 1, it)                 # reference backend.py:53
+        nt = len(range(start, it, thin))
+        if nt < 1:
+            raise ValueError("discard = %d, thin = %d select none of the %d stored steps" % (discard, thin, it))
+        n = nt * self.nwalkers
+        ranks, ilo, ihi, g = _summary.plan_ranks(n, q)
+        on_device = self._dev is not None and (name == "chain" or self._dev_nblobs())
+        if on_device:
+            width = self.ndim if name == "chain" else self._dev_nblobs()
+            if cov and width > self.COV_MAX_DEVICE:
+                raise ValueError("the covariance of %d columns is not computed on the device (at most %d): pass cov=False"
+                                 % (width, self.COV_MAX_DEVICE))
+            try:
+                nd, mean, c, order, mx, mlp = self._dev.summary(start, it, thin, ranks, cov, 0 if name == "chain" else 2)
+            except EmxError as e:
+                autocorr.logger.debug("device summary unavailable (%s): NumPy on a copy of the chain", e)
+            else:
+                assert nd == n
+                return _summary.BatchSummary(n, mean, c, _summary.interpolate(order[None], ilo, ihi, g)[0], mx, mlp)
+        x = self.get_value(name, discard=discard, thin=thin, flat=True)
+        if name == "blobs":
+            x = np.asarray(x)
+            if x.dtype.kind != "f" or x.ndim not in (1, 2):
+                raise TypeError("get_blob_summary needs plain float blobs of shape (nsteps, nwalkers) or (nsteps, nwalkers, K); "
+                                "got dtype %s, shape %s a step" % (x.dtype, x.shape[1:]))
+        x = np.asarray(x, dtype=np.float64).reshape(n, -1)
+        lp = np.asarray(self.get_value("log_prob", discard=discard, thin=thin, flat=True))
+        at = int(np.argmax(lp))                             # the first maximum in (step, walker) order
+        with np.errstate(invalid="ignore", divide="ignore"):
+            c = np.atleast_2d(np.cov(x.T)) if cov and n > 1 else np.full((x.shape[1], x.shape[1]), np.nan) if cov else None
+        qs = np.quantile(x, q, axis=0) if len(q) else np.empty((0, x.shape[1]))
+        return _summary.BatchSummary(n, x.mean(axis=0), c, qs, x[at].copy(), float(lp[at]))
 
     @property
     def shape(self):

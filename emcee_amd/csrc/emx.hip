@@ -438,6 +438,8 @@ struct emx_ctx {
     // chain
     double *chain = nullptr, *chain_lp = nullptr;
     int64_t cap = 0, stored = 0, proposals = 0;
+    EnsSummary* summary = nullptr;        // emx_summary's scratch (emx_batch_summary.hip)
+    int64_t tune_summary_compact = 1;     // emx_summary: passes 2 ... 7 of the selection on a compacted list: 0 never, 1 where a quarter or less is left, 2 always
     // split-phase buffers
     double *qout = nullptr, *fout = nullptr, *newlp = nullptr;
     double* tp1_full = nullptr;        // dense target, ndim <= 112: the full image the wide-target kernels read (tuning "dense_wide")
@@ -1213,7 +1215,20 @@ int emx_internal_chain_view(emx_ctx* c, EmxChainView* v) {
     v->stored = c->stored;
     v->stream = c->stream;
     v->device = c->device;
+    v->chain_blobs = c->blob_plane;
+    v->nblobs = c->nblobs;
+    v->cap = c->cap;
+    v->summary_compact = c->tune_summary_compact;
+    v->summary = &c->summary;
     return 0;
+}
+
+int emx_internal_settle(emx_ctx* c) {
+    if (!c) {
+        g_err = "null context";
+        return -1;
+    }
+    return persist_settle(c);
 }
 
 int emx_internal_state_view(emx_ctx* c, const double** X, int64_t* N, int32_t* D, int* device) {
@@ -1396,6 +1411,7 @@ int emx_destroy(emx_ctx* c) {
         if (s) hipFree(s);
     for (double* s : {c->blobs, c->evalblobs, c->blob_plane})
         if (s) hipFree(s);
+    emx_internal_ens_summary_release(c->summary);
 
     for (auto& s : c->ring) {
         if (s.order) hipFree(s.order);       // the slot's single block
@@ -1617,6 +1633,10 @@ int emx_set_tuning(emx_ctx* c, const char* key, int64_t v) {
     }
     if (!strcmp(key, "persist_slab_local_max_walkers")) {
         c->tune_persist_slab_local_max = v;
+        return 0;
+    }
+    if (!strcmp(key, "summary_compact")) {   // emx_summary's selection: 0 never a compacted list, 1 auto, 2 wherever it fits
+        c->tune_summary_compact = v < 0 ? 0 : (v > 2 ? 2 : v);
         return 0;
     }
     if (!strcmp(key, "persist_odd")) {       // 0: odd ndim on the per-half-step launches

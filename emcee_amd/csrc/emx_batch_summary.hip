@@ -415,6 +415,9 @@ __global__ __launch_bounds__(64) void k_bsum_scan(u64* __restrict__ prefix, int6
     }
 }
 
+// ---- one ensemble's chain (emx_summary) -----------------------------------------------------------------------------------
+#include "emx_summary_single.hpp"
+
 // ---- host -----------------------------------------------------------------------------------------------------------
 int sfail(emx_batch* b, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 int sfail(emx_batch* b, int code, const char* fmt, ...) {
@@ -442,6 +445,36 @@ int grow(emx_batch* b, Buf& u, size_t bytes, const char* what) {
     return 0;
 }
 
+int efail(emx_ctx* c, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
+int efail(emx_ctx* c, int code, const char* fmt, ...) {
+    char buf[384];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return emx_internal_fail(c, code, buf);
+}
+
+int egrow(emx_ctx* c, Buf& u, size_t bytes, const char* what) {
+    if (bytes <= u.bytes) return 0;
+    if (u.p) hipFree(u.p);
+    u.p = nullptr;
+    u.bytes = 0;
+    const hipError_t e = hipMalloc(&u.p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return efail(c, -2, "emx_summary: %s allocation (%zu bytes): %s", what, bytes, hipGetErrorString(e));
+    }
+    u.bytes = bytes;
+    return 0;
+}
+
+#define ESUM_HIP(what, expr)                                                                                           \
+    do {                                                                                                               \
+        const hipError_t e_ = (expr);                                                                                  \
+        if (e_ != hipSuccess) return efail(c, -2, "emx_summary: %s: %s", what, hipGetErrorString(e_));                 \
+    } while (0)
+
 #define SUM_HIP(what, expr)                                                                                            \
     do {                                                                                                               \
         const hipError_t e_ = (expr);                                                                                  \
@@ -462,8 +495,234 @@ void emx_internal_batch_summary_release(BatchSummary* s) {
     delete s;
 }
 
+struct EnsSummary {
+    Buf part, fold, gpart, gfold, mean, cov, order, map_x, map_lp, map_pv, map_pi, hist, prefix, rem, slotof, slotpf, nlead, info, ranks, lkey, ldim;
+    int64_t sel_reads = 0, listed = -1, list_reads = 0;      // the last call's selection (emx_summary_info)
+};
+
+void emx_internal_ens_summary_release(EnsSummary* s) {
+    if (!s) return;
+    for (Buf* u : {&s->part, &s->fold, &s->gpart, &s->gfold, &s->mean, &s->cov, &s->order, &s->map_x, &s->map_lp, &s->map_pv, &s->map_pi,
+                   &s->hist, &s->prefix, &s->rem, &s->slotof, &s->slotpf, &s->nlead, &s->info, &s->ranks, &s->lkey, &s->ldim})
+        if (u->p) hipFree(u->p);
+    delete s;
+}
+
+namespace {
+
+// `count` partials of `width` doubles in a -> one, by k_esum_fold levels between a and b; *out: where it is
+int es_fold(emx_ctx* c, hipStream_t st, double* a, double* b, int64_t count, int64_t width, const double** out) {
+    while (count > 1) {
+        const int64_t groups = (count + ES_FOLD - 1) / ES_FOLD;
+        hipLaunchKernelGGL(k_esum_fold, dim3((unsigned)((width + 255) / 256), (unsigned)groups), dim3(256), 0, st, (const double*)a, b, count, width);
+        ESUM_HIP("fold launch", hipGetLastError());
+        std::swap(a, b);
+        count = groups;
+    }
+    *out = a;
+    return 0;
+}
+
+size_t es_hist_lds(int DT, int ns) { return (size_t)((DT * ns * 257 + 1) & ~1) * 4 + (size_t)DT * ns * 8; }
+
+}  // namespace
+
 #pragma GCC visibility push(default)
 extern "C" {
+
+int emx_summary(emx_ctx* c, int32_t plane, int64_t start, int64_t stop, int64_t stride, double* mean_out, double* cov_out, int32_t nranks,
+                const int64_t* ranks, double* order_out, double* map_coords_out, double* map_log_prob_out, int64_t* nsamples_out) {
+    if (const int rc = emx_internal_settle(c)) return rc;
+    EmxChainView v;
+    if (const int rc = emx_internal_chain_view(c, &v)) return rc;
+    if (plane != 0 && plane != 2) return efail(c, -1, "emx_summary: plane 0 (coordinates) or 2 (blobs); got %d", plane);
+    const double* X = v.chain;
+    int64_t W = v.D;
+    if (plane == 2) {
+        if (v.nblobs < 1) return efail(c, -1, "emx_summary: the context's target has no blobs");
+        X = v.chain_blobs;
+        W = v.nblobs;
+    }
+    if (!X || !v.chain_lp || v.stored <= 0) return efail(c, -1, "emx_summary: no stored chain (emx_chain_config + stored steps)");
+    if (stride < 1 || start < 0 || stop > v.stored) return efail(c, -1, "emx_summary: rows need 0 <= start, stop <= stored, stride >= 1");
+    const int64_t nt = start < stop ? (stop - start + stride - 1) / stride : 0;
+    const int64_t N = v.N, NW = N * W, n = nt * N;
+    if (nsamples_out) *nsamples_out = n;
+    if (nt < 1) return efail(c, -1, "emx_summary: the selection is empty");
+    if (nranks < 0 || nranks > SEL_MAX_RANKS || (nranks > 0 && !ranks)) return efail(c, -1, "emx_summary: 0 ... %d ranks", SEL_MAX_RANKS);
+    for (int r = 0; r < nranks; ++r)
+        if (ranks[r] < 0 || ranks[r] >= n) return efail(c, -1, "emx_summary: rank %lld outside [0, %lld)", (long long)ranks[r], (long long)n);
+    const bool want_cov = cov_out != nullptr, want_mean = mean_out != nullptr || want_cov;
+    const bool want_sel = order_out != nullptr && nranks > 0, want_map = map_coords_out != nullptr || map_log_prob_out != nullptr;
+    if (want_cov && W > ES_COV_MAX_W) return efail(c, -1, "emx_summary: the covariance is computed for at most %d columns; got %lld", ES_COV_MAX_W, (long long)W);
+    const int nr = want_sel ? nranks : 0;
+
+    ESUM_HIP("hipSetDevice", hipSetDevice(v.device));
+    if (!*v.summary) *v.summary = new EnsSummary();
+    EnsSummary* a = *v.summary;
+    const hipStream_t st = v.stream;
+    ESel g;
+    g.x = X + start * NW;
+    g.lp = v.chain_lp + start * N;
+    g.N = N;
+    g.NW = NW;
+    g.rowstep = stride * NW;
+    g.lprowstep = stride * N;
+    g.n = n;
+    g.nt = nt;
+    g.W = (int32_t)W;
+    Sel fin;                   // what the batch's finishing kernels read: one member, one slice
+    std::memset(&fin, 0, sizeof fin);
+    fin.N = N;
+    fin.nt = nt;
+    fin.D = (int32_t)W;
+    fin.S = 1;
+
+    if (want_mean) {
+        const int64_t C = es_chunk(n, ES_MAX_CHUNKS), G = (n + C - 1) / C;
+        const int CW = (int)std::min<int64_t>(W, 256);
+        if (int rc = egrow(c, a->part, (size_t)G * W * 8, "mean partials")) return rc;
+        if (int rc = egrow(c, a->fold, (size_t)((G + ES_FOLD - 1) / ES_FOLD) * W * 8, "mean partials")) return rc;
+        if (int rc = egrow(c, a->mean, (size_t)W * 8, "mean")) return rc;
+        hipLaunchKernelGGL(k_esum_mean_part, dim3((unsigned)G, (unsigned)((W + CW - 1) / CW)), dim3(256), 0, st, g, C, CW, (double*)a->part.p);
+        ESUM_HIP("mean launch", hipGetLastError());
+        const double* sum = nullptr;
+        if (int rc = es_fold(c, st, (double*)a->part.p, (double*)a->fold.p, G, W, &sum)) return rc;
+        hipLaunchKernelGGL(k_esum_mean_fin, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, sum, (double*)a->mean.p, (int)W, n);
+        ESUM_HIP("mean launch", hipGetLastError());
+        if (mean_out) ESUM_HIP("copy", hipMemcpyAsync(mean_out, a->mean.p, (size_t)W * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (want_cov) {
+        const bool mfma = W >= 16;
+        const int Dp = (int)((W + 15) / 16 * 16), DPB = Dp / 16, NP = DPB * (DPB + 1) / 2, P = (int)(W * (W + 1) / 2);
+        const int64_t width = mfma ? (int64_t)NP * 256 : P;
+        const int64_t gmax = std::min<int64_t>(ES_MAX_CHUNKS, std::max<int64_t>(64, ((int64_t)256 << 20) / (width * 8)));
+        const int64_t C = es_chunk(n, gmax), G = (n + C - 1) / C;
+        if (int rc = egrow(c, a->gpart, (size_t)G * width * 8, "Gram partials")) return rc;
+        if (int rc = egrow(c, a->gfold, (size_t)((G + ES_FOLD - 1) / ES_FOLD) * width * 8, "Gram partials")) return rc;
+        if (int rc = egrow(c, a->cov, (size_t)W * W * 8, "covariance")) return rc;
+        if (mfma)
+            hipLaunchKernelGGL(k_esum_gram_mfma, dim3((unsigned)((NP + GM_PAIRS_WG - 1) / GM_PAIRS_WG), (unsigned)G), dim3(256), 0, st, g, C,
+                               (const double*)a->mean.p, (double*)a->gpart.p, Dp, NP);
+        else
+            hipLaunchKernelGGL(k_esum_gram_small, dim3((unsigned)G), dim3(256), 0, st, g, C, (const double*)a->mean.p, (double*)a->gpart.p);
+        ESUM_HIP("Gram launch", hipGetLastError());
+        const double* sum = nullptr;
+        if (int rc = es_fold(c, st, (double*)a->gpart.p, (double*)a->gfold.p, G, width, &sum)) return rc;
+        if (mfma)
+            hipLaunchKernelGGL(k_bsum_gram_fin_mfma, dim3((unsigned)NP), dim3(256), 0, st, fin, sum, (double*)a->cov.p, (int64_t)1, Dp, NP);
+        else
+            hipLaunchKernelGGL(k_bsum_gram_fin_small, dim3(1), dim3(256), 0, st, fin, sum, (double*)a->cov.p, (int64_t)1);
+        ESUM_HIP("Gram launch", hipGetLastError());
+        ESUM_HIP("copy", hipMemcpyAsync(cov_out, a->cov.p, (size_t)W * W * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (want_map) {
+        const int np = (int)std::min<int64_t>((n + 4095) / 4096, 2048);
+        if (int rc = egrow(c, a->map_pv, (size_t)2048 * 8, "MAP partials")) return rc;
+        if (int rc = egrow(c, a->map_pi, (size_t)2048 * 8, "MAP partials")) return rc;
+        if (int rc = egrow(c, a->map_x, (size_t)W * 8, "MAP coordinates")) return rc;
+        if (int rc = egrow(c, a->map_lp, 8, "MAP log-prob")) return rc;
+        hipLaunchKernelGGL(k_esum_map_part, dim3((unsigned)np), dim3(256), 0, st, g, (double*)a->map_pv.p, (int64_t*)a->map_pi.p);
+        ESUM_HIP("MAP launch", hipGetLastError());
+        hipLaunchKernelGGL(k_esum_map_fin, dim3(1), dim3(256), 0, st, g, (const double*)a->map_pv.p, (const int64_t*)a->map_pi.p, np,
+                           (double*)a->map_x.p, (double*)a->map_lp.p);
+        ESUM_HIP("MAP launch", hipGetLastError());
+        if (map_coords_out) ESUM_HIP("copy", hipMemcpyAsync(map_coords_out, a->map_x.p, (size_t)W * 8, hipMemcpyDeviceToHost, st));
+        if (map_log_prob_out) ESUM_HIP("copy", hipMemcpyAsync(map_log_prob_out, a->map_lp.p, 8, hipMemcpyDeviceToHost, st));
+    }
+    if (want_sel) {
+        const int64_t slots = W * nr, nel = n * W;
+        if (int rc = egrow(c, a->hist, (size_t)slots * 256 * 8, "histograms")) return rc;
+        if (int rc = egrow(c, a->prefix, (size_t)slots * 8, "prefixes")) return rc;
+        if (int rc = egrow(c, a->rem, (size_t)slots * 8, "ranks left")) return rc;
+        if (int rc = egrow(c, a->slotof, (size_t)slots * 4, "slots")) return rc;
+        if (int rc = egrow(c, a->slotpf, (size_t)slots * 8, "slot prefixes")) return rc;
+        if (int rc = egrow(c, a->nlead, (size_t)W * 4, "slot counts")) return rc;
+        if (int rc = egrow(c, a->info, 16, "counters")) return rc;
+        if (int rc = egrow(c, a->order, (size_t)slots * 8, "order statistics")) return rc;
+        if (int rc = egrow(c, a->ranks, (size_t)SEL_MAX_RANKS * 8, "ranks")) return rc;
+        ESUM_HIP("copy", hipMemcpyAsync(a->ranks.p, ranks, (size_t)nr * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_esum_sel_init, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, (u64*)a->prefix.p, (int64_t*)a->rem.p,
+                           (int32_t*)a->slotof.p, (u64*)a->slotpf.p, (int32_t*)a->nlead.p, (const int64_t*)a->ranks.p, nr, slots);
+        ESUM_HIP("selection launch", hipGetLastError());
+        ESUM_HIP("LDS size", hipFuncSetAttribute((const void*)k_esum_hist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)es_hist_lds(ES_SLOTS, 1)));
+        ESUM_HIP("LDS size", hipFuncSetAttribute((const void*)k_esum_hist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)es_hist_lds(ES_SLOTS, 1)));
+        ESUM_HIP("LDS size", hipFuncSetAttribute((const void*)k_esum_compact, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 ES_COMPACT_TABLE * 8 + ES_STAGE * 12));
+        // workgroups of `per` elements (a multiple of ES_STAGE): at most 1024 of them
+        auto cut = [](int64_t count, int64_t* per) {
+            const int64_t wg = std::max<int64_t>(1, std::min<int64_t>((count + 4 * ES_STAGE - 1) / (4 * ES_STAGE), 1024));
+            *per = ((count + wg - 1) / wg + ES_STAGE - 1) / ES_STAGE * ES_STAGE;
+            return (count + *per - 1) / *per;
+        };
+        int ns = 1;
+        int64_t listed = -1;             // >= 0: passes read the compacted list of that many elements
+        a->sel_reads = a->list_reads = 0;
+        a->listed = -1;
+        u64 info[2] = {1, (u64)nel};
+        for (int pass = 0; pass < SEL_PASSES; ++pass) {
+            // compaction before pass 2: auto (1) where at most a quarter of the selection is left, forced (2) wherever the table fits
+            if (pass == 2 && v.summary_compact > 0 && W * ns <= ES_COMPACT_TABLE && (v.summary_compact > 1 || info[1] * 4 <= (u64)nel)) {
+                const int64_t cap = (int64_t)info[1];
+                // no room for the list next to a long chain: the passes read the selection instead
+                const bool room = a->lkey.bytes >= (size_t)cap * 8 && a->ldim.bytes >= (size_t)cap * 4;
+                Buf nk, nd;
+                bool ok = room;
+                if (!room) {
+                    ok = hipMalloc(&nk.p, (size_t)cap * 8) == hipSuccess && hipMalloc(&nd.p, (size_t)cap * 4) == hipSuccess;
+                    if (ok) {
+                        if (a->lkey.p) hipFree(a->lkey.p);
+                        if (a->ldim.p) hipFree(a->ldim.p);
+                        a->lkey.p = nk.p, a->lkey.bytes = (size_t)cap * 8;
+                        a->ldim.p = nd.p, a->ldim.bytes = (size_t)cap * 4;
+                    } else {
+                        (void)hipGetLastError();
+                        if (nk.p) hipFree(nk.p);
+                        if (nd.p) hipFree(nd.p);
+                    }
+                }
+                if (ok) {
+                    int64_t per;
+                    const int64_t wg = cut(nel, &per);
+                    ESUM_HIP("memset", hipMemsetAsync(a->info.p, 0, 16, st));
+                    hipLaunchKernelGGL(k_esum_compact, dim3((unsigned)wg), dim3(ES_HT), (size_t)W * ns * 8 + (size_t)ES_STAGE * 12, st, g, nel, per,
+                                       (const u64*)a->slotpf.p, (const int32_t*)a->nlead.p, nr, ns, 16, (u64*)a->lkey.p, (uint32_t*)a->ldim.p,
+                                       (u64*)a->info.p, (u64)cap);
+                    ESUM_HIP("compaction launch", hipGetLastError());
+                    listed = a->listed = cap;
+                    ++a->sel_reads;
+                }
+            }
+            const int DT = (int)std::min<int64_t>(W, ES_SLOTS / ns);
+            const int64_t count = listed >= 0 ? listed : nel;
+            int64_t per;
+            const int64_t wg = cut(count, &per);
+            const dim3 grid((unsigned)wg, (unsigned)((W + DT - 1) / DT));
+            (listed >= 0 ? a->list_reads : a->sel_reads) += grid.y;
+            ESUM_HIP("memset", hipMemsetAsync(a->hist.p, 0, (size_t)slots * 256 * 8, st));
+            ESUM_HIP("memset", hipMemsetAsync(a->info.p, 0, 16, st));
+            if (listed >= 0)
+                hipLaunchKernelGGL(k_esum_hist<true>, grid, dim3(ES_HT), es_hist_lds(DT, ns), st, g, (const u64*)a->lkey.p, (const uint32_t*)a->ldim.p,
+                                   count, per, (const u64*)a->slotpf.p, (const int32_t*)a->nlead.p, (u64*)a->hist.p, nr, ns, DT, pass);
+            else
+                hipLaunchKernelGGL(k_esum_hist<false>, grid, dim3(ES_HT), es_hist_lds(DT, ns), st, g, (const u64*)nullptr, (const uint32_t*)nullptr,
+                                   count, per, (const u64*)a->slotpf.p, (const int32_t*)a->nlead.p, (u64*)a->hist.p, nr, ns, DT, pass);
+            ESUM_HIP("histogram launch", hipGetLastError());
+            hipLaunchKernelGGL(k_esum_scan, dim3((unsigned)((W + 63) / 64)), dim3(64), 0, st, (u64*)a->prefix.p, (int64_t*)a->rem.p,
+                               (int32_t*)a->slotof.p, (u64*)a->slotpf.p, (int32_t*)a->nlead.p, (const u64*)a->hist.p, (u64*)a->info.p,
+                               (double*)a->order.p, nr, (int)W, pass);
+            ESUM_HIP("scan launch", hipGetLastError());
+            // the next pass's slots a dim (and, after pass 1, the length of the list) come back
+            ESUM_HIP("copy", hipMemcpyAsync(info, a->info.p, 16, hipMemcpyDeviceToHost, st));
+            ESUM_HIP("synchronize", hipStreamSynchronize(st));
+            ns = (int)info[0];
+            if (ns < 1 || ns > nr) return efail(c, -2, "emx_summary: the selection's state is inconsistent (%d slots for %d ranks)", ns, nr);
+        }
+        ESUM_HIP("copy", hipMemcpyAsync(order_out, a->order.p, (size_t)slots * 8, hipMemcpyDeviceToHost, st));
+    }
+    ESUM_HIP("synchronize", hipStreamSynchronize(st));
+    return 0;
+}
 
 int emx_summary_batch(emx_batch* b, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop, int64_t stride, double* mean_out,
                       double* cov_out, int32_t nranks, const int64_t* ranks, double* order_out, double* map_coords_out,
@@ -608,6 +867,16 @@ int emx_summary_batch_plane(emx_batch* b, int32_t plane, int32_t member_lo, int3
         // the pass's outputs leave before the next pass reuses the buffers
         SUM_HIP("synchronize", hipStreamSynchronize(v.stream));
     }
+    return 0;
+}
+
+int emx_summary_info(emx_ctx* c, int64_t* selection_reads_out, int64_t* listed_out, int64_t* list_reads_out) {
+    EmxChainView v;
+    if (const int rc = emx_internal_chain_view(c, &v)) return rc;
+    const EnsSummary* a = *v.summary;
+    if (selection_reads_out) *selection_reads_out = a ? a->sel_reads : 0;
+    if (listed_out) *listed_out = a ? a->listed : -1;
+    if (list_reads_out) *list_reads_out = a ? a->list_reads : 0;
     return 0;
 }
 

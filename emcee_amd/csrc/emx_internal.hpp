@@ -7,6 +7,7 @@
 
 #include "../../include/emx.h"
 
+struct EnsSummary;     // emx_summary's scratch (emx_batch_summary.hip), kept on the context between calls
 struct EmxChainView {
     double* chain;       // (stored, N, D) device-resident chain, or nullptr
     double* chain_lp;    // (stored, N)
@@ -15,12 +16,20 @@ struct EmxChainView {
     int64_t stored;
     hipStream_t stream;
     int device;
+    double* chain_blobs; // (stored, N, nblobs) next to the chain, or nullptr
+    int32_t nblobs;
+    int64_t cap;         // rows the three planes have room for
+    int64_t summary_compact;     // tuning "summary_compact"
+    EnsSummary** summary;        // the context's slot (nullptr until the first call)
 };
 
 // implemented in emx.hip
 int emx_internal_chain_view(emx_ctx* c, EmxChainView* v);
 int emx_internal_state_view(emx_ctx* c, const double** X, int64_t* N, int32_t* D, int* device);      // settles and synchronises the context first
 int emx_internal_fail(emx_ctx* c, int code, const char* msg);      // records the message for emx_last_error, returns code
+int emx_internal_settle(emx_ctx* c);      // everything the context was asked to run is known to be done (or is done again): before a chain is read
+// implemented in emx_batch_summary.hip: frees the scratch (emx_destroy)
+void emx_internal_ens_summary_release(EnsSummary* s);
 
 // ---- hipFFT, resolved at run time (PyTorch bundles its own copy; the process should hold one).  Implemented in emx_aux.hip;
 // emx_autocorr and emx_autocorr_batch (emx_batch_acf.hip) share the one dlopen.

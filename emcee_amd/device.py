@@ -423,6 +423,28 @@ class DeviceEnsemble:
         self._ck(self.lib.emx_autocorr(self.ctx, int(discard), int(thin), float(c), tau, win, C.byref(nt)))
         return tau, win, nt.value
 
+    def summary(self, start, stop, stride=1, ranks=(), cov=True, plane=0):
+        """-> (n, mean (W), cov (W, W) or None, order statistics (len(ranks), W), MAP coordinates (W), MAP log-prob): emx_summary
+        over the stored rows ``start, start + stride, ... < stop`` and every walker, ``n`` samples; W is ndim (``plane`` 0) or
+        the number of blobs (``plane`` 2).  ``order[r, d]`` is the ``ranks[r]``-th smallest (0-based) value of column d."""
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
+        W = self.nblobs() if plane == 2 else self.ndim
+        mean, mx, mlp = np.empty(W), np.empty(W), np.empty(1)
+        c = np.empty((W, W)) if cov else None
+        order = np.empty((len(ranks), W))
+        ptr = (lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p))
+        ns = C.c_int64(0)
+        self._ck(self.lib.emx_summary(self.ctx, int(plane), int(start), int(stop), int(stride), ptr(mean), ptr(c), len(ranks), ptr(ranks),
+                                      ptr(order), ptr(mx), ptr(mlp), C.byref(ns)))
+        return ns.value, mean, c, order, mx, float(mlp[0])
+
+    def summary_info(self):
+        """-> (reads of the selection, length of the compacted list or -1, reads of that list) of the last :meth:`summary`'s
+        order statistics (emx_summary_info)"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        self._ck(self.lib.emx_summary_info(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     @staticmethod
     def _load_hipfft(lib):
         import os

@@ -748,6 +748,14 @@ class EnsembleSampler(object):
     def get_autocorr_time(self, **kwargs):
         return self.backend.get_autocorr_time(**kwargs)
 
+    def get_summary(self, **kwargs):
+        return self.backend.get_summary(**kwargs)
+
+    def get_blob_summary(self, **kwargs):
+        return self.backend.get_blob_summary(**kwargs)
+
+    get_summary.__doc__ = Backend.get_summary.__doc__
+    get_blob_summary.__doc__ = Backend.get_blob_summary.__doc__
     get_chain.__doc__ = Backend.get_chain.__doc__
     get_blobs.__doc__ = Backend.get_blobs.__doc__
     get_log_prob.__doc__ = Backend.get_log_prob.__doc__

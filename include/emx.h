@@ -146,6 +146,9 @@ int emx_status(emx_ctx* ctx, uint32_t* bits);
  *                                        (786432) where the host pipeline's stretch steps are regen steps; 2: from 8192 on
  *   "persist_exact_regen_max_walkers"  131072   exact mode: largest ensemble of the device-wide persistent form when its plans go up as generator states
  *   "mt_tok_wshift" / "mt_tok_tail"  11 / 2048   the device tokenizer's window rule    "mt_device_lookahead"  batches ahead
+ *   -- summaries --
+ *   "summary_compact"          1         emx_summary's order statistics: 0 every pass reads the chain, 1 passes 2 ... 7 read a compacted list where at
+ *                                        most a quarter of the selection is left, 2 wherever the list's table fits (no bit depends on it)
  *   -- exchanges --
  *   "direct_timeout_ms"        bound of the device-side barriers of the direct and replay exchanges (the first of an emx_run: 6x)
  *   "replay_two_pass"          0         1: the replay exchange's own pass and replay pass as separate launches
@@ -471,6 +474,22 @@ int emx_autocorr(emx_ctx* ctx, int64_t discard, int64_t thin, double c, double* 
  * number <= 1e8.  The (n, ndim) host matrix goes to `device`; Householder QR there (one reflector per coordinate), then the
  * extreme singular values of the ndim x ndim triangular factor by (inverse) power iteration on the host.  *independent: 0 / 1;
  * *cond_out (or NULL): the condition number (inf for a constant coordinate, non-finite input, n < ndim or a singular factor). */
+/* Posterior summaries of the device-resident chain over stored rows start, start + stride, ... < stop and every walker
+ * (n = rows x nwalkers samples; *nsamples_out), computed next to the chain -- what emx_summary_batch returns for a member of a
+ * batch, by kernels that tile over walkers (csrc/emx_summary_single.hpp): mean_out (W), cov_out (W, W) (ddof = 1, symmetric bit
+ * for bit, W <= 256), order_out (nranks, W): the ranks[r]-th smallest (0-based, at most 32 ranks) of every column, exactly;
+ * map_coords_out (W) / map_log_prob_out: the stored sample of the largest stored log-prob, the smallest (row, walker) among
+ * equals.  plane: 0 coordinates (W = ndim), 2 blobs (W = nblobs; emx_chain_read's numbering).  Outputs may be NULL, which skips
+ * the work.  The floating-point sums run in an order fixed by (rows, nwalkers, W); no bit depends on the launch shape or on the
+ * tuning key "summary_compact" (1; 0: the selection's passes 2 ... 7 read the chain instead of a compacted list, 2: the list
+ * wherever it fits).  Scratch stays on the context.  -1 for bad arguments, -2 for a device failure. */
+int emx_summary(emx_ctx* ctx, int32_t plane, int64_t start, int64_t stop, int64_t stride, double* mean_out, double* cov_out,
+                int32_t nranks, const int64_t* ranks, double* order_out, double* map_coords_out, double* map_log_prob_out,
+                int64_t* nsamples_out);
+/* What the order statistics of the context's last emx_summary call read: *selection_reads_out how many times the selected
+ * elements were read from the chain (histogram passes, times the dim tiles of each, and the compaction), *listed_out the
+ * length of the compacted list (-1: none was made), *list_reads_out how many times that list was read.  Outputs may be NULL. */
+int emx_summary_info(emx_ctx* ctx, int64_t* selection_reads_out, int64_t* listed_out, int64_t* list_reads_out);
 int emx_walkers_independent(int32_t device, const double* coords, int64_t n, int32_t ndim, int32_t* independent,
                             double* cond_out);
 /* The same check on the state a context holds (a run continued from the State the previous run returned: the reference re-checks
