@@ -1,4 +1,5 @@
-"""Double-double reference arithmetic for the device WalkMove / KDEMove proposals (csrc/emx_walkkde.hip), test-side only.
+"""Double-double reference arithmetic for the device WalkMove / KDEMove proposals (csrc/emx_walkkde.hip) and for the built-in
+log-probabilities (every kernel that evaluates one: tests/test_gpu_logprob_reference.py), test-side only.
 
 A double-double value is a pair (hi, lo) of float64 arrays, hi = fl(hi + lo), carrying about 106 significant bits.  Everything is
 built on two error-free transformations: Knuth's TwoSum and Dekker's TwoProduct with Veltkamp's split.  No fused multiply-add is
@@ -12,7 +13,9 @@ On top of that, the references the GPU tests compare against:
   * linear_proposal: q = base + L z (whole-complement walk, KDE);
   * kde_bandwidth / kde_log_ratio: gaussian_kde's bandwidth factor and logpdf(s) - logpdf(q) from direct whitened distances
     |y - Y_j|^2, then a log-sum-exp.  Only that last exp / log is float64: its absolute error is a few ulps of 1.
-The inputs are the device's plan (DeviceEnsemble.plan_get) and the host twin of its draws (emx_host_walk_kde_draws)."""
+The inputs are the device's plan (DeviceEnsemble.plan_get) and the host twin of its draws (emx_host_walk_kde_draws).
+  * iso_logprob / diag_logprob / dense_logprob / rosenbrock_logprob / box_logprob: the built-in targets on rows x (n, D), each with
+    the running-error quantity its forward-error bound is made of (tests/lp_families.py holds the bounds and their derivations)."""
 import numpy as np
 
 _SPLITTER = 134217729.0             # 2^27 + 1
@@ -264,3 +267,88 @@ def kde_log_ratio(mu, Lh, C, s_rows, k, z):
     f = _lse_neg_half_sq(ys, YC) - _lse_neg_half_sq(yq, YC)
     R = max(np.sqrt(np.max(np.sum(to_float(Y) ** 2, axis=1))) for Y in (YC, ys, yq))
     return f, R
+
+
+# ---- the built-in log-probabilities ---------------------------------------------------------------------------------------------
+def dabs(x):
+    neg_ = x[0] < 0
+    return np.where(neg_, -x[0], x[0]), np.where(neg_, -x[1], x[1])
+
+
+def iso_logprob(x):
+    """-1/2 sum x_d^2 on rows x (n, D) -> (log-prob (n,) double-double, M = sum x_d^2 (n,) float)"""
+    s = dsum(two_prod(x, x), axis=1)
+    return mul_d(s, -0.5), to_float(s)
+
+
+def diag_logprob(x, mu, ivar):
+    """-1/2 sum ivar_d (x_d - mu_d)^2 -> (log-prob double-double, M = sum |ivar_d| (x_d - mu_d)^2 float)"""
+    x = np.asarray(x, dtype=np.float64)
+    r = two_sum(x, -np.asarray(mu, dtype=np.float64)[None, :])               # exact
+    t = mul_d(mul(r, r), np.asarray(ivar, dtype=np.float64)[None, :])
+    return mul_d(dsum(t, axis=1), -0.5), to_float(dsum(dabs(t), axis=1))
+
+
+def sym(icov):
+    """(icov + icov^T) / 2 as double-double (the halving is exact)"""
+    icov = np.asarray(icov, dtype=np.float64)
+    a = two_sum(icov, icov.T)
+    return a[0] * 0.5, a[1] * 0.5
+
+
+def dense_factor(icov):
+    """-> the lower Cholesky factor L of A = (icov + icov^T) / 2, double-double: A = L L^T"""
+    return cholesky(sym(icov), semidefinite=False)
+
+
+def rowvec_lower(r, L):
+    """rows r (n, D), L lower triangular (D, D), both double-double -> y_n = sum_{k >= n} r_k L_kn, (n, D) double-double"""
+    n, D = r[0].shape
+    y = dd(np.zeros((n, D)))
+    for k in range(D):
+        p = mul((r[0][:, k:k + 1], r[1][:, k:k + 1]), (L[0][k, :k + 1][None, :], L[1][k, :k + 1][None, :]))
+        t = add((y[0][:, :k + 1], y[1][:, :k + 1]), p)
+        y[0][:, :k + 1], y[1][:, :k + 1] = t
+    return y
+
+
+def dense_logprob(x, mu, icov, L=None):
+    """-1/2 r^T A r, A = (icov + icov^T) / 2, r = x - mu (exact), evaluated as -1/2 |r L|^2 with the double-double Cholesky factor L
+    of A (dense_factor; it may be handed in): L L^T = A to D 2^-104 |L||L^T|, far below anything float64 can see.
+    -> (log-prob (n,) double-double, S = sum_n a_n^2 with a_n = sum_k |r_k| |L_kn| (n,) float)"""
+    x = np.asarray(x, dtype=np.float64)
+    if L is None:
+        L = dense_factor(icov)
+    r = two_sum(x, -np.asarray(mu, dtype=np.float64)[None, :])
+    y = rowvec_lower(r, L)
+    a = np.abs(to_float(r)) @ np.abs(to_float(L))
+    return mul_d(dsum(mul(y, y), axis=1), -0.5), np.sum(a * a, axis=1)
+
+
+def dense_logprob_direct(x, mu, icov):
+    """-1/2 sum_ij r_i A_ij r_j term by term (no factorisation): the check of dense_logprob on small cases"""
+    x = np.asarray(x, dtype=np.float64)
+    A = sym(icov)
+    r = two_sum(x, -np.asarray(mu, dtype=np.float64)[None, :])
+    t = mul(mul((r[0][:, :, None], r[1][:, :, None]), (A[0][None], A[1][None])), (r[0][:, None, :], r[1][:, None, :]))
+    return mul_d(dsum(dsum(t, axis=2), axis=1), -0.5)
+
+
+def rosenbrock_logprob(x, scale):
+    """-(sum_{d < D-1} 100 (x_{d+1} - x_d^2)^2 + (1 - x_d)^2) / scale
+    -> (log-prob (n,) double-double, |a1| (n, D-1), x_d^2 (n, D-1), |b1| (n, D-1) floats; a1 = x_{d+1} - x_d^2, b1 = 1 - x_d)"""
+    x = np.asarray(x, dtype=np.float64)
+    n = x.shape[0]
+    sq = two_prod(x[:, :-1], x[:, :-1])                                   # exact
+    a1 = sub(dd(x[:, 1:]), sq)
+    b1 = two_sum(np.ones_like(x[:, :-1]), -x[:, :-1])                       # exact
+    t = add(mul_d(mul(a1, a1), 100.0), mul(b1, b1))
+    s = dsum(t, axis=1)
+    lp = neg(div(s, dd(np.full(n, float(scale)))))
+    return lp, np.abs(to_float(a1)), sq[0], np.abs(to_float(b1))
+
+
+def box_logprob(x):
+    """0 inside [0, 1]^D, -inf outside (exact)"""
+    x = np.asarray(x, dtype=np.float64)
+    return np.where(np.any((x > 1.0) | (x < 0.0), axis=1), -np.inf, 0.0)

@@ -185,3 +185,117 @@ def test_kde_bandwidth_and_log_ratio_against_scipy(rule, bw):
     want = dens.logpdf(s_rows.T) - dens.logpdf(q.T)
     np.testing.assert_allclose(f, want, rtol=0, atol=1e-9)
     assert R > 0
+
+
+# ---- the built-in log-probabilities (hp.*_logprob, lp_families): references against mpmath, and what the bounds detect ---------------
+import lp_families as lpf  # noqa: E402
+
+LP_CASES = [(k, f) for f in sorted(lpf.FAMILIES) for k in lpf.FAMILIES[f]]
+
+
+def _mp_logprob(t, row):
+    mp = mpmath.mpf
+    D, kind = t["D"], t["kind"]
+    if kind == "iso":
+        return -sum(mp(v) ** 2 for v in row) / 2
+    if kind == "diag":
+        return -sum(mp(t["ivar"][d]) * (mp(row[d]) - mp(t["mu"][d])) ** 2 for d in range(D)) / 2
+    if kind == "dense":
+        r = [mp(row[d]) - mp(t["mu"][d]) for d in range(D)]
+        A = t["icov"]
+        return -sum(r[i] * (mp(A[i, j]) + mp(A[j, i])) / 2 * r[j] for i in range(D) for j in range(D)) / 2
+    return -sum(100 * (mp(row[d + 1]) - mp(row[d]) ** 2) ** 2 + (1 - mp(row[d])) ** 2 for d in range(D - 1)) / mp(t["scale"])
+
+
+@pytest.mark.parametrize("D", [1, 2, 5, 17])
+@pytest.mark.parametrize("kind,family", LP_CASES)
+def test_logprob_references_against_mpmath(kind, family, D):
+    """300 bits: the reference's own error is at most 1 % of the bound it is paired with"""
+    mpmath.mp.prec = 300
+    t = lpf.make(kind, family, D, 6)
+    ref, bound, refdd = lpf.reference(t, t["x"])
+    if kind == "box":
+        want = np.where(np.any((t["x"] > 1) | (t["x"] < 0), axis=1), -np.inf, 0.0)
+        assert np.array_equal(ref, want) and not np.all(np.isfinite(want)) and np.any(want == 0)
+        return
+    for i in range(len(ref)):
+        want = _mp_logprob(t, t["x"][i])
+        got = mpmath.mpf(refdd[0][i]) + mpmath.mpf(refdd[1][i])
+        assert abs(got - want) <= mpmath.mpf(0.01 * bound[i]), (i, float(abs(got - want)), bound[i])
+        assert bound[i] > 0 or (kind == "rosenbrock" and D == 1 and got == 0)
+        if family not in ("illcond", "valley"):           # (there the bound is honestly far above eps |lp|: r L cancels, a1 does)
+            assert bound[i] <= 1e-12 * abs(float(want))
+    if kind == "dense" and family == "illcond" and D > 1:
+        ev = np.linalg.eigvalsh(t["corr"])
+        assert np.allclose(np.diag(t["corr"]), 1.0) and ev[0] > 0 and 1e9 <= ev[-1] / ev[0] <= 1e11
+    if kind == "dense":                                     # the factorised form against the term-by-term one
+        d2 = hp.dense_logprob_direct(t["x"], t["mu"], t["icov"])
+        assert np.all(np.abs(hp.to_float(hp.sub(refdd, d2))) <= 0.01 * bound)
+
+
+def test_offset_does_not_loosen_a_bound():
+    """the same differences next to a mean of 0 and of 2^21 (the draws are on the grid of the large mean): the same bound"""
+    for kind in ("diag", "dense"):
+        t = lpf.make(kind, "offset", 5, 8)
+        near = dict(t, mu=t["mu"] - 2.0 ** 21)
+        b0 = lpf.reference(t, t["x"])[1]
+        b1 = lpf.reference(near, t["x"] - 2.0 ** 21)[1]
+        assert np.array_equal(b0, b1)
+
+
+def _twin_dense(t, x, mistake=None):
+    """the kernels' arithmetic in host float64: r = x - mu, y = r L, -1/2 sum y^2 -- or one plausible mistake"""
+    icov = t["icov"]
+    A = 0.5 * (icov + icov.T)
+    if mistake == "lower":
+        A = np.tril(icov) + np.tril(icov, -1).T
+    L = np.linalg.cholesky(A)
+    if mistake == "folded":
+        y = x @ L - t["mu"] @ L
+    elif mistake == "f32":
+        r = x - t["mu"]
+        y = np.sum((r[:, :, None] * L[None]).astype(np.float32), axis=1, dtype=np.float32).astype(np.float64)
+    else:
+        y = (x - t["mu"]) @ L
+    return -0.5 * np.sum(y * y, axis=1)
+
+
+def _twin_rosen(t, x, mistake=None):
+    sq = x[:, :-1] * x[:, :-1]
+    if mistake == "f32":
+        sq = sq.astype(np.float32).astype(np.float64)
+    a1, b1 = x[:, 1:] - sq, 1.0 - x[:, :-1]
+    return -np.sum(100.0 * a1 * a1 + b1 * b1, axis=1) / t["scale"]
+
+
+@pytest.mark.parametrize("kind,family,mistake", [("dense", "offset", "folded"), ("dense", "benign", "f32"), ("dense", "asym", "lower"),
+                                                 ("rosenbrock", "valley", "f32")])
+@pytest.mark.parametrize("D", [5, 17])
+def test_bounds_catch_plausible_kernel_mistakes(kind, family, mistake, D):
+    """a host float64 twin with the mistake exceeds the bound by a factor of 100 at least; the correct twin stays inside it"""
+    t = lpf.make(kind, family, D, 64)
+    twin = _twin_dense if kind == "dense" else _twin_rosen
+    good = lpf.ratio(twin(t, t["x"]), t, t["x"])
+    bad = lpf.ratio(twin(t, t["x"], mistake), t, t["x"])
+    assert good.max() <= 1.0, good.max()
+    assert bad.max() >= 100.0, bad.max()
+    assert np.median(bad) >= 100.0, np.median(bad)
+
+
+@pytest.mark.parametrize("kind,family", LP_CASES)
+def test_correct_float64_twins_stay_inside_their_bounds(kind, family):
+    for D in (1, 2, 5, 17, 33):
+        t = lpf.make(kind, family, D, 40)
+        x = t["x"]
+        if kind == "dense":
+            got = _twin_dense(t, x)
+        elif kind == "rosenbrock":
+            got = _twin_rosen(t, x)
+        elif kind == "diag":
+            r = x - t["mu"]
+            got = -0.5 * np.sum(t["ivar"] * r * r, axis=1)
+        elif kind == "iso":
+            got = -0.5 * np.sum(x * x, axis=1)
+        else:
+            got = hp.box_logprob(x)
+        assert lpf.ratio(got, t, x).max() <= 1.0, D
