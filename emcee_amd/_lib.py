@@ -239,6 +239,9 @@ SIGNATURES = {
     "emx_summary": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     "emx_summary_info": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "emx_host_order_stats": (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int32, _i64p, _dp]),
+    "emx_chain_minmax": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
+    "emx_histograms": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P,
+                                 C.POINTER(C.c_int64)]),
     "emx_set_batch_target_fused_blobs": (C.c_int, [_P, FUSED_BATCH_FN, C.c_int32, _P, C.c_int32]),
     "emx_set_batch_target_callback_blobs": (C.c_int, [_P, BATCH_LOG_PROB_BLOBS_FN, _P, C.c_int32]),
     "emx_check_batch_blobs": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MoveDesc), C.c_int32, C.c_char_p, C.c_int32]),

@@ -260,6 +260,115 @@ class Backend(object):
         qs = np.quantile(x, q, axis=0) if len(q) else np.empty((0, x.shape[1]))
         return _summary.BatchSummary(n, x.mean(axis=0), c, qs, x[at].copy(), float(lp[at]))
 
+    def get_histograms(self, bins=64, range=None, discard=0, thin=1, pairs="all", pair_bins=None):
+        """-> :class:`~emcee_amd.summary.Histograms`: the marginal histogram of every parameter and the 2-d histogram of every
+        requested parameter pair (a corner plot's panels) over the steps of ``get_chain(discard=discard, thin=thin)`` and all
+        walkers -- ``np.histogram`` / ``np.histogram2d`` count for count.
+
+        ``bins``: an int (1 ... 1024) for every column, one strictly increasing edge array for every column, or a sequence of
+        such arrays, one a column.  ``range`` (with an integer ``bins``): None (every column's min and max), ``(lo, hi)`` or
+        ``(ndim, 2)``; the edges are ``np.linspace(lo, hi, bins + 1)``.  ``pairs``: ``"all"`` (every ``i < j``), None (marginals
+        only) or a sequence of ``(i, j)``.  ``pair_bins``: as ``bins``, at most 128; None: ``min(bins, 64)`` over the same range,
+        or the edges given as ``bins``.  A value falls in bin ``b`` iff ``edges[b] <= x < edges[b + 1]``, the last bin closed on
+        the right; NaN and everything outside are counted nowhere.  A non-finite value in a column whose range is taken from
+        the data raises ``ValueError``.
+
+        A device-resident chain is counted where it lives (``emx_chain_minmax``, ``emx_histograms``): the chain is read once
+        whatever the number of pairs and only the integer counts cross to the host.  A chain on the host (user-written moves,
+        Python blobs) is counted with NumPy into the same tuple, and so is a device chain whose call fails (no room for the
+        scratch next to a long chain)."""
+        return self._histograms("chain", bins, range, discard, thin, pairs, pair_bins)
+
+    def get_blob_histograms(self, bins=64, range=None, discard=0, thin=1, pairs="all", pair_bins=None):
+        """-> :class:`~emcee_amd.summary.Histograms` of the stored BLOBS: what :meth:`get_histograms` returns with the blobs of a
+        sample in its coordinates' place.  The blob plane of a ``DeviceFused`` target is counted on the device; blobs kept on the
+        host must be plain floats of shape ``(nsteps, nwalkers)`` or ``(nsteps, nwalkers, K)`` (``TypeError`` otherwise).
+        ``ValueError`` when there are no blobs."""
+        return self._histograms("blobs", bins, range, discard, thin, pairs, pair_bins)
+
+    def _histograms(self, name, bins, rng, discard, thin, pairs, pair_bins):
+        if int(thin) != thin or thin < 1:
+            raise ValueError("thin must be an integer >= 1; got %r" % (thin,))
+        if int(discard) != discard or discard < 0:
+            raise ValueError("discard must be an integer >= 0; got %r" % (discard,))
+        thin, discard = int(thin), int(discard)
+        bins = _summary.check_bins(bins, "bins", _summary.MAX_BINS)
+        rng = _summary.check_range(rng)
+        pairs = _summary.check_pairs(pairs)
+        if pair_bins is not None:
+            pair_bins = _summary.check_bins(pair_bins, "pair_bins", _summary.MAX_PAIR_BINS)
+        elif isinstance(bins, int):
+            pair_bins = min(bins, 64)
+        if name == "chain" and self.initialized:                # the checks that need the number of columns
+            _summary.check_columns(bins, rng, self.ndim, "bins")
+            _summary.check_columns(pair_bins, None, self.ndim, "pair_bins")
+            _summary.column_pairs(pairs, self.ndim)
+        it = self.iteration if self.initialized else 0
+        if it <= 0:
+            raise AttributeError("you must run the sampler with 'store == True' before accessing the results")
+        if name == "blobs" and not self.has_blobs():
+            raise ValueError("the target has no blobs (nblobs = 0): there is no blob plane to histogram")
+        start = min(discard + thin - 1, it)                 # reference backend.py:53
+        nt = len(range(start, it, thin))
+        if nt < 1:
+            raise ValueError("discard = %d, thin = %d select none of the %d stored steps" % (discard, thin, it))
+        n = nt * self.nwalkers
+        on_device = self._dev is not None and (name == "chain" or self._dev_nblobs())
+        x = None
+        if on_device:
+            W = self.ndim if name == "chain" else self._dev_nblobs()
+        else:
+            x = self.get_value(name, discard=discard, thin=thin, flat=True)
+            if name == "blobs":
+                x = np.asarray(x)
+                if x.dtype.kind != "f" or x.ndim not in (1, 2):
+                    raise TypeError("get_blob_histograms needs plain float blobs of shape (nsteps, nwalkers) or (nsteps, nwalkers, K); "
+                                    "got dtype %s, shape %s a step" % (x.dtype, x.shape[1:]))
+            x = np.asarray(x, dtype=np.float64).reshape(n, -1)
+            W = x.shape[1]
+        _summary.check_columns(bins, rng, W, "bins")
+        _summary.check_columns(pair_bins, None, W, "pair_bins")
+        pairs = _summary.column_pairs(pairs, W)
+        if pair_bins is None:                               # the edges given as bins serve the panels too
+            if len(pairs) and max(len(e) - 1 for e in (bins if isinstance(bins, list) else [bins])) > _summary.MAX_PAIR_BINS:
+                raise ValueError("pair panels have at most %d bins a column: pass pair_bins, or pairs=None for the marginals alone"
+                                 % _summary.MAX_PAIR_BINS)
+            pair_bins = bins
+        plane = 0 if name == "chain" else 2
+
+        def finish(minmax, count):
+            edges = _summary.column_edges(bins, rng, W, minmax)
+            pedges = _summary.column_edges(pair_bins, rng, W, minmax)
+            counts, pc = count(edges, pedges)
+            return _summary.Histograms(n, edges, counts, pairs, pedges, pc)
+
+        def finite(nonfinite):
+            if np.any(nonfinite):
+                raise ValueError("autodetected range of column(s) %s is not finite" % np.flatnonzero(nonfinite).tolist())
+
+        auto = _summary.needs_minmax(bins, pair_bins, rng)
+        if on_device:
+            try:
+                minmax = None
+                if auto:
+                    lo, hi, nf = self._dev.chain_minmax(start, it, thin, plane)
+                    finite(nf)
+                    minmax = (lo, hi)
+
+                def count(edges, pedges):
+                    nd, counts, pc = self._dev.histograms(start, it, edges, pedges, pairs, thin, plane)
+                    assert nd == n
+                    return counts, pc
+                return finish(minmax, count)
+            except EmxError as e:
+                autocorr.logger.debug("device histograms unavailable (%s): NumPy on a copy of the chain", e)
+            x = np.asarray(self.get_value(name, discard=discard, thin=thin, flat=True), dtype=np.float64).reshape(n, -1)
+        minmax = None
+        if auto:
+            finite(~np.isfinite(x).all(axis=0))
+            minmax = (x.min(axis=0), x.max(axis=0))
+        return finish(minmax, lambda edges, pedges: _summary.host_histograms(x, edges, pedges, pairs))
+
     @property
     def shape(self):
         """``(nwalkers, ndim)`` of the ensemble this backend was reset for."""

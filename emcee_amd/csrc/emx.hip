@@ -440,6 +440,7 @@ struct emx_ctx {
     int64_t cap = 0, stored = 0, proposals = 0;
     EnsSummary* summary = nullptr;        // emx_summary's scratch (emx_batch_summary.hip)
     int64_t tune_summary_compact = 1;     // emx_summary: passes 2 ... 7 of the selection on a compacted list: 0 never, 1 where a quarter or less is left, 2 always
+    int64_t tune_hist_chunk_rows = 0;     // emx_histograms: selected rows a chunk of the code plane (0: about 256 MB of codes)
     // split-phase buffers
     double *qout = nullptr, *fout = nullptr, *newlp = nullptr;
     double* tp1_full = nullptr;        // dense target, ndim <= 112: the full image the wide-target kernels read (tuning "dense_wide")
@@ -1220,6 +1221,7 @@ int emx_internal_chain_view(emx_ctx* c, EmxChainView* v) {
     v->cap = c->cap;
     v->summary_compact = c->tune_summary_compact;
     v->summary = &c->summary;
+    v->hist_chunk_rows = c->tune_hist_chunk_rows;
     return 0;
 }
 
@@ -1637,6 +1639,10 @@ int emx_set_tuning(emx_ctx* c, const char* key, int64_t v) {
     }
     if (!strcmp(key, "summary_compact")) {   // emx_summary's selection: 0 never a compacted list, 1 auto, 2 wherever it fits
         c->tune_summary_compact = v < 0 ? 0 : (v > 2 ? 2 : v);
+        return 0;
+    }
+    if (!strcmp(key, "hist_chunk_rows")) {   // emx_histograms: selected rows a chunk of the code plane; 0: auto
+        c->tune_hist_chunk_rows = v < 0 ? 0 : v;
         return 0;
     }
     if (!strcmp(key, "persist_odd")) {       // 0: odd ndim on the per-half-step launches

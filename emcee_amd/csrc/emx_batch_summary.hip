@@ -418,6 +418,9 @@ __global__ __launch_bounds__(64) void k_bsum_scan(u64* __restrict__ prefix, int6
 // ---- one ensemble's chain (emx_summary) -----------------------------------------------------------------------------------
 #include "emx_summary_single.hpp"
 
+// ---- one ensemble's histograms (emx_chain_minmax, emx_histograms) ---------------------------------------------------------
+#include "emx_hist.hpp"
+
 // ---- host -----------------------------------------------------------------------------------------------------------
 int sfail(emx_batch* b, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 int sfail(emx_batch* b, int code, const char* fmt, ...) {
@@ -455,7 +458,7 @@ int efail(emx_ctx* c, int code, const char* fmt, ...) {
     return emx_internal_fail(c, code, buf);
 }
 
-int egrow(emx_ctx* c, Buf& u, size_t bytes, const char* what) {
+int egrow(emx_ctx* c, Buf& u, size_t bytes, const char* what, const char* fn = "emx_summary") {
     if (bytes <= u.bytes) return 0;
     if (u.p) hipFree(u.p);
     u.p = nullptr;
@@ -463,7 +466,7 @@ int egrow(emx_ctx* c, Buf& u, size_t bytes, const char* what) {
     const hipError_t e = hipMalloc(&u.p, bytes);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return efail(c, -2, "emx_summary: %s allocation (%zu bytes): %s", what, bytes, hipGetErrorString(e));
+        return efail(c, -2, "%s: %s allocation (%zu bytes): %s", fn, what, bytes, hipGetErrorString(e));
     }
     u.bytes = bytes;
     return 0;
@@ -498,12 +501,16 @@ void emx_internal_batch_summary_release(BatchSummary* s) {
 struct EnsSummary {
     Buf part, fold, gpart, gfold, mean, cov, order, map_x, map_lp, map_pv, map_pi, hist, prefix, rem, slotof, slotpf, nlead, info, ranks, lkey, ldim;
     int64_t sel_reads = 0, listed = -1, list_reads = 0;      // the last call's selection (emx_summary_info)
+    // emx_chain_minmax / emx_histograms
+    Buf h_plo, h_phi, h_pnf, h_lo, h_hi, h_nf, h_edges, h_pedges, h_eoff, h_poff, h_pairs, h_pairoff, h_counts, h_pcounts, h_codes;
 };
 
 void emx_internal_ens_summary_release(EnsSummary* s) {
     if (!s) return;
     for (Buf* u : {&s->part, &s->fold, &s->gpart, &s->gfold, &s->mean, &s->cov, &s->order, &s->map_x, &s->map_lp, &s->map_pv, &s->map_pi,
-                   &s->hist, &s->prefix, &s->rem, &s->slotof, &s->slotpf, &s->nlead, &s->info, &s->ranks, &s->lkey, &s->ldim})
+                   &s->hist, &s->prefix, &s->rem, &s->slotof, &s->slotpf, &s->nlead, &s->info, &s->ranks, &s->lkey, &s->ldim, &s->h_plo,
+                   &s->h_phi, &s->h_pnf, &s->h_lo, &s->h_hi, &s->h_nf, &s->h_edges, &s->h_pedges, &s->h_eoff, &s->h_poff, &s->h_pairs,
+                   &s->h_pairoff, &s->h_counts, &s->h_pcounts, &s->h_codes})
         if (u->p) hipFree(u->p);
     delete s;
 }
@@ -521,6 +528,69 @@ int es_fold(emx_ctx* c, hipStream_t st, double* a, double* b, int64_t count, int
     }
     *out = a;
     return 0;
+}
+
+#define EHIST_HIP(what, expr)                                                                                          \
+    do {                                                                                                               \
+        const hipError_t e_ = (expr);                                                                                  \
+        if (e_ != hipSuccess) return efail(c, -2, "%s: %s: %s", fn, what, hipGetErrorString(e_));                      \
+    } while (0)
+
+// the rows start, start + stride, ... < stop of plane 0 / 2 as an ESel; the checks of emx_summary
+int eh_selection(emx_ctx* c, const char* fn, const EmxChainView& v, int32_t plane, int64_t start, int64_t stop, int64_t stride, ESel* g) {
+    if (plane != 0 && plane != 2) return efail(c, -1, "%s: plane 0 (coordinates) or 2 (blobs); got %d", fn, plane);
+    const double* X = v.chain;
+    int64_t W = v.D;
+    if (plane == 2) {
+        if (v.nblobs < 1) return efail(c, -1, "%s: the context's target has no blobs", fn);
+        X = v.chain_blobs;
+        W = v.nblobs;
+    }
+    if (!X || !v.chain_lp || v.stored <= 0) return efail(c, -1, "%s: no stored chain (emx_chain_config + stored steps)", fn);
+    if (stride < 1 || start < 0 || stop > v.stored) return efail(c, -1, "%s: rows need 0 <= start, stop <= stored, stride >= 1", fn);
+    const int64_t nt = start < stop ? (stop - start + stride - 1) / stride : 0;
+    if (nt < 1) return efail(c, -1, "%s: the selection is empty", fn);
+    g->x = X + start * v.N * W;
+    g->lp = v.chain_lp + start * v.N;
+    g->N = v.N;
+    g->NW = v.N * W;
+    g->rowstep = stride * v.N * W;
+    g->lprowstep = stride * v.N;
+    g->n = nt * v.N;
+    g->nt = nt;
+    g->W = (int32_t)W;
+    return 0;
+}
+
+// off[0 ... W] and the edges they cut: 0 first, 1 ... maxbins bins a column, strictly increasing, no NaN
+int eh_check_edges(emx_ctx* c, const char* fn, const char* what, const int64_t* off, const double* e, int64_t W, int maxbins) {
+    if (!off || !e) return efail(c, -1, "%s: the %s edges and their offsets are needed", fn, what);
+    if (off[0] != 0) return efail(c, -1, "%s: the %s edge offsets start at 0", fn, what);
+    for (int64_t d = 0; d < W; ++d) {
+        const int64_t nb = off[d + 1] - off[d] - 1;
+        if (nb < 1 || nb > maxbins) return efail(c, -1, "%s: column %lld has %lld %s bins; 1 ... %d", fn, (long long)d, (long long)nb, what, maxbins);
+        for (int64_t i = off[d]; i < off[d + 1]; ++i)
+            if (e[i] != e[i] || (i > off[d] && !(e[i] > e[i - 1])))
+                return efail(c, -1, "%s: the %s edges of column %lld are not strictly increasing", fn, what, (long long)d);
+    }
+    return 0;
+}
+
+struct EHTileSpan {
+    int d0, dc;
+    size_t lds;
+};
+
+constexpr int EH_MAX_DEVICES = 64;      // function attributes are per device: one process may drive several GPUs
+
+// raises a kernel's dynamic LDS limit to `lds` on device `dev`; granted[]: the largest size set so far per device, shared by
+// every context of the process, as the attribute is the function's and not a context's
+hipError_t eh_grant_lds(const void* kern, size_t* granted, int dev, size_t lds) {
+    const bool known = dev >= 0 && dev < EH_MAX_DEVICES;
+    if (known && lds <= granted[dev]) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess && known) granted[dev] = lds;
+    return e;
 }
 
 size_t es_hist_lds(int DT, int ns) { return (size_t)((DT * ns * 257 + 1) & ~1) * 4 + (size_t)DT * ns * 8; }
@@ -877,6 +947,172 @@ int emx_summary_info(emx_ctx* c, int64_t* selection_reads_out, int64_t* listed_o
     if (selection_reads_out) *selection_reads_out = a ? a->sel_reads : 0;
     if (listed_out) *listed_out = a ? a->listed : -1;
     if (list_reads_out) *list_reads_out = a ? a->list_reads : 0;
+    return 0;
+}
+
+int emx_chain_minmax(emx_ctx* c, int32_t plane, int64_t start, int64_t stop, int64_t stride, double* lo_out, double* hi_out, int64_t* nonfinite_out) {
+    const char* fn = "emx_chain_minmax";
+    if (const int rc = emx_internal_settle(c)) return rc;
+    EmxChainView v;
+    if (const int rc = emx_internal_chain_view(c, &v)) return rc;
+    ESel g;
+    if (const int rc = eh_selection(c, fn, v, plane, start, stop, stride, &g)) return rc;
+    if (!lo_out || !hi_out || !nonfinite_out) return efail(c, -1, "%s: the three outputs are needed", fn);
+    const int64_t W = g.W;
+    EHIST_HIP("hipSetDevice", hipSetDevice(v.device));
+    if (!*v.summary) *v.summary = new EnsSummary();
+    EnsSummary* a = *v.summary;
+    const hipStream_t st = v.stream;
+    const int64_t C = es_chunk(g.n, ES_MAX_CHUNKS), G = (g.n + C - 1) / C;
+    const int CW = (int)std::min<int64_t>(W, 256);
+    for (Buf* u : {&a->h_plo, &a->h_phi, &a->h_pnf})
+        if (int rc = egrow(c, *u, (size_t)G * W * 8, "min / max partials", fn)) return rc;
+    for (Buf* u : {&a->h_lo, &a->h_hi, &a->h_nf})
+        if (int rc = egrow(c, *u, (size_t)W * 8, "min / max", fn)) return rc;
+    hipLaunchKernelGGL(k_hist_minmax, dim3((unsigned)G, (unsigned)((W + CW - 1) / CW)), dim3(256), 0, st, g, C, CW, (double*)a->h_plo.p,
+                       (double*)a->h_phi.p, (u64*)a->h_pnf.p);
+    EHIST_HIP("min / max launch", hipGetLastError());
+    hipLaunchKernelGGL(k_hist_minmax_fin, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, (const double*)a->h_plo.p, (const double*)a->h_phi.p,
+                       (const u64*)a->h_pnf.p, G, (int)W, (double*)a->h_lo.p, (double*)a->h_hi.p, (u64*)a->h_nf.p);
+    EHIST_HIP("min / max launch", hipGetLastError());
+    EHIST_HIP("copy", hipMemcpyAsync(lo_out, a->h_lo.p, (size_t)W * 8, hipMemcpyDeviceToHost, st));
+    EHIST_HIP("copy", hipMemcpyAsync(hi_out, a->h_hi.p, (size_t)W * 8, hipMemcpyDeviceToHost, st));
+    EHIST_HIP("copy", hipMemcpyAsync(nonfinite_out, a->h_nf.p, (size_t)W * 8, hipMemcpyDeviceToHost, st));
+    EHIST_HIP("synchronize", hipStreamSynchronize(st));
+    return 0;
+}
+
+int emx_histograms(emx_ctx* c, int32_t plane, int64_t start, int64_t stop, int64_t stride, const int64_t* edge_off, const double* edges,
+                   int64_t* counts_out, const int64_t* pedge_off, const double* pedges, int64_t npairs, const int32_t* pairs,
+                   const int64_t* pair_off, int64_t* pair_counts_out, int64_t* nsamples_out) {
+    const char* fn = "emx_histograms";
+    if (const int rc = emx_internal_settle(c)) return rc;
+    EmxChainView v;
+    if (const int rc = emx_internal_chain_view(c, &v)) return rc;
+    ESel g;
+    if (const int rc = eh_selection(c, fn, v, plane, start, stop, stride, &g)) return rc;
+    const int64_t W = g.W, N = g.N, nt = g.nt, P = npairs;
+    if (nsamples_out) *nsamples_out = g.n;
+    if (!counts_out) return efail(c, -1, "%s: counts_out is needed", fn);
+    if (const int rc = eh_check_edges(c, fn, "marginal", edge_off, edges, W, EH_MAX_BINS)) return rc;
+    if (P < 0 || P > 0x7fffffff) return efail(c, -1, "%s: %lld pairs", fn, (long long)P);
+    if (P > 0) {
+        if (!pairs || !pair_off || !pair_counts_out) return efail(c, -1, "%s: pairs, pair_off and pair_counts_out are needed with npairs > 0", fn);
+        if (const int rc = eh_check_edges(c, fn, "pair", pedge_off, pedges, W, EH_MAX_PAIR_BINS)) return rc;
+        if (pair_off[0] != 0) return efail(c, -1, "%s: the pair offsets start at 0", fn);
+        for (int64_t p = 0; p < P; ++p) {
+            const int64_t i = pairs[2 * p], j = pairs[2 * p + 1];
+            if (i < 0 || i >= W || j < 0 || j >= W || i == j)
+                return efail(c, -1, "%s: pair %lld is (%lld, %lld); two different columns of [0, %lld)", fn, (long long)p, (long long)i, (long long)j, (long long)W);
+            const int64_t want = (pedge_off[i + 1] - pedge_off[i] - 1) * (pedge_off[j + 1] - pedge_off[j] - 1);
+            if (pair_off[p + 1] - pair_off[p] != want)
+                return efail(c, -1, "%s: pair %lld has room for %lld counters, its panel has %lld", fn, (long long)p, (long long)(pair_off[p + 1] - pair_off[p]), (long long)want);
+        }
+    }
+    const int64_t nme = edge_off[W], npe = P ? pedge_off[W] : 0, ncnt = nme - W, npc = P ? pair_off[P] : 0;
+    const bool same = P > 0 && !std::memcmp(edge_off, pedge_off, (size_t)(W + 1) * 8) && !std::memcmp(edges, pedges, (size_t)nme * 8);
+    // column tiles: as many consecutive columns as EH_LDS_TABLES hold
+    std::vector<EHTileSpan> tiles;
+    size_t lds_max = 0;
+    for (int64_t d0 = 0; d0 < W;) {
+        int64_t d1 = d0;
+        size_t bytes = 0;
+        while (d1 < W && d1 - d0 < EH_MAX_TILE_COLS) {
+            const int64_t nb = edge_off[d1 + 1] - edge_off[d1] - 1, pb = (P && !same) ? pedge_off[d1 + 1] - pedge_off[d1] - 1 : -1;
+            const size_t add = (size_t)(nb + 1) * 8 + (size_t)(pb + 1) * 8 + (size_t)nb * 4;
+            if (d1 > d0 && bytes + add > EH_LDS_TABLES) break;
+            bytes += add;
+            ++d1;
+        }
+        EHTileSpan t;
+        t.d0 = (int)d0;
+        t.dc = (int)(d1 - d0);
+        t.lds = eh_code_lds(edge_off[d1] - edge_off[d0], (P && !same) ? pedge_off[d1] - pedge_off[d0] : 0, t.dc, P > 0);
+        lds_max = std::max(lds_max, t.lds);
+        tiles.push_back(t);
+        d0 = d1;
+    }
+    // chunks of R selected rows: the code plane (W, Mp) of a chunk stays near 256 MB
+    int64_t R = v.hist_chunk_rows > 0 ? v.hist_chunk_rows : (P ? std::max<int64_t>(1, ((int64_t)256 << 20) / (N * W)) : nt);
+    R = std::min<int64_t>(R, nt);
+    while (R * N > ((int64_t)1 << 40)) R = (R + 1) / 2;
+    const int64_t Mp = (R * N + 15) / 16 * 16;
+
+    EHIST_HIP("hipSetDevice", hipSetDevice(v.device));
+    if (!*v.summary) *v.summary = new EnsSummary();
+    EnsSummary* a = *v.summary;
+    const hipStream_t st = v.stream;
+    if (int rc = egrow(c, a->h_edges, (size_t)nme * 8, "edges", fn)) return rc;
+    if (int rc = egrow(c, a->h_eoff, (size_t)(W + 1) * 8, "edge offsets", fn)) return rc;
+    if (int rc = egrow(c, a->h_counts, (size_t)ncnt * 8, "counters", fn)) return rc;
+    EHIST_HIP("copy", hipMemcpyAsync(a->h_edges.p, edges, (size_t)nme * 8, hipMemcpyHostToDevice, st));
+    EHIST_HIP("copy", hipMemcpyAsync(a->h_eoff.p, edge_off, (size_t)(W + 1) * 8, hipMemcpyHostToDevice, st));
+    EHIST_HIP("memset", hipMemsetAsync(a->h_counts.p, 0, (size_t)ncnt * 8, st));
+    size_t pair_lds = 0;
+    if (P) {
+        if (int rc = egrow(c, a->h_pedges, (size_t)npe * 8, "pair edges", fn)) return rc;
+        if (int rc = egrow(c, a->h_poff, (size_t)(W + 1) * 8, "pair edge offsets", fn)) return rc;
+        if (int rc = egrow(c, a->h_pairs, (size_t)P * 8, "pairs", fn)) return rc;
+        if (int rc = egrow(c, a->h_pairoff, (size_t)(P + 1) * 8, "pair offsets", fn)) return rc;
+        if (int rc = egrow(c, a->h_pcounts, (size_t)npc * 8, "pair counters", fn)) return rc;
+        if (int rc = egrow(c, a->h_codes, (size_t)W * Mp, "bin codes", fn)) return rc;
+        EHIST_HIP("copy", hipMemcpyAsync(a->h_pedges.p, pedges, (size_t)npe * 8, hipMemcpyHostToDevice, st));
+        EHIST_HIP("copy", hipMemcpyAsync(a->h_poff.p, pedge_off, (size_t)(W + 1) * 8, hipMemcpyHostToDevice, st));
+        EHIST_HIP("copy", hipMemcpyAsync(a->h_pairs.p, pairs, (size_t)P * 8, hipMemcpyHostToDevice, st));
+        EHIST_HIP("copy", hipMemcpyAsync(a->h_pairoff.p, pair_off, (size_t)(P + 1) * 8, hipMemcpyHostToDevice, st));
+        EHIST_HIP("memset", hipMemsetAsync(a->h_pcounts.p, 0, (size_t)npc * 8, st));
+        for (int64_t p = 0; p < P; ++p) pair_lds = std::max(pair_lds, (size_t)(pair_off[p + 1] - pair_off[p]) * 4);
+        static size_t pair_granted[EH_MAX_DEVICES] = {};
+        EHIST_HIP("LDS size", eh_grant_lds((const void*)k_hist_pair, pair_granted, v.device, pair_lds));
+    }
+    static size_t code_granted[EH_MAX_DEVICES] = {};
+    EHIST_HIP("LDS size", eh_grant_lds((const void*)k_hist_code, code_granted, v.device, lds_max));
+
+    for (int64_t r0 = 0; r0 < nt; r0 += R) {
+        const int64_t M = std::min<int64_t>(R, nt - r0) * N;
+        for (const EHTileSpan& t : tiles) {
+            const int64_t TS = (int64_t)EH_K * (EH_T / t.dc);
+            const int64_t wg = std::max<int64_t>(1, std::min<int64_t>((M + 4 * TS - 1) / (4 * TS), 1024));
+            EHCode k;
+            k.x = g.x + r0 * g.rowstep;
+            k.N = N;
+            k.rowstep = g.rowstep;
+            k.M = M;
+            k.per = ((M + wg - 1) / wg + TS - 1) / TS * TS;
+            k.W = (int32_t)W;
+            k.d0 = t.d0;
+            k.dc = t.dc;
+            k.same = same ? 1 : 0;
+            k.edge_off = (const int64_t*)a->h_eoff.p;
+            k.pedge_off = (const int64_t*)a->h_poff.p;
+            k.edges = (const double*)a->h_edges.p;
+            k.pedges = (const double*)a->h_pedges.p;
+            k.counts = (u64*)a->h_counts.p;
+            k.codes = P ? (uint8_t*)a->h_codes.p : nullptr;
+            k.Mp = Mp;
+            hipLaunchKernelGGL(k_hist_code, dim3((unsigned)((M + k.per - 1) / k.per)), dim3(EH_T), t.lds, st, k);
+            EHIST_HIP("binning launch", hipGetLastError());
+        }
+        if (P) {
+            // slices: enough workgroups for the device where the pairs are few; a slice stays below 2^31 samples and grid.y below 65 536
+            int64_t slices = std::max<int64_t>(1, std::min<int64_t>((2048 + P - 1) / P, (M + 16383) / 16384));
+            slices = std::max<int64_t>(slices, (M + ((int64_t)1 << 31) - 1) >> 31);
+            EHPair k;
+            k.codes = (const uint8_t*)a->h_codes.p;
+            k.Mp = Mp;
+            k.M = M;
+            k.per = ((M + slices - 1) / slices + 15) / 16 * 16;
+            k.pairs = (const int32_t*)a->h_pairs.p;
+            k.pair_off = (const int64_t*)a->h_pairoff.p;
+            k.pedge_off = (const int64_t*)a->h_poff.p;
+            k.out = (u64*)a->h_pcounts.p;
+            hipLaunchKernelGGL(k_hist_pair, dim3((unsigned)P, (unsigned)((M + k.per - 1) / k.per)), dim3(256), pair_lds, st, k);
+            EHIST_HIP("pair launch", hipGetLastError());
+        }
+    }
+    EHIST_HIP("copy", hipMemcpyAsync(counts_out, a->h_counts.p, (size_t)ncnt * 8, hipMemcpyDeviceToHost, st));
+    if (P) EHIST_HIP("copy", hipMemcpyAsync(pair_counts_out, a->h_pcounts.p, (size_t)npc * 8, hipMemcpyDeviceToHost, st));
+    EHIST_HIP("synchronize", hipStreamSynchronize(st));
     return 0;
 }
 

@@ -21,6 +21,7 @@ struct EmxChainView {
     int64_t cap;         // rows the three planes have room for
     int64_t summary_compact;     // tuning "summary_compact"
     EnsSummary** summary;        // the context's slot (nullptr until the first call)
+    int64_t hist_chunk_rows;     // tuning "hist_chunk_rows" (0: auto)
 };
 
 // implemented in emx.hip

@@ -438,6 +438,47 @@ class DeviceEnsemble:
                                       ptr(order), ptr(mx), ptr(mlp), C.byref(ns)))
         return ns.value, mean, c, order, mx, float(mlp[0])
 
+    def chain_minmax(self, start, stop, stride=1, plane=0):
+        """-> (lo (W), hi (W), nonfinite (W) int64): emx_chain_minmax over the stored rows ``start, start + stride, ... < stop`` and
+        every walker: per column the smallest and the largest finite value and the number of non-finite ones."""
+        W = self.nblobs() if plane == 2 else self.ndim
+        lo, hi, nf = np.empty(W), np.empty(W), np.zeros(W, dtype=np.int64)
+        ptr = (lambda a: a.ctypes.data_as(C.c_void_p))
+        self._ck(self.lib.emx_chain_minmax(self.ctx, int(plane), int(start), int(stop), int(stride), ptr(lo), ptr(hi), ptr(nf)))
+        return lo, hi, nf
+
+    def histograms(self, start, stop, edges, pair_edges=None, pairs=(), stride=1, plane=0):
+        """-> (n, counts, pair_counts): emx_histograms over the stored rows ``start, start + stride, ... < stop`` and every walker.
+        ``edges`` / ``pair_edges``: one float64 edge array a column (W of them; ``pair_edges`` may be None without pairs),
+        ``pairs`` ``(P, 2)`` column pairs.  ``counts``: W int64 arrays; ``pair_counts``: P int64 arrays ``(pb_i, pb_j)``.  The
+        rule is np.histogram's: ``e[b] <= v < e[b + 1]``, the last bin closed."""
+        def pack(es):
+            es = [np.ascontiguousarray(e, dtype=np.float64).ravel() for e in es]
+            off = np.zeros(len(es) + 1, dtype=np.int64)
+            off[1:] = np.cumsum([len(e) for e in es])
+            return off, (np.concatenate(es) if es else np.empty(0))
+        ptr = (lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p))
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        P = len(pairs)
+        off, e = pack(edges)
+        counts = np.zeros(int(off[-1]) - len(edges), dtype=np.int64)
+        poff = pe = pair_off = pc = None
+        if P:
+            poff, pe = pack(pair_edges)
+            pb = np.diff(poff) - 1
+            pair_off = np.zeros(P + 1, dtype=np.int64)
+            # indices the library will refuse must not fail here first
+            ok = ((pairs >= 0) & (pairs < len(pb))).all()
+            pair_off[1:] = np.cumsum(pb[pairs[:, 0]] * pb[pairs[:, 1]]) if ok else 0
+            pc = np.zeros(max(int(pair_off[-1]), 1), dtype=np.int64)
+        ns = C.c_int64(0)
+        self._ck(self.lib.emx_histograms(self.ctx, int(plane), int(start), int(stop), int(stride), ptr(off), ptr(e), ptr(counts), ptr(poff),
+                                         ptr(pe), P, ptr(pairs), ptr(pair_off), ptr(pc), C.byref(ns)))
+        co = off[:-1] - np.arange(len(edges))
+        out = [counts[co[d]:co[d] + len(edges[d]) - 1] for d in range(len(edges))]
+        pout = [pc[pair_off[p]:pair_off[p + 1]].reshape(pb[pairs[p, 0]], pb[pairs[p, 1]]) for p in range(P)]
+        return ns.value, out, pout
+
     def summary_info(self):
         """-> (reads of the selection, length of the compacted list or -1, reads of that list) of the last :meth:`summary`'s
         order statistics (emx_summary_info)"""

@@ -754,7 +754,15 @@ class EnsembleSampler(object):
     def get_blob_summary(self, **kwargs):
         return self.backend.get_blob_summary(**kwargs)
 
+    def get_histograms(self, **kwargs):
+        return self.backend.get_histograms(**kwargs)
+
+    def get_blob_histograms(self, **kwargs):
+        return self.backend.get_blob_histograms(**kwargs)
+
     get_summary.__doc__ = Backend.get_summary.__doc__
+    get_histograms.__doc__ = Backend.get_histograms.__doc__
+    get_blob_histograms.__doc__ = Backend.get_blob_histograms.__doc__
     get_blob_summary.__doc__ = Backend.get_blob_summary.__doc__
     get_chain.__doc__ = Backend.get_chain.__doc__
     get_blobs.__doc__ = Backend.get_blobs.__doc__

@@ -10,7 +10,7 @@ from collections import namedtuple
 
 import numpy as np
 
-__all__ = ["BatchSummary", "quantile_ranks", "lerp", "MAX_QUANTILES"]
+__all__ = ["BatchSummary", "Histograms", "quantile_ranks", "lerp", "MAX_QUANTILES", "MAX_BINS", "MAX_PAIR_BINS"]
 
 MAX_QUANTILES = 16          # two ranks a quantile: the 32 ranks of one emx_summary_batch call
 
@@ -18,6 +18,15 @@ BatchSummary = namedtuple("BatchSummary", ["nsamples", "mean", "cov", "quantiles
 BatchSummary.__doc__ = """The result of ``get_summary``: ``nsamples`` (selected steps x walkers), ``mean`` ``(..., ndim)``, ``cov``
 ``(..., ndim, ndim)`` (``ddof = 1``; None when not asked for), ``quantiles`` ``(..., nq, ndim)``, ``map_coords`` ``(..., ndim)`` and
 ``map_log_prob`` ``(...)``: the stored sample with the largest stored log-prob."""
+
+MAX_BINS = 1024             # marginal bins a column of one emx_histograms call
+MAX_PAIR_BINS = 128         # pair-panel bins a column: a panel's counters fit a workgroup's LDS
+
+Histograms = namedtuple("Histograms", ["nsamples", "edges", "counts", "pairs", "pair_edges", "pair_counts"])
+Histograms.__doc__ = """The result of ``get_histograms``: ``nsamples`` (selected steps x walkers); per column ``edges`` (float64,
+``(nb_d + 1,)``) and ``counts`` (int64, ``(nb_d,)``): ``np.histogram``'s; ``pairs`` ``(P, 2)`` column pairs ``(i, j)``, per column
+``pair_edges`` (``(pb_d + 1,)``) and per pair ``pair_counts`` (int64, ``(pb_i, pb_j)``, axis 0 is column ``i``):
+``np.histogram2d(x[:, i], x[:, j], bins=[pair_edges[i], pair_edges[j]])``'s."""
 
 
 def quantile_ranks(n, q):
@@ -67,3 +76,134 @@ def interpolate(order, ilo, ihi, g):
     if len(g) == 0:
         return np.empty((order.shape[0], 0, order.shape[2]))
     return lerp(order[:, ilo, :], order[:, ihi, :], g[None, :, None])
+
+
+# ---- histograms: the host side (argument forms, edges, and the NumPy twin of emx_histograms) --------------------------------
+def _edge_array(e, what, maxbins):
+    e = np.asarray(e, dtype=np.float64)
+    if e.ndim != 1 or len(e) < 2:
+        raise ValueError("%s: bin edges are a 1-D array of at least 2 values; got shape %s" % (what, e.shape))
+    if not (np.diff(e) > 0).all():              # NaN fails too
+        raise ValueError("%s: bin edges must be strictly increasing" % what)
+    if len(e) - 1 > maxbins:
+        raise ValueError("%s: at most %d bins a column; got %d" % (what, maxbins, len(e) - 1))
+    return e
+
+
+def check_bins(bins, what, maxbins):
+    """-> an int (bins of every column), one float64 edge array (for every column) or a list of edge arrays (one a column, its
+    length checked by :func:`column_edges`), or ValueError / TypeError: nothing here needs the number of columns."""
+    if isinstance(bins, (bool, np.bool_)):
+        raise TypeError("%s must be an integer or bin edges; got %r" % (what, bins))
+    if isinstance(bins, (int, np.integer)):
+        if not 1 <= bins <= maxbins:
+            raise ValueError("%s must be between 1 and %d; got %d" % (what, maxbins, bins))
+        return int(bins)
+    if np.isscalar(bins) or (isinstance(bins, np.ndarray) and bins.ndim == 0):
+        raise TypeError("%s must be an integer or bin edges; got %r" % (what, bins))
+    if all(np.isscalar(b) for b in bins):
+        return _edge_array(bins, what, maxbins)
+    return [_edge_array(b, what, maxbins) for b in bins]
+
+
+def check_range(range):
+    """-> None, or a float64 ``(2,)`` / ``(W, 2)`` array with finite ``lo <= hi``"""
+    if range is None:
+        return None
+    r = np.asarray(range, dtype=np.float64)
+    if r.shape != (2,) and not (r.ndim == 2 and r.shape[1] == 2):
+        raise ValueError("range is None, (lo, hi) or an array (ncolumns, 2); got shape %s" % (r.shape,))
+    if not np.isfinite(r).all():
+        raise ValueError("range must be finite; got %r" % (r.tolist(),))
+    if (r[..., 0] > r[..., 1]).any():
+        raise ValueError("range needs lo <= hi; got %r" % (r.tolist(),))
+    return r
+
+
+def check_pairs(pairs):
+    """-> "all", or an int64 ``(P, 2)`` array of pairs ``i != j``, none negative (the upper bound needs the number of columns:
+    :func:`column_pairs`)"""
+    if isinstance(pairs, str):
+        if pairs != "all":
+            raise ValueError("pairs is 'all', None or a sequence of (i, j); got %r" % (pairs,))
+        return pairs
+    if pairs is None or len(pairs) == 0:
+        return np.empty((0, 2), dtype=np.int64)
+    p = np.asarray(pairs)
+    if p.ndim != 2 or p.shape[1] != 2 or p.dtype.kind not in "iu":
+        raise ValueError("pairs is 'all', None or a sequence of integer (i, j); got %r" % (pairs,))
+    p = p.astype(np.int64)
+    if (p[:, 0] == p[:, 1]).any():
+        raise ValueError("a pair needs two different columns; got %r" % (p[p[:, 0] == p[:, 1]][0].tolist(),))
+    if (p < 0).any():
+        raise ValueError("pair columns are counted from 0; got %r" % (p[(p < 0).any(axis=1)][0].tolist(),))
+    return p
+
+
+def column_pairs(pairs, W):
+    """the checked ``pairs`` for ``W`` columns -> int64 ``(P, 2)``"""
+    if isinstance(pairs, str):
+        i, j = np.triu_indices(W, 1)
+        return np.stack([i, j], axis=1).astype(np.int64)
+    if (pairs >= W).any():
+        raise ValueError("pair %r is outside the %d columns" % (pairs[(pairs >= W).any(axis=1)][0].tolist(), W))
+    return pairs
+
+
+def check_columns(bins, range, W, what):
+    """what of the checked ``bins`` / ``range`` depends on the number of columns"""
+    if isinstance(bins, list) and len(bins) != W:
+        raise ValueError("%s: one edge array for every one of the %d columns; got %d" % (what, W, len(bins)))
+    if range is not None and range.ndim == 2 and len(range) != W:
+        raise ValueError("range: one (lo, hi) for every one of the %d columns; got %d" % (W, len(range)))
+
+
+def needs_minmax(bins, pair_bins, range):
+    """whether some column's edges come from the data's min and max"""
+    return range is None and (isinstance(bins, int) or isinstance(pair_bins, int))
+
+
+def column_edges(bins, range, W, minmax):
+    """-> the W edge arrays: ``np.linspace(lo, hi, bins + 1)`` -- ``np.histogram``'s own expression -- for an integer ``bins``
+    (``lo == hi`` widened by 0.5 each way as NumPy does), else the caller's edges.  ``minmax``: ``(lo (W), hi (W))`` of the data,
+    used where ``range`` is None."""
+    if isinstance(bins, int):
+        if range is None:
+            lo, hi = (np.asarray(v, dtype=np.float64) for v in minmax)
+        else:
+            r = np.broadcast_to(range, (W, 2))
+            lo, hi = r[:, 0], r[:, 1]
+        out = []
+        for a, b in zip(lo, hi):
+            if a == b:
+                a, b = a - 0.5, b + 0.5
+            out.append(np.linspace(a, b, bins + 1))
+        return out
+    return list(bins) if isinstance(bins, list) else [bins] * W
+
+
+def bin_index(x, e):
+    """-> (bin of every x in the edges e under np.histogram's rule, whether it has one)"""
+    ok = (x >= e[0]) & (x <= e[-1])                     # NaN: False
+    b = np.searchsorted(e, x, side="right") - 1
+    b[b == len(e) - 1] = len(e) - 2                     # the last bin is closed
+    return b, ok
+
+
+def host_histograms(x, edges, pair_edges, pairs):
+    """the NumPy twin of ``emx_histograms`` on the ``(n, W)`` samples ``x`` -> ``(counts, pair_counts)``"""
+    W = x.shape[1]
+    counts = []
+    for d in range(W):
+        b, ok = bin_index(x[:, d], edges[d])
+        counts.append(np.bincount(b[ok], minlength=len(edges[d]) - 1).astype(np.int64))
+    code = {}
+    for d in sorted(set(np.asarray(pairs).ravel().tolist())):
+        code[d] = bin_index(x[:, d], pair_edges[d])
+    pc = []
+    for i, j in pairs:
+        (bi, oi), (bj, oj) = code[i], code[j]
+        ni, nj = len(pair_edges[i]) - 1, len(pair_edges[j]) - 1
+        ok = oi & oj
+        pc.append(np.bincount(bi[ok] * nj + bj[ok], minlength=ni * nj).astype(np.int64).reshape(ni, nj))
+    return counts, pc

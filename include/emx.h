@@ -149,6 +149,8 @@ int emx_status(emx_ctx* ctx, uint32_t* bits);
  *   -- summaries --
  *   "summary_compact"          1         emx_summary's order statistics: 0 every pass reads the chain, 1 passes 2 ... 7 read a compacted list where at
  *                                        most a quarter of the selection is left, 2 wherever the list's table fits (no bit depends on it)
+ *   "hist_chunk_rows"          0 (auto)  emx_histograms: selected rows a chunk of the one-byte bin-code plane (auto: about 256 MB of codes); no count
+ *                                        depends on it
  *   -- exchanges --
  *   "direct_timeout_ms"        bound of the device-side barriers of the direct and replay exchanges (the first of an emx_run: 6x)
  *   "replay_two_pass"          0         1: the replay exchange's own pass and replay pass as separate launches
@@ -490,6 +492,26 @@ int emx_summary(emx_ctx* ctx, int32_t plane, int64_t start, int64_t stop, int64_
  * elements were read from the chain (histogram passes, times the dim tiles of each, and the compaction), *listed_out the
  * length of the compacted list (-1: none was made), *list_reads_out how many times that list was read.  Outputs may be NULL. */
 int emx_summary_info(emx_ctx* ctx, int64_t* selection_reads_out, int64_t* listed_out, int64_t* list_reads_out);
+/* Histograms of the device-resident chain over the rows and walkers of emx_summary's selection (plane 0: coordinates, W = ndim;
+ * 2: blobs, W = nblobs), counted next to the chain (csrc/emx_hist.hpp).  The bin edges are the caller's and are never recomputed on
+ * the device; a value v falls in bin b iff e[b] <= v < e[b + 1], the last bin closed on the right (np.histogram's rule); NaN,
+ * +-inf beyond the edges and everything outside are counted nowhere.
+ * emx_chain_minmax: per column the smallest and the largest FINITE value (+inf / -inf where there is none) and the number of
+ * non-finite ones: lo_out[W], hi_out[W], nonfinite_out[W].  Exact, whatever the order of the reduction.
+ * emx_histograms: column d's marginal edges are edges[edge_off[d] ... edge_off[d + 1]) (edge_off[0] = 0; 1 ... 1024 bins, strictly
+ * increasing); its counts go to counts_out[edge_off[d] - d ...).  With npairs > 0: the pair edges pedge_off / pedges in the same
+ * form (1 ... 128 bins a column), pairs[2 p], pairs[2 p + 1] the two different columns (i, j) of panel p, whose pb_i x pb_j counts
+ * (column i the slow axis, a sample counted iff both coordinates fall in a bin) go to pair_counts_out[pair_off[p] ...),
+ * pair_off[p + 1] - pair_off[p] = pb_i pb_j, pair_off[0] = 0.  *nsamples_out: rows x nwalkers.  The chain is read once whatever
+ * the number of pairs: one pass bins every value and leaves a one-byte bin code per value in a dim-major plane, from which the
+ * panels are counted; the selection goes in chunks of rows (tuning "hist_chunk_rows") so that this plane stays near 256 MB.
+ * Every count is a sum of integers: no count depends on the launch shape, the chunking or the order of the atomics.  Scratch stays
+ * on the context.  -1 for bad arguments, -2 for a device failure. */
+int emx_chain_minmax(emx_ctx* ctx, int32_t plane, int64_t start, int64_t stop, int64_t stride, double* lo_out, double* hi_out,
+                     int64_t* nonfinite_out);
+int emx_histograms(emx_ctx* ctx, int32_t plane, int64_t start, int64_t stop, int64_t stride, const int64_t* edge_off,
+                   const double* edges, int64_t* counts_out, const int64_t* pedge_off, const double* pedges, int64_t npairs,
+                   const int32_t* pairs, const int64_t* pair_off, int64_t* pair_counts_out, int64_t* nsamples_out);
 int emx_walkers_independent(int32_t device, const double* coords, int64_t n, int32_t ndim, int32_t* independent,
                             double* cond_out);
 /* The same check on the state a context holds (a run continued from the State the previous run returned: the reference re-checks
