@@ -248,6 +248,10 @@ SIGNATURES = {
     "emx_get_blobs_batch": (C.c_int, [_P, _P, C.POINTER(C.c_int32)]),
     "emx_summary_batch_plane": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int32, _P, _P,
                                           _P, _P, C.POINTER(C.c_int64)]),
+    "emx_chain_minmax_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
+    "emx_histograms_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P, _P, _P,
+                                       C.c_int64, C.c_int64, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "emx_histograms_batch_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
 }
 
 

@@ -243,7 +243,8 @@ class EnsembleBatch(object):
     def set_tuning(self, key, value):
         """``"batch_threads"`` / ``"batch_plan_steps"`` (include/emx.h): the launch shape; ``"batch_acf_series"``: series per
         FFT chunk of ``get_autocorr_time(on_device=True)``; ``"batch_summary_members"``: members per pass of
-        ``get_summary``.  No bit depends on them."""
+        ``get_summary``; ``"batch_hist_members"`` / ``"batch_hist_rows"``: members and rows of a member per chunk of
+        ``get_histograms``.  No bit depends on them."""
         self._tuning[key] = int(value)
         if self._h is not None:
             self._ck(self._lib().emx_batch_set_tuning(self._h, key.encode(), int(value)))
@@ -483,6 +484,122 @@ class EnsembleBatch(object):
         assert ns.value == n
         return n, mean, c, order, mx, mlp
 
+    def get_histograms(self, bins=64, range=None, discard=0, thin=1, pairs="all", pair_bins=None):
+        """-> :class:`~emcee_amd.summary.BatchHistograms`: for EVERY member the marginal histogram of every parameter and the 2-d
+        histogram of every requested parameter pair (a corner plot's panels) over the selected steps (``get_chain``'s
+        ``discard`` / ``thin``) and all walkers, counted next to the chain (``emx_chain_minmax_batch``,
+        ``emx_histograms_batch``) -- ``np.histogram`` / ``np.histogram2d`` of each member, count for count.  One launch grid
+        covers all members; only the integer counts cross to the host.
+
+        The arguments are ``EnsembleSampler.get_histograms``'s: ``bins`` an int (1 ... 1024), one edge array for every column or
+        one a column; ``range`` (with an integer ``bins``) None, ``(lo, hi)``, ``(ndim, 2)`` or additionally ``(B, ndim, 2)``: a
+        range of its own for every member; ``pairs`` ``"all"``, None or a sequence of ``(i, j)``; ``pair_bins`` as ``bins``, at
+        most 128 (None: ``min(bins, 64)`` over the same range, or the edges given as ``bins``).  With ``range=None`` every member
+        gets ``np.linspace`` between ITS OWN minimum and maximum of every column, so ``edges[d]`` is ``(B, nb_d + 1)``; a
+        non-finite value in such a column raises ``ValueError`` naming the members and columns.  Edges given as arrays are
+        shared by all members.  A device failure raises :class:`emcee_amd._lib.EmxError` (no fallback)."""
+        return self._histograms(0, bins, range, discard, thin, pairs, pair_bins, 0, self.nbatch)
+
+    def get_blob_histograms(self, bins=64, range=None, discard=0, thin=1, pairs="all", pair_bins=None):
+        """-> :class:`~emcee_amd.summary.BatchHistograms` of every member's BLOBS: what :meth:`get_histograms` returns, counted over
+        the blob plane by the same kernels with ``nblobs`` in ``ndim``'s place.  ``ValueError`` when the target has no blobs."""
+        return self._histograms(4, bins, range, discard, thin, pairs, pair_bins, 0, self.nbatch)
+
+    def _histograms(self, plane, bins, rng, discard, thin, pairs, pair_bins, lo, hi):
+        """members [lo, hi) -> BatchHistograms; a 3-d ``rng`` has one entry for every member of the BATCH.  Every argument is
+        checked before any device is touched."""
+        if int(thin) != thin or thin < 1:
+            raise ValueError("thin must be an integer >= 1; got %r" % (thin,))
+        if int(discard) != discard or discard < 0:
+            raise ValueError("discard must be an integer >= 0; got %r" % (discard,))
+        bins = _summary.check_bins(bins, "bins", _summary.MAX_BINS)
+        rng = _summary.check_batch_range(rng)
+        pairs = _summary.check_pairs(pairs)
+        if pair_bins is not None:
+            pair_bins = _summary.check_bins(pair_bins, "pair_bins", _summary.MAX_PAIR_BINS)
+        elif isinstance(bins, int):
+            pair_bins = min(bins, 64)
+        if plane == 4 and not self.nblobs:
+            raise ValueError("the target has no blobs (nblobs = 0): there is no blob plane to histogram")
+        W, M = (self.nblobs if plane == 4 else self.ndim), hi - lo
+        _summary.check_batch_columns(bins, rng, self.nbatch, W, "bins")
+        _summary.check_columns(pair_bins, None, W, "pair_bins")
+        pairs = _summary.column_pairs(pairs, W)
+        if pair_bins is None:                               # the edges given as bins serve the panels too
+            if len(pairs) and max(len(e) - 1 for e in (bins if isinstance(bins, list) else [bins])) > _summary.MAX_PAIR_BINS:
+                raise ValueError("pair panels have at most %d bins a column: pass pair_bins, or pairs=None for the marginals alone"
+                                 % _summary.MAX_PAIR_BINS)
+            pair_bins = bins
+        if not 0 <= lo < hi <= self.nbatch:
+            raise ValueError("members [%d, %d) outside a batch of %d" % (lo, hi, self.nbatch))
+        start, it, nt = self._summary_rows(discard, thin)
+        thin, n = int(thin), nt * self.nwalkers
+        if rng is not None and rng.ndim == 3:
+            rng = rng[lo:hi]
+        minmax = None
+        if _summary.needs_minmax(bins, pair_bins, rng):
+            mlo, mhi, nf = self._minmax_device(plane, lo, hi, start, it, thin)
+            if nf.any():
+                bad = np.argwhere(nf > 0)
+                named = ", ".join("member %d column %d" % (lo + m, d) for m, d in bad[:8].tolist())
+                raise ValueError("autodetected range of %s%s is not finite" % (named, " and %d more" % (len(bad) - 8) if len(bad) > 8 else ""))
+            minmax = (mlo, mhi)
+        edges = _summary.member_edges(bins, rng, M, W, minmax)
+        pedges = _summary.member_edges(pair_bins, rng, M, W, minmax)
+        shared = _summary.shared_edges(bins, rng), _summary.shared_edges(pair_bins, rng)
+        counts, pc = self._hist_device(plane, lo, hi, start, it, thin, edges, pedges, pairs, shared, n)
+        return _summary.BatchHistograms(n, edges, counts, pairs, pedges, pc)
+
+    def _minmax_device(self, plane, lo, hi, start, stop, stride):
+        """-> (lo, hi, nonfinite), each (hi - lo, W): ``emx_chain_minmax_batch`` on members [lo, hi)"""
+        W = self.nblobs if plane == 4 else self.ndim
+        mlo, mhi, nf = np.empty((hi - lo, W)), np.empty((hi - lo, W)), np.zeros((hi - lo, W), dtype=np.int64)
+        ptr = (lambda a: a.ctypes.data_as(C.c_void_p))
+        self._ck(self._lib().emx_chain_minmax_batch(self._h, plane, lo, hi, start, stop, stride, ptr(mlo), ptr(mhi), ptr(nf)))
+        return mlo, mhi, nf
+
+    def _hist_device(self, plane, lo, hi, start, stop, stride, edges, pedges, pairs, shared, n):
+        """-> (counts, pair_counts): ``emx_histograms_batch`` on members [lo, hi) with the per-member ``edges`` / ``pedges``
+        (W arrays ``(M, nb_d + 1)``; ``shared``: whether all rows of the marginal / the pair edges are one, which then goes to
+        the device once)"""
+        M, W, P = hi - lo, len(edges), len(pairs)
+
+        def pack(es, one):
+            off = np.zeros(W + 1, dtype=np.int64)
+            off[1:] = np.cumsum([e.shape[1] for e in es])
+            e = np.ascontiguousarray(np.concatenate(es, axis=1), dtype=np.float64)
+            return (off, e[0].copy(), 0) if one else (off, e, int(off[-1]))
+        ptr = (lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p))
+        off, e, es = pack(edges, shared[0])
+        counts = np.empty((M, int(off[-1]) - W), dtype=np.int64)
+        pairs32 = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        poff = pe = pair_off = pc = pb = None
+        ps = 0
+        if P:
+            poff, pe, ps = pack(pedges, shared[1])
+            pb = np.diff(poff) - 1
+            pair_off = np.zeros(P + 1, dtype=np.int64)
+            pair_off[1:] = np.cumsum(pb[pairs32[:, 0]] * pb[pairs32[:, 1]])
+            pc = np.empty((M, int(pair_off[-1])), dtype=np.int64)
+        ns = C.c_int64(0)
+        self._ck(self._lib().emx_histograms_batch(self._h, plane, lo, hi, start, stop, stride, ptr(off), ptr(e), es, ptr(counts), ptr(poff),
+                                                  ptr(pe), ps, P, ptr(pairs32), ptr(pair_off), ptr(pc), C.byref(ns)))
+        assert ns.value == n
+        co = off[:-1] - np.arange(W)
+        # views of the two buffers the library filled (a panel's last axis is split, which copies nothing): at 1 024 members and
+        # ten 64 x 64 panels the counts are a third of a gigabyte
+        out = [counts[:, co[d]:co[d] + edges[d].shape[1] - 1] for d in range(W)]
+        pout = [pc[:, pair_off[p]:pair_off[p + 1]].reshape(M, pb[pairs32[p, 0]], pb[pairs32[p, 1]]) for p in range(P)]
+        return out, pout
+
+    def histogram_launches(self):
+        """kernel launches of the last ``get_histograms`` / ``get_blob_histograms`` call's counting (``emx_histograms_batch_info``):
+        it does not grow with the number of members of a chunk."""
+        n = C.c_int64(0)
+        if self._h is not None:
+            self._ck(self._lib().emx_histograms_batch_info(self._h, C.byref(n)))
+        return n.value
+
     def get_last_sample(self):
         """:class:`State` with ``(B, nwalkers, ndim)`` coordinates and ``(B, nwalkers)`` log-probs."""
         if self._h is None or not self._ran:
@@ -620,6 +737,20 @@ class _Member(object):
         """:meth:`EnsembleBatch.get_summary` of this member alone, without the leading axis."""
         r = self._batch._summary(discard, thin, quantiles, cov, self.index, self.index + 1)
         return _summary.BatchSummary(r.nsamples, *[None if a is None else a[0] for a in r[1:]])
+
+    def get_histograms(self, bins=64, range=None, discard=0, thin=1, pairs="all", pair_bins=None):
+        """:meth:`EnsembleBatch.get_histograms` of this member alone -> a plain :class:`~emcee_amd.summary.Histograms`, what
+        ``EnsembleSampler.get_histograms`` returns (``range``: None, ``(lo, hi)`` or ``(ndim, 2)``)."""
+        return self._histograms(0, bins, range, discard, thin, pairs, pair_bins)
+
+    def get_blob_histograms(self, bins=64, range=None, discard=0, thin=1, pairs="all", pair_bins=None):
+        """:meth:`EnsembleBatch.get_blob_histograms` of this member alone -> a plain :class:`~emcee_amd.summary.Histograms`."""
+        return self._histograms(4, bins, range, discard, thin, pairs, pair_bins)
+
+    def _histograms(self, plane, bins, rng, discard, thin, pairs, pair_bins):
+        r = self._batch._histograms(plane, bins, _summary.check_range(rng), discard, thin, pairs, pair_bins, self.index, self.index + 1)
+        return _summary.Histograms(r.nsamples, [e[0] for e in r.edges], [c[0] for c in r.counts], r.pairs, [e[0] for e in r.pair_edges],
+                                   [c[0] for c in r.pair_counts])
 
     def get_last_sample(self):
         s = self._batch.get_last_sample()

@@ -86,6 +86,8 @@ struct emx_batch {
     // emx_summary_batch (emx_batch_summary.hip): its scratch; tuning "batch_summary_members" (0: auto)
     BatchSummary* summary = nullptr;
     int64_t tune_summary_members = 0;
+    // emx_histograms_batch (emx_batch_summary.hip): tuning "batch_hist_members" / "batch_hist_rows" (0: auto); its scratch is summary's
+    int64_t tune_hist_members = 0, tune_hist_rows = 0;
     // parallel tempering (emx_pt_set_tempering; pt_T 0: untempered): groups of pt_T members, member m at rung m % pt_T; each
     // member's beta, the box prior, L and P per walker, the L chain, the caller's prior, the swap cadence and counters
     int32_t pt_T = 0;
@@ -877,6 +879,8 @@ int emx_internal_batch_view(emx_batch* b, EmxBatchView* v) {
     v->summary = &b->summary;
     v->chain_blobs = b->chain_blobs;
     v->nblobs = b->nblobs;
+    v->hist_members = b->tune_hist_members;
+    v->hist_rows = b->tune_hist_rows;
     return 0;
 }
 
@@ -970,6 +974,12 @@ int emx_batch_set_tuning(emx_batch* b, const char* key, int64_t value) {
     } else if (!std::strcmp(key, "batch_summary_members")) {
         BNEED(b, value >= 0, "batch_summary_members: 0 (auto) or a positive number of members");
         b->tune_summary_members = value;
+    } else if (!std::strcmp(key, "batch_hist_members")) {
+        BNEED(b, value >= 0, "batch_hist_members: 0 (auto) or a positive number of members");
+        b->tune_hist_members = value;
+    } else if (!std::strcmp(key, "batch_hist_rows")) {
+        BNEED(b, value >= 0, "batch_hist_rows: 0 (auto) or a positive number of rows");
+        b->tune_hist_rows = value;
     } else {
         return fail(b, -1, "unknown batch tuning key '%s'", key);
     }

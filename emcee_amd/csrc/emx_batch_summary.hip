@@ -421,6 +421,9 @@ __global__ __launch_bounds__(64) void k_bsum_scan(u64* __restrict__ prefix, int6
 // ---- one ensemble's histograms (emx_chain_minmax, emx_histograms) ---------------------------------------------------------
 #include "emx_hist.hpp"
 
+// ---- every member's histograms (emx_chain_minmax_batch, emx_histograms_batch) ---------------------------------------------
+#include "emx_batch_hist.hpp"
+
 // ---- host -----------------------------------------------------------------------------------------------------------
 int sfail(emx_batch* b, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 int sfail(emx_batch* b, int code, const char* fmt, ...) {
@@ -488,12 +491,16 @@ int egrow(emx_ctx* c, Buf& u, size_t bytes, const char* what, const char* fn = "
 
 struct BatchSummary {
     Buf mpart, gpart, mean, cov, order, map_x, map_lp, hist, prefix, rem, leader, ranks;
+    // emx_chain_minmax_batch / emx_histograms_batch
+    Buf h_plo, h_phi, h_pnf, h_lo, h_hi, h_nf, h_edges, h_pedges, h_eoff, h_poff, h_pairs, h_pairoff, h_counts, h_pcounts, h_codes;
+    int64_t h_launches = 0;      // kernel launches of the last emx_histograms_batch call (emx_histograms_batch_info)
 };
 
 void emx_internal_batch_summary_release(BatchSummary* s) {
     if (!s) return;
     for (Buf* u : {&s->mpart, &s->gpart, &s->mean, &s->cov, &s->order, &s->map_x, &s->map_lp, &s->hist, &s->prefix, &s->rem, &s->leader,
-                   &s->ranks})
+                   &s->ranks, &s->h_plo, &s->h_phi, &s->h_pnf, &s->h_lo, &s->h_hi, &s->h_nf, &s->h_edges, &s->h_pedges, &s->h_eoff, &s->h_poff,
+                   &s->h_pairs, &s->h_pairoff, &s->h_counts, &s->h_pcounts, &s->h_codes})
         if (u->p) hipFree(u->p);
     delete s;
 }
@@ -1148,6 +1155,321 @@ int emx_host_order_stats(const double* x, int64_t n, int64_t stride, int32_t nra
         const u64 bits = sel_unkey(prefix[r]);
         std::memcpy(out + r, &bits, 8);
     }
+    return 0;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop
+
+// ---- every member's histograms --------------------------------------------------------------------------------------------
+namespace {
+
+#define BHIST_HIP(what, expr)                                                                                          \
+    do {                                                                                                               \
+        const hipError_t e_ = (expr);                                                                                  \
+        if (e_ != hipSuccess) return sfail(b, -2, "%s: %s: %s", fn, what, hipGetErrorString(e_));                      \
+    } while (0)
+
+int bgrow(emx_batch* b, const char* fn, Buf& u, size_t bytes, const char* what) {
+    if (bytes <= u.bytes) return 0;
+    if (u.p) hipFree(u.p);
+    u.p = nullptr;
+    u.bytes = 0;
+    const hipError_t e = hipMalloc(&u.p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return sfail(b, -2, "%s: %s allocation (%zu bytes): %s", fn, what, bytes, hipGetErrorString(e));
+    }
+    u.bytes = bytes;
+    return 0;
+}
+
+// The selection of both entry points: the plane, the members and the rows start, start + stride, ... < stop, checked as
+// emx_summary_batch_plane checks them.  *x: member_lo's first selected row; *W: the plane's width; *nt: selected rows.
+int bh_selection(emx_batch* b, const char* fn, const EmxBatchView& v, int32_t plane, int32_t member_lo, int32_t member_hi, int64_t start,
+                 int64_t stop, int64_t stride, const double** x, int64_t* W, int64_t* nt) {
+    if (plane != 0 && plane != 4) return sfail(b, -1, "%s: plane 0 (coordinates) or 4 (blobs); got %d", fn, plane);
+    const double* X = v.chain;
+    *W = v.D;
+    if (plane == 4) {
+        if (v.nblobs < 1) return sfail(b, -1, "%s: the handle's target has no blobs", fn);
+        X = v.chain_blobs;
+        *W = v.nblobs;
+    }
+    if (!(0 <= member_lo && member_lo < member_hi && member_hi <= v.B))
+        return sfail(b, -1, "%s: members [%d, %d) outside [0, %d) or empty", fn, member_lo, member_hi, v.B);
+    if (!X || v.stored <= 0) return sfail(b, -1, "%s: no stored chain (emx_batch_chain_config + a stored run)", fn);
+    if (stride < 1 || start < 0 || stop > v.stored) return sfail(b, -1, "%s: rows need 0 <= start, stop <= stored, stride >= 1", fn);
+    *nt = start < stop ? (stop - start + stride - 1) / stride : 0;
+    if (*nt < 1) return sfail(b, -1, "%s: the selection is empty", fn);
+    *x = X + ((int64_t)member_lo * v.cap + start) * v.N * *W;
+    return 0;
+}
+
+// eh_check_edges for members [0, M) of a batch: member m's edges at e + m step
+int bh_check_edges(emx_batch* b, const char* fn, const char* what, const int64_t* off, const double* e, int64_t step, int64_t M, int64_t W,
+                   int maxbins) {
+    if (!off || !e) return sfail(b, -1, "%s: the %s edges and their offsets are needed", fn, what);
+    if (off[0] != 0) return sfail(b, -1, "%s: the %s edge offsets start at 0", fn, what);
+    for (int64_t d = 0; d < W; ++d) {
+        const int64_t nb = off[d + 1] - off[d] - 1;
+        if (nb < 1 || nb > maxbins) return sfail(b, -1, "%s: column %lld has %lld %s bins; 1 ... %d", fn, (long long)d, (long long)nb, what, maxbins);
+    }
+    if (step != 0 && step < off[W]) return sfail(b, -1, "%s: the %s edges of a member lie %lld doubles apart; 0 (shared) or at least %lld", fn, what, (long long)step, (long long)off[W]);
+    for (int64_t m = 0; m < (step ? M : 1); ++m) {
+        const double* em = e + m * step;
+        for (int64_t d = 0; d < W; ++d)
+            for (int64_t i = off[d]; i < off[d + 1]; ++i)
+                if (em[i] != em[i] || (i > off[d] && !(em[i] > em[i - 1])))
+                    return sfail(b, -1, "%s: the %s edges of column %lld of member %lld of the range are not strictly increasing", fn, what, (long long)d, (long long)m);
+    }
+    return 0;
+}
+
+// members [m0, m0 + mc) of a per-member host table (rows of `row` doubles, `step` apart; step 0: one shared row) -> dev, packed
+int bh_upload(emx_batch* b, const char* fn, hipStream_t st, void* dev, const double* host, int64_t step, int64_t row, int64_t m0, int64_t mc,
+              std::vector<double>& stage) {
+    if (step == 0) return 0;             // the shared row went up once, before the chunks
+    const double* src = host + m0 * step;
+    if (step != row) {
+        stage.resize((size_t)mc * row);
+        for (int64_t m = 0; m < mc; ++m) std::memcpy(&stage[(size_t)m * row], src + m * step, (size_t)row * 8);
+        src = stage.data();
+    }
+    BHIST_HIP("copy", hipMemcpyAsync(dev, src, (size_t)mc * row * 8, hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+}  // namespace
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int emx_chain_minmax_batch(emx_batch* b, int32_t plane, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop, int64_t stride,
+                           double* lo_out, double* hi_out, int64_t* nonfinite_out) {
+    const char* fn = "emx_chain_minmax_batch";
+    EmxBatchView v;
+    if (emx_internal_batch_view(b, &v)) return -1;
+    const double* x = nullptr;
+    int64_t W = 0, nt = 0;
+    if (const int rc = bh_selection(b, fn, v, plane, member_lo, member_hi, start, stop, stride, &x, &W, &nt)) return rc;
+    if (!lo_out || !hi_out || !nonfinite_out) return sfail(b, -1, "%s: the three outputs are needed", fn);
+    const int64_t N = v.N, n = nt * N, M = member_hi - member_lo;
+    BHIST_HIP("hipSetDevice", hipSetDevice(v.device));
+    if (!*v.summary) *v.summary = new BatchSummary();
+    BatchSummary* a = *v.summary;
+    const hipStream_t st = v.stream;
+    const int CW = (int)std::min<int64_t>(W, 256), SPB = 256 / CW;
+    const int64_t mp = std::min<int64_t>(M, 65535);                    // members a launch: grid.z
+    // slices: about 2 048 workgroups from the members of a launch, a slice no shorter than 16 rounds of the workgroup's lanes
+    const int64_t ctiles = (W + CW - 1) / CW;
+    int64_t S = std::max<int64_t>(1, std::min<int64_t>((2048 + mp * ctiles - 1) / (mp * ctiles), (n + 16 * SPB - 1) / (16 * SPB)));
+    S = std::min<int64_t>(S, 65535);
+    const int64_t per = (n + S - 1) / S;
+    S = (n + per - 1) / per;
+    for (Buf* u : {&a->h_plo, &a->h_phi, &a->h_pnf})
+        if (int rc = bgrow(b, fn, *u, (size_t)mp * S * W * 8, "min / max partials")) return rc;
+    for (Buf* u : {&a->h_lo, &a->h_hi, &a->h_nf})
+        if (int rc = bgrow(b, fn, *u, (size_t)mp * W * 8, "min / max")) return rc;
+    BHMinMax g;
+    g.xstep = v.cap * N * W;
+    g.N = N;
+    g.rowstep = stride * N * W;
+    g.n = n;
+    g.per = per;
+    g.W = (int32_t)W;
+    g.S = (int32_t)S;
+    for (int64_t m0 = 0; m0 < M; m0 += mp) {
+        const int64_t mc = std::min<int64_t>(mp, M - m0);
+        g.x = x + m0 * g.xstep;
+        hipLaunchKernelGGL(k_bhist_minmax, dim3((unsigned)S, (unsigned)ctiles, (unsigned)mc), dim3(256), 0, st, g, CW, (double*)a->h_plo.p,
+                           (double*)a->h_phi.p, (u64*)a->h_pnf.p);
+        BHIST_HIP("min / max launch", hipGetLastError());
+        hipLaunchKernelGGL(k_bhist_minmax_fin, dim3((unsigned)((mc * W + 255) / 256)), dim3(256), 0, st, (const double*)a->h_plo.p,
+                           (const double*)a->h_phi.p, (const u64*)a->h_pnf.p, S, W, mc * W, (double*)a->h_lo.p, (double*)a->h_hi.p, (u64*)a->h_nf.p);
+        BHIST_HIP("min / max launch", hipGetLastError());
+        BHIST_HIP("copy", hipMemcpyAsync(lo_out + m0 * W, a->h_lo.p, (size_t)mc * W * 8, hipMemcpyDeviceToHost, st));
+        BHIST_HIP("copy", hipMemcpyAsync(hi_out + m0 * W, a->h_hi.p, (size_t)mc * W * 8, hipMemcpyDeviceToHost, st));
+        BHIST_HIP("copy", hipMemcpyAsync(nonfinite_out + m0 * W, a->h_nf.p, (size_t)mc * W * 8, hipMemcpyDeviceToHost, st));
+        BHIST_HIP("synchronize", hipStreamSynchronize(st));          // the outputs leave before the next launch reuses the buffers
+    }
+    return 0;
+}
+
+int emx_histograms_batch(emx_batch* b, int32_t plane, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop, int64_t stride,
+                         const int64_t* edge_off, const double* edges, int64_t edge_member_stride, int64_t* counts_out,
+                         const int64_t* pedge_off, const double* pedges, int64_t pedge_member_stride, int64_t npairs, const int32_t* pairs,
+                         const int64_t* pair_off, int64_t* pair_counts_out, int64_t* nsamples_out) {
+    const char* fn = "emx_histograms_batch";
+    EmxBatchView v;
+    if (emx_internal_batch_view(b, &v)) return -1;
+    const double* x = nullptr;
+    int64_t W = 0, nt = 0;
+    if (const int rc = bh_selection(b, fn, v, plane, member_lo, member_hi, start, stop, stride, &x, &W, &nt)) return rc;
+    const int64_t N = v.N, M = member_hi - member_lo, P = npairs, es = edge_member_stride, ps = P ? pedge_member_stride : 0;
+    if (nsamples_out) *nsamples_out = nt * N;
+    if (!counts_out) return sfail(b, -1, "%s: counts_out is needed", fn);
+    if (es < 0 || ps < 0) return sfail(b, -1, "%s: the member strides of the edges are 0 (shared) or positive", fn);
+    if (const int rc = bh_check_edges(b, fn, "marginal", edge_off, edges, es, M, W, EH_MAX_BINS)) return rc;
+    if (P < 0 || P > 0x7fffffff) return sfail(b, -1, "%s: %lld pairs", fn, (long long)P);
+    if (P > 0) {
+        if (!pairs || !pair_off || !pair_counts_out) return sfail(b, -1, "%s: pairs, pair_off and pair_counts_out are needed with npairs > 0", fn);
+        if (const int rc = bh_check_edges(b, fn, "pair", pedge_off, pedges, ps, M, W, EH_MAX_PAIR_BINS)) return rc;
+        if (pair_off[0] != 0) return sfail(b, -1, "%s: the pair offsets start at 0", fn);
+        for (int64_t p = 0; p < P; ++p) {
+            const int64_t i = pairs[2 * p], j = pairs[2 * p + 1];
+            if (i < 0 || i >= W || j < 0 || j >= W || i == j)
+                return sfail(b, -1, "%s: pair %lld is (%lld, %lld); two different columns of [0, %lld)", fn, (long long)p, (long long)i, (long long)j, (long long)W);
+            const int64_t want = (pedge_off[i + 1] - pedge_off[i] - 1) * (pedge_off[j + 1] - pedge_off[j] - 1);
+            if (pair_off[p + 1] - pair_off[p] != want)
+                return sfail(b, -1, "%s: pair %lld has room for %lld counters, its panel has %lld", fn, (long long)p, (long long)(pair_off[p + 1] - pair_off[p]), (long long)want);
+        }
+    }
+    const int64_t nme = edge_off[W], npe = P ? pedge_off[W] : 0, ncnt = nme - W, npc = P ? pair_off[P] : 0;
+    // one search a value where every member's pair edges are its marginal edges
+    bool same = P > 0 && !std::memcmp(edge_off, pedge_off, (size_t)(W + 1) * 8) && (es == 0) == (ps == 0);
+    for (int64_t m = 0; same && m < (es ? M : 1); ++m) same = !std::memcmp(edges + m * es, pedges + m * ps, (size_t)nme * 8);
+    // column tiles: as many consecutive columns as EH_LDS_TABLES hold
+    std::vector<EHTileSpan> tiles;
+    size_t lds_max = 0;
+    for (int64_t d0 = 0; d0 < W;) {
+        int64_t d1 = d0;
+        size_t bytes = 0;
+        while (d1 < W && d1 - d0 < EH_MAX_TILE_COLS) {
+            const int64_t nb = edge_off[d1 + 1] - edge_off[d1] - 1, pb = (P && !same) ? pedge_off[d1 + 1] - pedge_off[d1] - 1 : -1;
+            const size_t add = (size_t)(nb + 1) * 8 + (size_t)(pb + 1) * 8 + (size_t)nb * 4;
+            if (d1 > d0 && bytes + add > EH_LDS_TABLES) break;
+            bytes += add;
+            ++d1;
+        }
+        EHTileSpan t;
+        t.d0 = (int)d0;
+        t.dc = (int)(d1 - d0);
+        t.lds = eh_code_lds(edge_off[d1] - edge_off[d0], (P && !same) ? pedge_off[d1] - pedge_off[d0] : 0, t.dc, P > 0);
+        lds_max = std::max(lds_max, t.lds);
+        tiles.push_back(t);
+        d0 = d1;
+    }
+    // Chunks.  Rows: R selected rows of a member at a time, all of them unless the code plane of ONE member exceeds the budget
+    // (or "batch_hist_rows" says otherwise).  Members: mp at a time, so that the chunk's code plane, edges and counters stay near
+    // 256 MB (or "batch_hist_members").
+    const int64_t budget = (int64_t)256 << 20;
+    int64_t R = v.hist_rows > 0 ? v.hist_rows : (P ? std::max<int64_t>(1, budget / (N * W)) : nt);
+    R = std::min<int64_t>(R, nt);
+    while (R * N > ((int64_t)1 << 40)) R = (R + 1) / 2;
+    const int64_t Mp = (R * N + 15) / 16 * 16;
+    const int64_t per_member = (P ? W * Mp : 0) + (nme + npe + ncnt + npc) * 8;
+    int64_t mp = std::max<int64_t>(1, budget / per_member);
+    if (v.hist_members > 0) mp = v.hist_members;
+    mp = std::min<int64_t>(mp, std::min<int64_t>(M, 65535));
+
+    BHIST_HIP("hipSetDevice", hipSetDevice(v.device));
+    if (!*v.summary) *v.summary = new BatchSummary();
+    BatchSummary* a = *v.summary;
+    const hipStream_t st = v.stream;
+    if (int rc = bgrow(b, fn, a->h_edges, (size_t)(es ? mp : 1) * nme * 8, "edges")) return rc;
+    if (int rc = bgrow(b, fn, a->h_eoff, (size_t)(W + 1) * 8, "edge offsets")) return rc;
+    if (int rc = bgrow(b, fn, a->h_counts, (size_t)mp * ncnt * 8, "counters")) return rc;
+    BHIST_HIP("copy", hipMemcpyAsync(a->h_eoff.p, edge_off, (size_t)(W + 1) * 8, hipMemcpyHostToDevice, st));
+    if (!es) BHIST_HIP("copy", hipMemcpyAsync(a->h_edges.p, edges, (size_t)nme * 8, hipMemcpyHostToDevice, st));
+    size_t pair_lds = 0;
+    if (P) {
+        if (int rc = bgrow(b, fn, a->h_pedges, (size_t)(ps ? mp : 1) * npe * 8, "pair edges")) return rc;
+        if (int rc = bgrow(b, fn, a->h_poff, (size_t)(W + 1) * 8, "pair edge offsets")) return rc;
+        if (int rc = bgrow(b, fn, a->h_pairs, (size_t)P * 8, "pairs")) return rc;
+        if (int rc = bgrow(b, fn, a->h_pairoff, (size_t)(P + 1) * 8, "pair offsets")) return rc;
+        if (int rc = bgrow(b, fn, a->h_pcounts, (size_t)mp * npc * 8, "pair counters")) return rc;
+        if (int rc = bgrow(b, fn, a->h_codes, (size_t)mp * W * Mp, "bin codes")) return rc;
+        BHIST_HIP("copy", hipMemcpyAsync(a->h_poff.p, pedge_off, (size_t)(W + 1) * 8, hipMemcpyHostToDevice, st));
+        BHIST_HIP("copy", hipMemcpyAsync(a->h_pairs.p, pairs, (size_t)P * 8, hipMemcpyHostToDevice, st));
+        BHIST_HIP("copy", hipMemcpyAsync(a->h_pairoff.p, pair_off, (size_t)(P + 1) * 8, hipMemcpyHostToDevice, st));
+        if (!ps) BHIST_HIP("copy", hipMemcpyAsync(a->h_pedges.p, pedges, (size_t)npe * 8, hipMemcpyHostToDevice, st));
+        for (int64_t p = 0; p < P; ++p) pair_lds = std::max(pair_lds, (size_t)(pair_off[p + 1] - pair_off[p]) * 4);
+        static size_t pair_granted[EH_MAX_DEVICES] = {};
+        BHIST_HIP("LDS size", eh_grant_lds((const void*)k_bhist_pair, pair_granted, v.device, pair_lds));
+    }
+    static size_t code_granted[EH_MAX_DEVICES] = {};
+    BHIST_HIP("LDS size", eh_grant_lds((const void*)k_bhist_code, code_granted, v.device, lds_max));
+
+    const int64_t xstep = v.cap * N * W, rowstep = stride * N * W;
+    std::vector<double> estage, pstage;
+    a->h_launches = 0;
+    for (int64_t m0 = 0; m0 < M; m0 += mp) {
+        const int64_t mc = std::min<int64_t>(mp, M - m0);
+        if (int rc = bh_upload(b, fn, st, a->h_edges.p, edges, es, nme, m0, mc, estage)) return rc;
+        if (P)
+            if (int rc = bh_upload(b, fn, st, a->h_pedges.p, pedges, ps, npe, m0, mc, pstage)) return rc;
+        BHIST_HIP("memset", hipMemsetAsync(a->h_counts.p, 0, (size_t)mc * ncnt * 8, st));
+        if (P) BHIST_HIP("memset", hipMemsetAsync(a->h_pcounts.p, 0, (size_t)mc * npc * 8, st));
+        for (int64_t r0 = 0; r0 < nt; r0 += R) {
+            const int64_t Ms = std::min<int64_t>(R, nt - r0) * N;             // samples of a member in this chunk of rows
+            for (const EHTileSpan& t : tiles) {
+                // slices: about 2 048 workgroups from the mc members, a workgroup at least two rounds of TS samples where there are
+                // two, at most 2^30 samples (its LDS counters are uint32) and grid.x in bounds
+                const int64_t TS = (int64_t)EH_K * (EH_T / t.dc), rounds = (Ms + TS - 1) / TS;
+                int64_t wg = std::max<int64_t>(1, std::min<int64_t>((2048 + mc - 1) / mc, (rounds + 1) / 2));
+                wg = std::max<int64_t>(wg, (Ms + ((int64_t)1 << 30) - 1) >> 30);
+                BHCode k;
+                k.x = x + m0 * xstep + r0 * rowstep;
+                k.xstep = xstep;
+                k.N = N;
+                k.rowstep = rowstep;
+                k.M = Ms;
+                k.per = ((Ms + wg - 1) / wg + TS - 1) / TS * TS;
+                k.W = (int32_t)W;
+                k.d0 = t.d0;
+                k.dc = t.dc;
+                k.same = same ? 1 : 0;
+                k.edge_off = (const int64_t*)a->h_eoff.p;
+                k.pedge_off = (const int64_t*)a->h_poff.p;
+                k.edges = (const double*)a->h_edges.p;
+                k.pedges = (const double*)a->h_pedges.p;
+                k.estep = es ? nme : 0;
+                k.pstep = ps ? npe : 0;
+                k.counts = (u64*)a->h_counts.p;
+                k.cstep = ncnt;
+                k.codes = P ? (uint8_t*)a->h_codes.p : nullptr;
+                k.Mp = Mp;
+                hipLaunchKernelGGL(k_bhist_code, dim3((unsigned)((Ms + k.per - 1) / k.per), (unsigned)mc), dim3(EH_T), t.lds, st, k);
+                BHIST_HIP("binning launch", hipGetLastError());
+                ++a->h_launches;
+            }
+            if (P) {
+                // slices: enough workgroups for the device where panels x members are few; a slice stays below 2^31 samples and
+                // grid.y below 65 536
+                int64_t slices = std::max<int64_t>(1, std::min<int64_t>((2048 + P * mc - 1) / (P * mc), (Ms + 16383) / 16384));
+                slices = std::max<int64_t>(slices, (Ms + ((int64_t)1 << 31) - 1) >> 31);
+                BHPair k;
+                k.codes = (const uint8_t*)a->h_codes.p;
+                k.Mp = Mp;
+                k.M = Ms;
+                k.per = ((Ms + slices - 1) / slices + 15) / 16 * 16;
+                k.W = (int32_t)W;
+                const int64_t ny = (Ms + k.per - 1) / k.per;
+                k.store = (ny == 1 && R >= nt) ? 1 : 0;
+                k.pairs = (const int32_t*)a->h_pairs.p;
+                k.pair_off = (const int64_t*)a->h_pairoff.p;
+                k.pedge_off = (const int64_t*)a->h_poff.p;
+                k.out = (u64*)a->h_pcounts.p;
+                k.ostep = npc;
+                hipLaunchKernelGGL(k_bhist_pair, dim3((unsigned)P, (unsigned)ny, (unsigned)mc), dim3(256), pair_lds, st, k);
+                BHIST_HIP("pair launch", hipGetLastError());
+                ++a->h_launches;
+            }
+        }
+        BHIST_HIP("copy", hipMemcpyAsync(counts_out + m0 * ncnt, a->h_counts.p, (size_t)mc * ncnt * 8, hipMemcpyDeviceToHost, st));
+        if (P) BHIST_HIP("copy", hipMemcpyAsync(pair_counts_out + m0 * npc, a->h_pcounts.p, (size_t)mc * npc * 8, hipMemcpyDeviceToHost, st));
+        // the chunk's counts leave (and its staged edges are consumed) before the next chunk reuses the buffers
+        BHIST_HIP("synchronize", hipStreamSynchronize(st));
+    }
+    return 0;
+}
+
+int emx_histograms_batch_info(emx_batch* b, int64_t* launches_out) {
+    EmxBatchView v;
+    if (emx_internal_batch_view(b, &v)) return -1;
+    const BatchSummary* a = *v.summary;
+    if (launches_out) *launches_out = a ? a->h_launches : 0;
     return 0;
 }
 

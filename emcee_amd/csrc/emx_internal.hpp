@@ -62,6 +62,8 @@ struct EmxBatchView {
     BatchSummary** summary;  // the handle's slot (nullptr until the first call)
     const double* chain_blobs;   // (B, cap, N, nblobs) member-major, or nullptr
     int32_t nblobs;
+    int64_t hist_members;    // tuning "batch_hist_members" (0: auto)
+    int64_t hist_rows;       // tuning "batch_hist_rows" (0: auto)
 };
 // implemented in emx_batch.hip
 int emx_internal_batch_view(emx_batch* b, EmxBatchView* v);

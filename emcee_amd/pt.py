@@ -452,6 +452,19 @@ class PTSampler(object):
         lead = (self.nbatch, self.ntemps)
         return type(r)(r.nsamples, *[None if a is None else a.reshape(lead + a.shape[1:]) for a in r[1:]])
 
+    def get_histograms(self, bins=64, range=None, discard=0, thin=1, pairs="all", pair_bins=None):
+        """:meth:`EnsembleBatch.get_histograms` of every rung -> :class:`~emcee_amd.summary.BatchHistograms` with ``(nbatch, ntemps,
+        ...)`` leading axes on every per-column and per-panel array.  ``range`` may additionally be ``(nbatch, ntemps, ndim, 2)``."""
+        if range is not None and np.ndim(range) == 4:
+            range = np.asarray(range, dtype=np.float64)
+            if range.shape[:2] != (self.nbatch, self.ntemps):
+                raise ValueError("range: (nbatch, ntemps, ndim, 2) = (%d, %d, %d, 2); got %s" % (self.nbatch, self.ntemps, self.ndim, range.shape))
+            range = range.reshape((self.nbatch * self.ntemps,) + range.shape[2:])
+        r = self._b.get_histograms(bins=bins, range=range, discard=discard, thin=thin, pairs=pairs, pair_bins=pair_bins)
+        lead = (self.nbatch, self.ntemps)
+        split = (lambda arrays: [a.reshape(lead + a.shape[1:]) for a in arrays])
+        return type(r)(r.nsamples, split(r.edges), split(r.counts), r.pairs, split(r.pair_edges), split(r.pair_counts))
+
     def mean_log_likelihood(self, discard=0):
         """``(nbatch, ntemps)``: the mean of ``L`` over the stored steps from ``discard`` on and every walker, on the device."""
         it = self.iteration

@@ -10,7 +10,7 @@ from collections import namedtuple
 
 import numpy as np
 
-__all__ = ["BatchSummary", "Histograms", "quantile_ranks", "lerp", "MAX_QUANTILES", "MAX_BINS", "MAX_PAIR_BINS"]
+__all__ = ["BatchSummary", "Histograms", "BatchHistograms", "quantile_ranks", "lerp", "MAX_QUANTILES", "MAX_BINS", "MAX_PAIR_BINS"]
 
 MAX_QUANTILES = 16          # two ranks a quantile: the 32 ranks of one emx_summary_batch call
 
@@ -27,6 +27,14 @@ Histograms.__doc__ = """The result of ``get_histograms``: ``nsamples`` (selected
 ``(nb_d + 1,)``) and ``counts`` (int64, ``(nb_d,)``): ``np.histogram``'s; ``pairs`` ``(P, 2)`` column pairs ``(i, j)``, per column
 ``pair_edges`` (``(pb_d + 1,)``) and per pair ``pair_counts`` (int64, ``(pb_i, pb_j)``, axis 0 is column ``i``):
 ``np.histogram2d(x[:, i], x[:, j], bins=[pair_edges[i], pair_edges[j]])``'s."""
+
+BatchHistograms = namedtuple("BatchHistograms", ["nsamples", "edges", "counts", "pairs", "pair_edges", "pair_counts"])
+BatchHistograms.__doc__ = """The result of ``EnsembleBatch.get_histograms``: :class:`Histograms` with a leading member axis on every
+per-column and per-panel array -- ``nsamples`` (selected steps x walkers, of every member); per column ``edges`` (float64,
+``(M, nb_d + 1)``: every member has its own) and ``counts`` (int64, ``(M, nb_d)``); ``pairs`` ``(P, 2)``, common to all members; per
+column ``pair_edges`` (``(M, pb_d + 1)``) and per pair ``pair_counts`` (int64, ``(M, pb_i, pb_j)``, axis 1 is column ``i``).  Member
+``m``'s numbers are ``np.histogram`` / ``np.histogram2d``'s on that member's samples with that member's edges.  The count arrays
+may be views of the two buffers the device filled (copy one to keep it without the rest)."""
 
 
 def quantile_ranks(n, q):
@@ -206,4 +214,71 @@ def host_histograms(x, edges, pair_edges, pairs):
         ni, nj = len(pair_edges[i]) - 1, len(pair_edges[j]) - 1
         ok = oi & oj
         pc.append(np.bincount(bi[ok] * nj + bj[ok], minlength=ni * nj).astype(np.int64).reshape(ni, nj))
+    return counts, pc
+
+
+# ---- histograms of a batch: every member its own edges ----------------------------------------------------------------------
+def check_batch_range(range):
+    """:func:`check_range`, or additionally a float64 ``(B, W, 2)`` array: one ``(lo, hi)`` for every column of every member"""
+    if range is not None:
+        r = np.asarray(range, dtype=np.float64)
+        if r.ndim == 3:
+            if r.shape[2] != 2:
+                raise ValueError("range is None, (lo, hi), (ncolumns, 2) or (nmembers, ncolumns, 2); got shape %s" % (r.shape,))
+            if not np.isfinite(r).all():
+                raise ValueError("range must be finite; got a non-finite bound for member(s) %s"
+                                 % np.flatnonzero(~np.isfinite(r).all(axis=(1, 2))).tolist())
+            if (r[..., 0] > r[..., 1]).any():
+                raise ValueError("range needs lo <= hi; not so for member(s) %s" % np.flatnonzero((r[..., 0] > r[..., 1]).any(axis=1)).tolist())
+            return r
+    return check_range(range)
+
+
+def check_batch_columns(bins, range, B, W, what):
+    """:func:`check_columns` for a batch of ``B`` members: a 3-d ``range`` is ``(B, W, 2)``"""
+    if range is not None and range.ndim == 3:
+        if range.shape[:2] != (B, W):
+            raise ValueError("range: one (lo, hi) for every one of the %d columns of every one of the %d members, shape (%d, %d, 2); "
+                             "got %s" % (W, B, B, W, range.shape,))
+        range = None
+    check_columns(bins, range, W, what)
+
+
+def shared_edges(bins, range):
+    """whether every member of a batch has the same edges: the caller's own, or an integer ``bins`` over a ``range`` given once"""
+    return not isinstance(bins, int) or (range is not None and range.ndim < 3)
+
+
+def member_edges(bins, range, M, W, minmax):
+    """-> the W edge arrays of ``M`` members, each ``(M, nb_d + 1)``: row ``m`` is what :func:`column_edges` gives member ``m`` --
+    ``np.linspace(lo, hi, bins + 1)`` for an integer ``bins``, bit for bit (``lo == hi`` widened by 0.5 each way), else the
+    caller's edges for every member.  ``range``: None (``minmax`` = ``(lo (M, W), hi (M, W))`` of every member's data), one
+    ``(2,)`` / ``(W, 2)`` for all members, or ``(M, W, 2)``."""
+    if not isinstance(bins, int):
+        return [np.tile(e, (M, 1)) for e in column_edges(bins, None, W, None)]
+    if range is None:
+        lo, hi = (np.array(v, dtype=np.float64).reshape(M, W) for v in minmax)
+    else:
+        r = np.broadcast_to(range, (M, W, 2))
+        lo, hi = r[..., 0].copy(), r[..., 1].copy()
+    same = lo == hi
+    lo[same] -= 0.5
+    hi[same] += 0.5
+    # np.linspace over arrays runs the scalar call's operations element by element (arange * step + start, the last value set to
+    # stop) unless some step underflows to 0, where it takes another expression for ALL elements: then member by member
+    if M * W == 0 or ((hi - lo) / bins == 0).any():
+        rows = [column_edges(bins, np.stack([lo[m], hi[m]], axis=1), W, None) for m in np.arange(M)]
+        return [np.stack([rows[m][d] for m in np.arange(M)]) if M else np.empty((0, bins + 1)) for d in np.arange(W)]
+    e = np.linspace(lo, hi, bins + 1, axis=-1)                  # (M, W, bins + 1)
+    return [np.ascontiguousarray(e[:, d, :]) for d in np.arange(W)]
+
+
+def host_histograms_batch(x, edges, pair_edges, pairs):
+    """the NumPy twin of ``emx_histograms_batch`` on the ``(M, n, W)`` samples ``x`` with the per-member ``edges`` / ``pair_edges`` of
+    :func:`member_edges` -> ``(counts, pair_counts)``: per column ``(M, nb_d)``, per pair ``(M, pb_i, pb_j)``, int64"""
+    M, _, W = x.shape
+    per = [host_histograms(x[m], [e[m] for e in edges], None if pair_edges is None else [e[m] for e in pair_edges], pairs)
+           for m in range(M)]
+    counts = [np.stack([per[m][0][d] for m in range(M)]) for d in range(W)]
+    pc = [np.stack([per[m][1][p] for m in range(M)]) for p in range(len(pairs))]
     return counts, pc

@@ -654,7 +654,11 @@ int64_t emx_host_pull_capacity(int64_t nwalkers, int32_t world, int32_t nsplits,
  *   "batch_acf_series"   0 (auto)  emx_autocorr_batch: at most this many (member, walker, dim) series per FFT chunk (auto: the
  *                                  scratch within ~3 GB); a chunk may begin and end inside a member
  *   "batch_summary_members" 0 (auto) emx_summary_batch: at most this many members per pass (auto: the scratch within ~512 MB);
- *                                  every member is reduced on its own in an order fixed by its shape, so no bit depends on it */
+ *                                  every member is reduced on its own in an order fixed by its shape, so no bit depends on it
+ *   "batch_hist_members" 0 (auto)  emx_histograms_batch: at most this many members per chunk (auto: the chunk's one-byte bin-code
+ *                                  plane, edges and counters within ~256 MB); every count is a sum of integers, so none depends on it
+ *   "batch_hist_rows"    0 (auto)  emx_histograms_batch: selected rows of a member per chunk of the code plane (auto: all of them,
+ *                                  unless ONE member's code plane exceeds ~256 MB); no count depends on it */
 typedef struct emx_batch emx_batch;
 /* host only (no device touched): 0 when the kernel takes the shape, else -1 and the reason in msg */
 int emx_batch_check(int64_t nwalkers, int32_t ndim, int32_t target, int32_t nmoves, const emx_move_desc* moves, char* msg,
@@ -792,6 +796,35 @@ int emx_summary_batch(emx_batch* b, int32_t member_lo, int32_t member_hi, int64_
 int emx_summary_batch_plane(emx_batch* b, int32_t plane, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop,
                             int64_t stride, double* mean_out, double* cov_out, int32_t nranks, const int64_t* ranks,
                             double* order_out, double* map_coords_out, double* map_log_prob_out, int64_t* nsamples_out);
+/* Histograms of members [member_lo, member_hi) of the batch over emx_summary_batch's selection of rows (plane 0: coordinates,
+ * W = ndim; 4: blobs, W = nblobs -- emx_batch_chain_read's numbering), counted next to the member-major chain
+ * (csrc/emx_batch_hist.hpp): what emx_chain_minmax / emx_histograms return for one ensemble, for every member at once.  One launch
+ * grid covers every member of a chunk, so the number of launches does not grow with the number of members.  The rule is
+ * emx_histograms': v falls in bin b iff e[b] <= v < e[b + 1], the last bin closed on the right; NaN, +-inf beyond the edges and
+ * everything outside are counted nowhere.
+ * emx_chain_minmax_batch: per (member, column) the smallest and the largest FINITE value (+inf / -inf where there is none) and
+ * the number of non-finite ones: lo_out, hi_out, nonfinite_out, each (members, W).  Exact, whatever the order of the reduction.
+ * emx_histograms_batch: the offsets edge_off / pedge_off (W + 1 entries, as emx_histograms': 1 ... 1024 marginal and 1 ... 128
+ * pair bins a column), the pairs and pair_off are common to all members; the edge VALUES are per member: member m of the range
+ * reads edges + m edge_member_stride (pedges + m pedge_member_stride), strictly increasing; stride 0: one set shared by all
+ * members, else at least edge_off[W] (pedge_off[W]).  counts_out (members, edge_off[W] - W): member m's column d at
+ * [m][edge_off[d] - d ...); pair_counts_out (members, pair_off[npairs]): member m's panel p, pb_i x pb_j counts with column i the
+ * slow axis, at [m][pair_off[p] ...).  *nsamples_out: rows x nwalkers, of every member.  Each member's chain is read once whatever
+ * the number of pairs (a one-byte bin code per value in a dim-major plane per member, from which the panels are counted); members
+ * go in chunks (tuning "batch_hist_members"), and the rows of a member whose code plane alone exceeds the budget too
+ * ("batch_hist_rows").  Every count is a sum of integers: no count depends on the launch shape, the chunking, the member range or
+ * the order of the atomics.  Tempered handles: members are nbatch x ntemps.  Scratch stays on the handle.  -1 for bad arguments
+ * (plane 4 of a handle without blobs, an empty selection, a member range outside the batch, edges that do not increase), -2 for
+ * a device failure.  (Named like emx_summary_batch: the emx_batch_ prefix is the handle's own closed set.)
+ * emx_histograms_batch_info: *launches_out the kernel launches of the handle's last emx_histograms_batch call. */
+int emx_chain_minmax_batch(emx_batch* b, int32_t plane, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop,
+                           int64_t stride, double* lo_out, double* hi_out, int64_t* nonfinite_out);
+int emx_histograms_batch(emx_batch* b, int32_t plane, int32_t member_lo, int32_t member_hi, int64_t start, int64_t stop,
+                         int64_t stride, const int64_t* edge_off, const double* edges, int64_t edge_member_stride,
+                         int64_t* counts_out, const int64_t* pedge_off, const double* pedges, int64_t pedge_member_stride,
+                         int64_t npairs, const int32_t* pairs, const int64_t* pair_off, int64_t* pair_counts_out,
+                         int64_t* nsamples_out);
+int emx_histograms_batch_info(emx_batch* b, int64_t* launches_out);
 /* host twin of the selection (no device): the ranks[r]-th smallest of x[0], x[stride], ..., n values, with the same key
  * transform and digit search as the kernels.  0, or -1 for bad arguments (n < 1, stride < 1, nranks outside [0, 32], a rank
  * outside [0, n)). */
