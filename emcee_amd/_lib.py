@@ -60,10 +60,17 @@ class FusedEnsembleBlobsLaunch(C.Structure):
                                                ("blobs_row", C.c_void_p)]
 
 
+class FusedEnsembleDataLaunch(C.Structure):
+    """emx_fused_ensemble_data_launch of include/emx.h: FusedEnsembleLaunch's fields, then the data count and the rows a workgroup"""
+    _fields_ = FusedEnsembleLaunch._fields_ + [("ndata", C.c_int64), ("rows", C.c_int32), ("reserved", C.c_int32)]
+
+
 # emx_fused_ensemble_fn: (const emx_fused_ensemble_launch*) -> int
 FUSED_ENSEMBLE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 # emx_fused_ensemble_blobs_fn: (const emx_fused_ensemble_blobs_launch*) -> int
 FUSED_ENSEMBLE_BLOBS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
+# emx_fused_ensemble_data_fn: (const emx_fused_ensemble_data_launch*) -> int
+FUSED_ENSEMBLE_DATA_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 # emx_fused_batch_fn: (const emx_fused_launch*) -> int
 FUSED_BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 # emx_pt_fused_fn: (emx_pt_fused_launch*) -> int
@@ -101,6 +108,7 @@ SIGNATURES = {
     "emx_set_target_fused": (C.c_int, [_P, FUSED_ENSEMBLE_FN, _P]),
     "emx_set_target_fused_blobs": (C.c_int, [_P, FUSED_ENSEMBLE_BLOBS_FN, _P, C.c_int32]),
     "emx_set_target_fused_small": (C.c_int, [_P, FUSED_BATCH_FN]),
+    "emx_set_target_fused_data": (C.c_int, [_P, FUSED_ENSEMBLE_DATA_FN, _P, C.c_int64]),
     "emx_small_fused_check": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(MoveDesc), C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
     "emx_small_fused_pays": (C.c_int, [C.c_int64, C.c_int32, C.c_int32]),
     "emx_small_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),

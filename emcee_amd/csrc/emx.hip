@@ -18,6 +18,7 @@
 
 #include "../../include/emx.h"
 #include "emx_fused_ensemble.hpp"
+#include "emx_fused_ensemble_data.hpp"
 #include "emx_internal.hpp"
 #include "emx_kernels.hpp"
 #include "emx_launch.hpp"
@@ -551,6 +552,10 @@ struct emx_ctx {
     std::vector<hipEvent_t> prof;
     int prof_max = 0, prof_n = 0;
     std::string err;
+    // a fused user target that sums over data (emx_set_target_fused_data; k_halfstep_user_data): the launcher and the data count
+    emx_fused_ensemble_data_fn fused_data_fn = nullptr;
+    int64_t fused_ndata = 0;
+    int64_t tune_fused_data_rows = 0;         // rows a workgroup of that kernel; 0: fused_ens_data_rows_rule
 };
 
 static void graph_invalidate(emx_ctx* c);
@@ -850,7 +855,7 @@ int launch_split(emx_ctx* c, int move, int target, int S, int split, int pos0, i
     const bool fused = target == EMX_TARGET_FUSED_ENSEMBLE;
     if (fused) {
         // the caller's function compiled into the half-step (emx_fused_ensemble.hpp): one launch, one replica, no replay
-        if (c->nblobs > 0 ? !c->fused_blobs_fn : !c->fused_fn) {
+        if (c->fused_data_fn ? c->nblobs > 0 : c->nblobs > 0 ? !c->fused_blobs_fn : !c->fused_fn) {
             c->err = "fused user target without a launcher (emx_set_target_fused)";
             return -1;
         }
@@ -1124,7 +1129,26 @@ int launch_split(emx_ctx* c, int move, int target, int S, int split, int pos0, i
                       (move == MOVE_STRETCH || move == MOVE_DE) && lean_kind(a, 16, 2, 4, move, true) == 1;
     if (fused) {
         int rcf;
-        if (c->nblobs > 0) {
+        if (c->fused_data_fn) {
+            // a wave a row in the data sum (emx_fused_ensemble_data.hpp): the rows a workgroup takes spread the split over the chip
+            const int tile = fused_ens_tile_rule(D);
+            const int rows = c->tune_fused_data_rows > 0 ? (int)std::min<int64_t>(c->tune_fused_data_rows, tile)
+                                                         : fused_ens_data_rows_rule(D, nown, c->num_cu);
+            emx_fused_ensemble_data_launch fl{};
+            fl.abi = EMX_FUSED_ENSEMBLE_DATA_ABI;
+            fl.args_bytes = (uint32_t)sizeof(HalfStepArgs);
+            fl.ndim = D;
+            fl.move = move;
+            fl.grid = (int32_t)std::min<int64_t>((nown + rows - 1) / rows, (int64_t)c->num_cu * 64);
+            fl.threads = FUSED_ENS_THREADS;
+            fl.lds_bytes = fused_ens_lds_of(D, rows);
+            fl.hip_stream = (void*)c->stream;
+            fl.args = &a;
+            fl.user = c->fused_user;
+            fl.ndata = c->fused_ndata;
+            fl.rows = rows;
+            rcf = c->fused_data_fn(&fl);
+        } else if (c->nblobs > 0) {
             // the blobs go where lp and chain_lp go: the walkers' array (an evaluation of other rows: the evaluation buffer), and the
             // plane's row of the stored step chain_lp points into
             const int K = c->nblobs, tile = fused_ens_blobs_tile_rule(D, K);
@@ -1756,6 +1780,11 @@ int emx_set_tuning(emx_ctx* c, const char* key, int64_t v) {
         c->tune_bpc = v > 0 ? v : 2;
         return 0;
     }
+    if (!strcmp(key, "fused_data_rows")) {      // rows a workgroup of k_halfstep_user_data; 0: the rule (clamped to the tile at launch)
+        NEED(c, v == 0 || (v >= FUSED_ENS_DATA_MIN_ROWS && v <= FUSED_ENS_THREADS), "tuning \"fused_data_rows\": 0 (the rule) or 4 ... 256; got %lld", (long long)v);
+        c->tune_fused_data_rows = v;
+        return 0;
+    }
     FAIL(c, -1, "unknown tuning key %s", key);
 }
 
@@ -1908,6 +1937,7 @@ int emx_set_target_fused(emx_ctx* c, emx_fused_ensemble_fn launcher, const void*
     c->fused_fn = launcher;
     c->fused_blobs_fn = nullptr;
     c->fused_small_fn = nullptr;
+    c->fused_data_fn = nullptr;
     c->fused_user = user;
     c->Dp = 0;
     graph_invalidate(c);
@@ -1969,6 +1999,48 @@ int emx_set_target_fused_blobs(emx_ctx* c, emx_fused_ensemble_blobs_fn launcher,
     c->fused_blobs_fn = launcher;
     c->fused_fn = nullptr;
     c->fused_small_fn = nullptr;
+    c->fused_data_fn = nullptr;
+    c->fused_user = user;
+    c->Dp = 0;
+    graph_invalidate(c);
+    c->graph_warm = false;
+    c->target = EMX_TARGET_FUSED_ENSEMBLE;
+    c->tscale = 1.0;
+    return 0;
+}
+
+// A fused user target that sums over data (include/emx.h; emx_fused_ensemble_data.hpp): emx_set_target_fused with the data
+// launcher's descriptor and the number of data; no blobs, no one-workgroup launcher.
+int emx_set_target_fused_data(emx_ctx* c, emx_fused_ensemble_data_fn launcher, const void* user, int64_t ndata) {
+    { const int rcs_ = persist_settle(c); if (rcs_) return rcs_; }
+    NEED(c, launcher != nullptr, "emx_set_target_fused_data: no launcher");
+    NEED(c, ndata >= 0 && ndata < (1ll << 31), "emx_set_target_fused_data: 0 <= ndata < 2^31; got %lld", (long long)ndata);
+    NEED(c, c->D >= 1 && c->D <= FUSED_ENS_MAX_NDIM, "emx_set_target_fused_data: a fused user target has 1 <= ndim <= %d; the ensemble has ndim %d",
+         FUSED_ENS_MAX_NDIM, c->D);
+    NEED(c, c->world == 1 && !c->comm && !c->sendbuf && !c->peers_ready,
+         "emx_set_target_fused_data: a fused user target runs on one replica (no sharding, no exchange)");
+    emx_fused_ensemble_data_launch fl{};           // the probe: nothing is launched
+    fl.abi = EMX_FUSED_ENSEMBLE_DATA_ABI;
+    fl.args_bytes = (uint32_t)sizeof(HalfStepArgs);
+    fl.ndim = c->D;
+    fl.move = MOVE_EVAL;
+    const int rcp = launcher(&fl);
+    if (rcp == 2) FAIL(c, -1, "emx_set_target_fused_data: the fused user target was compiled for another ndim; the ensemble has ndim %d", c->D);
+    if (rcp)
+        FAIL(c, -8, "emx_set_target_fused_data: the launcher was built against another version of emx_fused_ensemble.hpp, or is not an "
+                    "EMX_FUSED_ENSEMBLE_DATA_TARGET launcher (it answered %d); rebuild it against this library's headers", rcp);
+    NEED(c, c->nblobs == 0 || c->stored == 0, "emx_set_target_fused_data: the context holds %lld stored steps with %d blobs a sample; "
+         "reset the chain before the blob count changes", (long long)c->stored, c->nblobs);
+    HIPOK(c, hipSetDevice(c->device));
+    PIPE_STOP(c);
+    drop_prepared(c);
+    HIPOK(c, hipStreamSynchronize(c->stream));
+    blob_storage_free(c);
+    c->fused_data_fn = launcher;
+    c->fused_ndata = ndata;
+    c->fused_fn = nullptr;
+    c->fused_blobs_fn = nullptr;
+    c->fused_small_fn = nullptr;
     c->fused_user = user;
     c->Dp = 0;
     graph_invalidate(c);
@@ -1984,6 +2056,8 @@ int emx_set_target_fused_small(emx_ctx* c, emx_fused_batch_fn small_launcher) {
     { const int rcs_ = persist_settle(c); if (rcs_) return rcs_; }
     NEED(c, c->target == EMX_TARGET_FUSED_ENSEMBLE, "emx_set_target_fused_small: the context's target is not a fused user target "
          "(call emx_set_target_fused or emx_set_target_fused_blobs first)");
+    NEED(c, !c->fused_data_fn || !small_launcher, "emx_set_target_fused_small: a fused user target that sums over data "
+         "(emx_set_target_fused_data) has no one-workgroup form");
     if (small_launcher) {
         emx_fused_launch fl{};                     // the probe: nothing is launched
         fl.abi = EMX_FUSED_ENSEMBLE_SMALL_ABI;

@@ -205,6 +205,8 @@ class DeviceEnsemble:
         self._ck(self.lib.emx_set_stream(self.ctx, stream_ptr))
 
     def set_tuning(self, key, value):
+        if key == "fused_data_rows" and not (int(value) == 0 or 4 <= int(value) <= 256):      # (refused before the library is called)
+            raise ValueError("tuning \"fused_data_rows\": 0 (the library's rule) or the rows a workgroup takes, 4 ... 256; got %r" % (value,))
         self._ck(self.lib.emx_set_tuning(self.ctx, key.encode(), int(value)))
 
     # ---- target ----
@@ -279,16 +281,25 @@ class DeviceEnsemble:
         self._ck(self.lib.emx_set_target_callback(self.ctx, fn, C.c_void_p(user_ptr) if not isinstance(user_ptr, C.c_void_p) else user_ptr))
         self._target_kind = _lib.TARGET_CALLBACK
 
-    def set_target_fused(self, fn_ptr, user_address=None, nblobs=0, small_fn=None):
+    def set_target_fused(self, fn_ptr, user_address=None, nblobs=0, small_fn=None, ndata=None):
         """A launcher emitted by ``EMX_FUSED_ENSEMBLE_TARGET`` (``emx_fused_ensemble.hpp``) as the target: the user's per-row device
         function runs inside the half-step kernel.  ``fn_ptr``: a ctypes function or an address; ``user_address``: the device
         address its functor receives (None: null).  The library probes the launcher and refuses another header version or ndim.
         ``nblobs`` > 0: a launcher of ``EMX_FUSED_ENSEMBLE_TARGET_BLOBS`` with that many blobs a sample (another count is refused).
         ``small_fn``: the ``EMX_FUSED_ENSEMBLE_SMALL_TARGET[_BLOBS]`` launcher of the same functor (``emx_set_target_fused_small``): an
-        ensemble that fits one workgroup's LDS then runs ``run`` calls in one workgroup; None: none is bound."""
+        ensemble that fits one workgroup's LDS then runs ``run`` calls in one workgroup; None: none is bound.
+        ``ndata`` (an integer, 0 <= ndata < 2^31): ``fn_ptr`` is an ``EMX_FUSED_ENSEMBLE_DATA_TARGET`` launcher
+        (``emx_fused_ensemble_data.hpp``; ``emx_set_target_fused_data``) whose ``term`` runs over that many data, a wave a row;
+        no blobs and no ``small_fn`` then."""
+        if ndata is not None and (nblobs or small_fn is not None):
+            raise ValueError("a fused user target that sums over data (ndata) has no blobs and no one-workgroup launcher")
         if isinstance(fn_ptr, (int, np.integer)):
             fn_ptr = C.c_void_p(int(fn_ptr))
-        if nblobs:
+        if ndata is not None:
+            fn = fn_ptr if isinstance(fn_ptr, _lib.FUSED_ENSEMBLE_DATA_FN) else C.cast(fn_ptr, _lib.FUSED_ENSEMBLE_DATA_FN)
+            self._touch_target = fn                             # the library holds the pointer: keep the object alive
+            self._ck(self.lib.emx_set_target_fused_data(self.ctx, fn, C.c_void_p(user_address), int(ndata)))
+        elif nblobs:
             fn = fn_ptr if isinstance(fn_ptr, _lib.FUSED_ENSEMBLE_BLOBS_FN) else C.cast(fn_ptr, _lib.FUSED_ENSEMBLE_BLOBS_FN)
             self._touch_target = fn
             self._ck(self.lib.emx_set_target_fused_blobs(self.ctx, fn, C.c_void_p(user_address), int(nblobs)))

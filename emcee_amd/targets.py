@@ -22,7 +22,7 @@ from . import _lib
 
 __all__ = ["DeviceTarget", "IsoGaussian", "DiagGaussian", "DenseGaussian", "Rosenbrock", "UniformBox", "DeviceCallable", "DeviceKernel",
            "BatchCallable", "BatchKernel", "BatchFused", "BatchFusedLibrary", "compile_fused", "get_include", "PTFused", "PTFusedLibrary",
-           "compile_fused_pt", "DeviceFused", "DeviceFusedLibrary", "compile_fused_ensemble"]
+           "compile_fused_pt", "DeviceFused", "DeviceFusedLibrary", "compile_fused_ensemble", "fused_data_sum"]
 
 
 class DeviceTarget(object):
@@ -188,10 +188,23 @@ class DeviceFused(DeviceTarget):
     rng modes, with or without blobs, to the same bits -- where that was measured faster (``emx_small_fused_pays``: ndim <= 16 under
     ``rng="mt19937"``, ndim <= 10 and nwalkers x ndim <= 1 024 under ``rng="philox"``).  Larger ensembles, ``WalkMove`` / ``KDEMove``
     schedules, a ``GaussianMove`` under ``rng="mt19937"`` and ``sample()`` driven step by step keep the launch per half-step.  None:
-    always that path."""
+    always that path.
+
+    ``ndata`` (an integer, ``0 <= ndata < 2**31``): the log-probability sums over data, ``base(x) + sum_k term(x; datum k)``, and
+    ``fn_ptr`` is the launcher that ``EMX_FUSED_ENSEMBLE_DATA_TARGET(name, Model, ndim)`` of ``emx_fused_ensemble_data.hpp`` emits
+    around a model with ``base`` and ``term`` members.  The half-step then gives every row a WAVE for the data sum -- one lane calls
+    ``base``, 64 lanes stride over the data, a fixed pairwise tree adds the lane partials -- where the plain functor would loop over
+    the data in one lane, and a mid-size ensemble is spread over the chip in small tiles.  The value of a row is defined by the
+    header and reproduced on the host by :func:`fused_data_sum`; the run is bit for bit the :class:`DeviceKernel` run of a kernel
+    that sums in that order.  ``ndata`` is a run-time value: one launcher serves every data set.  No blobs and no ``small_fn``
+    with ``ndata`` (``ValueError``); such a target always runs one launch a half-step.  Where it pays, measured on the
+    straight-line fit against the one-lane functor of the same model (``profiles/ensemble_fused_data.md``): at 1 024 and 4 096
+    walkers from the smallest count measured, 64 data (3 to 4 times the speed; 17 to 25 times at 1 024 data, 35 to 48 times at
+    16 384); at 65 536 walkers the crossover lies between 64 data (0.89 times the speed of a plain one-accumulator loop, 1.95 times
+    that of the loop in the data target's order) and 1 024 data (3.9 and 9.6 times), with 6.6 and 16 times at 16 384."""
     kind = _lib.TARGET_FUSED_ENSEMBLE
 
-    def __init__(self, fn_ptr, ndim, user=None, nblobs=0, small_fn=None):
+    def __init__(self, fn_ptr, ndim, user=None, nblobs=0, small_fn=None, ndata=None):
         if not isinstance(fn_ptr, ctypes._CFuncPtr):
             addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
             if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
@@ -208,6 +221,11 @@ class DeviceFused(DeviceTarget):
                 raise TypeError("DeviceFused's small_fn is an EMX_FUSED_ENSEMBLE_SMALL_TARGET launcher: a ctypes function, a non-null address or None")
         self.fn_ptr, self.ndim, self.user, self.small_fn = fn_ptr, int(ndim), user, small_fn
         self.nblobs = _check_nblobs("DeviceFused", nblobs)
+        self.ndata = _check_ndata("DeviceFused", ndata)
+        if self.ndata is not None and self.nblobs > 0:
+            raise ValueError("DeviceFused: a target that sums over data (ndata) carries no blobs; nblobs=%d is refused" % self.nblobs)
+        if self.ndata is not None and small_fn is not None:
+            raise ValueError("DeviceFused: a target that sums over data (ndata) has no one-workgroup form; small_fn is refused")
 
     def user_address(self):
         """-> the device address handed to the functor (None: a null pointer)"""
@@ -222,7 +240,10 @@ class DeviceFused(DeviceTarget):
         if ens.ndim != self.ndim:
             raise ValueError("the DeviceFused target was compiled for ndim %d; the sampler has ndim %d" % (self.ndim, ens.ndim))
         if getattr(ens, "_cb_owner", None) is not self or ens._target_kind != self.kind:
-            ens.set_target_fused(self.fn_ptr, self.user_address(), self.nblobs, small_fn=self.small_fn)
+            if self.ndata is not None:
+                ens.set_target_fused(self.fn_ptr, self.user_address(), ndata=self.ndata)
+            else:
+                ens.set_target_fused(self.fn_ptr, self.user_address(), self.nblobs, small_fn=self.small_fn)
             ens._cb_owner = self
 
     def __call__(self, x):
@@ -233,6 +254,35 @@ def _check_nblobs(who, nblobs):
     if isinstance(nblobs, bool) or not isinstance(nblobs, (int, np.integer)) or not 0 <= nblobs <= _lib.MAX_BLOBS:
         raise ValueError("%s: nblobs is an integer in [0, %d] (float64 blobs a sample); got %r" % (who, _lib.MAX_BLOBS, nblobs))
     return int(nblobs)
+
+
+def _check_ndata(who, ndata):
+    if ndata is None:
+        return None
+    if isinstance(ndata, bool) or not isinstance(ndata, (int, np.integer)) or not 0 <= ndata < 2 ** 31:
+        raise ValueError("%s: ndata is an integer in [0, 2**31) (the data the target's term runs over), or None; got %r" % (who, ndata))
+    return int(ndata)
+
+
+def fused_data_sum(terms):
+    """Sum a 1-d float64 array in the order a data target's kernel sums its terms (``emx_fused_ensemble_data.hpp``): lane partial
+    ``p[l]``, ``l = 0 ... 63``, starts at +0.0 and adds ``terms[k]`` for ``k = l, l + 64, l + 128, ...`` in ascending ``k``; the
+    result is the balanced pairwise tree over ``p[0] ... p[63]``, adjacent pairs level by level.  With it the host reproduces a
+    device log-probability bit for bit: ``base + fused_data_sum(terms)``.  An empty array gives 0.0."""
+    t = np.asarray(terms, dtype=np.float64)
+    if t.ndim != 1:
+        raise ValueError("fused_data_sum: a 1-d array of terms; got shape %r" % (t.shape,))
+    n = t.shape[0]
+    pad = np.zeros(((n + 63) // 64) * 64, dtype=np.float64)
+    pad[:n] = t
+    p = np.zeros(64, dtype=np.float64)
+    for row in pad.reshape(-1, 64)[:n // 64]:        # whole strides: every lane adds
+        p = p + row
+    if n % 64:
+        p[:n % 64] = p[:n % 64] + pad[n - n % 64:n]  # the last, partial stride: the lanes past the end add nothing
+    while p.shape[0] > 1:
+        p = p[0::2] + p[1::2]
+    return float(p[0])
 
 
 class BatchTarget(DeviceTarget):
@@ -419,22 +469,32 @@ class DeviceFusedLibrary(object):
     ``extern "C"`` setup functions of ``source`` are there), ``name`` of the launcher, ``ndim``, ``nblobs``, ``small_name`` /
     ``small_launcher`` (the one-workgroup launcher, None when it was built with ``small=False``) and :meth:`target`."""
 
-    def __init__(self, path, name, ndim, nblobs=0, small_name=None):
+    def __init__(self, path, name, ndim, nblobs=0, small_name=None, data=False):
         self.path, self.name, self.ndim, self.nblobs = path, name, int(ndim), _check_nblobs("DeviceFusedLibrary", nblobs)
+        self.data = bool(data)            # the launcher is an EMX_FUSED_ENSEMBLE_DATA_TARGET one: target() takes the data count
         _lib.load()                       # one HIP runtime per process: the library's (torch's) first
         self.lib = ctypes.CDLL(path)
         self.launcher = getattr(self.lib, name)
         self.small_name = small_name
         self.small_launcher = getattr(self.lib, small_name) if small_name else None
 
-    def target(self, user=None):
-        """-> :class:`DeviceFused` of the compiled functor with the device pointer ``user``"""
+    def target(self, user=None, ndata=None):
+        """-> :class:`DeviceFused` of the compiled functor with the device pointer ``user``; a library built with ``data=True``
+        needs ``ndata``, the number of data its ``term`` runs over, and any other refuses it"""
+        if self.data and ndata is None:
+            raise ValueError("DeviceFusedLibrary.target: the library was built with data=True; give ndata, the number of data")
+        if not self.data and ndata is not None:
+            raise ValueError("DeviceFusedLibrary.target: ndata is for a library built with compile_fused_ensemble(..., data=True)")
+        if self.data:
+            t = DeviceFused(self.launcher, self.ndim, user, ndata=ndata)
+            t._library = self
+            return t
         t = DeviceFused(self.launcher, self.ndim, user, nblobs=self.nblobs, small_fn=self.small_launcher)
         t._library = self                 # the launcher's code lives as long as the target
         return t
 
 
-def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir=None, nblobs=0, small=True):
+def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir=None, nblobs=0, small=True, data=False):
     """Compile the user's model into the single sampler's half-step kernel -> :class:`DeviceFusedLibrary`.
 
     ``source``: HIP C++ that defines the functor type ``functor`` -- ``__device__ double operator()(const double* x, int ndim, int
@@ -449,8 +509,15 @@ def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir
 
     ``small`` (default True): the translation unit also ends in ``EMX_FUSED_ENSEMBLE_SMALL_TARGET[_BLOBS](name_small, functor, ndim[,
     K])``, the one-workgroup launcher of ensembles that fit one workgroup's LDS (:class:`DeviceFused`'s ``small_fn``; four more
-    kernels to compile, about 2 s more).  ``small=False`` builds the library without it: the translation unit it always was."""
+    kernels to compile, about 2 s more).  ``small=False`` builds the library without it: the translation unit it always was.
+
+    ``data=True``: ``functor`` is a model with ``base(x, ndim, user)`` and ``term(x, ndim, k, user)`` members whose log-probability
+    sums over data (:class:`DeviceFused`'s ``ndata``).  The translation unit is ``#include <emx_fused_ensemble_data.hpp>``,
+    ``source`` and ``EMX_FUSED_ENSEMBLE_DATA_TARGET(name, functor, ndim)``; no one-workgroup launcher is emitted and ``nblobs``
+    is refused.  ``data=False`` keeps the translation unit and the cache key it always had."""
     nblobs = _check_nblobs("compile_fused_ensemble", nblobs)
+    if data and nblobs:
+        raise ValueError("compile_fused_ensemble: a data target (data=True) carries no blobs; nblobs=%d is refused" % nblobs)
     ndim = int(ndim)
     if ndim < 1 or ndim > 256:
         raise ValueError("compile_fused_ensemble: 1 <= ndim <= 256; got %d" % ndim)
@@ -464,6 +531,10 @@ def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir
     if nblobs:                            # (a blob-free build keeps the key, and with it the cached library, it always had)
         tail = "EMX_FUSED_ENSEMBLE_TARGET_BLOBS(%s, %s, %d, %d)" % (name, functor, ndim, nblobs)
         key += ("nblobs", nblobs)
+    if data:
+        tail = "EMX_FUSED_ENSEMBLE_DATA_TARGET(%s, %s, %d)" % (name, functor, ndim)
+        so = _compile_cached("compile_fused_ensemble", "emx_fused_ensemble_data.hpp", source, tail, key + ("data target",), name, flags, cache_dir)
+        return DeviceFusedLibrary(so, name, ndim, 0, None, data=True)
     small_name = name + "_small" if small else None
     if not small:                         # (the default build keeps the form of key it always had; the headers are part of its hash)
         key += ("half-step launcher only",)

@@ -241,6 +241,33 @@ typedef struct emx_fused_ensemble_blobs_launch {
 } emx_fused_ensemble_blobs_launch;
 typedef int (*emx_fused_ensemble_blobs_fn)(const emx_fused_ensemble_blobs_launch*);
 int emx_set_target_fused_blobs(emx_ctx* ctx, emx_fused_ensemble_blobs_fn launcher, const void* user, int32_t nblobs);
+/* The same target for a log-probability that sums over data: log p(x) = base(x) + sum_k term(x; datum k), k < ndata.  The caller's
+ * translation unit includes emcee_amd/csrc/emx_fused_ensemble_data.hpp and emits the launcher with
+ * EMX_FUSED_ENSEMBLE_DATA_TARGET(name, Model, ndim) around a model with `base` and `term` members; k_halfstep_user_data then gives
+ * every row a WAVE for the data sum (one lane calls base, 64 lanes stride over the data, a fixed pairwise tree adds the lane
+ * partials -- the header defines the order, so the value depends on nothing but x, the data and ndata) where the launcher above
+ * loops in one lane.  The descriptor is one of its own: the fields of emx_fused_ensemble_launch, then `ndata` (0 <= ndata < 2^31, a
+ * run-time value: the one given to emx_set_target_fused_data) and `rows`, the slots a workgroup takes at once (4 ... the header's
+ * tile for ndim; lds_bytes is the header's fused_ens_lds_of(ndim, rows)).  `abi` is EMX_FUSED_ENSEMBLE_DATA_ABI, a constant of its
+ * own, so a data launcher and a data-free launcher answer 1 to each other's descriptor.  grid == 0 is the host-only probe; the
+ * answers are emx_fused_ensemble_fn's.  emx_set_target_fused_data probes once and refuses another header version or ndim with
+ * emx_set_target_fused's wording, refuses a sharded context, frees blob storage and unbinds a blob and a one-workgroup launcher:
+ * such a target has no blobs and always runs one launch a half-step.  The rows a workgroup come from the split's length and the
+ * CU count (fused_ens_data_rows_rule of the header) unless the tuning key "fused_data_rows" names them (0: the rule; else 4 ... 256,
+ * clamped to the tile); results do not depend on them. */
+typedef struct emx_fused_ensemble_data_launch {
+    uint32_t abi;            /* EMX_FUSED_ENSEMBLE_DATA_ABI the library was built with */
+    uint32_t args_bytes;     /* sizeof(HalfStepArgs) of the library */
+    int32_t ndim, move, grid, threads;
+    uint64_t lds_bytes;
+    void* hip_stream;
+    const void* args;        /* HalfStepArgs */
+    const void* user;        /* user_dev */
+    int64_t ndata;
+    int32_t rows, reserved;
+} emx_fused_ensemble_data_launch;
+typedef int (*emx_fused_ensemble_data_fn)(const emx_fused_ensemble_data_launch*);
+int emx_set_target_fused_data(emx_ctx* ctx, emx_fused_ensemble_data_fn launcher, const void* user, int64_t ndata);
 /* Small ensembles of a fused user target: whole emx_run calls inside ONE workgroup (k_small_run around the caller's functor:
  * ensemble, plans, log-probs and blobs in LDS), one launch per chunk of up to 4 096 steps where the half-step launcher takes two
  * launches a step, in both rng modes, bit for bit the same chain.  Opt-in: the caller's translation unit also emits
