@@ -295,7 +295,7 @@ struct emx_ctx {
     emx_device_log_prob_fn cb_fn = nullptr;   // EMX_TARGET_DEVICE_CALLBACK: the caller's batched log-prob, run on device buffers
     emx_fused_ensemble_fn fused_fn = nullptr; // EMX_TARGET_FUSED_ENSEMBLE: the launcher of the caller's translation unit (k_halfstep_user) ...
     const void* fused_user = nullptr;         // ... and the device pointer its functor receives
-    // blobs of a fused user target (emx_set_target_fused_blobs; k_halfstep_user_blobs): nblobs doubles a sample
+    // blobs of a fused user target (emx_set_target_fused_blobs; k_halfstep_user with NB > 0): nblobs doubles a sample
     emx_fused_ensemble_blobs_fn fused_blobs_fn = nullptr;
     // the same target's one-workgroup launcher (emx_set_target_fused_small; k_small_run around the caller's functor), or null
     emx_fused_batch_fn fused_small_fn = nullptr;
@@ -1128,14 +1128,9 @@ int launch_split(emx_ctx* c, int move, int target, int S, int split, int pos0, i
     const bool slab = dense && c->tune_slab && c->Dp >= (c->tune_slab == 2 ? 80 : 112) && sh.G == 16 && sh.V == 2 && sh.CH == 4 &&
                       (move == MOVE_STRETCH || move == MOVE_DE) && lean_kind(a, 16, 2, 4, move, true) == 1;
     if (fused) {
-        int rcf;
-        if (c->fused_data_fn) {
-            // a wave a row in the data sum (emx_fused_ensemble_data.hpp): the rows a workgroup takes spread the split over the chip
-            const int tile = fused_ens_tile_rule(D);
-            const int rows = c->tune_fused_data_rows > 0 ? (int)std::min<int64_t>(c->tune_fused_data_rows, tile)
-                                                         : fused_ens_data_rows_rule(D, nown, c->num_cu);
-            emx_fused_ensemble_data_launch fl{};
-            fl.abi = EMX_FUSED_ENSEMBLE_DATA_ABI;
+        // what the three half-step descriptors of a fused user target share (include/emx.h); `rows`: the slots a workgroup takes
+        auto fill = [&](auto& fl, uint32_t abi, int rows) {
+            fl.abi = abi;
             fl.args_bytes = (uint32_t)sizeof(HalfStepArgs);
             fl.ndim = D;
             fl.move = move;
@@ -1145,24 +1140,22 @@ int launch_split(emx_ctx* c, int move, int target, int S, int split, int pos0, i
             fl.hip_stream = (void*)c->stream;
             fl.args = &a;
             fl.user = c->fused_user;
+        };
+        int rcf;
+        if (c->fused_data_fn) {
+            // a wave a row in the data sum (emx_fused_ensemble_data.hpp): the rows a workgroup takes spread the split over the chip
+            emx_fused_ensemble_data_launch fl{};
+            fl.rows = c->tune_fused_data_rows > 0 ? (int)std::min<int64_t>(c->tune_fused_data_rows, fused_ens_tile_rule(D))
+                                                  : fused_ens_data_rows_rule(D, nown, c->num_cu);
+            fill(fl, EMX_FUSED_ENSEMBLE_DATA_ABI, fl.rows);
             fl.ndata = c->fused_ndata;
-            fl.rows = rows;
             rcf = c->fused_data_fn(&fl);
         } else if (c->nblobs > 0) {
             // the blobs go where lp and chain_lp go: the walkers' array (an evaluation of other rows: the evaluation buffer), and the
             // plane's row of the stored step chain_lp points into
-            const int K = c->nblobs, tile = fused_ens_blobs_tile_rule(D, K);
+            const int K = c->nblobs;
             emx_fused_ensemble_blobs_launch fl{};
-            fl.abi = EMX_FUSED_ENSEMBLE_BLOBS_ABI;
-            fl.args_bytes = (uint32_t)sizeof(HalfStepArgs);
-            fl.ndim = D;
-            fl.move = move;
-            fl.grid = (int32_t)std::min<int64_t>((nown + tile - 1) / tile, (int64_t)c->num_cu * 64);
-            fl.threads = FUSED_ENS_THREADS;
-            fl.lds_bytes = fused_ens_blobs_lds_bytes(D, K);
-            fl.hip_stream = (void*)c->stream;
-            fl.args = &a;
-            fl.user = c->fused_user;
+            fill(fl, EMX_FUSED_ENSEMBLE_BLOBS_ABI, fused_ens_blobs_tile_rule(D, K));
             fl.nblobs = K;
             fl.blobs_cur = lp == c->lp ? c->blobs : c->evalblobs;
             fl.blobs_row = chain_lp ? c->blob_plane + (size_t)((chain_lp - c->chain_lp) / c->N) * c->N * K : nullptr;
@@ -1173,16 +1166,7 @@ int launch_split(emx_ctx* c, int move, int target, int S, int split, int pos0, i
             rcf = c->fused_blobs_fn(&fl);
         } else {
             emx_fused_ensemble_launch fl{};
-            fl.abi = EMX_FUSED_ENSEMBLE_ABI;
-            fl.args_bytes = (uint32_t)sizeof(HalfStepArgs);
-            fl.ndim = D;
-            fl.move = move;
-            fl.grid = (int32_t)std::min<int64_t>((nown + fused_ens_tile_rule(D) - 1) / fused_ens_tile_rule(D), (int64_t)c->num_cu * 64);
-            fl.threads = FUSED_ENS_THREADS;
-            fl.lds_bytes = fused_ens_lds_bytes(D);
-            fl.hip_stream = (void*)c->stream;
-            fl.args = &a;
-            fl.user = c->fused_user;
+            fill(fl, EMX_FUSED_ENSEMBLE_ABI, fused_ens_tile_rule(D));
             rcf = c->fused_fn(&fl);
         }
         if (rcf) {
@@ -1906,15 +1890,48 @@ static void blob_storage_free(emx_ctx* c) {
     c->nblobs = 0;
 }
 
+// What emx_set_target_fused, _blobs and _data (`who`) share.  They begin alike: the context settled and a launcher there (_data
+// checks its count of data here) ...
+static int fused_bind_settle(emx_ctx* c, const char* who, bool launcher) {
+    { const int rcs_ = persist_settle(c); if (rcs_) return rcs_; }
+    NEED(c, launcher, "%s: no launcher", who);
+    return 0;
+}
+// ... an ndim the kernels have, one replica (then each probes its launcher with its own descriptor) ...
+static int fused_bind_checks(emx_ctx* c, const char* who) {
+    NEED(c, c->D >= 1 && c->D <= FUSED_ENS_MAX_NDIM, "%s: a fused user target has 1 <= ndim <= %d; the ensemble has ndim %d", who, FUSED_ENS_MAX_NDIM, c->D);
+    NEED(c, c->world == 1 && !c->comm && !c->sendbuf && !c->peers_ready, "%s: a fused user target runs on one replica (no sharding, no exchange)", who);
+    return 0;
+}
+// ... the context idle (then each frees or allocates its blob storage) ...
+static int fused_bind_idle(emx_ctx* c) {
+    HIPOK(c, hipSetDevice(c->device));
+    PIPE_STOP(c);
+    drop_prepared(c);          // plans made ahead were shaped (lean or full) for the previous target
+    HIPOK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+// ... and exactly one of the three launchers bound, every other one unbound.
+static int fused_bind_set(emx_ctx* c, emx_fused_ensemble_fn fn, emx_fused_ensemble_blobs_fn blobs_fn, emx_fused_ensemble_data_fn data_fn,
+                          const void* user) {
+    c->fused_fn = fn;
+    c->fused_blobs_fn = blobs_fn;
+    c->fused_data_fn = data_fn;
+    c->fused_small_fn = nullptr;
+    c->fused_user = user;
+    c->Dp = 0;
+    graph_invalidate(c);
+    c->graph_warm = false;
+    c->target = EMX_TARGET_FUSED_ENSEMBLE;
+    c->tscale = 1.0;
+    return 0;
+}
+
 // The caller's per-row device function compiled into the half-step (include/emx.h; emx_fused_ensemble.hpp): launch_split hands the
 // element-wise half-step, and every evaluation of rows, to the caller's launcher.
 int emx_set_target_fused(emx_ctx* c, emx_fused_ensemble_fn launcher, const void* user) {
-    { const int rcs_ = persist_settle(c); if (rcs_) return rcs_; }
-    NEED(c, launcher != nullptr, "emx_set_target_fused: no launcher");
-    NEED(c, c->D >= 1 && c->D <= FUSED_ENS_MAX_NDIM, "emx_set_target_fused: a fused user target has 1 <= ndim <= %d; the ensemble has ndim %d",
-         FUSED_ENS_MAX_NDIM, c->D);
-    NEED(c, c->world == 1 && !c->comm && !c->sendbuf && !c->peers_ready,
-         "emx_set_target_fused: a fused user target runs on one replica (no sharding, no exchange)");
+    if (const int rc = fused_bind_settle(c, "emx_set_target_fused", launcher != nullptr)) return rc;
+    if (const int rc = fused_bind_checks(c, "emx_set_target_fused")) return rc;
     // the probe: abi, args_bytes and ndim against what the launcher was compiled with; nothing is launched.  (A launcher of the
     // batch targets reads the same two leading fields, finds another constant and answers 1.)
     emx_fused_ensemble_launch fl{};
@@ -1929,22 +1946,9 @@ int emx_set_target_fused(emx_ctx* c, emx_fused_ensemble_fn launcher, const void*
                     "EMX_FUSED_ENSEMBLE_TARGET launcher (it answered %d); rebuild it against this library's headers", rcp);
     NEED(c, c->nblobs == 0 || c->stored == 0, "emx_set_target_fused: the context holds %lld stored steps with %d blobs a sample; "
          "reset the chain before the blob count changes", (long long)c->stored, c->nblobs);
-    HIPOK(c, hipSetDevice(c->device));
-    PIPE_STOP(c);
-    drop_prepared(c);          // plans made ahead were shaped (lean or full) for the previous target
-    HIPOK(c, hipStreamSynchronize(c->stream));
+    if (const int rc = fused_bind_idle(c)) return rc;
     blob_storage_free(c);
-    c->fused_fn = launcher;
-    c->fused_blobs_fn = nullptr;
-    c->fused_small_fn = nullptr;
-    c->fused_data_fn = nullptr;
-    c->fused_user = user;
-    c->Dp = 0;
-    graph_invalidate(c);
-    c->graph_warm = false;
-    c->target = EMX_TARGET_FUSED_ENSEMBLE;
-    c->tscale = 1.0;
-    return 0;
+    return fused_bind_set(c, launcher, nullptr, nullptr, user);
 }
 
 // The same with nblobs derived quantities a sample (include/emx.h): the walkers' blobs, an evaluation buffer and -- sized like the
@@ -1952,12 +1956,8 @@ int emx_set_target_fused(emx_ctx* c, emx_fused_ensemble_fn launcher, const void*
 int emx_set_target_fused_blobs(emx_ctx* c, emx_fused_ensemble_blobs_fn launcher, const void* user, int32_t nblobs) {
     NEED(c, nblobs >= 0 && nblobs <= FUSED_ENS_MAX_BLOBS, "emx_set_target_fused_blobs: 0 <= nblobs <= %d; got %d", FUSED_ENS_MAX_BLOBS, nblobs);
     if (nblobs == 0) return emx_set_target_fused(c, reinterpret_cast<emx_fused_ensemble_fn>(launcher), user);
-    { const int rcs_ = persist_settle(c); if (rcs_) return rcs_; }
-    NEED(c, launcher != nullptr, "emx_set_target_fused_blobs: no launcher");
-    NEED(c, c->D >= 1 && c->D <= FUSED_ENS_MAX_NDIM, "emx_set_target_fused_blobs: a fused user target has 1 <= ndim <= %d; the ensemble has ndim %d",
-         FUSED_ENS_MAX_NDIM, c->D);
-    NEED(c, c->world == 1 && !c->comm && !c->sendbuf && !c->peers_ready,
-         "emx_set_target_fused_blobs: a fused user target runs on one replica (no sharding, no exchange)");
+    if (const int rc = fused_bind_settle(c, "emx_set_target_fused_blobs", launcher != nullptr)) return rc;
+    if (const int rc = fused_bind_checks(c, "emx_set_target_fused_blobs")) return rc;
     NEED(c, c->nblobs == nblobs || c->stored == 0, "emx_set_target_fused_blobs: the context holds %lld stored steps with %d blobs a "
          "sample; reset the chain before the blob count changes to %d", (long long)c->stored, c->nblobs, nblobs);
     for (const auto& mv : c->moves)
@@ -1974,10 +1974,7 @@ int emx_set_target_fused_blobs(emx_ctx* c, emx_fused_ensemble_blobs_fn launcher,
     if (rcp)
         FAIL(c, -8, "emx_set_target_fused_blobs: the launcher was built against another version of emx_fused_ensemble.hpp, or is not an "
                     "EMX_FUSED_ENSEMBLE_TARGET_BLOBS launcher (it answered %d); rebuild it against this library's headers", rcp);
-    HIPOK(c, hipSetDevice(c->device));
-    PIPE_STOP(c);
-    drop_prepared(c);
-    HIPOK(c, hipStreamSynchronize(c->stream));
+    if (const int rc = fused_bind_idle(c)) return rc;
     if (c->nblobs != nblobs) {
         blob_storage_free(c);
         const size_t nb = (size_t)c->N * nblobs * 8;
@@ -1996,29 +1993,15 @@ int emx_set_target_fused_blobs(emx_ctx* c, emx_fused_ensemble_blobs_fn launcher,
         c->blob_plane = plane;
         c->nblobs = nblobs;
     }
-    c->fused_blobs_fn = launcher;
-    c->fused_fn = nullptr;
-    c->fused_small_fn = nullptr;
-    c->fused_data_fn = nullptr;
-    c->fused_user = user;
-    c->Dp = 0;
-    graph_invalidate(c);
-    c->graph_warm = false;
-    c->target = EMX_TARGET_FUSED_ENSEMBLE;
-    c->tscale = 1.0;
-    return 0;
+    return fused_bind_set(c, nullptr, launcher, nullptr, user);
 }
 
 // A fused user target that sums over data (include/emx.h; emx_fused_ensemble_data.hpp): emx_set_target_fused with the data
 // launcher's descriptor and the number of data; no blobs, no one-workgroup launcher.
 int emx_set_target_fused_data(emx_ctx* c, emx_fused_ensemble_data_fn launcher, const void* user, int64_t ndata) {
-    { const int rcs_ = persist_settle(c); if (rcs_) return rcs_; }
-    NEED(c, launcher != nullptr, "emx_set_target_fused_data: no launcher");
+    if (const int rc = fused_bind_settle(c, "emx_set_target_fused_data", launcher != nullptr)) return rc;
     NEED(c, ndata >= 0 && ndata < (1ll << 31), "emx_set_target_fused_data: 0 <= ndata < 2^31; got %lld", (long long)ndata);
-    NEED(c, c->D >= 1 && c->D <= FUSED_ENS_MAX_NDIM, "emx_set_target_fused_data: a fused user target has 1 <= ndim <= %d; the ensemble has ndim %d",
-         FUSED_ENS_MAX_NDIM, c->D);
-    NEED(c, c->world == 1 && !c->comm && !c->sendbuf && !c->peers_ready,
-         "emx_set_target_fused_data: a fused user target runs on one replica (no sharding, no exchange)");
+    if (const int rc = fused_bind_checks(c, "emx_set_target_fused_data")) return rc;
     emx_fused_ensemble_data_launch fl{};           // the probe: nothing is launched
     fl.abi = EMX_FUSED_ENSEMBLE_DATA_ABI;
     fl.args_bytes = (uint32_t)sizeof(HalfStepArgs);
@@ -2031,23 +2014,10 @@ int emx_set_target_fused_data(emx_ctx* c, emx_fused_ensemble_data_fn launcher, c
                     "EMX_FUSED_ENSEMBLE_DATA_TARGET launcher (it answered %d); rebuild it against this library's headers", rcp);
     NEED(c, c->nblobs == 0 || c->stored == 0, "emx_set_target_fused_data: the context holds %lld stored steps with %d blobs a sample; "
          "reset the chain before the blob count changes", (long long)c->stored, c->nblobs);
-    HIPOK(c, hipSetDevice(c->device));
-    PIPE_STOP(c);
-    drop_prepared(c);
-    HIPOK(c, hipStreamSynchronize(c->stream));
+    if (const int rc = fused_bind_idle(c)) return rc;
     blob_storage_free(c);
-    c->fused_data_fn = launcher;
     c->fused_ndata = ndata;
-    c->fused_fn = nullptr;
-    c->fused_blobs_fn = nullptr;
-    c->fused_small_fn = nullptr;
-    c->fused_user = user;
-    c->Dp = 0;
-    graph_invalidate(c);
-    c->graph_warm = false;
-    c->target = EMX_TARGET_FUSED_ENSEMBLE;
-    c->tscale = 1.0;
-    return 0;
+    return fused_bind_set(c, nullptr, nullptr, launcher, user);
 }
 
 // The one-workgroup launcher of the bound fused user target (include/emx.h; emx_fused_ensemble.hpp: EMX_FUSED_ENSEMBLE_SMALL_TARGET):

@@ -31,6 +31,9 @@
 // staged in LDS) and 3 (commit, chain append) are that kernel's text.  In phase 2 each wave takes rows of the tile in turn: lane 0
 // calls base, all 64 lanes stride over the data, the reduction runs with the whole wave active outside any lane-divergent region
 // (DPP and permlane reads of inactive lanes are undefined), and lane 0 takes the decision by k_halfstep_user's rule.
+// (The two phases and the rule stay this kernel's own text: made of functions shared with k_halfstep_user the kernel computed the
+// same bits and was 1.1 to 1.4 % slower at 4 096 walkers x 16, twice -- profiles/ensemble_fused_shared_text.md.  A change of the
+// rule there is a change here; tests/test_gpu_ensemble_fused_data.py compares the chains bit for bit.)
 // TILE stays the compile-time upper bound of the rows a workgroup takes (the register arrays of phase 1); the rows it actually
 // takes are a run-time argument, 4 ... TILE, so that a mid-size ensemble spreads over the chip (fused_ens_data_rows_rule;
 // profiles/ensemble_fused_data.md); passes of phase 1 / 3 without a live row are skipped by a workgroup-uniform branch.
@@ -46,7 +49,6 @@
 
 namespace emx {
 
-constexpr int FUSED_ENS_DATA_MIN_ROWS = 4;       // a row a wave
 // workgroups a CU the default rows-a-workgroup rule asks for before it stops halving the tile.  Measured (profiles/ensemble_fused_data.md,
 // the sweep): up to 4 096 walkers 4 rows are the fastest at every count of data, by up to 12x over the whole tile at 16 384 data; at
 // 65 536 walkers (128 slots a CU) 4 rows are the fastest at 16 384 data, by 7 %, and behind the fastest (8 rows) by 11 % at 64 data
@@ -222,45 +224,21 @@ static __global__ __launch_bounds__(FUSED_ENS_THREADS) void k_halfstep_user_data
     }
 }
 
-template <typename USER, int NDIM, int MOVE>
-hipError_t launch_fused_ens_data_move(int grid, size_t lds, hipStream_t st, const HalfStepArgs& a, const void* user, long long ndata, int rows) {
+// the launcher behind EMX_FUSED_ENSEMBLE_DATA_TARGET (include/emx.h: emx_fused_ensemble_data_launch): fused_ens_launch_checks'
+// answers (emx_fused_ensemble.hpp), then one launch with the descriptor's rows a workgroup: 0, or 100 + a hipError_t.
+template <typename USER, int NDIM>
+int fused_ensemble_data_launch(const emx_fused_ensemble_data_launch* L) {
     constexpr int G = fused_ens_g(NDIM), V = fused_ens_v(NDIM), CH = fused_ens_ch(NDIM), TILE = fused_ens_tile_rule(NDIM);
     static_assert(G * V * CH >= NDIM, "the row layout covers the row");
     static_assert(fused_ens_lds_of(NDIM, TILE) <= 48 * 1024, "the staging area stays below the LDS a kernel gets without asking");
-    hipLaunchKernelGGL((k_halfstep_user_data<G, V, CH, MOVE, USER, TILE>), dim3(grid), dim3(FUSED_ENS_THREADS), lds, st, a, user, ndata, rows);
-    return hipGetLastError();
-}
-
-// the launcher behind EMX_FUSED_ENSEMBLE_DATA_TARGET (include/emx.h: emx_fused_ensemble_data_launch): fused_ensemble_launch's checks
-// and answers; a count of data outside [0, 2^31) or rows a workgroup outside 4 ... the tile answer 3.
-template <typename USER, int NDIM>
-int fused_ensemble_data_launch(const emx_fused_ensemble_data_launch* L) {
-    static_assert(NDIM >= 1 && NDIM <= FUSED_ENS_MAX_NDIM, "a fused user target has 1 <= ndim <= 256");
-    if (!L || L->abi != EMX_FUSED_ENSEMBLE_DATA_ABI || L->args_bytes != (uint32_t)sizeof(HalfStepArgs)) return 1;
-    if (L->ndim != NDIM) return 2;
-    if (L->move != MOVE_STRETCH && L->move != MOVE_DE && L->move != MOVE_SNOOKER && L->move != MOVE_GAUSS && L->move != MOVE_EVAL) return 3;
-    if (L->grid == 0) return 0;                       // the probe of emx_set_target_fused_data
-    constexpr int TILE = fused_ens_tile_rule(NDIM);
-    if (L->rows < FUSED_ENS_DATA_MIN_ROWS || L->rows > TILE || L->ndata < 0 || L->ndata >= (1ll << 31)) return 3;
-    const size_t lds = fused_ens_lds_of(NDIM, L->rows);
-    if (!L->args || L->grid < 0 || L->threads != FUSED_ENS_THREADS || L->lds_bytes < lds) return 3;
+    int grid;
+    if (const int rc = fused_ens_launch_checks<NDIM, 0>(L, EMX_FUSED_ENSEMBLE_DATA_ABI, &grid); rc || !grid) return rc;
     const HalfStepArgs& a = *static_cast<const HalfStepArgs*>(L->args);
-    if (a.D != NDIM) return 2;
-    if (a.sendbuf || a.desc || a.t_hi_dev || a.peers || a.npeer || a.declp || a.push_peers || a.npush) return 5;
-    if (a.t_hi <= a.t_lo) return 0;
-    // `grid` is the most workgroups the library allows; `rows` slots a workgroup until then
-    const long long tiles = ((long long)a.t_hi - a.t_lo + L->rows - 1) / L->rows;
-    const int grid = (int)(tiles < L->grid ? tiles : L->grid);
-    const hipStream_t st = (hipStream_t)L->hip_stream;
-    const long long nd = (long long)L->ndata;
-    hipError_t e = hipErrorInvalidValue;
-    switch (L->move) {
-        case MOVE_STRETCH: e = launch_fused_ens_data_move<USER, NDIM, MOVE_STRETCH>(grid, lds, st, a, L->user, nd, L->rows); break;
-        case MOVE_DE: e = launch_fused_ens_data_move<USER, NDIM, MOVE_DE>(grid, lds, st, a, L->user, nd, L->rows); break;
-        case MOVE_SNOOKER: e = launch_fused_ens_data_move<USER, NDIM, MOVE_SNOOKER>(grid, lds, st, a, L->user, nd, L->rows); break;
-        case MOVE_GAUSS: e = launch_fused_ens_data_move<USER, NDIM, MOVE_GAUSS>(grid, lds, st, a, L->user, nd, L->rows); break;
-        case MOVE_EVAL: e = launch_fused_ens_data_move<USER, NDIM, MOVE_EVAL>(grid, lds, st, a, L->user, nd, L->rows); break;
-    }
+    const hipError_t e = fused_ens_with_move(L->move, [&](auto move) {
+        hipLaunchKernelGGL((k_halfstep_user_data<G, V, CH, decltype(move)::value, USER, TILE>), dim3(grid), dim3(FUSED_ENS_THREADS),
+                           fused_ens_lds_of(NDIM, L->rows), (hipStream_t)L->hip_stream, a, L->user, (long long)L->ndata, L->rows);
+        return hipGetLastError();
+    });
     return e == hipSuccess ? 0 : 100 + (int)e;
 }
 

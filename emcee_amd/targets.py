@@ -436,7 +436,7 @@ FUSED_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 
 
 def _compile_cached(what, header, source, tail, key_parts, name, flags, cache_dir):
-    """the shared build of compile_fused / compile_fused_pt: cache key, translation unit, hipcc, diagnostics -> path of the library"""
+    """the shared build of compile_fused, compile_fused_ensemble and compile_fused_pt: cache key, translation unit, hipcc, diagnostics -> path of the library"""
     from . import _build
     h = hashlib.sha256(repr(key_parts + (FUSED_FLAGS + flags,)).encode())
     for d in _build.DEPS:
@@ -598,7 +598,6 @@ def compile_fused(source, functor, ndim, nblobs=0, name=None, flags=(), cache_di
     ``nblobs = K > 0``: the functor has the five-argument form ``(const double* x, int ndim, int member, const void* user, double*
     blobs)`` and writes ``blobs[0 ... K)``; the translation unit ends with ``EMX_FUSED_BATCH_TARGET_BLOBS(name, functor, ndim, K)``
     and K is part of the cache key."""
-    from . import _build
     ndim = int(ndim)
     if ndim < 1 or ndim > 256:
         raise ValueError("compile_fused: 1 <= ndim <= 256; got %d" % ndim)
@@ -608,30 +607,9 @@ def compile_fused(source, functor, ndim, nblobs=0, name=None, flags=(), cache_di
             raise ValueError("compile_fused: %s must be a C++ identifier; got %r" % (what, ident))
     name = name or "emx_fused_%s_%d" % (functor.replace(":", "_"), ndim)
     flags = [str(f) for f in flags]
-    # (nblobs joins the key only when there are blobs: the keys of blob-free builds stay what they were)
-    h = hashlib.sha256(repr((source, functor, ndim, name, FUSED_FLAGS + flags) + ((nblobs,) if nblobs else ())).encode())
-    for d in _build.DEPS:
-        if d.endswith((".hpp", ".h")):
-            with open(d, "rb") as f:
-                h.update(f.read())
-    key = h.hexdigest()[:24]
-    cache_dir = cache_dir or os.environ.get("EMCEE_AMD_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "emcee_amd")
-    work = os.path.join(str(cache_dir), key)
-    so = os.path.join(work, "lib%s.so" % name)
-    if not os.path.exists(so):
-        os.makedirs(work, exist_ok=True)
-        src = os.path.join(work, "%s.hip" % name)
-        with open(src, "w") as f:
-            tail = ("EMX_FUSED_BATCH_TARGET_BLOBS(%s, %s, %d, %d)" % (name, functor, ndim, nblobs) if nblobs else
-                    "EMX_FUSED_BATCH_TARGET(%s, %s, %d)" % (name, functor, ndim))
-            f.write("#include <emx_fused_target.hpp>\n\n%s\n\n%s\n" % (source, tail))
-        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-        tmp = "%s.%d.tmp" % (so, os.getpid())
-        cmd = [hipcc] + FUSED_FLAGS + flags + ["-I" + d for d in get_include()] + [src, "-o", tmp]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-            raise RuntimeError("compile_fused: hipcc failed (%s):\n%s" % (src, (r.stderr or r.stdout)[-4000:]))
-        os.replace(tmp, so)
+    tail = ("EMX_FUSED_BATCH_TARGET_BLOBS(%s, %s, %d, %d)" % (name, functor, ndim, nblobs) if nblobs else
+            "EMX_FUSED_BATCH_TARGET(%s, %s, %d)" % (name, functor, ndim))
+    # (nblobs joins the key only when there are blobs: a blob-free build does not depend on how the count is spelt)
+    key = ("batch", source, functor, ndim, name) + (("nblobs", nblobs) if nblobs else ())
+    so = _compile_cached("compile_fused", "emx_fused_target.hpp", source, tail, key, name, flags, cache_dir)
     return BatchFusedLibrary(so, name, ndim, nblobs)

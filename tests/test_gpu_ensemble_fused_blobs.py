@@ -1,4 +1,4 @@
-"""Blobs of a DeviceFused target on the GPU (EMX_FUSED_ENSEMBLE_TARGET_BLOBS, k_halfstep_user_blobs).
+"""Blobs of a DeviceFused target on the GPU (EMX_FUSED_ENSEMBLE_TARGET_BLOBS, k_halfstep_user with NB > 0).
 
 The oracle is the blob-free functor through the blob-free DeviceFused (tests/test_gpu_ensemble_fused.py pins that one to
 DeviceKernel): the blob run samples the same chain BIT FOR BIT, and every blob is reproducible in NumPy from the stored row with one

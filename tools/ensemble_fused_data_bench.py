@@ -10,12 +10,14 @@ a flat box prior and  -0.5 ((y_k - m t_k - b) / sigma_k)^2  over ndata points be
 
     python tools/ensemble_fused_data_bench.py [--modes data,serial] [--shapes 1024x5,4096x16,65536x8] [--ndata 64,1024,16384]
                                               [--rows 4,8,16,32,64] [--seconds 1.0] [--block STEPS] [--cache DIR] [--out FILE]
+                                              [--flags="-IDIR ..."]
 
 `--modes serial,loop` needs nothing of the data target, so the same file measures a checkout that predates it.  Blocks of steps timed by
 a host clock around a device synchronise; the median and the p10 ... p90 spread of at least `--seconds` of blocks per mode (at least
 20 blocks where another mode is so slow that it has taken ten times `--seconds` by then), the modes of a shape taken in alternation
 so that drift of the machine hits them alike.  store=False.  Prints one JSON line per shape, ndata and
-mode; with both `data` and `serial` among the modes the two final states are compared (they must be equal bit for bit)."""
+mode; `--flags` are further compiler flags of the launchers (--flags=-IDIR puts another copy of the headers ahead of the library's);
+with both `data` and `serial` among the modes the two final states are compared (they must be equal bit for bit)."""
 import argparse
 import json
 import os
@@ -98,6 +100,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--block", type=int, default=0, help="steps a timed block (default: about 20 ms of the slowest mode, 8 ... 2 000)")
     ap.add_argument("--cache", default=None, help="directory of compiled user libraries (default: a temporary one)")
+    ap.add_argument("--flags", default="", help="further hipcc flags of the launchers, separated by blanks")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -111,9 +114,9 @@ def main():
         for mode in modes:
             kind = mode if mode in ("serial", "loop") else "data"
             if kind not in libs:
-                libs[kind] = (targets.compile_fused_ensemble(SERIAL, "LineSerial", D, cache_dir=work, small=False) if kind == "serial" else
-                              targets.compile_fused_ensemble(LOOP, "LineLoop", D, cache_dir=work, small=False) if kind == "loop" else
-                              targets.compile_fused_ensemble(MODEL, "LineModel", D, cache_dir=work, data=True))
+                libs[kind] = (targets.compile_fused_ensemble(SERIAL, "LineSerial", D, cache_dir=work, small=False, flags=a.flags.split()) if kind == "serial" else
+                              targets.compile_fused_ensemble(LOOP, "LineLoop", D, cache_dir=work, small=False, flags=a.flags.split()) if kind == "loop" else
+                              targets.compile_fused_ensemble(MODEL, "LineModel", D, cache_dir=work, data=True, flags=a.flags.split()))
         for ndata in (int(v) for v in a.ndata.split(",")):
             rs = np.random.RandomState(7)
             t = np.linspace(-1.0, 1.0, max(ndata, 2))[:ndata]

@@ -42,8 +42,9 @@ def main():
         body = m.group(1) if m else ""
         cnt = lambda pat: len(re.findall(pat, body))
         s = meta[name]
-        print("%-48s vgpr %3d agpr %3d sgpr %3d scratch %4d B  spilled v/s %d/%d | mfma %d, scratch ld/st %d/%d, global ld/st %d/%d, buffer ld/st %d/%d, ds rd/wr %d/%d, s_waitcnt %d"
-              % (d, s["vgpr_count"], s["agpr_count"], s["sgpr_count"], s["private_segment_fixed_size"], s["vgpr_spill_count"], s["sgpr_spill_count"],
+        insts = len(re.findall(r"^\s+[a-z]\w+", re.sub(r"^\s*;.*$", "", body, flags=re.M), re.M))      # (labels, directives and comments are none)
+        print("%-48s vgpr %3d agpr %3d sgpr %3d scratch %4d B  spilled v/s %d/%d  lds %d B  insts %d | mfma %d, scratch ld/st %d/%d, global ld/st %d/%d, buffer ld/st %d/%d, ds rd/wr %d/%d, s_waitcnt %d"
+              % (d, s["vgpr_count"], s["agpr_count"], s["sgpr_count"], s["private_segment_fixed_size"], s["vgpr_spill_count"], s["sgpr_spill_count"], s["group_segment_fixed_size"], insts,
                  cnt(r"v_mfma"), cnt(r"scratch_load"), cnt(r"scratch_store"), cnt(r"global_load"), cnt(r"global_store"), cnt(r"buffer_load"),
                  cnt(r"buffer_store"), cnt(r"ds_read|ds_load"), cnt(r"ds_write|ds_store"), cnt(r"s_waitcnt")))
 
