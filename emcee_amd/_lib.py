@@ -47,6 +47,11 @@ class FusedLaunch(C.Structure):
                 ("user", C.c_void_p), ("nblobs", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FusedBatchDataLaunch(C.Structure):
+    """emx_fused_batch_data_launch of include/emx.h: FusedLaunch's fields, then the device array of the members' data counts"""
+    _fields_ = FusedLaunch._fields_ + [("ndata", C.c_void_p)]
+
+
 class FusedEnsembleLaunch(C.Structure):
     """emx_fused_ensemble_launch of include/emx.h: the descriptor the launcher of a single sampler's fused user target is handed"""
     _fields_ = [("abi", C.c_uint32), ("args_bytes", C.c_uint32), ("ndim", C.c_int32), ("move", C.c_int32), ("grid", C.c_int32),
@@ -73,6 +78,8 @@ FUSED_ENSEMBLE_BLOBS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 FUSED_ENSEMBLE_DATA_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 # emx_fused_batch_fn: (const emx_fused_launch*) -> int
 FUSED_BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
+# emx_fused_batch_data_fn: (const emx_fused_batch_data_launch*) -> int
+FUSED_BATCH_DATA_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 # emx_pt_fused_fn: (emx_pt_fused_launch*) -> int
 PT_FUSED_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 
@@ -251,6 +258,7 @@ SIGNATURES = {
     "emx_histograms": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P,
                                  C.POINTER(C.c_int64)]),
     "emx_set_batch_target_fused_blobs": (C.c_int, [_P, FUSED_BATCH_FN, C.c_int32, _P, C.c_int32]),
+    "emx_set_batch_target_fused_data": (C.c_int, [_P, FUSED_BATCH_DATA_FN, C.c_int32, _P, _i64p]),
     "emx_set_batch_target_callback_blobs": (C.c_int, [_P, BATCH_LOG_PROB_BLOBS_FN, _P, C.c_int32]),
     "emx_check_batch_blobs": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MoveDesc), C.c_int32, C.c_char_p, C.c_int32]),
     "emx_get_blobs_batch": (C.c_int, [_P, _P, C.POINTER(C.c_int32)]),

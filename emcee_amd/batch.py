@@ -13,6 +13,8 @@ Philox mode only; fused device targets (``IsoGaussian``, ``DiagGaussian``, ``Den
 ``UniformBox``); stretch, DE, snooker and Gaussian moves; every member must fit one workgroup (``nwalkers <= 4096``,
 ``ndim <= 256`` and the LDS bound).  A :class:`~emcee_amd.targets.BatchFused` -- the user's per-row ``__device__`` function
 compiled into that kernel (:func:`~emcee_amd.targets.compile_fused`) -- runs the same way, at the same one launch per chunk.
+With ``ndata`` (``compile_fused(..., data=True)``: a model with ``base`` and ``term`` whose log-probability sums over per-member
+data, ragged counts included) every proposal gets a wave for the data sum instead of one lane.
 
 The user's own model -- one fit per catalogue object, with per-object data -- is a
 :class:`~emcee_amd.targets.BatchCallable` (or its native form, :class:`~emcee_amd.targets.BatchKernel`): one function called
@@ -111,6 +113,9 @@ class EnsembleBatch(object):
     def _parse_targets(self, target):
         if isinstance(target, BatchFused) and target.ndim != self.ndim:
             raise ValueError("the BatchFused target was compiled for ndim %d; the batch has ndim %d" % (target.ndim, self.ndim))
+        if isinstance(target, BatchFused) and target.ndata is not None and not np.isscalar(target.ndata) and len(target.ndata) != self.nbatch:
+            raise ValueError("the BatchFused target's ndata holds one count a member: nbatch = %d integers (or one for all); got %d"
+                             % (self.nbatch, len(target.ndata)))
         if isinstance(target, PTFused):
             if not self._tempered:
                 raise TypeError("a PTFused is a likelihood of PTSampler: its launcher carries the tempered kernel (for an EnsembleBatch "
@@ -229,7 +234,12 @@ class EnsembleBatch(object):
         t = self._targets[0]
         fn = t.fn_ptr if isinstance(t.fn_ptr, _lib.FUSED_BATCH_FN) else C.cast(t.fn_ptr, _lib.FUSED_BATCH_FN)
         self._cb_keep = (fn, t)           # the library holds the launcher and the user's device pointer: keep both alive
-        if self.nblobs:
+        if t.ndata is not None:           # a data target: its own launcher type, and the members' counts
+            fn = t.fn_ptr if isinstance(t.fn_ptr, _lib.FUSED_BATCH_DATA_FN) else C.cast(t.fn_ptr, _lib.FUSED_BATCH_DATA_FN)
+            self._cb_keep = (fn, t)
+            counts = np.ascontiguousarray(np.broadcast_to(np.asarray(t.ndata, dtype=np.int64), (self.nbatch,)))
+            self._ck(self._lib().emx_set_batch_target_fused_data(h, fn, t.ndim, C.c_void_p(t.user_address()), counts))
+        elif self.nblobs:
             self._ck(self._lib().emx_set_batch_target_fused_blobs(h, fn, t.ndim, C.c_void_p(t.user_address()), self.nblobs))
         else:
             self._ck(self._lib().emx_set_batch_target_fused(h, fn, t.ndim, C.c_void_p(t.user_address())))

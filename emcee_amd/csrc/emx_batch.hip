@@ -21,6 +21,7 @@
 #include "../../include/emx.h"
 #include "emx_batch_cb.hpp"
 #include "emx_fused_target.hpp"
+#include "emx_fused_target_data.hpp"
 #include "emx_internal.hpp"
 #include "emx_pt.hpp"
 #include "emx_pt_fused.hpp"
@@ -75,6 +76,10 @@ struct emx_batch {
     // EMX_TARGET_FUSED_USER: the caller's launcher of k_small_run around their device function, and their device pointer
     emx_fused_batch_fn fused_fn = nullptr;
     const void* fused_user = nullptr;
+    // ... whose log-probability sums over per-member data (emx_set_batch_target_fused_data): the data launcher instead of
+    // fused_fn, and the library's device copy of the members' counts (B values)
+    emx_fused_batch_data_fn fused_data_fn = nullptr;
+    int64_t* fused_ndata = nullptr;
     // blobs (emx_set_batch_target_fused_blobs / emx_set_batch_target_callback_blobs; 0: none): the walkers' current ones (B, N,
     // nblobs), the blob plane (B, cap, N, nblobs) next to the chain, the callback's function and its (B, R, nblobs) block
     int32_t nblobs = 0;
@@ -227,12 +232,14 @@ int grow(emx_batch* b, T*& p, size_t& cap, size_t n) {
 // has no more members than the device has CUs, each member has a CU of its own and the single-ensemble (latency) shape
 // is kept; beyond, the workgroup is cut to one half-step's lanes (>= one wave) with plan steps for one entry a thread, so
 // that several members share a CU (32 waves, 160 KB of LDS).  Neither changes a bit: plans do not depend on the state.
-// extra_lds: a fused user target's staging area, on top of small_lds_bytes.
-void launch_shape(const emx_batch* b, int num_cu, const Shape& sh, int minsplits, bool dense, size_t extra_lds, int* threads, int* plan_steps) {
+// extra_lds: a fused user target's staging area, on top of small_lds_bytes.  data: a data target, whose second pass takes a
+// WAVE a staged row: the cut is to a wave a row of the largest split, where G lanes a row would leave one wave for 64 / G rows.
+void launch_shape(const emx_batch* b, int num_cu, const Shape& sh, int minsplits, bool dense, size_t extra_lds, int* threads, int* plan_steps,
+                  bool data = false) {
     int t = small_threads(b->N, b->D, b->Dp, sh.G, minsplits, dense), ps = small_batch(b->N);
     if (b->B > num_cu) {
         const int64_t nsmax = (b->N + minsplits - 1) / minsplits;
-        const int64_t want = dense ? ((nsmax + 15) / 16) * 64 : nsmax * sh.G;
+        const int64_t want = dense ? ((nsmax + 15) / 16) * 64 : data ? nsmax * 64 : nsmax * sh.G;
         t = std::min(t, (int)std::min<int64_t>(1024, std::max<int64_t>(64, (want + 63) / 64 * 64)));
         ps = (int)std::max<int64_t>(1, std::min<int64_t>(64, t / b->N));
     }
@@ -246,8 +253,12 @@ void launch_shape(const emx_batch* b, int num_cu, const Shape& sh, int minsplits
 }
 
 // what a fused user target's launcher answered (include/emx.h: emx_fused_batch_fn), as the handle's error; 0: it launched (or probed)
-int fused_refusal(emx_batch* b, int rc, int movesel) {
+int fused_refusal(emx_batch* b, int rc, int movesel, bool data = false) {
     if (rc == 0) return 0;
+    if (rc == 1 && data)
+        return fail(b, -8, "the fused user target's launcher was built against another version of emx_fused_target_data.hpp (the library "
+                           "has EMX_FUSED_BATCH_DATA_ABI 0x%x and %zu bytes of kernel arguments): rebuild it with this library's headers",
+                    (unsigned)EMX_FUSED_BATCH_DATA_ABI, sizeof(SmallRunArgs));
     if (rc == 1)
         return fail(b, -8, "the fused user target's launcher was built against another version of emx_fused_target.hpp (the library has "
                            "EMX_FUSED_ABI %u and %zu bytes of kernel arguments): rebuild it with this library's headers",
@@ -351,8 +362,10 @@ int launch(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t st
     int num_cu = 256;
     if (hipGetDeviceProperties(&prop, b->device) == hipSuccess) num_cu = prop.multiProcessorCount;
     const bool fused_user = b->target == EMX_TARGET_FUSED_USER;
+    const bool fused_data = fused_user && b->fused_data_fn != nullptr;
     if (fused_user) {
-        BNEED(b, b->fused_fn != nullptr, "fused user target without a launcher (emx_set_batch_target_fused)");
+        BNEED(b, fused_data || b->fused_fn != nullptr, "fused user target without a launcher (emx_set_batch_target_fused)");
+        BNEED(b, !fused_data || (b->fused_ndata != nullptr && b->nblobs == 0), "data target without its counts (emx_set_batch_target_fused_data)");
         a.target = TGT_USER;
         a.user = b->fused_user;
         a.stage_rows = (int32_t)fused_stage_rows(b->N, nm, b->moves.data());
@@ -367,14 +380,28 @@ int launch(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t st
     }
     const size_t extra_lds = fused_user ? small_fused_stage_bytes(a.stage_rows, b->D) + small_blob_bytes(b->N, b->nblobs) : 0;
     int threads = 0, plan_steps = 0;
-    launch_shape(b, num_cu, sh, minsplits, dense, extra_lds, &threads, &plan_steps);
+    launch_shape(b, num_cu, sh, minsplits, dense, extra_lds, &threads, &plan_steps, fused_data);
     a.batch = plan_steps;
     const size_t lds = small_lds_bytes(b->N, b->D, dense ? b->Dp : 0, threads / 64, plan_steps) + extra_lds;
     BNEED(b, lds <= SMALL_LDS_MAX && threads >= 64 && threads <= 1024 && threads % 64 == 0,
           "batch launch shape: %d threads and %d plan steps need %zu bytes of LDS", threads, plan_steps, lds);
     // (a fused user target's translation unit carries the single-StretchMove selector and the any-schedule one)
     const int movesel = (nm == 1 && ((!dense && !fused_user) || b->moves[0].kind == EMX_MOVE_STRETCH)) ? (int)b->moves[0].kind : SMALL_ANY_MOVE;
-    if (fused_user) {
+    if (fused_data) {
+        emx_fused_batch_data_launch fl{};
+        fl.abi = EMX_FUSED_BATCH_DATA_ABI;
+        fl.args_bytes = (uint32_t)sizeof(SmallRunArgs);
+        fl.ndim = b->D;
+        fl.movesel = movesel;
+        fl.grid = b->B;
+        fl.threads = threads;
+        fl.lds_bytes = lds;
+        fl.hip_stream = (void*)b->stream;
+        fl.args = &a;
+        fl.user = b->fused_user;
+        fl.ndata = b->fused_ndata;
+        if (int rc = fused_refusal(b, b->fused_data_fn(&fl), movesel, true)) return rc;
+    } else if (fused_user) {
         emx_fused_launch fl{};
         fl.abi = EMX_FUSED_ABI;
         fl.args_bytes = (uint32_t)sizeof(SmallRunArgs);
@@ -950,7 +977,8 @@ int emx_batch_destroy(emx_batch* b) {
                     (void*)b->tscales, (void*)b->chain, (void*)b->chain_lp, (void*)b->fac_dev, (void*)b->col_dev, (void*)b->cb_q,
                     (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi, (void*)b->cb_nrows, (void*)b->pt_beta,
                     (void*)b->pt_lo, (void*)b->pt_hi, (void*)b->pt_L, (void*)b->pt_P, (void*)b->chain_L, (void*)b->cb_pr, (void*)b->sw_att,
-                    (void*)b->sw_acc, (void*)b->chain_beta, (void*)b->blobs, (void*)b->chain_blobs, (void*)b->cb_bq})
+                    (void*)b->sw_acc, (void*)b->chain_beta, (void*)b->blobs, (void*)b->chain_blobs, (void*)b->cb_bq,
+                    (void*)b->fused_ndata})
         if (p) hipFree(p);
     for (double* p : b->mscale)
         if (p) hipFree(p);
@@ -1126,6 +1154,51 @@ int emx_set_batch_target_fused_blobs(emx_batch* b, emx_fused_batch_fn fn, int32_
         }
     b->tp0_stride = b->tp1_stride = 0;
     b->fused_fn = fn;
+    b->fused_data_fn = nullptr;
+    b->fused_user = user_dev;
+    b->target = EMX_TARGET_FUSED_USER;
+    b->Dp = b->D;
+    return 0;
+}
+
+int emx_set_batch_target_fused_data(emx_batch* b, emx_fused_batch_data_fn fn, int32_t ndim_compiled, const void* user_dev,
+                                    const int64_t* ndata_host) {
+    BNEED(b, fn != nullptr, "emx_set_batch_target_fused_data: no launcher");
+    BNEED(b, ndata_host != nullptr, "emx_set_batch_target_fused_data: no data counts (nbatch values)");
+    BNEED(b, ndim_compiled == b->D, "the fused user target was compiled for ndim %d; the batch has ndim %d", ndim_compiled, b->D);
+    BNEED(b, b->pt_T == 0, "a tempered batch does not take a fused user target: the tempered commit and the swap pass belong to the "
+                           "batched callback path (emx_set_batch_target_callback)");
+    for (int32_t m = 0; m < b->B; ++m)
+        BNEED(b, ndata_host[m] >= 0 && ndata_host[m] < ((int64_t)1 << 31),
+              "emx_set_batch_target_fused_data: 0 <= ndata < 2^31 for every member; member %d has %lld", m, (long long)ndata_host[m]);
+    if (!b->moves.empty()) {
+        char buf[256];
+        const char* why = shape_refusal(b->N, b->D, EMX_TARGET_FUSED_USER, (int32_t)b->moves.size(), b->moves.data(), buf, sizeof buf, 0);
+        BNEED(b, !why, "%s", why);
+    }
+    // the probe: abi, args_bytes and ndim against what the launcher was compiled with; nothing is launched
+    emx_fused_batch_data_launch fl{};
+    SmallRunArgs probe_args{};
+    probe_args.D = b->D;
+    fl.abi = EMX_FUSED_BATCH_DATA_ABI;
+    fl.args_bytes = (uint32_t)sizeof(SmallRunArgs);
+    fl.ndim = b->D;
+    fl.movesel = MOVE_STRETCH;
+    fl.args = &probe_args;
+    if (int rc = fused_refusal(b, fn(&fl), fl.movesel, true)) return rc;
+    BHIP(b, hipSetDevice(b->device));
+    if (int rc = set_blobs(b, 0)) return rc;
+    BHIP(b, hipStreamSynchronize(b->stream));
+    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
+        if (*p) {
+            hipFree(*p);
+            *p = nullptr;
+        }
+    b->tp0_stride = b->tp1_stride = 0;
+    if (!b->fused_ndata) BHIP(b, hipMalloc((void**)&b->fused_ndata, (size_t)b->B * sizeof(int64_t)));
+    BHIP(b, hipMemcpy(b->fused_ndata, ndata_host, (size_t)b->B * sizeof(int64_t), hipMemcpyHostToDevice));
+    b->fused_data_fn = fn;
+    b->fused_fn = nullptr;
     b->fused_user = user_dev;
     b->target = EMX_TARGET_FUSED_USER;
     b->Dp = b->D;

@@ -66,7 +66,7 @@
 // ANY change of SmallRunArgs or of k_small_run's LDS layout.  A value of its own, so that a batch launcher (EMX_FUSED_BATCH_TARGET: the
 // BATCH kernel, which reads per-member arrays a single ensemble has none of) and a small launcher answer 1 to each other's descriptor
 #ifndef EMX_FUSED_ENSEMBLE_SMALL_ABI
-#define EMX_FUSED_ENSEMBLE_SMALL_ABI 0x45535301u
+#define EMX_FUSED_ENSEMBLE_SMALL_ABI 0x45535302u
 #endif
 
 namespace emx {

@@ -37,7 +37,7 @@
 // TILE stays the compile-time upper bound of the rows a workgroup takes (the register arrays of phase 1); the rows it actually
 // takes are a run-time argument, 4 ... TILE, so that a mid-size ensemble spreads over the chip (fused_ens_data_rows_rule;
 // profiles/ensemble_fused_data.md); passes of phase 1 / 3 without a live row are skipped by a workgroup-uniform branch.
-// Out of scope: blobs, the one-workgroup small form, EnsembleBatch, PTSampler, several GPUs.
+// Out of scope: blobs, the one-workgroup small form, PTSampler, several GPUs.  (A batch's data targets: emx_fused_target_data.hpp.)
 #pragma once
 #include "emx_fused_ensemble.hpp"
 
@@ -61,11 +61,6 @@ inline int fused_ens_data_rows_rule(int D, long long nslots, int num_cu) {
     int rows = fused_ens_tile_rule(D);
     while (rows > FUSED_ENS_DATA_MIN_ROWS && (nslots + rows - 1) / rows < (long long)num_cu * FUSED_ENS_DATA_WG_PER_CU) rows /= 2;
     return rows;
-}
-
-// lane 0's value in every lane; the whole wave is active
-__device__ __forceinline__ double wave_first(double x) {
-    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
 }
 
 template <int G, int V, int CH, int MOVE, typename USER, int TILE>
@@ -164,7 +159,7 @@ static __global__ __launch_bounds__(FUSED_ENS_THREADS) void k_halfstep_user_data
                 }
                 if (!bad) b = USER{}.base(x, D, user);
             }
-            const double base = wave_first(b);
+            const double base = wave_first(b);            // emx_kernels.hpp
             const bool go = !bad && base == base && base != -__builtin_inf();      // the same value in every lane
             double part = 0.0;
             if (go)

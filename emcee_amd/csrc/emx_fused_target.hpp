@@ -39,7 +39,7 @@
 
 // bumped with ANY change of SmallRunArgs or of k_small_run's LDS layout: a launcher and a library of different values refuse each other
 #ifndef EMX_FUSED_ABI
-#define EMX_FUSED_ABI 2u
+#define EMX_FUSED_ABI 3u
 #endif
 
 #define EMX_FUSED_MOVES_STRETCH 1      // the schedule is one StretchMove
@@ -52,10 +52,11 @@ constexpr int fused_v(int D) { return D % 2 == 0 ? 2 : 1; }
 constexpr int fused_g(int D) { return shape_g((D + fused_v(D) - 1) / fused_v(D)); }
 constexpr int fused_ch(int D) { return shape_ch((D + fused_v(D) - 1) / fused_v(D)); }
 
-template <typename USER, int NDIM, int MOVESEL, int NBLOBS = 0>
+// DATA: the wave-a-row form of a model with base and term (emx_fused_target_data.hpp)
+template <typename USER, int NDIM, int MOVESEL, int NBLOBS = 0, bool DATA = false>
 hipError_t launch_fused_move(int grid, int threads, size_t lds, hipStream_t st, const SmallRunArgs& a) {
     constexpr int G = fused_g(NDIM), V = fused_v(NDIM), CH = fused_ch(NDIM);
-    auto kern = k_small_run<G, V, CH, MOVESEL, false, 0, true, USER, NBLOBS>;
+    auto kern = k_small_run<G, V, CH, MOVESEL, false, 0, true, USER, NBLOBS, DATA>;
     static size_t lds_granted[MAX_DEVICES] = {};      // as launch_small_move: function attributes are per device
     int dev = 0;
     if (lds > 48 * 1024 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MAX_DEVICES && lds > lds_granted[dev]) {

@@ -2023,6 +2023,9 @@ struct SmallRunArgs {
     double* blobs;
     double* chain_blobs;
     int32_t nblobs;
+    // data targets (k_small_run<..., USER, 0, DATA>, emx_fused_target_data.hpp): the data every member's `term` runs over,
+    // member-indexed (nullptr: not a data target)
+    const long long* ndata;
 };
 
 constexpr int SMALL_STATUS_WORDS = 8;      // a member's status flags (raise_status: one word per bit)
@@ -2134,6 +2137,29 @@ __device__ __forceinline__ double fused_call_blobs(const double* x, int ndim, in
     }
 }
 
+// lane 0's value in every lane; the whole wave is active
+__device__ __forceinline__ double wave_first(double x) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
+}
+
+// a data target's value of one row, by a WHOLE wave (emx_fused_target_data.hpp, "THE VALUE"): lane 0 calls base, the 64 lanes
+// stride over the member's data, and the tree runs with every lane active and reconverged -- outside the strided loop and every
+// lane branch (DPP and permlane reads of inactive lanes are undefined).  `bad` (the same in every lane): the row does not reach
+// the model and the value is -inf.  base -inf or NaN: no term is evaluated, the value is base.  Every lane returns the value.
+template <typename USER>
+__device__ __forceinline__ double fused_data_value(const double* x, int ndim, int member, const void* user, long long ndata, bool bad,
+                                                   int lane) {
+    double b = -__builtin_inf();
+    if (lane == 0 && !bad) b = USER{}.base(x, ndim, member, user);
+    const double base = wave_first(b);
+    const bool go = !bad && base == base && base != -__builtin_inf();      // the same value in every lane
+    double part = 0.0;
+    if (go)
+        for (long long k = lane; k < ndata; k += 64) part = part + USER{}.term(x, ndim, member, k, user);
+    const double S = group_sum<64>(part);
+    return go ? base + S : base;
+}
+
 // the dense target's quadratic form of the 16 tile rows a wave holds, through the f64 MFMA against the LDS image (k_halfstep's
 // instructions in k_halfstep's order); the value of tile row (lane >> 4) + 4 (lane & 3) lands in lanes with (lane & 15) < 4
 template <int DPB, int KK, int RT>
@@ -2176,7 +2202,11 @@ __device__ __forceinline__ double small_dense_qf(const double* tile, const doubl
 // 1 / G of them a per-wave tile would leave busy.  A row with a non-finite coordinate is rejected without reaching the functor.
 // NBLOBS > 0 (fused user targets only): every walker carries NBLOBS doubles in LDS behind the staging area, written by the
 // functor with the walker's log-probability, committed exactly when that log-probability is, and stored with the chain rows.
-template <int G, int V, int CH, int MOVESEL, bool PLANNED, int DPB = 0, bool BATCH = false, typename USER = void, int NBLOBS = 0>
+// DATA (batches of a fused user target whose log-probability sums over per-member data, emx_fused_target_data.hpp): USER is a
+// model with base and term, and the second pass -- and the initial log-probs -- give every row a WAVE: fused_data_value, the
+// decision by lane 0, the commit by all 64 lanes.  The first pass, the plans and the chain are the text above.
+template <int G, int V, int CH, int MOVESEL, bool PLANNED, int DPB = 0, bool BATCH = false, typename USER = void, int NBLOBS = 0,
+          bool DATA = false>
 static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int WPW = 64 / G;
@@ -2185,6 +2215,7 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
     static_assert(!FUSED || !DENSE, "a fused user target has no dense form");
     static_assert(!FUSED || !(BATCH && PLANNED), "batches run in Philox mode only");
     static_assert(NBLOBS == 0 || FUSED, "blobs are a fused user target's");
+    static_assert(!DATA || (FUSED && BATCH && NBLOBS == 0), "a data target is a batch's fused user target without blobs");
     constexpr int Dp = DENSE ? DPB * 16 : 16, KK = Dp / 4, RT = Dp + 2, PPT = 16 / WPW;
     const int N = A.N, D = A.D, T = blockDim.x, tid = threadIdx.x, B = A.batch;
     const int lane = tid & 63, wv = tid >> 6, nwave = T >> 6, sub = lane / G, gl = lane % G;
@@ -2235,7 +2266,16 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
         // proposal's -- eval_valu_target, or the dense tile and MFMA contraction -- which is eval_rows' arithmetic
         if (A.eval0) {
             __syncthreads();
-            if constexpr (FUSED) {
+            if constexpr (DATA) {
+                const long long nd = A.ndata[M.m()];
+                for (int t = __builtin_amdgcn_readfirstlane(wv); t < N; t += nwave) {      // wave-uniform: a wave a walker's own row
+                    const double lpn = fused_data_value<USER>(Xs + (size_t)t * D, D, (int)M.m(), A.user, nd, false, lane);
+                    if (lane == 0) {
+                        if (lpn != lpn) raise_status(M.status(), ST_NAN_LOGP);
+                        lps[t] = lpn;
+                    }
+                }
+            } else if constexpr (FUSED) {
                 for (int t = tid; t < N; t += T) {                                // the functor on the walker's own row
                     double lpn;
                     if constexpr (NBLOBS > 0) {
@@ -2397,6 +2437,31 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                         }
                     }
                     __syncthreads();
+                    if constexpr (DATA) {
+                        // pass 2, a wave a row -- the model over the member's data, small_update's decision by lane 0, the commit by
+                        // every lane; the values stored are the one-lane form's
+                        const long long nd = A.ndata[M.m()];
+                        for (int t = __builtin_amdgcn_readfirstlane(wv); t < ns && t < A.stage_rows; t += nwave) {      // wave-uniform
+                            const int pos = pos0 + t;
+                            const int i = orders[pos];
+                            const double* qrow = stage + (size_t)t * DS;
+                            const double fac = sfac[t];                                  // the same value in every lane
+                            const bool bad = fac == -__builtin_inf();                    // (-inf: as below)
+                            const double lp_new = fused_data_value<USER>(qrow, D, (int)M.m(), A.user, nd, bad, lane);
+                            int acc = 0;
+                            if (lane == 0 && !bad) {
+                                if (lp_new != lp_new) raise_status(M.status(), ST_NAN_LOGP);
+                                const double lnpdiff = fac + lp_new - lps[i];            // red_blue.py:99
+                                acc = lnpdiff > logus[pos] ? 1 : 0;                      // red_blue.py:100
+                            }
+                            const bool accept = __builtin_amdgcn_readfirstlane(acc) != 0;
+                            if (accept) {
+                                for (int d = lane; d < D; d += 64) Xs[(size_t)i * D + d] = qrow[d];
+                                if (lane == 0) lps[i] = lp_new;
+                            }
+                            if (lane == 0) accs[i] = accept ? 1 : 0;
+                        }
+                    } else
                     // pass 2: one lane a row -- the functor, small_update's decision, the commit
                     for (int t = tid; t < ns && t < A.stage_rows; t += T) {
                         const int pos = pos0 + t;

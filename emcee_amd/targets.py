@@ -352,10 +352,26 @@ class BatchFused(BatchTarget):
 
     ``nblobs = K > 0``: the launcher was emitted by ``EMX_FUSED_BATCH_TARGET_BLOBS(name, Functor, ndim, K)`` around the functor's
     five-argument form, which writes K doubles a row (``EnsembleBatch.get_blobs``); a launcher compiled for another count is
-    refused when the target is bound."""
+    refused when the target is bound.
+
+    ``ndata`` (an integer for every member, or a sequence / array of ``nbatch`` integers, each ``0 <= ndata < 2**31``): the
+    log-probability sums over per-member data, ``base(x) + sum_k term(x; datum k)``, and ``fn_ptr`` is the launcher that
+    ``EMX_FUSED_BATCH_DATA_TARGET(name, Model, ndim)`` of ``emx_fused_target_data.hpp`` emits around a model with ``base(x, ndim,
+    member, user)`` and ``term(x, ndim, member, k, user)`` members (an ``emx_fused_batch_data_fn``).  The kernel then gives every
+    proposal a WAVE for the data sum -- one lane calls ``base``, 64 lanes stride over the member's ``ndata[member]`` data, a fixed
+    pairwise tree adds the lane partials, the wave commits the row -- where the plain functor loops over the data in one of the
+    few lanes a small ensemble keeps busy.  The counts are run-time values and may differ from member to member (a catalogue's
+    objects have different numbers of points): one launcher serves them all.  The value of a row is defined by the header and
+    reproduced on the host by :func:`fused_data_sum`; member b is bit for bit the :class:`~emcee_amd.EnsembleSampler` run of the
+    same model as a :class:`DeviceFused` with ``ndata[b]`` under ``rng="philox"``.  Everything else of the batch -- one launch per
+    chunk, ``get_summary``, ``get_histograms``, the device autocorrelation times, thinning, ``store=False`` -- is unchanged.  No
+    blobs with ``ndata`` (``ValueError``); a length other than ``nbatch`` is refused when the batch takes the target.  Where it pays,
+    measured on a straight-line fit against the one-lane, one-accumulator functor of the same model
+    (``profiles/batch_fused_data.md``): at 64 members of 32 x 5 from the smallest count measured (1.17 times the speed at 16 data,
+    12 times at 1 024); at 1 024 members, which share CUs, from 256 data (0.34 times at 16, 1.9 times at 256, 3.6 times at 1 024)."""
     kind = _lib.TARGET_FUSED_USER
 
-    def __init__(self, fn_ptr, ndim, user=None, nblobs=0):
+    def __init__(self, fn_ptr, ndim, user=None, nblobs=0, ndata=None):
         if not isinstance(fn_ptr, ctypes._CFuncPtr):
             addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
             if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
@@ -368,6 +384,13 @@ class BatchFused(BatchTarget):
             raise TypeError("BatchFused's user tensor must live on the GPU (the functor reads it on the device)")
         self.fn_ptr, self.ndim, self.user = fn_ptr, int(ndim), user
         self.nblobs = _check_nblobs("BatchFused", nblobs)
+        if ndata is None or isinstance(ndata, (bool, int, float, np.generic)):
+            self.ndata = _check_ndata("BatchFused", ndata)
+        else:                             # one count a member: _check_ndata's rule for every entry
+            self.ndata = tuple(_check_ndata("BatchFused", n) for n in (ndata.tolist() if isinstance(ndata, np.ndarray) and ndata.dtype == object
+                                                                       else list(ndata)))
+        if self.ndata is not None and self.nblobs > 0:
+            raise ValueError("BatchFused: a target that sums over data (ndata) carries no blobs; nblobs=%d is refused" % self.nblobs)
 
     def user_address(self):
         """-> the device address handed to the functor (None: a null pointer)"""
@@ -417,17 +440,24 @@ def get_include():
 
 class BatchFusedLibrary(object):
     """What :func:`compile_fused` built: ``path`` of the shared library, ``lib`` (its ``ctypes.CDLL``: the user's own ``extern
-    "C"`` setup functions of ``source`` are there), ``name`` of the launcher, ``ndim``, ``nblobs``, and :meth:`target`."""
+    "C"`` setup functions of ``source`` are there), ``name`` of the launcher, ``ndim``, ``nblobs``, ``data`` (the launcher is an
+    ``EMX_FUSED_BATCH_DATA_TARGET`` one) and :meth:`target`."""
 
-    def __init__(self, path, name, ndim, nblobs=0):
+    def __init__(self, path, name, ndim, nblobs=0, data=False):
         self.path, self.name, self.ndim, self.nblobs = path, name, int(ndim), int(nblobs)
+        self.data = bool(data)            # target() takes the members' data counts
         _lib.load()                       # one HIP runtime per process: the library's (torch's) first
         self.lib = ctypes.CDLL(path)
         self.launcher = getattr(self.lib, name)
 
-    def target(self, user=None):
-        """-> :class:`BatchFused` of the compiled functor with the device pointer ``user``"""
-        t = BatchFused(self.launcher, self.ndim, user, nblobs=self.nblobs)
+    def target(self, user=None, ndata=None):
+        """-> :class:`BatchFused` of the compiled functor with the device pointer ``user``; a library built with ``data=True``
+        needs ``ndata`` -- the data every member's ``term`` runs over, an integer or ``nbatch`` of them -- and any other refuses it"""
+        if self.data and ndata is None:
+            raise ValueError("BatchFusedLibrary.target: the library was built with data=True; give ndata, the members' numbers of data")
+        if not self.data and ndata is not None:
+            raise ValueError("BatchFusedLibrary.target: ndata is for a library built with compile_fused(..., data=True)")
+        t = BatchFused(self.launcher, self.ndim, user, nblobs=self.nblobs, ndata=ndata)
         t._library = self                 # the launcher's code lives as long as the target
         return t
 
@@ -584,7 +614,7 @@ def compile_fused_pt(source, likelihood, ndim, prior=None, name=None, flags=(), 
     return PTFusedLibrary(so, name, ndim, prior is not None)
 
 
-def compile_fused(source, functor, ndim, nblobs=0, name=None, flags=(), cache_dir=None):
+def compile_fused(source, functor, ndim, nblobs=0, name=None, flags=(), cache_dir=None, data=False):
     """Compile the user's model into the batch kernel -> :class:`BatchFusedLibrary`.
 
     ``source``: HIP C++ that defines the functor type ``functor`` -- ``__device__ double operator()(const double* x, int ndim,
@@ -597,11 +627,18 @@ def compile_fused(source, functor, ndim, nblobs=0, name=None, flags=(), cache_di
 
     ``nblobs = K > 0``: the functor has the five-argument form ``(const double* x, int ndim, int member, const void* user, double*
     blobs)`` and writes ``blobs[0 ... K)``; the translation unit ends with ``EMX_FUSED_BATCH_TARGET_BLOBS(name, functor, ndim, K)``
-    and K is part of the cache key."""
+    and K is part of the cache key.
+
+    ``data=True``: ``functor`` is a model with ``base(x, ndim, member, user)`` and ``term(x, ndim, member, k, user)`` members whose
+    log-probability sums over per-member data (:class:`BatchFused`'s ``ndata``).  The translation unit is ``#include
+    <emx_fused_target_data.hpp>``, ``source`` and ``EMX_FUSED_BATCH_DATA_TARGET(name, functor, ndim)``; ``nblobs`` is refused.
+    ``data=False`` keeps the translation unit and the cache key it always had."""
     ndim = int(ndim)
     if ndim < 1 or ndim > 256:
         raise ValueError("compile_fused: 1 <= ndim <= 256; got %d" % ndim)
     nblobs = _check_nblobs("compile_fused", nblobs)
+    if data and nblobs:
+        raise ValueError("compile_fused: a data target (data=True) carries no blobs; nblobs=%d is refused" % nblobs)
     for what, ident in (("functor", functor), ("name", name)):
         if ident is not None and not re.match(r"^[A-Za-z_][A-Za-z0-9_:]*$", ident):
             raise ValueError("compile_fused: %s must be a C++ identifier; got %r" % (what, ident))
@@ -611,5 +648,9 @@ def compile_fused(source, functor, ndim, nblobs=0, name=None, flags=(), cache_di
             "EMX_FUSED_BATCH_TARGET(%s, %s, %d)" % (name, functor, ndim))
     # (nblobs joins the key only when there are blobs: a blob-free build does not depend on how the count is spelt)
     key = ("batch", source, functor, ndim, name) + (("nblobs", nblobs) if nblobs else ())
+    if data:
+        tail = "EMX_FUSED_BATCH_DATA_TARGET(%s, %s, %d)" % (name, functor, ndim)
+        so = _compile_cached("compile_fused", "emx_fused_target_data.hpp", source, tail, key + ("data target",), name, flags, cache_dir)
+        return BatchFusedLibrary(so, name, ndim, 0, data=True)
     so = _compile_cached("compile_fused", "emx_fused_target.hpp", source, tail, key, name, flags, cache_dir)
     return BatchFusedLibrary(so, name, ndim, nblobs)

@@ -766,6 +766,34 @@ int emx_set_batch_target_fused_blobs(emx_batch* b, emx_fused_batch_fn fn, int32_
 typedef int (*emx_batch_log_prob_blobs_fn)(void* user, const double* coords_dev, int32_t nbatch, int64_t rows, int32_t ndim,
                                            double* log_prob_dev, int32_t nblobs, double* blobs_dev, void* hip_stream);
 int emx_set_batch_target_callback_blobs(emx_batch* b, emx_batch_log_prob_blobs_fn fn, void* user, int32_t nblobs);
+/* Fused user targets of a batch whose log-probability SUMS OVER PER-MEMBER DATA (emcee_amd.targets.BatchFused(..., ndata=) /
+ * compile_fused(..., data=True)): base(theta) + sum_k term(theta; datum k), k in [0, ndata[member]).  The caller's translation unit
+ * includes emcee_amd/csrc/emx_fused_target_data.hpp and emits the launcher with EMX_FUSED_BATCH_DATA_TARGET(name, Model, ndim)
+ * around a model with `base` and `term` members; k_small_run then gives every staged row a WAVE for the data sum -- and commits
+ * it with all 64 lanes -- where the plain functor loops over the member's data in one lane.  The value of a row is defined in that
+ * header (the lane-strided partial sums and the pairwise tree; emcee_amd.targets.fused_data_sum on the host) and depends on
+ * neither the launch shape nor the size of the batch.  The descriptor is one of its own: the fields of emx_fused_launch, then
+ * `ndata`, the library's member-indexed DEVICE array of the counts.  `abi` is EMX_FUSED_BATCH_DATA_ABI, a constant of its own, so
+ * a data launcher handed emx_fused_launch and an EMX_FUSED_BATCH_TARGET launcher handed this one answer 1; the other answers are
+ * emx_fused_batch_fn's (4: nblobs is not 0).  emx_set_batch_target_fused_data copies `ndata_host` (nbatch values, each in
+ * [0, 2^31)) to the device, probes once and refuses another header version or ndim, a count out of range and a tempered handle
+ * with emx_set_batch_target_fused's codes; it frees blob storage.  When members share CUs the workgroup is cut to a wave a row of
+ * the largest split (not to its G lanes a row); "batch_threads" and "batch_plan_steps" apply and change no bit. */
+typedef struct emx_fused_batch_data_launch {
+    uint32_t abi;            /* EMX_FUSED_BATCH_DATA_ABI the library was built with */
+    uint32_t args_bytes;     /* sizeof(SmallRunArgs) of the library */
+    int32_t ndim, movesel, grid, threads;
+    uint64_t lds_bytes;
+    void* hip_stream;
+    const void* args;        /* SmallRunArgs */
+    const void* user;        /* user_dev */
+    int32_t nblobs;          /* 0 */
+    int32_t reserved;        /* 0 */
+    const int64_t* ndata;    /* device: the data of every member, `grid` values */
+} emx_fused_batch_data_launch;
+typedef int (*emx_fused_batch_data_fn)(const emx_fused_batch_data_launch*);     /* 0, or non-zero and nothing launched */
+int emx_set_batch_target_fused_data(emx_batch* b, emx_fused_batch_data_fn fn, int32_t ndim_compiled, const void* user_dev,
+                                    const int64_t* ndata_host);
 /* emx_batch_check for a target with nblobs blobs a sample (host only): 0, or -1 and the reason in msg */
 int emx_check_batch_blobs(int64_t nwalkers, int32_t ndim, int32_t target, int32_t nmoves, const emx_move_desc* moves, int32_t nblobs,
                           char* msg, int32_t msglen);
