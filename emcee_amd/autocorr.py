@@ -35,7 +35,10 @@ def _batched_acf(series):
     """Normalised ACF along axis 0 of a (n_t, m) array, all m columns in one real FFT pair."""
     n_t = series.shape[0]
     size = 2 * next_pow_two(n_t)
+    # centred twice: the rounding error of the first mean (relative to |mean|, not to the spread) enters the lagged products
+    # linearly; what the second mean removes is relative to the spread
     centred = series - series.mean(axis=0)
+    centred -= centred.mean(axis=0)
     spectrum = np.fft.rfft(centred, n=size, axis=0)
     power = spectrum.real ** 2 + spectrum.imag ** 2
     acf = np.fft.irfft(power, n=size, axis=0)[:n_t]

@@ -205,7 +205,11 @@ class Backend(object):
 
         A device-resident chain is reduced where it lives (``emx_summary``): only these numbers cross to the host.  A chain on
         the host (user-written moves, Python blobs) is reduced with NumPy into the same tuple, and so is a device chain whose
-        call fails (no room for the scratch next to a long chain).  On the device ``cov=True`` needs ``ndim <= 256``."""
+        call fails (no room for the scratch next to a long chain).  On the device ``cov=True`` needs ``ndim <= 256``.
+
+        Far from the origin (|mean| / sd of 2^20 ... 2^40) only the device path keeps the mean to one rounding and the
+        covariance to its summation error (a residual pass and the corrected two-pass form); the NumPy path is ``x.mean`` and
+        ``np.cov`` bit for bit and loses what they lose."""
         return self._summary("chain", discard, thin, quantiles, cov)
 
     def get_blob_summary(self, discard=0, thin=1, quantiles=(0.16, 0.5, 0.84), cov=True):

@@ -62,27 +62,38 @@ namespace {
 // ---- autocorrelation kernels ----------------------------------------------------------------------------------------
 // series s = (walker, dim) of the chunk, sample t = stored step t0 + t * thin.  The chain is [step][walker][dim]: threads
 // that are consecutive in s read consecutive doubles.
-__global__ __launch_bounds__(256) void k_series_mean(const double* __restrict__ chain, double* __restrict__ mean, int64_t s0,
-                                                     int64_t nser, int64_t ND, int64_t t0, int64_t thin, int64_t nt) {
+//
+// The series is centred with a two-part mean: m1 = mean(x), then m2 = mean(x - m1) in the same order (sub = m1).  The rounding
+// error of m1 is relative to |m1| and would enter the lagged products linearly through the partial sums; what is left after
+// m2 is relative to the spread of the series.
+__global__ __launch_bounds__(256) void k_series_mean(const double* __restrict__ chain, const double* __restrict__ sub,
+                                                     double* __restrict__ mean, int64_t s0, int64_t nser, int64_t ND, int64_t t0,
+                                                     int64_t thin, int64_t nt) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nser) return;
     const double* p = chain + t0 * ND + s0 + s;
     double acc = 0.0;
-    for (int64_t t = 0; t < nt; ++t) acc += p[t * thin * ND];
+    if (sub) {
+        const double m1 = sub[s];
+        for (int64_t t = 0; t < nt; ++t) acc += p[t * thin * ND] - m1;
+    } else {
+        for (int64_t t = 0; t < nt; ++t) acc += p[t * thin * ND];
+    }
     mean[s] = acc / (double)nt;
 }
 
-// buf[s][t] = x[t][s] - mean[s] for t < nt, 0 up to L: a 64 x 64 tile goes through LDS so that both sides are coalesced
+// buf[s][t] = (x[t][s] - mean[s]) - mean2[s] for t < nt, 0 up to L: a 64 x 64 tile goes through LDS so that both sides are
+// coalesced
 __global__ __launch_bounds__(256) void k_series_gather(const double* __restrict__ chain, const double* __restrict__ mean,
-                                                       double* __restrict__ buf, int64_t s0, int64_t nser, int64_t ND,
-                                                       int64_t t0, int64_t thin, int64_t nt, int64_t L) {
+                                                       const double* __restrict__ mean2, double* __restrict__ buf, int64_t s0,
+                                                       int64_t nser, int64_t ND, int64_t t0, int64_t thin, int64_t nt, int64_t L) {
     __shared__ double tile[64][65];
     const int64_t sb = (int64_t)blockIdx.x * 64, tb = (int64_t)blockIdx.y * 64;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;          // 64 x 4
     for (int r = ty; r < 64; r += 4) {                               // r: time inside the tile, tx: series
         const int64_t t = tb + r, s = sb + tx;
         double v = 0.0;
-        if (t < nt && s < nser) v = chain[(t0 + t * thin) * ND + s0 + s] - mean[s];
+        if (t < nt && s < nser) v = (chain[(t0 + t * thin) * ND + s0 + s] - mean[s]) - mean2[s];
         tile[r][tx] = v;
     }
     __syncthreads();
@@ -304,7 +315,7 @@ int emx_autocorr(emx_ctx* c, int64_t discard, int64_t thin, double cwin, double*
     };
     AUX_TRY(hipok(hipMalloc((void**)&buf, (size_t)wc * D * L * 8), "buffer allocation"));
     AUX_TRY(hipok(hipMalloc(&spec, (size_t)wc * D * LC * 16), "spectrum allocation"));
-    AUX_TRY(hipok(hipMalloc((void**)&mean, (size_t)wc * D * 8), "allocation"));
+    AUX_TRY(hipok(hipMalloc((void**)&mean, (size_t)wc * D * 16), "allocation"));
     AUX_TRY(hipok(hipMalloc((void**)&macf, (size_t)D * nt * 8), "allocation"));
     AUX_TRY(hipok(hipMemsetAsync(macf, 0, (size_t)D * nt * 8, v.stream), "memset"));
     for (int64_t w0 = 0; w0 < N; w0 += wc) {
@@ -327,10 +338,13 @@ int emx_autocorr(emx_ctx* c, int64_t discard, int64_t thin, double cwin, double*
             plan_batch = nser;
         }
         const int64_t s0 = w0 * D;
-        hipLaunchKernelGGL(k_series_mean, dim3((unsigned)((nser + 255) / 256)), dim3(256), 0, v.stream, v.chain, mean, s0, nser, ND, t0,
-                           thin, nt);
+        double* mean2 = mean + wc * D;      // the second part of the mean
+        hipLaunchKernelGGL(k_series_mean, dim3((unsigned)((nser + 255) / 256)), dim3(256), 0, v.stream, v.chain, (const double*)nullptr,
+                           mean, s0, nser, ND, t0, thin, nt);
+        hipLaunchKernelGGL(k_series_mean, dim3((unsigned)((nser + 255) / 256)), dim3(256), 0, v.stream, v.chain, (const double*)mean,
+                           mean2, s0, nser, ND, t0, thin, nt);
         hipLaunchKernelGGL(k_series_gather, dim3((unsigned)((nser + 63) / 64), (unsigned)((L + 63) / 64)), dim3(256), 0, v.stream,
-                           v.chain, mean, buf, s0, nser, ND, t0, thin, nt, L);
+                           v.chain, (const double*)mean, (const double*)mean2, buf, s0, nser, ND, t0, thin, nt, L);
         AUX_TRY(hipok(hipGetLastError(), "gather launch"));
         int e = g_fft.ExecD2Z(plan_f, buf, spec);
         if (!e) {

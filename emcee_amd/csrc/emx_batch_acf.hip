@@ -5,9 +5,11 @@
 //
 // Series s = (member, walker, dim): within a member the N D series of one stored step are contiguous, members are cap N D
 // doubles apart.  Members go in groups (their mean ACF within ~1 GB); per group
-//   k_bacf_mean        mean of every series of the group over the selected samples
+//   k_bacf_mean        mean of every series of the group over the selected samples, in two parts: m1 = mean(x), then
+//                      m2 = mean(x - m1) in the same order -- m1's rounding error is relative to |m1| and would enter the
+//                      lagged products linearly; what is left after m2 is relative to the spread
 // then per chunk of consecutive series (a chunk may begin and end inside a member):
-//   k_bacf_gather      buf[s][t] = x - mean for t < nt, 0 up to L (a tile transposed through LDS)
+//   k_bacf_gather      buf[s][t] = (x - m1) - m2 for t < nt, 0 up to L (a tile transposed through LDS)
 //   hipFFT D2Z         spectrum
 //   k_bacf_power       |z|^2
 //   hipFFT Z2D         autocovariance of every series
@@ -59,9 +61,9 @@ namespace {
 //
 // mean[s]: lane = series (64 consecutive series a block, reading consecutive doubles but across a member boundary), the 4 waves
 // sum consecutive quarters of the samples, combined in wave order.  The order depends on nt alone: no bit depends on the
-// grouping or the chunking.
-__global__ __launch_bounds__(256) void k_bacf_mean(const double* __restrict__ chain, double* __restrict__ mean, int64_t g0, int64_t nser,
-                                                   int64_t ND, int64_t cap, int64_t t0, int64_t thin, int64_t nt) {
+// grouping or the chunking.  sub: nothing, or the first part of the mean, subtracted from every sample before it is added.
+__global__ __launch_bounds__(256) void k_bacf_mean(const double* __restrict__ chain, const double* __restrict__ sub, double* __restrict__ mean,
+                                                   int64_t g0, int64_t nser, int64_t ND, int64_t cap, int64_t t0, int64_t thin, int64_t nt) {
     __shared__ double part[4][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t s = (int64_t)blockIdx.x * 64 + lane;
@@ -71,18 +73,24 @@ __global__ __launch_bounds__(256) void k_bacf_mean(const double* __restrict__ ch
         const int64_t g = g0 + s, m = g / ND, j = g - m * ND;
         const double* p = chain + (m * cap + t0) * ND + j;
         const int64_t step = thin * ND;
+        if (sub) {
+            const double m1 = sub[s];
 #pragma unroll 8
-        for (int64_t t = ta; t < tb; ++t) acc += p[t * step];
+            for (int64_t t = ta; t < tb; ++t) acc += p[t * step] - m1;
+        } else {
+#pragma unroll 8
+            for (int64_t t = ta; t < tb; ++t) acc += p[t * step];
+        }
     }
     part[wv][lane] = acc;
     __syncthreads();
     if (wv == 0 && s < nser) mean[s] = (((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]) / (double)nt;
 }
 
-// buf[s][t] = x[t][s] - mean[s] for t < nt, 0 up to L: a 64 x 64 tile (64 series x 64 samples) goes through LDS so that the
+// buf[s][t] = (x[t][s] - mean[s]) - mean2[s] for t < nt, 0 up to L: a 64 x 64 tile (64 series x 64 samples) goes through LDS so that the
 // chain reads (along s) and the buffer writes (along t) are both coalesced.  grid.y strides over L's tiles.
 __global__ __launch_bounds__(256) void k_bacf_gather(const double* __restrict__ chain, const double* __restrict__ mean,
-                                                     double* __restrict__ buf, int64_t g0, int64_t nser, int64_t ND, int64_t cap,
+                                                     const double* __restrict__ mean2, double* __restrict__ buf, int64_t g0, int64_t nser, int64_t ND, int64_t cap,
                                                      int64_t t0, int64_t thin, int64_t nt, int64_t L) {
     __shared__ double tile[64][65];
     const int64_t sb = (int64_t)blockIdx.x * 64;
@@ -91,17 +99,18 @@ __global__ __launch_bounds__(256) void k_bacf_gather(const double* __restrict__ 
     const int64_t sr = sb + tx;
     const bool live = sr < nser;
     const double* src = nullptr;
-    double mu = 0.0;
+    double mu = 0.0, mu2 = 0.0;
     if (live) {
         const int64_t g = g0 + sr, m = g / ND, j = g - m * ND;
         src = chain + (m * cap + t0) * ND + j;
         mu = mean[sr];
+        mu2 = mean2[sr];
     }
     const int64_t step = thin * ND;
     for (int64_t tb = (int64_t)blockIdx.y * 64; tb < L; tb += (int64_t)gridDim.y * 64) {
         for (int r = ty; r < 64; r += 4) {                           // r: sample inside the tile, tx: series
             const int64_t t = tb + r;
-            tile[r][tx] = (live && t < nt) ? src[t * step] - mu : 0.0;
+            tile[r][tx] = (live && t < nt) ? (src[t * step] - mu) - mu2 : 0.0;
         }
         __syncthreads();
         for (int r = ty; r < 64; r += 4) {                           // r: series inside the tile, tx: sample
@@ -283,7 +292,7 @@ int emx_autocorr_batch(emx_batch* b, int32_t member_lo, int32_t member_hi, int64
     if (v.acf_series > 0) sc = std::min<int64_t>(sc, v.acf_series);
     if (int rc = grow(b, a->buf, a->buf_n, (size_t)(sc * L), "buffer")) return rc;
     if (int rc = grow(b, a->spec, a->spec_n, (size_t)(sc * LC), "spectrum")) return rc;
-    if (int rc = grow(b, a->mean, a->mean_n, (size_t)(gm * ND), "mean")) return rc;
+    if (int rc = grow(b, a->mean, a->mean_n, (size_t)(2 * gm * ND), "mean")) return rc;
     if (int rc = grow(b, a->macf, a->macf_n, (size_t)(gm * D * nt), "mean-ACF")) return rc;
     if (int rc = grow(b, a->tau, a->tau_n, (size_t)(M * D), "tau")) return rc;
     if (int rc = grow(b, a->win, a->win_n, (size_t)(M * D), "window")) return rc;
@@ -292,15 +301,18 @@ int emx_autocorr_batch(emx_batch* b, int32_t member_lo, int32_t member_hi, int64
         const int64_t mcount = std::min<int64_t>(gm, member_hi - mg);
         ACF_HIP("memset", hipMemsetAsync(a->macf, 0, (size_t)(mcount * D * nt) * 8, v.stream));
         const int64_t gbeg = mg * ND, gend = (mg + mcount) * ND;
-        hipLaunchKernelGGL(k_bacf_mean, dim3((unsigned)((gend - gbeg + 63) / 64)), dim3(256), 0, v.stream, v.chain, a->mean, gbeg, gend - gbeg, ND,
-                           v.cap, t0, thin, nt);
+        double* mean2 = a->mean + gm * ND;      // the second part of the mean
+        hipLaunchKernelGGL(k_bacf_mean, dim3((unsigned)((gend - gbeg + 63) / 64)), dim3(256), 0, v.stream, v.chain, (const double*)nullptr, a->mean,
+                           gbeg, gend - gbeg, ND, v.cap, t0, thin, nt);
+        hipLaunchKernelGGL(k_bacf_mean, dim3((unsigned)((gend - gbeg + 63) / 64)), dim3(256), 0, v.stream, v.chain, (const double*)a->mean, mean2,
+                           gbeg, gend - gbeg, ND, v.cap, t0, thin, nt);
         ACF_HIP("mean launch", hipGetLastError());
         for (int64_t g0 = gbeg; g0 < gend; g0 += sc) {
             const int64_t nser = std::min<int64_t>(sc, gend - g0), g1 = g0 + nser;
             BatchAcf::Plan plan;
             if (int rc = get_plan(b, a, v.stream, L, nser, &plan)) return rc;
             hipLaunchKernelGGL(k_bacf_gather, dim3((unsigned)((nser + 63) / 64), (unsigned)std::min<int64_t>(65535, (L + 63) / 64)), dim3(256), 0,
-                               v.stream, v.chain, a->mean + (g0 - gbeg), a->buf, g0, nser, ND, v.cap, t0, thin, nt, L);
+                               v.stream, v.chain, (const double*)(a->mean + (g0 - gbeg)), (const double*)(mean2 + (g0 - gbeg)), a->buf, g0, nser, ND, v.cap, t0, thin, nt, L);
             ACF_HIP("gather launch", hipGetLastError());
             if (g_fft.ExecD2Z(plan.fwd, a->buf, a->spec)) return bfail(b, -6, "emx_autocorr_batch: hipFFT D2Z execution failed");
             const int64_t ne = nser * LC;

@@ -8,14 +8,18 @@
 // "batch_summary_members"; every member is reduced on its own.  Per pass
 //   k_bsum_mean_part    slab[member][slice][j = w D + d]: sum over the slice's rows, lane = j (coalesced), the 4 waves of a
 //                       workgroup sum consecutive quarters of the slice and are added in wave order
-//   k_bsum_mean_fin     mean[d] = (sum over walkers in order of (sum over slices in order)) / n
+//   k_bsum_mean_fin     mean[d] = (sum over walkers in order of (sum over slices in order)) / n.  The two run twice: the second
+//                       time on x - mean, which gives the residual sums r[d]; the mean reported is mean[d] + r[d] / n
 //   k_bsum_gram_small   D < 16: centred Gram sum (x_j - m_j)(x_k - m_k), j <= k, per slice: 256 samples at a time are centred
 //                       into LDS; thread (pair, group g) adds the samples g, g + G, ... of every tile with an explicit fma
 //                       (the file is built with -ffp-contract=off: nothing else is fused), groups are added in order
 //   k_bsum_gram_mfma    D >= 16: the same per slice on v_mfma_f64_16x16x4_f64, D padded to 16 Dp' with zero columns: a wave
 //                       holds up to 8 of the 16 x 16 blocks (jb <= kb) and runs the tile's samples four at a time; a diagonal
 //                       block's A and B operands are one LDS value
-//   k_bsum_gram_fin_*   cov[j][k] = cov[k][j] = (sum over slices in order) / (n - 1)
+//   k_bsum_gram_fin_*   cov[j][k] = cov[k][j] = ((sum over slices in order) - r[j] r[k] / n) / (n - 1): the corrected two-pass
+//                       form.  The first mean's rounding error is relative to |mean|, not to the spread; the plain form is off
+//                       by n / (n - 1) times the product of two such errors, which exceeds the summation error once
+//                       |mean| / sd is large (a posterior far from the origin)
 //   k_bsum_map          arg-max of the member's selected log-probs, ties to the smallest (row, walker) index -- (value, index)
 //                       pairs under that rule form a total order, so the reduction's shape does not matter; then the D coordinates
 //   k_bsum_sel_init / k_bsum_hist / k_bsum_scan, 8 passes of 8 bits, most significant first: radix select of every requested
@@ -90,7 +94,8 @@ struct Sel {
     int32_t D, S;
 };
 
-__global__ __launch_bounds__(256) void k_bsum_mean_part(const Sel g, double* __restrict__ mpart) {
+// sub: nothing, or (mp, D) values (the first mean) subtracted from every sample before it is added: the residual pass
+__global__ __launch_bounds__(256) void k_bsum_mean_part(const Sel g, const double* __restrict__ sub, double* __restrict__ mpart) {
     __shared__ double part[4][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t j = (int64_t)blockIdx.x * 64 + lane, s = blockIdx.y, ml = blockIdx.z;
@@ -100,16 +105,19 @@ __global__ __launch_bounds__(256) void k_bsum_mean_part(const Sel g, double* __r
     if (j < g.ND) {
         const double* p = g.chain + ((g.m0 + ml) * g.cap + g.t0) * g.ND + j;
         const int64_t step = g.stride * g.ND;
+        const double m = sub ? sub[ml * g.D + j % g.D] : 0.0;       // x - 0.0 is x
 #pragma unroll 8
-        for (int64_t t = ta; t < tb; ++t) acc += p[t * step];
+        for (int64_t t = ta; t < tb; ++t) acc += p[t * step] - m;
     }
     part[wv][lane] = acc;
     __syncthreads();
     if (wv == 0 && j < g.ND) mpart[(ml * g.S + s) * g.ND + j] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
 }
 
-// mean (mp, D) of the pass; one thread a (member, d)
-__global__ __launch_bounds__(256) void k_bsum_mean_fin(const Sel g, const double* __restrict__ mpart, double* __restrict__ mean, int64_t mp) {
+// one thread a (member, d) of the pass.  First pass (mu0 = nothing): out (mp, D) = sum / n, the mean the residuals and the Gram are
+// centred on.  Residual pass: resid = sum = the sum of (x - mu0), out = mu0 + resid / n, the mean that is reported
+__global__ __launch_bounds__(256) void k_bsum_mean_fin(const Sel g, const double* __restrict__ mpart, const double* __restrict__ mu0,
+                                                       double* __restrict__ out, double* __restrict__ resid, int64_t mp) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= mp * g.D) return;
     const int64_t ml = i / g.D, d = i - ml * g.D;
@@ -119,7 +127,13 @@ __global__ __launch_bounds__(256) void k_bsum_mean_fin(const Sel g, const double
         for (int64_t s = 0; s < g.S; ++s) col += mpart[(ml * g.S + s) * g.ND + w * g.D + d];
         acc += col;
     }
-    mean[i] = acc / (double)(g.nt * g.N);
+    const double n = (double)(g.nt * g.N);
+    if (!mu0) {
+        out[i] = acc / n;
+        return;
+    }
+    resid[i] = acc;
+    out[i] = isfinite(mu0[i]) ? mu0[i] + acc / n : mu0[i];      // a column that holds inf keeps the mean NumPy gives it (x - inf is NaN)
 }
 
 // pair p of the upper triangle of an L x L matrix in row order -> (j, k), j <= k
@@ -184,8 +198,10 @@ __global__ __launch_bounds__(256) void k_bsum_gram_small(const Sel g, const doub
     }
 }
 
-// cov (mp, D, D) of the pass from gpart (mp, S, P)
-__global__ __launch_bounds__(256) void k_bsum_gram_fin_small(const Sel g, const double* __restrict__ gpart, double* __restrict__ cov, int64_t mp) {
+// cov (mp, D, D) of the pass from gpart (mp, S, P) and the residual sums r (mp, D): the corrected two-pass form
+// (G_jk - r_j r_k / n) / (n - 1), G being centred on the first mean, whose rounding error the second term takes out
+__global__ __launch_bounds__(256) void k_bsum_gram_fin_small(const Sel g, const double* __restrict__ gpart, const double* __restrict__ resid,
+                                                             double* __restrict__ cov, int64_t mp) {
     const int D = g.D, P = D * (D + 1) / 2;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= mp * P) return;
@@ -195,7 +211,8 @@ __global__ __launch_bounds__(256) void k_bsum_gram_fin_small(const Sel g, const 
     tri_pair(p, D, &j, &k);
     double acc = 0.0;
     for (int64_t s = 0; s < g.S; ++s) acc += gpart[(ml * g.S + s) * P + p];
-    const double c = acc / (double)(g.nt * g.N - 1);
+    const double n = (double)(g.nt * g.N);
+    const double c = (acc - resid[ml * D + j] * resid[ml * D + k] / n) / (n - 1.0);
     cov[(ml * D + j) * D + k] = c;
     cov[(ml * D + k) * D + j] = c;
 }
@@ -263,8 +280,8 @@ __global__ __launch_bounds__(256) void k_bsum_gram_mfma(const Sel g, const doubl
     }
 }
 
-__global__ __launch_bounds__(256) void k_bsum_gram_fin_mfma(const Sel g, const double* __restrict__ gpart, double* __restrict__ cov, int64_t mp,
-                                                            int Dp, int NP) {
+__global__ __launch_bounds__(256) void k_bsum_gram_fin_mfma(const Sel g, const double* __restrict__ gpart, const double* __restrict__ resid,
+                                                            double* __restrict__ cov, int64_t mp, int Dp, int NP) {
     const int D = g.D;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= mp * NP * 256) return;
@@ -277,7 +294,8 @@ __global__ __launch_bounds__(256) void k_bsum_gram_fin_mfma(const Sel g, const d
     if (j >= D || k >= D || j > k) return;
     double acc = 0.0;
     for (int64_t s = 0; s < g.S; ++s) acc += gpart[((ml * g.S + s) * NP + pi) * 256 + e];
-    const double c = acc / (double)(g.nt * g.N - 1);
+    const double n = (double)(g.nt * g.N);
+    const double c = (acc - resid[ml * D + j] * resid[ml * D + k] / n) / (n - 1.0);
     cov[(ml * D + j) * D + k] = c;
     cov[(ml * D + k) * D + j] = c;
 }
@@ -490,7 +508,7 @@ int egrow(emx_ctx* c, Buf& u, size_t bytes, const char* what, const char* fn = "
 }  // namespace
 
 struct BatchSummary {
-    Buf mpart, gpart, mean, cov, order, map_x, map_lp, hist, prefix, rem, leader, ranks;
+    Buf mpart, gpart, mean, meanc, resid, cov, order, map_x, map_lp, hist, prefix, rem, leader, ranks;
     // emx_chain_minmax_batch / emx_histograms_batch
     Buf h_plo, h_phi, h_pnf, h_lo, h_hi, h_nf, h_edges, h_pedges, h_eoff, h_poff, h_pairs, h_pairoff, h_counts, h_pcounts, h_codes;
     int64_t h_launches = 0;      // kernel launches of the last emx_histograms_batch call (emx_histograms_batch_info)
@@ -498,7 +516,7 @@ struct BatchSummary {
 
 void emx_internal_batch_summary_release(BatchSummary* s) {
     if (!s) return;
-    for (Buf* u : {&s->mpart, &s->gpart, &s->mean, &s->cov, &s->order, &s->map_x, &s->map_lp, &s->hist, &s->prefix, &s->rem, &s->leader,
+    for (Buf* u : {&s->mpart, &s->gpart, &s->mean, &s->meanc, &s->resid, &s->cov, &s->order, &s->map_x, &s->map_lp, &s->hist, &s->prefix, &s->rem, &s->leader,
                    &s->ranks, &s->h_plo, &s->h_phi, &s->h_pnf, &s->h_lo, &s->h_hi, &s->h_nf, &s->h_edges, &s->h_pedges, &s->h_eoff, &s->h_poff,
                    &s->h_pairs, &s->h_pairoff, &s->h_counts, &s->h_pcounts, &s->h_codes})
         if (u->p) hipFree(u->p);
@@ -506,7 +524,7 @@ void emx_internal_batch_summary_release(BatchSummary* s) {
 }
 
 struct EnsSummary {
-    Buf part, fold, gpart, gfold, mean, cov, order, map_x, map_lp, map_pv, map_pi, hist, prefix, rem, slotof, slotpf, nlead, info, ranks, lkey, ldim;
+    Buf part, fold, gpart, gfold, mean, meanc, resid, cov, order, map_x, map_lp, map_pv, map_pi, hist, prefix, rem, slotof, slotpf, nlead, info, ranks, lkey, ldim;
     int64_t sel_reads = 0, listed = -1, list_reads = 0;      // the last call's selection (emx_summary_info)
     // emx_chain_minmax / emx_histograms
     Buf h_plo, h_phi, h_pnf, h_lo, h_hi, h_nf, h_edges, h_pedges, h_eoff, h_poff, h_pairs, h_pairoff, h_counts, h_pcounts, h_codes;
@@ -514,7 +532,7 @@ struct EnsSummary {
 
 void emx_internal_ens_summary_release(EnsSummary* s) {
     if (!s) return;
-    for (Buf* u : {&s->part, &s->fold, &s->gpart, &s->gfold, &s->mean, &s->cov, &s->order, &s->map_x, &s->map_lp, &s->map_pv, &s->map_pi,
+    for (Buf* u : {&s->part, &s->fold, &s->gpart, &s->gfold, &s->mean, &s->meanc, &s->resid, &s->cov, &s->order, &s->map_x, &s->map_lp, &s->map_pv, &s->map_pi,
                    &s->hist, &s->prefix, &s->rem, &s->slotof, &s->slotpf, &s->nlead, &s->info, &s->ranks, &s->lkey, &s->ldim, &s->h_plo,
                    &s->h_phi, &s->h_pnf, &s->h_lo, &s->h_hi, &s->h_nf, &s->h_edges, &s->h_pedges, &s->h_eoff, &s->h_poff, &s->h_pairs,
                    &s->h_pairoff, &s->h_counts, &s->h_pcounts, &s->h_codes})
@@ -661,13 +679,20 @@ int emx_summary(emx_ctx* c, int32_t plane, int64_t start, int64_t stop, int64_t 
         if (int rc = egrow(c, a->part, (size_t)G * W * 8, "mean partials")) return rc;
         if (int rc = egrow(c, a->fold, (size_t)((G + ES_FOLD - 1) / ES_FOLD) * W * 8, "mean partials")) return rc;
         if (int rc = egrow(c, a->mean, (size_t)W * 8, "mean")) return rc;
-        hipLaunchKernelGGL(k_esum_mean_part, dim3((unsigned)G, (unsigned)((W + CW - 1) / CW)), dim3(256), 0, st, g, C, CW, (double*)a->part.p);
-        ESUM_HIP("mean launch", hipGetLastError());
-        const double* sum = nullptr;
-        if (int rc = es_fold(c, st, (double*)a->part.p, (double*)a->fold.p, G, W, &sum)) return rc;
-        hipLaunchKernelGGL(k_esum_mean_fin, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, sum, (double*)a->mean.p, (int)W, n);
-        ESUM_HIP("mean launch", hipGetLastError());
-        if (mean_out) ESUM_HIP("copy", hipMemcpyAsync(mean_out, a->mean.p, (size_t)W * 8, hipMemcpyDeviceToHost, st));
+        if (int rc = egrow(c, a->resid, (size_t)W * 8, "residual sums")) return rc;
+        if (int rc = egrow(c, a->meanc, (size_t)W * 8, "mean")) return rc;
+        // pass 0: mean = the first mean mu0; pass 1: resid = the sum of (x - mu0) in the same order, meanc = mu0 + resid / n
+        for (int pass = 0; pass < 2; ++pass) {
+            const double* mu0 = pass ? (const double*)a->mean.p : nullptr;
+            hipLaunchKernelGGL(k_esum_mean_part, dim3((unsigned)G, (unsigned)((W + CW - 1) / CW)), dim3(256), 0, st, g, C, CW, mu0, (double*)a->part.p);
+            ESUM_HIP("mean launch", hipGetLastError());
+            const double* sum = nullptr;
+            if (int rc = es_fold(c, st, (double*)a->part.p, (double*)a->fold.p, G, W, &sum)) return rc;
+            hipLaunchKernelGGL(k_esum_mean_fin, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, sum, mu0, (double*)(pass ? a->meanc.p : a->mean.p),
+                               (double*)a->resid.p, (int)W, n);
+            ESUM_HIP("mean launch", hipGetLastError());
+        }
+        if (mean_out) ESUM_HIP("copy", hipMemcpyAsync(mean_out, a->meanc.p, (size_t)W * 8, hipMemcpyDeviceToHost, st));
     }
     if (want_cov) {
         const bool mfma = W >= 16;
@@ -687,9 +712,10 @@ int emx_summary(emx_ctx* c, int32_t plane, int64_t start, int64_t stop, int64_t 
         const double* sum = nullptr;
         if (int rc = es_fold(c, st, (double*)a->gpart.p, (double*)a->gfold.p, G, width, &sum)) return rc;
         if (mfma)
-            hipLaunchKernelGGL(k_bsum_gram_fin_mfma, dim3((unsigned)NP), dim3(256), 0, st, fin, sum, (double*)a->cov.p, (int64_t)1, Dp, NP);
+            hipLaunchKernelGGL(k_bsum_gram_fin_mfma, dim3((unsigned)NP), dim3(256), 0, st, fin, sum, (const double*)a->resid.p, (double*)a->cov.p,
+                               (int64_t)1, Dp, NP);
         else
-            hipLaunchKernelGGL(k_bsum_gram_fin_small, dim3(1), dim3(256), 0, st, fin, sum, (double*)a->cov.p, (int64_t)1);
+            hipLaunchKernelGGL(k_bsum_gram_fin_small, dim3(1), dim3(256), 0, st, fin, sum, (const double*)a->resid.p, (double*)a->cov.p, (int64_t)1);
         ESUM_HIP("Gram launch", hipGetLastError());
         ESUM_HIP("copy", hipMemcpyAsync(cov_out, a->cov.p, (size_t)W * W * 8, hipMemcpyDeviceToHost, st));
     }
@@ -855,6 +881,8 @@ int emx_summary_batch_plane(emx_batch* b, int32_t plane, int32_t member_lo, int3
     if (want_mean) {
         if (int rc = grow(b, a->mpart, (size_t)mp * S * ND * 8, "mean slab")) return rc;
         if (int rc = grow(b, a->mean, (size_t)mp * D * 8, "mean")) return rc;
+        if (int rc = grow(b, a->meanc, (size_t)mp * D * 8, "mean")) return rc;
+        if (int rc = grow(b, a->resid, (size_t)mp * D * 8, "residual sums")) return rc;
     }
     if (want_cov) {
         if (int rc = grow(b, a->gpart, (size_t)mp * gram_member, "Gram slab")) return rc;
@@ -894,11 +922,16 @@ int emx_summary_batch_plane(emx_batch* b, int32_t plane, int32_t member_lo, int3
         g.m0 = m0;
         const dim3 slices_j((unsigned)((ND + 63) / 64), (unsigned)S, (unsigned)mc);
         if (want_mean) {
-            hipLaunchKernelGGL(k_bsum_mean_part, slices_j, dim3(256), 0, v.stream, g, (double*)a->mpart.p);
-            SUM_HIP("mean launch", hipGetLastError());
-            hipLaunchKernelGGL(k_bsum_mean_fin, blocks(mc * D, 256), dim3(256), 0, v.stream, g, (const double*)a->mpart.p, (double*)a->mean.p, mc);
-            SUM_HIP("mean launch", hipGetLastError());
-            if (mean_out) SUM_HIP("copy", hipMemcpyAsync(mean_out + mo * D, a->mean.p, (size_t)mc * D * 8, hipMemcpyDeviceToHost, v.stream));
+            // pass 0: mean = the first mean mu0; pass 1: resid = the sum of (x - mu0) in the same order, meanc = mu0 + resid / n
+            for (int pass = 0; pass < 2; ++pass) {
+                const double* mu0 = pass ? (const double*)a->mean.p : nullptr;
+                hipLaunchKernelGGL(k_bsum_mean_part, slices_j, dim3(256), 0, v.stream, g, mu0, (double*)a->mpart.p);
+                SUM_HIP("mean launch", hipGetLastError());
+                hipLaunchKernelGGL(k_bsum_mean_fin, blocks(mc * D, 256), dim3(256), 0, v.stream, g, (const double*)a->mpart.p, mu0,
+                                   (double*)(pass ? a->meanc.p : a->mean.p), (double*)a->resid.p, mc);
+                SUM_HIP("mean launch", hipGetLastError());
+            }
+            if (mean_out) SUM_HIP("copy", hipMemcpyAsync(mean_out + mo * D, a->meanc.p, (size_t)mc * D * 8, hipMemcpyDeviceToHost, v.stream));
         }
         if (want_cov) {
             if (mfma) {
@@ -906,13 +939,13 @@ int emx_summary_batch_plane(emx_batch* b, int32_t plane, int32_t member_lo, int3
                                    v.stream, g, (const double*)a->mean.p, (double*)a->gpart.p, Dp, NP);
                 SUM_HIP("Gram launch", hipGetLastError());
                 hipLaunchKernelGGL(k_bsum_gram_fin_mfma, blocks(mc * NP * 256, 256), dim3(256), 0, v.stream, g, (const double*)a->gpart.p,
-                                   (double*)a->cov.p, mc, Dp, NP);
+                                   (const double*)a->resid.p, (double*)a->cov.p, mc, Dp, NP);
             } else {
                 hipLaunchKernelGGL(k_bsum_gram_small, dim3(1, (unsigned)S, (unsigned)mc), dim3(256), 0, v.stream, g, (const double*)a->mean.p,
                                    (double*)a->gpart.p);
                 SUM_HIP("Gram launch", hipGetLastError());
-                hipLaunchKernelGGL(k_bsum_gram_fin_small, blocks(mc * P, 256), dim3(256), 0, v.stream, g, (const double*)a->gpart.p, (double*)a->cov.p,
-                                   mc);
+                hipLaunchKernelGGL(k_bsum_gram_fin_small, blocks(mc * P, 256), dim3(256), 0, v.stream, g, (const double*)a->gpart.p,
+                                   (const double*)a->resid.p, (double*)a->cov.p, mc);
             }
             SUM_HIP("Gram launch", hipGetLastError());
             SUM_HIP("copy", hipMemcpyAsync(cov_out + mo * D * D, a->cov.p, (size_t)mc * D * D * 8, hipMemcpyDeviceToHost, v.stream));

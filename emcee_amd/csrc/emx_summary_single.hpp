@@ -9,7 +9,9 @@
 //   k_esum_mean_part   chunk c = samples [c C, c C + C): a workgroup is 256 / CW sample lanes x CW columns and walks its chunk with
 //                      coalesced loads; the sample lanes are added in order -> part (G, W)
 //   k_esum_fold        64 consecutive partials -> one, in order; applied until one is left.  C, G and so the whole tree are fixed
-//                      by (nt, N, W): the sums have one order on every call and launch shape
+//                      by (nt, N, W): the sums have one order on every call and launch shape.  The three run twice: the
+//                      second time on x - mean, which gives the residual sums r; the mean reported is mean + r / n and the
+//                      covariance (G_jk - r_j r_k / n) / (n - 1), the corrected two-pass form (emx_batch_summary.hip says why)
 //   k_esum_gram_small  W < 16: k_bsum_gram_small's explicit-fma form on a chunk of samples -> gpart (G, P)
 //   k_esum_gram_mfma   W >= 16: k_bsum_gram_mfma's v_mfma_f64_16x16x4_f64 form on a chunk -> gpart (G, NP, 4, 64); both are
 //                      folded like the mean and finished by the batch's k_bsum_gram_fin_* (one member, one slice)
@@ -49,8 +51,9 @@ inline int64_t es_chunk(int64_t n, int64_t gmax) {
     return m * ES_CHUNK;
 }
 
-// grid (G, column tiles of CW): part (G, W)
-__global__ __launch_bounds__(256) void k_esum_mean_part(const ESel g, int64_t C, int CW, double* __restrict__ part) {
+// grid (G, column tiles of CW): part (G, W).  sub: nothing, or W values (the first mean) subtracted from every sample before it
+// is added: the residual pass, in the mean's order
+__global__ __launch_bounds__(256) void k_esum_mean_part(const ESel g, int64_t C, int CW, const double* __restrict__ sub, double* __restrict__ part) {
     __shared__ double red[256];
     const int tid = threadIdx.x, SPB = 256 / CW, s = tid / CW, c = tid - s * CW;
     const int64_t d = (int64_t)blockIdx.y * CW + c;
@@ -60,9 +63,10 @@ __global__ __launch_bounds__(256) void k_esum_mean_part(const ESel g, int64_t C,
         int64_t i = i0 + s, t = i / g.N, w = i - t * g.N;
         const int64_t qstep = SPB / g.N, wstep = SPB - qstep * g.N;
         const double* p = g.x + d;
+        const double m = sub ? sub[d] : 0.0;            // x - 0.0 is x
 #pragma unroll 8
         for (; i < i1; i += SPB) {
-            acc += p[t * g.rowstep + w * g.W];
+            acc += p[t * g.rowstep + w * g.W] - m;
             t += qstep;
             w += wstep;
             if (w >= g.N) {
@@ -91,9 +95,18 @@ __global__ __launch_bounds__(256) void k_esum_fold(const double* __restrict__ in
     out[(int64_t)blockIdx.y * width + e] = acc;
 }
 
-__global__ __launch_bounds__(256) void k_esum_mean_fin(const double* __restrict__ sum, double* __restrict__ mean, int W, int64_t n) {
+// first pass (mu0 = nothing): out = sum / n, the mean the residuals and the Gram are centred on.  Residual pass: resid = sum =
+// the sum of (x - mu0), out = mu0 + resid / n, the mean that is reported
+__global__ __launch_bounds__(256) void k_esum_mean_fin(const double* __restrict__ sum, const double* __restrict__ mu0, double* __restrict__ out,
+                                                       double* __restrict__ resid, int W, int64_t n) {
     const int d = blockIdx.x * 256 + threadIdx.x;
-    if (d < W) mean[d] = sum[d] / (double)n;
+    if (d >= W) return;
+    if (!mu0) {
+        out[d] = sum[d] / (double)n;
+        return;
+    }
+    resid[d] = sum[d];
+    out[d] = isfinite(mu0[d]) ? mu0[d] + sum[d] / (double)n : mu0[d];      // a column that holds inf keeps the mean NumPy gives it
 }
 
 // W < 16.  One workgroup a chunk: gpart (G, P), P = W (W + 1) / 2

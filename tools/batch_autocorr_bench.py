@@ -4,8 +4,8 @@ on_device=True (emx_autocorr_batch: one call for every member, only (B, ndim) nu
 The host path is timed on the first `--host-members` members and extrapolated linearly to B (it is a loop over members, each
 the same work).  The device call is timed twice: the first call creates the hipFFT plans and grows the scratch, the second
 reuses them (the median of three such calls).  Bytes per device call are computed from the shapes:
-series x (7 L + 3 nt) x 8 with L = 2 next_pow_two(nt): the gather's write, the D2Z, power and Z2D passes' reads and writes
-(2 L each: the half spectrum of L / 2 + 1 complex doubles is ~L doubles), the mean's and the gather's chain reads and the
+series x (7 L + 4 nt) x 8 with L = 2 next_pow_two(nt): the gather's write, the D2Z, power and Z2D passes' reads and writes
+(2 L each: the half spectrum of L / 2 + 1 complex doubles is ~L doubles), the two-part mean's (two) and the gather's chain reads and the
 accumulate's read (nt each); rocFFT's own intermediate passes are not counted.
 usage: python tools/batch_autocorr_bench.py [--quick] [--out batch_autocorr_bench.json] [--host-members 8]
        python tools/batch_autocorr_bench.py --prof        (device calls only at B = 1 024 x 5 000 steps: for rocprofv3)"""
@@ -51,7 +51,7 @@ def bench(B, N, D, kind, mf, steps, host_members, rs):
     nt = steps
     L = 2 * next_pow_two(nt)
     series = B * N * D
-    gbytes = series * (7 * L + 3 * nt) * 8 / 1e9
+    gbytes = series * (7 * L + 4 * nt) * 8 / 1e9
     return dict(B=B, N=N, D=D, steps=steps, host_members_timed=k, host_s_timed=t_host_k, host_s_extrapolated=host_all,
                 device_first_s=cold, device_warm_s=warm, speedup_warm=host_all / warm, speedup_first=host_all / cold,
                 bytes_per_call_GB=gbytes, GBps_warm=gbytes / warm,

@@ -5,7 +5,7 @@ The host path is timed on the first `--host-members` members in blocks of 64 (a 
 comfortably: at 1 024 members of 32 x 5 x 5 000 the whole copy is 6.5 GB) and extrapolated linearly to B: it is the same work for
 every member.  The device call is timed once cold (scratch allocated) and then repeatedly for at least `--seconds` (default 1 s)
 and at least 5 calls: the median.  Bytes per call are computed from the shapes: the chain once for the mean, once for the
-Gram matrix and once per selection pass (8), the log-probs once for the MAP.
+residual sums (the mean kernels again, on x - mean), once for the Gram matrix and once per selection pass (8), the log-probs once for the MAP.
 usage: python tools/batch_summary_bench.py [--quick] [--out batch_summary_bench.json] [--host-members 128] [--seconds 1]
        python tools/batch_summary_bench.py --prof        (two device calls per shape: for rocprofv3 --kernel-trace --stats)"""
 import json
@@ -68,7 +68,7 @@ def bench(name, B, N, D, kind, steps, host_members, seconds, rs):
     h_mean, h_cov, h_q, h_x, h_lp = [np.concatenate([p[i] for p in parts]) for i in range(5)]
     bt.close()
     chain_gb = B * steps * N * D * 8 / 1e9
-    gbytes = chain_gb * (2 + 8) + B * steps * N * 8 / 1e9
+    gbytes = chain_gb * (3 + 8) + B * steps * N * 8 / 1e9
     host_all = t_host_k * B / k
     return dict(shape=name, B=B, N=N, D=D, steps=steps, nsamples=s.nsamples, host_members_timed=k, host_s_timed=t_host_k,
                 host_s_extrapolated=host_all, device_first_s=cold, device_warm_s=warm, device_calls_timed=len(times),

@@ -70,11 +70,11 @@ def bench(N, D, kind, rows, seconds, host_budget, host_calls_slow, rs):
     host_copy = float(np.median([u[1] for u in runs]))
     sel = rows * N * D * 8
     gram_reads = (((D + 15) // 16) * ((D + 15) // 16 + 1) // 2 + 31) // 32 if D >= 16 else 1
-    moment_bytes = sel * (1 + gram_reads) + rows * N * 8
+    moment_bytes = sel * (2 + gram_reads) + rows * N * 8
     order_bytes = sel * sel_reads + max(listed, 0) * 12 * (1 + list_reads)
     return dict(N=N, D=D, kind=kind, rows=rows, nsamples=r.nsamples, selection_GB=sel / 1e9, device_first_s=cold, device_warm_s=warm,
                 device_calls_timed=len(times), host_s=host, host_copy_s=host_copy, host_calls_timed=len(runs), host_over_device=host / warm,
-                reads_mean_cov_map=1 + gram_reads + 1.0 / D, reads_selection=sel_reads, listed_elements=listed, list_reads=list_reads,
+                reads_mean_cov_map=2 + gram_reads + 1.0 / D, reads_selection=sel_reads, listed_elements=listed, list_reads=list_reads,
                 bytes_per_call_GB=(moment_bytes + order_bytes) / 1e9, GBps_warm=(moment_bytes + order_bytes) / warm / 1e9,
                 share_of_8TBps=(moment_bytes + order_bytes) / warm / PEAK,
                 max_abs_mean_diff=float(np.abs(r.mean - h[0]).max()), max_rel_cov_diff=float((np.abs(r.cov - h[1]) / np.abs(h[1]).max()).max()),
