@@ -247,6 +247,7 @@ SIGNATURES = {
     "emx_pt_set_ladder": (C.c_int, [_P, _dp, C.POINTER(C.c_int64)]),
     "emx_host_pt_adapt_ladder": (C.c_int, [_dp, _i64p, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_int64, _dp]),
     "emx_pt_set_target_fused": (C.c_int, [_P, PT_FUSED_FN, C.c_int32, _P]),
+    "emx_pt_set_target_fused_data": (C.c_int, [_P, PT_FUSED_FN, C.c_int32, _P, _i64p]),
     "emx_pt_fused_check": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(MoveDesc), C.c_char_p, C.c_int32]),
     "emx_autocorr_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double, _dp, _ip, C.POINTER(C.c_int64)]),
     "emx_summary_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int32, _P, _P, _P, _P,

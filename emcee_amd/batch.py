@@ -66,7 +66,7 @@ class EnsembleBatch(object):
     DESnookerMove and GaussianMove.  ``seeds``: B integers; member b draws as a sampler whose generator was seeded with
     ``np.random.RandomState(seeds[b])``.  ``None`` draws them from NumPy's global state."""
 
-    def __init__(self, nbatch, nwalkers, ndim, target, moves=None, seeds=None, device=None, rng="philox", _tempered=False):
+    def __init__(self, nbatch, nwalkers, ndim, target, moves=None, seeds=None, device=None, rng="philox", _tempered=False, _ntemps=1):
         if rng != "philox":
             raise ValueError("EnsembleBatch runs rng='philox' only (the MT19937 stream is made by one host generator a "
                              "sampler; use EnsembleSampler for rng=%r)" % (rng,))
@@ -76,6 +76,7 @@ class EnsembleBatch(object):
         self.rng = rng
         self.device = 0 if device is None else int(device)
         self._tempered = bool(_tempered)      # PTSampler's handle: the only one that takes a PTFused
+        self._pt_ntemps = int(_ntemps)        # (its rungs an object: members of the handle = objects x rungs)
         self._targets, self._per_member = self._parse_targets(target)
         self._moves, self._weights = _parse_move_schedule(moves)
         self._descs = []
@@ -122,6 +123,10 @@ class EnsembleBatch(object):
                                 "compile the model as a BatchFused)")
             if target.ndim != self.ndim:
                 raise ValueError("the PTFused target was compiled for ndim %d; the sampler has ndim %d" % (target.ndim, self.ndim))
+            nobj = self.nbatch // self._pt_ntemps
+            if target.ndata is not None and not np.isscalar(target.ndata) and len(target.ndata) != nobj:
+                raise ValueError("the PTFused target's ndata holds one count an object: nbatch = %d integers (or one for all); got %d"
+                                 % (nobj, len(target.ndata)))
         if isinstance(target, BatchTarget):
             return [target], False
         if isinstance(target, DeviceFused):
@@ -248,7 +253,13 @@ class EnsembleBatch(object):
         t = self._targets[0]
         fn = t.fn_ptr if isinstance(t.fn_ptr, _lib.PT_FUSED_FN) else C.cast(t.fn_ptr, _lib.PT_FUSED_FN)
         self._cb_keep = (fn, t)
-        self._ck(self._lib().emx_pt_set_target_fused(h, fn, t.ndim, C.c_void_p(t.user_address())))
+        if t.ndata is not None:           # a data target: one count an object, every rung of an object its object's
+            T = self._pt_ntemps
+            counts = np.broadcast_to(np.asarray(t.ndata, dtype=np.int64), (self.nbatch // T,))
+            counts = np.ascontiguousarray(np.repeat(counts, T))
+            self._ck(self._lib().emx_pt_set_target_fused_data(h, fn, t.ndim, C.c_void_p(t.user_address()), counts))
+        else:
+            self._ck(self._lib().emx_pt_set_target_fused(h, fn, t.ndim, C.c_void_p(t.user_address())))
 
     def set_tuning(self, key, value):
         """``"batch_threads"`` / ``"batch_plan_steps"`` (include/emx.h): the launch shape; ``"batch_acf_series"``: series per

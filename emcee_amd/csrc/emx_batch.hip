@@ -25,6 +25,7 @@
 #include "emx_internal.hpp"
 #include "emx_pt.hpp"
 #include "emx_pt_fused.hpp"
+#include "emx_pt_fused_data.hpp"
 #include "emx_rng.hpp"
 #include "emx_small_host.hpp"
 #include "emx_small_launch.hpp"
@@ -113,6 +114,10 @@ struct emx_batch {
     emx_pt_fused_fn ptf_fn = nullptr;
     const void* ptf_user = nullptr;
     int32_t ptf_has_prior = 0;
+    // ... whose likelihood sums over the object's data (emx_pt_set_target_fused_data): the launcher carries k_pt_run's DATA form, and
+    // the library's device copy of the members' counts (B values)
+    bool ptf_data = false;
+    int64_t* ptf_ndata = nullptr;
 };
 
 namespace {
@@ -465,8 +470,13 @@ const char* pt_fused_refusal(int32_t T, int64_t N, int32_t D, int32_t nmoves, co
 }
 
 // what a fused tempered target's launcher answered, as the handle's error; 0: it launched (or probed)
-int pt_fused_launcher_refusal(emx_batch* b, int rc, int movesel) {
+int pt_fused_launcher_refusal(emx_batch* b, int rc, int movesel, bool data = false) {
     if (rc == 0) return 0;
+    if (rc == 1 && data)
+        return fail(b, -8, "the fused tempered data target's launcher was built against another version of emx_pt_fused_data.hpp, or is "
+                           "not an EMX_FUSED_PT_DATA_TARGET launcher (the library has EMX_FUSED_PT_DATA_ABI 0x%x and %zu bytes of kernel "
+                           "arguments): rebuild it with this library's headers",
+                    (unsigned)EMX_FUSED_PT_DATA_ABI, sizeof(PtRunArgs));
     if (rc == 1)
         return fail(b, -8, "the fused tempered target's launcher was built against another version of emx_pt_fused.hpp (the library has "
                            "EMX_FUSED_PT_ABI %u and %zu bytes of kernel arguments): rebuild it with this library's headers",
@@ -483,6 +493,7 @@ int pt_fused_launcher_refusal(emx_batch* b, int rc, int movesel) {
 // follows launch_shape's rule for the rows of one half-step of ALL rungs, plan steps for one entry a thread, shrunk to fit.
 int launch_pt(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t store, bool eval0) {
     BNEED(b, b->ptf_fn != nullptr, "fused tempered target without a launcher (emx_pt_set_target_fused)");
+    BNEED(b, !b->ptf_data || b->ptf_ndata != nullptr, "fused tempered data target without its counts (emx_pt_set_target_fused_data)");
     BNEED(b, b->pt_T > 0, "a fused tempered target runs on a tempered handle (emx_pt_set_tempering)");
     const int nm = (int)b->moves.size();
     const int32_t T = b->pt_T;
@@ -543,6 +554,7 @@ int launch_pt(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t
     a.time = b->pt_time;
     a.adapt_t0 = (long long)b->pt_updates;
     a.user = b->ptf_user;
+    a.ndata = b->ptf_data ? reinterpret_cast<const long long*>(b->ptf_ndata) : nullptr;
     if (any_gauss && nsteps > 0) {
         // the step-size factors and the sequential column: launch's host arithmetic
         std::vector<double> facs((size_t)b->B * nsteps, 1.0);
@@ -575,6 +587,7 @@ int launch_pt(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t
     const Shape sh = pick_shape(b->D, b->D);
     const int64_t rows = (int64_t)T * a.stage_rows;
     int threads = (int)std::min<int64_t>(PT_RUN_MAX_THREADS, std::max<int64_t>(64, (rows * sh.G + 63) / 64 * 64));
+    if (b->ptf_data) threads = (int)std::min<int64_t>(PT_RUN_MAX_THREADS, std::max<int64_t>(64, rows * 64));      // a wave a row
     int plan_steps = (int)std::max<int64_t>(1, std::min<int64_t>(64, threads / ((int64_t)T * b->N)));
     if (b->tune_threads > 0) threads = (int)b->tune_threads;
     if (b->tune_plan_steps > 0) plan_steps = (int)b->tune_plan_steps;
@@ -586,7 +599,7 @@ int launch_pt(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t
           "fused tempered launch shape: %d threads and %d plan steps need %zu bytes of LDS", threads, plan_steps, lds);
     const int movesel = (nm == 1 && b->moves[0].kind == EMX_MOVE_STRETCH) ? (int)EMX_MOVE_STRETCH : SMALL_ANY_MOVE;
     emx_pt_fused_launch fl{};
-    fl.abi = EMX_FUSED_PT_ABI;
+    fl.abi = b->ptf_data ? EMX_FUSED_PT_DATA_ABI : EMX_FUSED_PT_ABI;
     fl.args_bytes = (uint32_t)sizeof(PtRunArgs);
     fl.ndim = b->D;
     fl.movesel = movesel;
@@ -596,7 +609,7 @@ int launch_pt(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t
     fl.hip_stream = (void*)b->stream;
     fl.args = &a;
     fl.user = b->ptf_user;
-    if (int rc = pt_fused_launcher_refusal(b, b->ptf_fn(&fl), movesel)) return rc;
+    if (int rc = pt_fused_launcher_refusal(b, b->ptf_fn(&fl), movesel, b->ptf_data)) return rc;
     b->last_threads = threads;
     b->last_plan_steps = plan_steps;
     ++b->launches;
@@ -978,7 +991,7 @@ int emx_batch_destroy(emx_batch* b) {
                     (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi, (void*)b->cb_nrows, (void*)b->pt_beta,
                     (void*)b->pt_lo, (void*)b->pt_hi, (void*)b->pt_L, (void*)b->pt_P, (void*)b->chain_L, (void*)b->cb_pr, (void*)b->sw_att,
                     (void*)b->sw_acc, (void*)b->chain_beta, (void*)b->blobs, (void*)b->chain_blobs, (void*)b->cb_bq,
-                    (void*)b->fused_ndata})
+                    (void*)b->fused_ndata, (void*)b->ptf_ndata})
         if (p) hipFree(p);
     for (double* p : b->mscale)
         if (p) hipFree(p);
@@ -1231,6 +1244,47 @@ int emx_pt_set_target_fused(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compi
         }
     b->tp0_stride = b->tp1_stride = 0;
     b->ptf_fn = fn;
+    b->ptf_data = false;
+    b->ptf_user = user_dev;
+    b->ptf_has_prior = fl.has_prior ? 1 : 0;
+    b->target = EMX_TARGET_FUSED_PT;
+    b->Dp = b->D;
+    return 0;
+}
+
+int emx_pt_set_target_fused_data(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compiled, const void* user_dev, const int64_t* ndata_host) {
+    BNEED(b, fn != nullptr, "emx_pt_set_target_fused_data: no launcher");
+    BNEED(b, ndata_host != nullptr, "emx_pt_set_target_fused_data: no data counts (one value a member of the handle)");
+    BNEED(b, ndim_compiled == b->D, "the fused tempered target was compiled for ndim %d; the batch has ndim %d", ndim_compiled, b->D);
+    BNEED(b, b->pt_T == 0, "emx_pt_set_target_fused_data comes before emx_pt_set_tempering");
+    for (int32_t m = 0; m < b->B; ++m)
+        BNEED(b, ndata_host[m] >= 0 && ndata_host[m] < ((int64_t)1 << 31),
+              "emx_pt_set_target_fused_data: 0 <= ndata < 2^31 for every member; member %d has %lld", m, (long long)ndata_host[m]);
+    if (!b->moves.empty()) {
+        char buf[256];
+        const char* why = shape_refusal(b->N, b->D, EMX_TARGET_FUSED_PT, (int32_t)b->moves.size(), b->moves.data(), buf, sizeof buf);
+        BNEED(b, !why, "%s", why);
+    }
+    // the probe with the data ABI: a plain EMX_FUSED_PT_TARGET launcher answers 1; nothing is launched
+    emx_pt_fused_launch fl{};
+    fl.abi = EMX_FUSED_PT_DATA_ABI;
+    fl.args_bytes = (uint32_t)sizeof(PtRunArgs);
+    fl.ndim = b->D;
+    fl.movesel = MOVE_STRETCH;
+    if (int rc = pt_fused_launcher_refusal(b, fn(&fl), fl.movesel, true)) return rc;
+    BHIP(b, hipSetDevice(b->device));
+    if (int rc = set_blobs(b, 0)) return rc;
+    BHIP(b, hipStreamSynchronize(b->stream));
+    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
+        if (*p) {
+            hipFree(*p);
+            *p = nullptr;
+        }
+    b->tp0_stride = b->tp1_stride = 0;
+    if (!b->ptf_ndata) BHIP(b, hipMalloc((void**)&b->ptf_ndata, (size_t)b->B * sizeof(int64_t)));
+    BHIP(b, hipMemcpy(b->ptf_ndata, ndata_host, (size_t)b->B * sizeof(int64_t), hipMemcpyHostToDevice));
+    b->ptf_fn = fn;
+    b->ptf_data = true;
     b->ptf_user = user_dev;
     b->ptf_has_prior = fl.has_prior ? 1 : 0;
     b->target = EMX_TARGET_FUSED_PT;

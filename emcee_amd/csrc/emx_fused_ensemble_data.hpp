@@ -37,7 +37,8 @@
 // TILE stays the compile-time upper bound of the rows a workgroup takes (the register arrays of phase 1); the rows it actually
 // takes are a run-time argument, 4 ... TILE, so that a mid-size ensemble spreads over the chip (fused_ens_data_rows_rule;
 // profiles/ensemble_fused_data.md); passes of phase 1 / 3 without a live row are skipped by a workgroup-uniform branch.
-// Out of scope: blobs, the one-workgroup small form, PTSampler, several GPUs.  (A batch's data targets: emx_fused_target_data.hpp.)
+// Out of scope: blobs, the one-workgroup small form, several GPUs.  (A batch's data targets: emx_fused_target_data.hpp; PTSampler's:
+// emx_pt_fused_data.hpp.)
 #pragma once
 #include "emx_fused_ensemble.hpp"
 

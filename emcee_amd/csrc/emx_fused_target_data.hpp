@@ -36,7 +36,7 @@
 // lane 0 calls base, all 64 lanes stride over the member's data, the reduction runs with the whole wave active outside any
 // lane-divergent region, lane 0 takes the decision and the wave commits the row with all its lanes.  The initial log-probs take the
 // same form over every walker.  Both move selectors are carried (a single StretchMove; any schedule), Philox plans only.
-// Out of scope: blobs, PTSampler, the single sampler's one-workgroup form.
+// Out of scope: blobs, the single sampler's one-workgroup form.  (PTSampler's data targets: emx_pt_fused_data.hpp.)
 #pragma once
 #include <type_traits>
 #include <utility>

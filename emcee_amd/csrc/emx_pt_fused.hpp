@@ -23,6 +23,11 @@
 // proposal with small_propose into its staging row; pass 2 (one lane a row) is prior, likelihood, k_batch_cb<..., TEMPERED>'s
 // decision and the commit.  The swap pass is k_pt_swap's on LDS, its draws made by every lane before the step's half-steps (they do
 // not depend on the state), the pair chain itself nothing but LDS reads, writes and one barrier a pair.
+//
+// DATA form (emx_pt_fused_data.hpp: EMX_FUSED_PT_DATA_TARGET): LIKE is a model with base and term members whose likelihood sums over
+// the object's data, and pass 2 -- and the initial state -- give every row a WAVE where the plain form gives it a lane: lane 0
+// evaluates the prior, fused_data_value (emx_kernels.hpp) the likelihood with the 64 lanes striding over the data, lane 0 takes the
+// decision and the wave commits the row.  Pass 1, the plans, the swap pass, the ladder update and the chain append are the text above.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,7 +39,7 @@
 
 // bumped with ANY change of PtRunArgs or of k_pt_run's LDS layout: a launcher and a library of different values refuse each other
 #ifndef EMX_FUSED_PT_ABI
-#define EMX_FUSED_PT_ABI 1u
+#define EMX_FUSED_PT_ABI 2u
 #endif
 
 namespace emx {
@@ -72,6 +77,7 @@ struct PtRunArgs {
     double lag, time;
     long long adapt_t0;                          // the update counter t before this launch's first pass
     const void* user;
+    const long long* ndata;                      // DATA form: the data count of every member (B); nullptr for a plain target
 };
 
 // the LDS map of one object, in bytes from the start of dynamic LDS (host and device: one definition)
@@ -141,7 +147,38 @@ __device__ __forceinline__ bool pt_row_eval(const double* x, int D, int member, 
     return (!pinf && lraw != lraw) || lpn != lpn;
 }
 
-template <int G, int V, int CH, int MOVESEL, typename LIKE, typename PRIOR>
+// the DATA form's prior and untempered likelihood of one row, by a WHOLE wave (every lane active; `bad`, the same in every lane: the
+// row reaches neither prior nor model): lane 0 evaluates the prior -- pt_row_eval's -- and every lane gets it; where it is finite the
+// likelihood is fused_data_value's (emx_fused_target_data.hpp, "THE VALUE").  -> pinf (the same in every lane): the row is outside
+// the prior, or bad
+template <typename MODEL, typename PRIOR>
+__device__ __forceinline__ bool pt_row_eval_data(const double* x, int D, int member, const void* user, long long ndata, const double* lo,
+                                                 const double* hi, bool box, bool bad, int lane, double& pq, double& lraw) {
+    double p = -__builtin_inf();
+    if (lane == 0 && !bad) {
+        if constexpr (!std::is_same<PRIOR, NoFusedPrior>::value) {
+            p = PRIOR{}(x, D, member, user);
+        } else {
+            bool in = true;
+            if (box)
+                for (int d = 0; d < D; ++d) in = in && x[d] >= lo[d] && x[d] <= hi[d];
+            p = in ? 0.0 : -__builtin_inf();
+        }
+    }
+    pq = wave_first(p);
+    const bool pinf = bad || pq == -__builtin_inf();
+    lraw = fused_data_value<MODEL>(x, D, member, user, ndata, pinf, lane);      // (the model of a row outside the prior is not called)
+    return pinf;
+}
+
+// the rest of pt_row_eval's rule from those two values (lane 0).  -> the NaN status
+__device__ __forceinline__ bool pt_row_finish(bool pinf, double pq, double lraw, double beta, double& lq, double& lpn) {
+    lq = pinf ? -__builtin_inf() : lraw;
+    lpn = pt_tempered(beta, lq, pq);
+    return (!pinf && lraw != lraw) || lpn != lpn;
+}
+
+template <int G, int V, int CH, int MOVESEL, typename LIKE, typename PRIOR, bool DATA = false>
 static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRunArgs A) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int WPW = 64 / G;
@@ -200,6 +237,21 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
     __syncthreads();
     if (A.eval0) {
         // the initial state (k_pt_init's rule), every walker's own row through the functors
+        if constexpr (DATA) {
+            for (int r = __builtin_amdgcn_readfirstlane(wv); r < TN; r += nwave) {      // wave-uniform: a wave a walker's own row
+                const int t = r / N;
+                double pq, lraw;
+                const bool pinf = pt_row_eval_data<LIKE, PRIOR>(Xs + (size_t)r * D, D, (int)(m0 + t), A.user, A.ndata[m0 + t], loS, hiS, box,
+                                                                false, lane, pq, lraw);
+                if (lane == 0) {
+                    double lq, lpn;
+                    if (pt_row_finish(pinf, pq, lraw, betaS[t], lq, lpn)) raise_status(A.status + (m0 + t) * SMALL_STATUS_WORDS, ST_NAN_LOGP);
+                    Ps[r] = pq;
+                    Ls[r] = lq;
+                    lps[r] = lpn;
+                }
+            }
+        } else
         for (int r = tid; r < TN; r += NT) {
             const int t = r / N;
             double pq, lq, lpn;
@@ -315,6 +367,44 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
                     }
                 }
                 __syncthreads();
+                if constexpr (DATA) {
+                    // pass 2, a wave a row -- the prior by lane 0, the model over the object's data by the wave, the tempered
+                    // decision by lane 0, the commit by every lane; the values stored are the one-lane form's
+                    for (int r = __builtin_amdgcn_readfirstlane(wv); r < TR; r += nwave) {      // wave-uniform, as every skip below
+                        const int t = r / R, slot = c0 + (r - t * R);
+                        const int m = mvs[b * T + t];
+                        const int kind = MOVESEL == SMALL_ANY_MOVE ? A.kind[m] : MOVESEL;
+                        const int S = kind == MOVE_GAUSS ? 1 : A.nsplits[m];
+                        if (k >= S) continue;
+                        const SplitSizes sz = split_sizes(N, S);
+                        const int ns = sz.of(k), pos0 = k * sz.q + min(k, sz.r);
+                        if (slot >= ns) continue;
+                        const int pos = (b * T + t) * N + pos0 + slot;
+                        const int w = t * N + orders[pos];
+                        const double* qrow = stage + (size_t)r * DS;
+                        const double fac = sfac[r];                                 // the same value in every lane
+                        const bool bad = fac == -__builtin_inf();                   // (-inf: as below)
+                        double pq, lraw, lq = 0.0, lpn = 0.0;
+                        const bool pinf = pt_row_eval_data<LIKE, PRIOR>(qrow, D, (int)(m0 + t), A.user, A.ndata[m0 + t], loS, hiS, box, bad,
+                                                                        lane, pq, lraw);
+                        int acc = 0;
+                        if (lane == 0 && !bad) {
+                            if (pt_row_finish(pinf, pq, lraw, betaS[t], lq, lpn)) raise_status(A.status + (m0 + t) * SMALL_STATUS_WORDS, ST_NAN_LOGP);
+                            const double lnpdiff = fac + lpn - lps[w];
+                            acc = lnpdiff > logus[pos] ? 1 : 0;
+                        }
+                        const bool accept = __builtin_amdgcn_readfirstlane(acc) != 0;
+                        if (accept) {
+                            for (int d = lane; d < D; d += 64) Xs[(size_t)w * D + d] = qrow[d];
+                            if (lane == 0) {
+                                lps[w] = lpn;
+                                Ls[w] = lq;
+                                Ps[w] = pq;
+                            }
+                        }
+                        if (lane == 0) accs[w] = accept ? 1 : 0;
+                    }
+                } else
                 // pass 2: one lane a row -- prior, likelihood, the tempered decision, the commit
                 for (int r = tid; r < TR; r += NT) {
                     const int t = r / R, slot = c0 + (r - t * R);
@@ -432,10 +522,10 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
         }
 }
 
-template <typename LIKE, typename PRIOR, int NDIM, int MOVESEL>
+template <typename LIKE, typename PRIOR, int NDIM, int MOVESEL, bool DATA = false>
 hipError_t launch_pt_move(int grid, int threads, size_t lds, hipStream_t st, const PtRunArgs& a) {
     constexpr int G = fused_g(NDIM), V = fused_v(NDIM), CH = fused_ch(NDIM);
-    auto kern = k_pt_run<G, V, CH, MOVESEL, LIKE, PRIOR>;
+    auto kern = k_pt_run<G, V, CH, MOVESEL, LIKE, PRIOR, DATA>;
     static size_t lds_granted[MAX_DEVICES] = {};      // as launch_small_move: function attributes are per device
     int dev = 0;
     if (lds > 48 * 1024 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MAX_DEVICES && lds > lds_granted[dev]) {

@@ -11,6 +11,7 @@ object: all its rungs in LDS, the half-steps of every rung side by side, the swa
 barriers, ONE launch per ``run_mcmc`` chunk of up to 4 096 steps.  Everything below holds unchanged, and the run is bit for bit the
 ``BatchKernel`` run of the same functions (while no proposal has a non-finite coordinate: the fused form rejects such a row without
 calling a functor).  An object must fit one workgroup's LDS (``emx_pt_fused_check``); larger ones keep the callback path.
+A ``PTFused(..., ndata=)`` likelihood (``compile_fused_pt(..., data=True)``) sums over the object's data with a wave a row.
 
 Tempered log-probability.  ``lp = beta * L + P`` as two separate IEEE operations (no contraction).  At ``beta == 0``,
 ``lp = P``, so ``0 * -inf`` never occurs.  Where ``P == -inf`` the row's ``L`` is ignored (NaN included) and kept as ``-inf``.
@@ -213,7 +214,7 @@ class PTSampler(object):
         self.member_seeds = np.stack([np.random.RandomState(s).randint(0, 2 ** 32, size=self.ntemps, dtype=np.uint64)
                                       for s in seeds])
         self._b = EnsembleBatch(self.nbatch * self.ntemps, self.nwalkers, self.ndim, self._wrap(log_likelihood), moves=moves,
-                                seeds=self.member_seeds.reshape(-1), device=device, _tempered=True)
+                                seeds=self.member_seeds.reshape(-1), device=device, _tempered=True, _ntemps=self.ntemps)
         self._fused = log_likelihood if fused else None
         if fused:           # an object must fit one workgroup's LDS: refused here, before any device is touched
             msg = C.create_string_buffer(512)

@@ -412,9 +412,23 @@ class PTFused(BatchTarget):
 
     One workgroup then runs one object -- all its rungs, the swap pass and the ladder adaptation -- in LDS: one launch per
     ``run_mcmc`` chunk, bit for bit the :class:`BatchKernel` run of the same functions.  :func:`compile_fused_pt` builds such a
-    launcher from source.  A likelihood of :class:`~emcee_amd.PTSampler` only."""
+    launcher from source.  A likelihood of :class:`~emcee_amd.PTSampler` only.
 
-    def __init__(self, fn_ptr, ndim, user=None, has_prior=None):
+    ``ndata`` (an integer for every object, or a sequence / array of ``nbatch`` integers, one count an object, each ``0 <= ndata <
+    2**31``; None: the plain target above): the log-likelihood sums over the object's data, ``base(x) + sum_k term(x; datum k)``, and
+    ``fn_ptr`` is the launcher that ``EMX_FUSED_PT_DATA_TARGET(name, Model, PriorFunctor, ndim)`` of ``emx_pt_fused_data.hpp`` emits
+    around a model with ``base(x, ndim, member, user)`` and ``term(x, ndim, member, k, user)`` members (:class:`BatchFused`'s data
+    contract).  Every rung of an object sees the object's data.  The tempered kernel then gives every proposal a WAVE for the data sum
+    -- one lane evaluates the prior and ``base``, 64 lanes stride over the data, a fixed pairwise tree adds the lane partials, the
+    wave commits the row -- where the plain functor loops over the data in one of the ``ntemps x rows`` lanes the second pass keeps
+    busy.  The value of a row is the one ``emx_fused_target_data.hpp`` defines, reproduced on the host by :func:`fused_data_sum`; a
+    row outside the prior does not reach the model; the run is bit for bit the plain :class:`PTFused` run of a one-lane functor that
+    computes the same value.  A length other than ``nbatch`` is refused when the sampler takes the target.  Nothing chooses between
+    the two forms for the user.  Where it pays, measured on a straight-line fit against the one-lane, one-accumulator functor
+    (``profiles/pt_fused_data.md``): at 8 rungs of 32 x 5 from about 1 024 data an object (2.0 times the speed there, 2.6 to 2.8
+    times at 4 096; 3.4 times SLOWER at 16 data, 12 to 15 % slower at 256); at 8 rungs of 64 x 16 only at 4 096 (1.5 times)."""
+
+    def __init__(self, fn_ptr, ndim, user=None, has_prior=None, ndata=None):
         if not isinstance(fn_ptr, ctypes._CFuncPtr):
             addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
             if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
@@ -427,6 +441,11 @@ class PTFused(BatchTarget):
             raise TypeError("PTFused's user tensor must live on the GPU (the functors read it on the device)")
         self.fn_ptr, self.ndim, self.user = fn_ptr, int(ndim), user
         self.has_prior = None if has_prior is None else bool(has_prior)
+        if ndata is None or isinstance(ndata, (bool, int, float, np.generic)):
+            self.ndata = _check_ndata("PTFused", ndata)
+        else:                             # one count an object: _check_ndata's rule for every entry
+            self.ndata = tuple(_check_ndata("PTFused", n) for n in (ndata.tolist() if isinstance(ndata, np.ndarray) and ndata.dtype == object
+                                                                    else list(ndata)))
 
     user_address = BatchFused.user_address
 
@@ -577,29 +596,40 @@ def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir
 
 class PTFusedLibrary(object):
     """What :func:`compile_fused_pt` built: ``path``, ``lib`` (its ``ctypes.CDLL``), ``name`` of the launcher, ``ndim``,
-    ``has_prior``, and :meth:`target`."""
+    ``has_prior``, ``data`` (the launcher is an ``EMX_FUSED_PT_DATA_TARGET`` one) and :meth:`target`."""
 
-    def __init__(self, path, name, ndim, has_prior):
+    def __init__(self, path, name, ndim, has_prior, data=False):
         self.path, self.name, self.ndim, self.has_prior = path, name, int(ndim), bool(has_prior)
+        self.data = bool(data)            # target() takes the objects' data counts
         _lib.load()                       # one HIP runtime per process: the library's (torch's) first
         self.lib = ctypes.CDLL(path)
         self.launcher = getattr(self.lib, name)
 
-    def target(self, user=None):
-        """-> :class:`PTFused` of the compiled functors with the device pointer ``user``"""
-        t = PTFused(self.launcher, self.ndim, user, has_prior=self.has_prior)
+    def target(self, user=None, ndata=None):
+        """-> :class:`PTFused` of the compiled functors with the device pointer ``user``; a library built with ``data=True``
+        needs ``ndata`` -- the data every object's ``term`` runs over, an integer or ``nbatch`` of them -- and any other refuses it"""
+        if self.data and ndata is None:
+            raise ValueError("PTFusedLibrary.target: the library was built with data=True; give ndata, the objects' numbers of data")
+        if not self.data and ndata is not None:
+            raise ValueError("PTFusedLibrary.target: ndata is for a library built with compile_fused_pt(..., data=True)")
+        t = PTFused(self.launcher, self.ndim, user, has_prior=self.has_prior, ndata=ndata)
         t._library = self                 # the launcher's code lives as long as the target
         return t
 
 
-def compile_fused_pt(source, likelihood, ndim, prior=None, name=None, flags=(), cache_dir=None):
+def compile_fused_pt(source, likelihood, ndim, prior=None, name=None, flags=(), cache_dir=None, data=False):
     """Compile the user's model into the tempered kernel -> :class:`PTFusedLibrary`.
 
     ``source``: HIP C++ that defines the functor type ``likelihood`` and, unless ``prior`` is None, the functor type ``prior`` (both
     ``__device__ double operator()(const double* x, int ndim, int member, const void* user) const``).  The translation unit is
     ``#include <emx_pt_fused.hpp>``, ``source`` and ``EMX_FUSED_PT_TARGET(name, likelihood, prior or emx::NoFusedPrior, ndim)``,
     compiled and cached as :func:`compile_fused` does (the same flags; the key is the hash of source, both names, ndim, name, flags
-    and every header of the library); a compiler failure raises ``RuntimeError`` with the compiler's last lines."""
+    and every header of the library); a compiler failure raises ``RuntimeError`` with the compiler's last lines.
+
+    ``data=True``: ``likelihood`` is a model with ``base(x, ndim, member, user)`` and ``term(x, ndim, member, k, user)`` members whose
+    log-likelihood sums over the object's data (:class:`PTFused`'s ``ndata``); ``prior`` is what it is above.  The translation unit
+    is ``#include <emx_pt_fused_data.hpp>``, ``source`` and ``EMX_FUSED_PT_DATA_TARGET(name, likelihood, prior or emx::NoFusedPrior,
+    ndim)``.  ``data=False`` keeps the translation unit and the cache key it always had."""
     ndim = int(ndim)
     if ndim < 1 or ndim > 256:
         raise ValueError("compile_fused_pt: 1 <= ndim <= 256; got %d" % ndim)
@@ -608,9 +638,13 @@ def compile_fused_pt(source, likelihood, ndim, prior=None, name=None, flags=(), 
             raise ValueError("compile_fused_pt: %s must be a C++ identifier; got %r" % (what, ident))
     name = name or "emx_pt_fused_%s_%d" % (likelihood.replace(":", "_"), ndim)
     flags = [str(f) for f in flags]
+    key = ("pt", source, likelihood, prior, ndim, name)
+    if data:                              # (a plain build keeps the key, and with it the cached library, it always had)
+        tail = "EMX_FUSED_PT_DATA_TARGET(%s, %s, %s, %d)" % (name, likelihood, prior or "emx::NoFusedPrior", ndim)
+        so = _compile_cached("compile_fused_pt", "emx_pt_fused_data.hpp", source, tail, key + ("data target",), name, flags, cache_dir)
+        return PTFusedLibrary(so, name, ndim, prior is not None, data=True)
     tail = "EMX_FUSED_PT_TARGET(%s, %s, %s, %d)" % (name, likelihood, prior or "emx::NoFusedPrior", ndim)
-    so = _compile_cached("compile_fused_pt", "emx_pt_fused.hpp", source, tail, ("pt", source, likelihood, prior, ndim, name), name, flags,
-                         cache_dir)
+    so = _compile_cached("compile_fused_pt", "emx_pt_fused.hpp", source, tail, key, name, flags, cache_dir)
     return PTFusedLibrary(so, name, ndim, prior is not None)
 
 

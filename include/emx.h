@@ -976,6 +976,22 @@ typedef struct emx_pt_fused_launch {
 } emx_pt_fused_launch;
 typedef int (*emx_pt_fused_fn)(emx_pt_fused_launch*);     /* 0, or non-zero and nothing launched */
 int emx_pt_set_target_fused(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compiled, const void* user_dev);
+/* ... whose log-likelihood SUMS OVER AN OBJECT'S DATA (emcee_amd.targets.PTFused(..., ndata=) / compile_fused_pt(..., data=True)):
+ * log L(x) = base(x) + sum_k term(x; datum k).  The caller's translation unit includes emcee_amd/csrc/emx_pt_fused_data.hpp and emits
+ * the launcher with EMX_FUSED_PT_DATA_TARGET(name, Model, PriorFunctor, ndim) around a model with base(x, ndim, member, user) and
+ * term(x, ndim, member, k, user) members (emx_set_batch_target_fused_data's contract; member = object * ntemps + rung); the prior is
+ * emx_pt_set_target_fused's.  k_pt_run's second pass and the initial state then give every row a WAVE: lane 0 evaluates the prior and
+ * base, 64 lanes stride over the member's data, a fixed pairwise tree adds the lane partials, lane 0 takes the tempered decision and
+ * the wave commits the row.  The value of a row is defined by emx_fused_target_data.hpp ("THE VALUE";
+ * emcee_amd.targets.fused_data_sum on the host) and depends on no launch shape; a row outside the prior does not reach the model.
+ * The launcher type and the descriptor are emx_pt_set_target_fused's with EMX_FUSED_PT_DATA_ABI in `abi` (a value of its own: a plain
+ * launcher handed to this setter, and a data launcher handed to emx_pt_set_target_fused, are refused with -8) and the same answers.
+ * `ndata_host` holds one count a member of the handle (nbatch values of emx_batch_create: object-major, every rung of an object
+ * its object's count), each in [0, 2^31) -- else -1 and a message naming the member -- and is copied to the device.  Comes before
+ * emx_pt_set_tempering; emx_pt_fused_check is unchanged (the data form needs no LDS of its own).  The default launch shape is a wave
+ * a row of one half-step of all rungs (at most 512 threads); "batch_threads" and "batch_plan_steps" apply and change no bit. */
+int emx_pt_set_target_fused_data(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compiled, const void* user_dev,
+                                 const int64_t* ndata_host);
 /* host only (no device touched): 0 when one workgroup's LDS holds an object of ntemps rungs of (nwalkers, ndim) under this
  * schedule with at least one plan step, else -1 and the reason (with the bytes needed) in msg */
 int emx_pt_fused_check(int32_t ntemps, int64_t nwalkers, int32_t ndim, int32_t nmoves, const emx_move_desc* moves, char* msg,
