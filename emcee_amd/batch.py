@@ -114,19 +114,15 @@ class EnsembleBatch(object):
     def _parse_targets(self, target):
         if isinstance(target, BatchFused) and target.ndim != self.ndim:
             raise ValueError("the BatchFused target was compiled for ndim %d; the batch has ndim %d" % (target.ndim, self.ndim))
-        if isinstance(target, BatchFused) and target.ndata is not None and not np.isscalar(target.ndata) and len(target.ndata) != self.nbatch:
-            raise ValueError("the BatchFused target's ndata holds one count a member: nbatch = %d integers (or one for all); got %d"
-                             % (self.nbatch, len(target.ndata)))
+        if isinstance(target, BatchFused):
+            self._check_counts_length("BatchFused", target.ndata, self.nbatch, "a member")
         if isinstance(target, PTFused):
             if not self._tempered:
                 raise TypeError("a PTFused is a likelihood of PTSampler: its launcher carries the tempered kernel (for an EnsembleBatch "
                                 "compile the model as a BatchFused)")
             if target.ndim != self.ndim:
                 raise ValueError("the PTFused target was compiled for ndim %d; the sampler has ndim %d" % (target.ndim, self.ndim))
-            nobj = self.nbatch // self._pt_ntemps
-            if target.ndata is not None and not np.isscalar(target.ndata) and len(target.ndata) != nobj:
-                raise ValueError("the PTFused target's ndata holds one count an object: nbatch = %d integers (or one for all); got %d"
-                                 % (nobj, len(target.ndata)))
+            self._check_counts_length("PTFused", target.ndata, self.nbatch // self._pt_ntemps, "an object")
         if isinstance(target, BatchTarget):
             return [target], False
         if isinstance(target, DeviceFused):
@@ -152,6 +148,11 @@ class EnsembleBatch(object):
             if t.ndim is not None and t.ndim != self.ndim:
                 raise ValueError("member %d: target of ndim %d in a batch of ndim %d" % (b, t.ndim, self.ndim))
         return targets, per_member
+
+    @staticmethod
+    def _check_counts_length(who, ndata, n, each):      # a fused data target's counts: None, one for all, or n (one `each`)
+        if ndata is not None and not np.isscalar(ndata) and len(ndata) != n:
+            raise ValueError("the %s target's ndata holds one count %s: nbatch = %d integers (or one for all); got %d" % (who, each, n, len(ndata)))
 
     def _check_state(self, coords):
         coords = np.asarray(coords)
@@ -235,31 +236,30 @@ class EnsembleBatch(object):
         else:
             self._ck(self._lib().emx_set_batch_target_callback(h, fn, user))
 
-    def _bind_user_fused(self, h):
+    def _bind_fused_target(self, h, ftype, setter, *extra, counts=None, repeat=1):
+        """``setter(h, fn, ndim, user, *extra)``, `extra` the counts of a data target: ``counts``, one for all or one each, each ``repeat`` times"""
         t = self._targets[0]
-        fn = t.fn_ptr if isinstance(t.fn_ptr, _lib.FUSED_BATCH_FN) else C.cast(t.fn_ptr, _lib.FUSED_BATCH_FN)
+        fn = t.fn_ptr if isinstance(t.fn_ptr, ftype) else C.cast(t.fn_ptr, ftype)
         self._cb_keep = (fn, t)           # the library holds the launcher and the user's device pointer: keep both alive
+        if counts is not None:
+            extra = (np.ascontiguousarray(np.repeat(np.broadcast_to(np.asarray(counts, dtype=np.int64), (self.nbatch // repeat,)), repeat)),)
+        self._ck(setter(h, fn, t.ndim, C.c_void_p(t.user_address()), *extra))
+
+    def _bind_user_fused(self, h):
+        t, lib = self._targets[0], self._lib()
         if t.ndata is not None:           # a data target: its own launcher type, and the members' counts
-            fn = t.fn_ptr if isinstance(t.fn_ptr, _lib.FUSED_BATCH_DATA_FN) else C.cast(t.fn_ptr, _lib.FUSED_BATCH_DATA_FN)
-            self._cb_keep = (fn, t)
-            counts = np.ascontiguousarray(np.broadcast_to(np.asarray(t.ndata, dtype=np.int64), (self.nbatch,)))
-            self._ck(self._lib().emx_set_batch_target_fused_data(h, fn, t.ndim, C.c_void_p(t.user_address()), counts))
+            self._bind_fused_target(h, _lib.FUSED_BATCH_DATA_FN, lib.emx_set_batch_target_fused_data, counts=t.ndata)
         elif self.nblobs:
-            self._ck(self._lib().emx_set_batch_target_fused_blobs(h, fn, t.ndim, C.c_void_p(t.user_address()), self.nblobs))
+            self._bind_fused_target(h, _lib.FUSED_BATCH_FN, lib.emx_set_batch_target_fused_blobs, self.nblobs)
         else:
-            self._ck(self._lib().emx_set_batch_target_fused(h, fn, t.ndim, C.c_void_p(t.user_address())))
+            self._bind_fused_target(h, _lib.FUSED_BATCH_FN, lib.emx_set_batch_target_fused)
 
     def _bind_pt_fused(self, h):
-        t = self._targets[0]
-        fn = t.fn_ptr if isinstance(t.fn_ptr, _lib.PT_FUSED_FN) else C.cast(t.fn_ptr, _lib.PT_FUSED_FN)
-        self._cb_keep = (fn, t)
+        t, lib = self._targets[0], self._lib()
         if t.ndata is not None:           # a data target: one count an object, every rung of an object its object's
-            T = self._pt_ntemps
-            counts = np.broadcast_to(np.asarray(t.ndata, dtype=np.int64), (self.nbatch // T,))
-            counts = np.ascontiguousarray(np.repeat(counts, T))
-            self._ck(self._lib().emx_pt_set_target_fused_data(h, fn, t.ndim, C.c_void_p(t.user_address()), counts))
+            self._bind_fused_target(h, _lib.PT_FUSED_FN, lib.emx_pt_set_target_fused_data, counts=t.ndata, repeat=self._pt_ntemps)
         else:
-            self._ck(self._lib().emx_pt_set_target_fused(h, fn, t.ndim, C.c_void_p(t.user_address())))
+            self._bind_fused_target(h, _lib.PT_FUSED_FN, lib.emx_pt_set_target_fused)
 
     def set_tuning(self, key, value):
         """``"batch_threads"`` / ``"batch_plan_steps"`` (include/emx.h): the launch shape; ``"batch_acf_series"``: series per

@@ -257,8 +257,28 @@ void launch_shape(const emx_batch* b, int num_cu, const Shape& sh, int minsplits
     *plan_steps = ps;
 }
 
-// what a fused user target's launcher answered (include/emx.h: emx_fused_batch_fn), as the handle's error; 0: it launched (or probed)
-int fused_refusal(emx_batch* b, int rc, int movesel, bool data = false) {
+// the fields the three fused descriptors share (emx_fused_launch, emx_fused_batch_data_launch, emx_pt_fused_launch).  grid 0: the
+// setters' probe, which carries no launch shape, stream or user pointer
+template <typename DESC>
+DESC fused_desc(const emx_batch* b, uint32_t abi, size_t args_bytes, int movesel, const void* args, int grid = 0, int threads = 0, size_t lds = 0,
+                const void* user = nullptr) {
+    DESC fl{};
+    fl.abi = abi;
+    fl.args_bytes = (uint32_t)args_bytes;
+    fl.ndim = b->D;
+    fl.movesel = movesel;
+    fl.grid = grid;
+    fl.threads = threads;
+    fl.lds_bytes = lds;
+    fl.hip_stream = grid ? (void*)b->stream : nullptr;
+    fl.args = args;
+    fl.user = user;
+    return fl;
+}
+
+// what a fused user target's launcher answered (include/emx.h: emx_fused_batch_fn), as the handle's error; 0: it launched (or probed).
+// nblobs: the count that answer 4 is about
+int fused_refusal(emx_batch* b, int rc, int movesel, int nblobs, bool data = false) {
     if (rc == 0) return 0;
     if (rc == 1 && data)
         return fail(b, -8, "the fused user target's launcher was built against another version of emx_fused_target_data.hpp (the library "
@@ -271,7 +291,7 @@ int fused_refusal(emx_batch* b, int rc, int movesel, bool data = false) {
     if (rc == 2) return fail(b, -1, "the fused user target's launcher was compiled for another ndim than the batch's %d", b->D);
     if (rc == 4)
         return fail(b, -1, "the fused user target's launcher was compiled for another number of blobs than the %d asked for "
-                           "(EMX_FUSED_BATCH_TARGET_BLOBS's nblobs; EMX_FUSED_BATCH_TARGET has none)", b ? b->nblobs : 0);
+                           "(EMX_FUSED_BATCH_TARGET_BLOBS's nblobs; EMX_FUSED_BATCH_TARGET has none)", nblobs);
     if (rc == 3)
         return fail(b, -1, "the fused user target's launcher does not carry the kernel of this schedule (move selector %d): compile it with "
                            "EMX_FUSED_MOVES_ANY", movesel);
@@ -393,33 +413,13 @@ int launch(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t st
     // (a fused user target's translation unit carries the single-StretchMove selector and the any-schedule one)
     const int movesel = (nm == 1 && ((!dense && !fused_user) || b->moves[0].kind == EMX_MOVE_STRETCH)) ? (int)b->moves[0].kind : SMALL_ANY_MOVE;
     if (fused_data) {
-        emx_fused_batch_data_launch fl{};
-        fl.abi = EMX_FUSED_BATCH_DATA_ABI;
-        fl.args_bytes = (uint32_t)sizeof(SmallRunArgs);
-        fl.ndim = b->D;
-        fl.movesel = movesel;
-        fl.grid = b->B;
-        fl.threads = threads;
-        fl.lds_bytes = lds;
-        fl.hip_stream = (void*)b->stream;
-        fl.args = &a;
-        fl.user = b->fused_user;
+        auto fl = fused_desc<emx_fused_batch_data_launch>(b, EMX_FUSED_BATCH_DATA_ABI, sizeof(SmallRunArgs), movesel, &a, b->B, threads, lds, b->fused_user);
         fl.ndata = b->fused_ndata;
-        if (int rc = fused_refusal(b, b->fused_data_fn(&fl), movesel, true)) return rc;
+        if (int rc = fused_refusal(b, b->fused_data_fn(&fl), movesel, 0, true)) return rc;
     } else if (fused_user) {
-        emx_fused_launch fl{};
-        fl.abi = EMX_FUSED_ABI;
-        fl.args_bytes = (uint32_t)sizeof(SmallRunArgs);
-        fl.ndim = b->D;
-        fl.movesel = movesel;
-        fl.grid = b->B;
-        fl.threads = threads;
-        fl.lds_bytes = lds;
-        fl.hip_stream = (void*)b->stream;
-        fl.args = &a;
-        fl.user = b->fused_user;
+        auto fl = fused_desc<emx_fused_launch>(b, EMX_FUSED_ABI, sizeof(SmallRunArgs), movesel, &a, b->B, threads, lds, b->fused_user);
         fl.nblobs = b->nblobs;
-        if (int rc = fused_refusal(b, b->fused_fn(&fl), movesel)) return rc;
+        if (int rc = fused_refusal(b, b->fused_fn(&fl), movesel, b->nblobs)) return rc;
     } else {
         const hipError_t e = small_dispatch<true>(sh.G, sh.V, sh.CH, dense ? b->Dp / 16 : 0, movesel, b->B, threads, lds, b->stream, a);
         if (e != hipSuccess)
@@ -598,17 +598,8 @@ int launch_pt(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t
     BNEED(b, lds <= SMALL_LDS_MAX && threads >= 64 && threads % 64 == 0,
           "fused tempered launch shape: %d threads and %d plan steps need %zu bytes of LDS", threads, plan_steps, lds);
     const int movesel = (nm == 1 && b->moves[0].kind == EMX_MOVE_STRETCH) ? (int)EMX_MOVE_STRETCH : SMALL_ANY_MOVE;
-    emx_pt_fused_launch fl{};
-    fl.abi = b->ptf_data ? EMX_FUSED_PT_DATA_ABI : EMX_FUSED_PT_ABI;
-    fl.args_bytes = (uint32_t)sizeof(PtRunArgs);
-    fl.ndim = b->D;
-    fl.movesel = movesel;
-    fl.grid = b->B / T;
-    fl.threads = threads;
-    fl.lds_bytes = lds;
-    fl.hip_stream = (void*)b->stream;
-    fl.args = &a;
-    fl.user = b->ptf_user;
+    auto fl = fused_desc<emx_pt_fused_launch>(b, b->ptf_data ? EMX_FUSED_PT_DATA_ABI : EMX_FUSED_PT_ABI, sizeof(PtRunArgs), movesel, &a, b->B / T, threads,
+                                              lds, b->ptf_user);
     if (int rc = pt_fused_launcher_refusal(b, b->ptf_fn(&fl), movesel, b->ptf_data)) return rc;
     b->last_threads = threads;
     b->last_plan_steps = plan_steps;
@@ -900,6 +891,59 @@ int set_blobs(emx_batch* b, int32_t K) {
     return 0;
 }
 
+// the built-in target's parameter arrays go: every other target has none
+void drop_builtin_params(emx_batch* b) {
+    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
+        if (*p) {
+            hipFree(*p);
+            *p = nullptr;
+        }
+    b->tp0_stride = b->tp1_stride = 0;
+}
+
+// the settle step of every target setter: the handle takes `nblobs` blobs a sample, no kernel still reads the old target's
+// parameters, and they go
+int settle_target(emx_batch* b, int32_t nblobs) {
+    BHIP(b, hipSetDevice(b->device));
+    if (int rc = set_blobs(b, nblobs)) return rc;
+    BHIP(b, hipStreamSynchronize(b->stream));
+    drop_builtin_params(b);
+    return 0;
+}
+
+// the checks of the four fused setters ahead of the probe, in the order their callers rely on.  `who`: the setter, `kind`:
+// EMX_TARGET_FUSED_USER or EMX_TARGET_FUSED_PT, `data`: a setter that takes per-member counts (`ndata_host`)
+int fused_bind_checks(emx_batch* b, const char* who, int32_t kind, bool have_fn, int32_t ndim_compiled, bool data, const int64_t* ndata_host,
+                      int32_t nblobs = 0) {
+    const bool pt = kind == EMX_TARGET_FUSED_PT;
+    BNEED(b, have_fn, "%s: no launcher", who);
+    BNEED(b, !data || ndata_host != nullptr, "%s: no data counts (%s)", who, pt ? "one value a member of the handle" : "nbatch values");
+    BNEED(b, nblobs >= 0 && nblobs <= BATCH_MAX_BLOBS, "emx_set_batch_target_fused_blobs: 0 <= nblobs <= %d; got %d", BATCH_MAX_BLOBS, nblobs);
+    BNEED(b, ndim_compiled == b->D, "the fused %s target was compiled for ndim %d; the batch has ndim %d", pt ? "tempered" : "user", ndim_compiled,
+          b->D);
+    if (pt)
+        BNEED(b, b->pt_T == 0, "%s comes before emx_pt_set_tempering", who);
+    else
+        BNEED(b, b->pt_T == 0, "a tempered batch does not take a fused user target: the tempered commit and the swap pass belong to the "
+                               "batched callback path (emx_set_batch_target_callback)");
+    for (int32_t m = 0; data && m < b->B; ++m)
+        BNEED(b, ndata_host[m] >= 0 && ndata_host[m] < ((int64_t)1 << 31), "%s: 0 <= ndata < 2^31 for every member; member %d has %lld", who, m,
+              (long long)ndata_host[m]);
+    if (!b->moves.empty()) {
+        char buf[256];
+        const char* why = shape_refusal(b->N, b->D, kind, (int32_t)b->moves.size(), b->moves.data(), buf, sizeof buf, nblobs);
+        BNEED(b, !why, "%s", why);
+    }
+    return 0;
+}
+
+// the per-member data counts of a fused data target, on the device
+int upload_counts(emx_batch* b, int64_t** dev, const int64_t* ndata_host) {
+    if (!*dev) BHIP(b, hipMalloc((void**)dev, (size_t)b->B * sizeof(int64_t)));
+    BHIP(b, hipMemcpy(*dev, ndata_host, (size_t)b->B * sizeof(int64_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
 }  // namespace
 
 int emx_internal_batch_view(emx_batch* b, EmxBatchView* v) {
@@ -1062,13 +1106,7 @@ int emx_batch_set_target(emx_batch* b, int32_t kind, const double* p0, const dou
             const double v = scales ? scales[per_member ? m : 0] : 0.0;
             sc[m] = v != 0.0 ? v : 20.0;
         }
-    if (int rc = set_blobs(b, 0)) return rc;       // the built-in targets have none
-    BHIP(b, hipStreamSynchronize(b->stream));      // no kernel still reads the old parameters
-    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
-        if (*p) {
-            hipFree(*p);
-            *p = nullptr;
-        }
+    if (int rc = settle_target(b, 0)) return rc;       // the built-in targets have no blobs
     if (!h0.empty()) {
         BHIP(b, hipMalloc((void**)&b->tp0, h0.size() * 8));
         BHIP(b, hipMemcpy(b->tp0, h0.data(), h0.size() * 8, hipMemcpyHostToDevice));
@@ -1088,15 +1126,7 @@ int emx_set_batch_target_callback_blobs(emx_batch* b, emx_batch_log_prob_blobs_f
     BNEED(b, fn != nullptr, "emx_set_batch_target_callback_blobs: no function");
     BNEED(b, nblobs >= 1 && nblobs <= BATCH_MAX_BLOBS, "emx_set_batch_target_callback_blobs: 1 <= nblobs <= %d; got %d", BATCH_MAX_BLOBS, nblobs);
     BNEED(b, b->pt_T == 0, "a tempered batch does not take blobs");
-    BHIP(b, hipSetDevice(b->device));
-    if (int rc = set_blobs(b, nblobs)) return rc;
-    BHIP(b, hipStreamSynchronize(b->stream));
-    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
-        if (*p) {
-            hipFree(*p);
-            *p = nullptr;
-        }
-    b->tp0_stride = b->tp1_stride = 0;
+    if (int rc = settle_target(b, nblobs)) return rc;
     b->cb_fn = nullptr;
     b->cbb_fn = fn;
     b->cb_user = user;
@@ -1109,14 +1139,9 @@ int emx_set_batch_target_callback(emx_batch* b, emx_batch_log_prob_fn fn, void* 
     BNEED(b, fn != nullptr, "emx_set_batch_target_callback: no function");
     BHIP(b, hipSetDevice(b->device));
     if (int rc = set_blobs(b, 0)) return rc;
-    b->cbb_fn = nullptr;
+    b->cbb_fn = nullptr;       // (ahead of the synchronise: settle_target's steps, with this between them)
     BHIP(b, hipStreamSynchronize(b->stream));
-    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
-        if (*p) {
-            hipFree(*p);
-            *p = nullptr;
-        }
-    b->tp0_stride = b->tp1_stride = 0;
+    drop_builtin_params(b);
     b->cb_fn = fn;
     b->cb_user = user;
     b->target = EMX_TARGET_DEVICE_CALLBACK;
@@ -1129,43 +1154,15 @@ int emx_set_batch_target_fused(emx_batch* b, emx_fused_batch_fn fn, int32_t ndim
 }
 
 int emx_set_batch_target_fused_blobs(emx_batch* b, emx_fused_batch_fn fn, int32_t ndim_compiled, const void* user_dev, int32_t nblobs) {
-    BNEED(b, fn != nullptr, "emx_set_batch_target_fused: no launcher");
-    BNEED(b, nblobs >= 0 && nblobs <= BATCH_MAX_BLOBS, "emx_set_batch_target_fused_blobs: 0 <= nblobs <= %d; got %d", BATCH_MAX_BLOBS, nblobs);
-    BNEED(b, ndim_compiled == b->D, "the fused user target was compiled for ndim %d; the batch has ndim %d", ndim_compiled, b->D);
-    BNEED(b, b->pt_T == 0, "a tempered batch does not take a fused user target: the tempered commit and the swap pass belong to the "
-                           "batched callback path (emx_set_batch_target_callback)");
-    if (!b->moves.empty()) {
-        char buf[256];
-        const char* why = shape_refusal(b->N, b->D, EMX_TARGET_FUSED_USER, (int32_t)b->moves.size(), b->moves.data(), buf, sizeof buf, nblobs);
-        BNEED(b, !why, "%s", why);
-    }
+    if (int rc = fused_bind_checks(b, "emx_set_batch_target_fused", EMX_TARGET_FUSED_USER, fn != nullptr, ndim_compiled, false, nullptr, nblobs)) return rc;
     // the probe: abi, args_bytes, ndim and nblobs against what the launcher was compiled with; nothing is launched
-    emx_fused_launch fl{};
     SmallRunArgs probe_args{};
     probe_args.D = b->D;
     probe_args.nblobs = nblobs;
-    fl.abi = EMX_FUSED_ABI;
-    fl.args_bytes = (uint32_t)sizeof(SmallRunArgs);
-    fl.ndim = b->D;
-    fl.movesel = MOVE_STRETCH;
-    fl.args = &probe_args;
+    auto fl = fused_desc<emx_fused_launch>(b, EMX_FUSED_ABI, sizeof(SmallRunArgs), MOVE_STRETCH, &probe_args);
     fl.nblobs = nblobs;
-    if (int rc = fn(&fl)) {
-        const int32_t had = b->nblobs;
-        b->nblobs = nblobs;               // (the count the message names)
-        rc = fused_refusal(b, rc, fl.movesel);
-        b->nblobs = had;
-        return rc;
-    }
-    BHIP(b, hipSetDevice(b->device));
-    if (int rc = set_blobs(b, nblobs)) return rc;
-    BHIP(b, hipStreamSynchronize(b->stream));
-    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
-        if (*p) {
-            hipFree(*p);
-            *p = nullptr;
-        }
-    b->tp0_stride = b->tp1_stride = 0;
+    if (int rc = fused_refusal(b, fn(&fl), fl.movesel, nblobs)) return rc;
+    if (int rc = settle_target(b, nblobs)) return rc;
     b->fused_fn = fn;
     b->fused_data_fn = nullptr;
     b->fused_user = user_dev;
@@ -1176,40 +1173,14 @@ int emx_set_batch_target_fused_blobs(emx_batch* b, emx_fused_batch_fn fn, int32_
 
 int emx_set_batch_target_fused_data(emx_batch* b, emx_fused_batch_data_fn fn, int32_t ndim_compiled, const void* user_dev,
                                     const int64_t* ndata_host) {
-    BNEED(b, fn != nullptr, "emx_set_batch_target_fused_data: no launcher");
-    BNEED(b, ndata_host != nullptr, "emx_set_batch_target_fused_data: no data counts (nbatch values)");
-    BNEED(b, ndim_compiled == b->D, "the fused user target was compiled for ndim %d; the batch has ndim %d", ndim_compiled, b->D);
-    BNEED(b, b->pt_T == 0, "a tempered batch does not take a fused user target: the tempered commit and the swap pass belong to the "
-                           "batched callback path (emx_set_batch_target_callback)");
-    for (int32_t m = 0; m < b->B; ++m)
-        BNEED(b, ndata_host[m] >= 0 && ndata_host[m] < ((int64_t)1 << 31),
-              "emx_set_batch_target_fused_data: 0 <= ndata < 2^31 for every member; member %d has %lld", m, (long long)ndata_host[m]);
-    if (!b->moves.empty()) {
-        char buf[256];
-        const char* why = shape_refusal(b->N, b->D, EMX_TARGET_FUSED_USER, (int32_t)b->moves.size(), b->moves.data(), buf, sizeof buf, 0);
-        BNEED(b, !why, "%s", why);
-    }
+    if (int rc = fused_bind_checks(b, "emx_set_batch_target_fused_data", EMX_TARGET_FUSED_USER, fn != nullptr, ndim_compiled, true, ndata_host)) return rc;
     // the probe: abi, args_bytes and ndim against what the launcher was compiled with; nothing is launched
-    emx_fused_batch_data_launch fl{};
     SmallRunArgs probe_args{};
     probe_args.D = b->D;
-    fl.abi = EMX_FUSED_BATCH_DATA_ABI;
-    fl.args_bytes = (uint32_t)sizeof(SmallRunArgs);
-    fl.ndim = b->D;
-    fl.movesel = MOVE_STRETCH;
-    fl.args = &probe_args;
-    if (int rc = fused_refusal(b, fn(&fl), fl.movesel, true)) return rc;
-    BHIP(b, hipSetDevice(b->device));
-    if (int rc = set_blobs(b, 0)) return rc;
-    BHIP(b, hipStreamSynchronize(b->stream));
-    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
-        if (*p) {
-            hipFree(*p);
-            *p = nullptr;
-        }
-    b->tp0_stride = b->tp1_stride = 0;
-    if (!b->fused_ndata) BHIP(b, hipMalloc((void**)&b->fused_ndata, (size_t)b->B * sizeof(int64_t)));
-    BHIP(b, hipMemcpy(b->fused_ndata, ndata_host, (size_t)b->B * sizeof(int64_t), hipMemcpyHostToDevice));
+    auto fl = fused_desc<emx_fused_batch_data_launch>(b, EMX_FUSED_BATCH_DATA_ABI, sizeof(SmallRunArgs), MOVE_STRETCH, &probe_args);
+    if (int rc = fused_refusal(b, fn(&fl), fl.movesel, 0, true)) return rc;
+    if (int rc = settle_target(b, 0)) return rc;
+    if (int rc = upload_counts(b, &b->fused_ndata, ndata_host)) return rc;
     b->fused_data_fn = fn;
     b->fused_fn = nullptr;
     b->fused_user = user_dev;
@@ -1218,33 +1189,19 @@ int emx_set_batch_target_fused_data(emx_batch* b, emx_fused_batch_data_fn fn, in
     return 0;
 }
 
-int emx_pt_set_target_fused(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compiled, const void* user_dev) {
-    BNEED(b, fn != nullptr, "emx_pt_set_target_fused: no launcher");
-    BNEED(b, ndim_compiled == b->D, "the fused tempered target was compiled for ndim %d; the batch has ndim %d", ndim_compiled, b->D);
-    BNEED(b, b->pt_T == 0, "emx_pt_set_target_fused comes before emx_pt_set_tempering");
-    if (!b->moves.empty()) {
-        char buf[256];
-        const char* why = shape_refusal(b->N, b->D, EMX_TARGET_FUSED_PT, (int32_t)b->moves.size(), b->moves.data(), buf, sizeof buf);
-        BNEED(b, !why, "%s", why);
-    }
+// emx_pt_set_target_fused and emx_pt_set_target_fused_data (`ndata_host` non-null: the data ABI, a plain EMX_FUSED_PT_TARGET launcher
+// answers 1)
+static int pt_set_target_fused(emx_batch* b, const char* who, emx_pt_fused_fn fn, int32_t ndim_compiled, const void* user_dev, bool data,
+                               const int64_t* ndata_host) {
+    if (int rc = fused_bind_checks(b, who, EMX_TARGET_FUSED_PT, fn != nullptr, ndim_compiled, data, ndata_host)) return rc;
     // the probe: abi, args_bytes and ndim against what the launcher was compiled with; nothing is launched
-    emx_pt_fused_launch fl{};
-    fl.abi = EMX_FUSED_PT_ABI;
-    fl.args_bytes = (uint32_t)sizeof(PtRunArgs);
-    fl.ndim = b->D;
-    fl.movesel = MOVE_STRETCH;
-    if (int rc = pt_fused_launcher_refusal(b, fn(&fl), fl.movesel)) return rc;
-    BHIP(b, hipSetDevice(b->device));
-    if (int rc = set_blobs(b, 0)) return rc;
-    BHIP(b, hipStreamSynchronize(b->stream));
-    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
-        if (*p) {
-            hipFree(*p);
-            *p = nullptr;
-        }
-    b->tp0_stride = b->tp1_stride = 0;
+    auto fl = fused_desc<emx_pt_fused_launch>(b, data ? EMX_FUSED_PT_DATA_ABI : EMX_FUSED_PT_ABI, sizeof(PtRunArgs), MOVE_STRETCH, nullptr);
+    if (int rc = pt_fused_launcher_refusal(b, fn(&fl), fl.movesel, data)) return rc;
+    if (int rc = settle_target(b, 0)) return rc;
+    if (data)
+        if (int rc = upload_counts(b, &b->ptf_ndata, ndata_host)) return rc;
     b->ptf_fn = fn;
-    b->ptf_data = false;
+    b->ptf_data = data;
     b->ptf_user = user_dev;
     b->ptf_has_prior = fl.has_prior ? 1 : 0;
     b->target = EMX_TARGET_FUSED_PT;
@@ -1252,44 +1209,12 @@ int emx_pt_set_target_fused(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compi
     return 0;
 }
 
+int emx_pt_set_target_fused(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compiled, const void* user_dev) {
+    return pt_set_target_fused(b, "emx_pt_set_target_fused", fn, ndim_compiled, user_dev, false, nullptr);
+}
+
 int emx_pt_set_target_fused_data(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compiled, const void* user_dev, const int64_t* ndata_host) {
-    BNEED(b, fn != nullptr, "emx_pt_set_target_fused_data: no launcher");
-    BNEED(b, ndata_host != nullptr, "emx_pt_set_target_fused_data: no data counts (one value a member of the handle)");
-    BNEED(b, ndim_compiled == b->D, "the fused tempered target was compiled for ndim %d; the batch has ndim %d", ndim_compiled, b->D);
-    BNEED(b, b->pt_T == 0, "emx_pt_set_target_fused_data comes before emx_pt_set_tempering");
-    for (int32_t m = 0; m < b->B; ++m)
-        BNEED(b, ndata_host[m] >= 0 && ndata_host[m] < ((int64_t)1 << 31),
-              "emx_pt_set_target_fused_data: 0 <= ndata < 2^31 for every member; member %d has %lld", m, (long long)ndata_host[m]);
-    if (!b->moves.empty()) {
-        char buf[256];
-        const char* why = shape_refusal(b->N, b->D, EMX_TARGET_FUSED_PT, (int32_t)b->moves.size(), b->moves.data(), buf, sizeof buf);
-        BNEED(b, !why, "%s", why);
-    }
-    // the probe with the data ABI: a plain EMX_FUSED_PT_TARGET launcher answers 1; nothing is launched
-    emx_pt_fused_launch fl{};
-    fl.abi = EMX_FUSED_PT_DATA_ABI;
-    fl.args_bytes = (uint32_t)sizeof(PtRunArgs);
-    fl.ndim = b->D;
-    fl.movesel = MOVE_STRETCH;
-    if (int rc = pt_fused_launcher_refusal(b, fn(&fl), fl.movesel, true)) return rc;
-    BHIP(b, hipSetDevice(b->device));
-    if (int rc = set_blobs(b, 0)) return rc;
-    BHIP(b, hipStreamSynchronize(b->stream));
-    for (double** p : {&b->tp0, &b->tp1, &b->tscales})
-        if (*p) {
-            hipFree(*p);
-            *p = nullptr;
-        }
-    b->tp0_stride = b->tp1_stride = 0;
-    if (!b->ptf_ndata) BHIP(b, hipMalloc((void**)&b->ptf_ndata, (size_t)b->B * sizeof(int64_t)));
-    BHIP(b, hipMemcpy(b->ptf_ndata, ndata_host, (size_t)b->B * sizeof(int64_t), hipMemcpyHostToDevice));
-    b->ptf_fn = fn;
-    b->ptf_data = true;
-    b->ptf_user = user_dev;
-    b->ptf_has_prior = fl.has_prior ? 1 : 0;
-    b->target = EMX_TARGET_FUSED_PT;
-    b->Dp = b->D;
-    return 0;
+    return pt_set_target_fused(b, "emx_pt_set_target_fused_data", fn, ndim_compiled, user_dev, true, ndata_host);
 }
 
 int emx_pt_fused_check(int32_t ntemps, int64_t nwalkers, int32_t ndim, int32_t nmoves, const emx_move_desc* moves, char* msg,

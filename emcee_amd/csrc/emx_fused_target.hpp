@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #if __has_include(<emx.h>)
 #include <emx.h>
@@ -52,12 +53,42 @@ constexpr int fused_v(int D) { return D % 2 == 0 ? 2 : 1; }
 constexpr int fused_g(int D) { return shape_g((D + fused_v(D) - 1) / fused_v(D)); }
 constexpr int fused_ch(int D) { return shape_ch((D + fused_v(D) - 1) / fused_v(D)); }
 
-// DATA: the wave-a-row form of a model with base and term (emx_fused_target_data.hpp)
-template <typename USER, int NDIM, int MOVESEL, int NBLOBS = 0, bool DATA = false>
-hipError_t launch_fused_move(int grid, int threads, size_t lds, hipStream_t st, const SmallRunArgs& a) {
-    constexpr int G = fused_g(NDIM), V = fused_v(NDIM), CH = fused_ch(NDIM);
-    auto kern = k_small_run<G, V, CH, MOVESEL, false, 0, true, USER, NBLOBS, DATA>;
-    static size_t lds_granted[MAX_DEVICES] = {};      // as launch_small_move: function attributes are per device
+// THE launcher check of every fused batch and tempered target (fused_batch_launch below, fused_batch_data_launch, fused_pt_launch,
+// fused_pt_data_launch), in the order that is part of their contract.  `before_probe(L)`: the checks ONE launcher has between the
+// selectors and the probe (its answer, or FUSED_GO_ON).  Returns the answer, or FUSED_GO_ON with *stretch: the schedule is one StretchMove.
+constexpr int FUSED_GO_ON = -1;
+template <typename DESC, typename SITE>
+int fused_launch_checks(DESC* L, uint32_t abi, size_t args_bytes, int ndim, int moves, int max_threads, bool* stretch, SITE&& before_probe) {
+    if (!L || L->abi != abi || L->args_bytes != (uint32_t)args_bytes) return 1;
+    if (L->ndim != ndim) return 2;
+    *stretch = L->movesel == MOVE_STRETCH;
+    if (!*stretch && L->movesel != SMALL_ANY_MOVE) return 3;
+    if (!*stretch && !(moves & EMX_FUSED_MOVES_ANY)) return 3;
+    if (const int rc = before_probe(L); rc != FUSED_GO_ON) return rc;
+    if (L->grid == 0) return 0;                       // the probe of the library's setters
+    if (!L->args || L->grid < 0 || L->threads < 64 || L->threads > max_threads || L->threads % 64 != 0) return 3;
+    return FUSED_GO_ON;
+}
+
+// `launch(std::integral_constant<int, MOVESEL>)` under the stretch selector, the any selector, or the one of them the MOVES mask
+// compiled in (a mask of 0: none), as the launcher's answer: 0, or 100 + hipError_t
+template <int MOVES, typename LAUNCH>
+int fused_launch_by_moves(bool stretch, LAUNCH&& launch) {
+    [[maybe_unused]] hipError_t e = hipErrorInvalidValue;
+    if constexpr ((MOVES & EMX_FUSED_MOVES_STRETCH) != 0) {
+        if (stretch) e = launch(std::integral_constant<int, MOVE_STRETCH>{});
+    }
+    if constexpr ((MOVES & EMX_FUSED_MOVES_ANY) != 0) {
+        if (!stretch || !(MOVES & EMX_FUSED_MOVES_STRETCH))      // the any-schedule kernel runs a single StretchMove to the same bits
+            e = launch(std::integral_constant<int, SMALL_ANY_MOVE>{});
+    }
+    return e == hipSuccess ? 0 : 100 + (int)e;
+}
+
+// grant `kern` its dynamic LDS above 48 KiB once per device, launch it, hipGetLastError.  `lds_granted`: the CALLER's static table
+// (MAX_DEVICES entries), one per kernel instantiation -- function attributes are per kernel and device, as launch_small_move's
+template <typename KERN, typename ARGS>
+hipError_t fused_launch_kernel(KERN kern, size_t* lds_granted, int grid, int threads, size_t lds, hipStream_t st, const ARGS& a) {
     int dev = 0;
     if (lds > 48 * 1024 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MAX_DEVICES && lds > lds_granted[dev]) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -68,35 +99,34 @@ hipError_t launch_fused_move(int grid, int threads, size_t lds, hipStream_t st, 
     return hipGetLastError();
 }
 
+// DATA: the wave-a-row form of a model with base and term (emx_fused_target_data.hpp)
+template <typename USER, int NDIM, int MOVESEL, int NBLOBS = 0, bool DATA = false>
+hipError_t launch_fused_move(int grid, int threads, size_t lds, hipStream_t st, const SmallRunArgs& a) {
+    static size_t lds_granted[MAX_DEVICES] = {};
+    return fused_launch_kernel(k_small_run<fused_g(NDIM), fused_v(NDIM), fused_ch(NDIM), MOVESEL, false, 0, true, USER, NBLOBS, DATA>, lds_granted,
+                               grid, threads, lds, st, a);
+}
+
 // the launcher behind EMX_FUSED_BATCH_TARGET: the checks, then one launch of the batch (include/emx.h: emx_fused_launch)
 template <typename USER, int NDIM, int MOVES, int NBLOBS = 0>
 int fused_batch_launch(const emx_fused_launch* L) {
     static_assert(NDIM >= 1 && NDIM <= 256, "a fused user target has 1 <= ndim <= 256");
     static_assert(NBLOBS >= 0 && NBLOBS <= 32, "a fused user target has 0 <= nblobs <= 32");
     static_assert((MOVES & (EMX_FUSED_MOVES_STRETCH | EMX_FUSED_MOVES_ANY)) != 0, "no move selector compiled in");
-    if (!L || L->abi != EMX_FUSED_ABI || L->args_bytes != (uint32_t)sizeof(SmallRunArgs)) return 1;
-    if (L->ndim != NDIM) return 2;
-    const bool stretch = L->movesel == MOVE_STRETCH;
-    if (!stretch && L->movesel != SMALL_ANY_MOVE) return 3;
-    if (!stretch && !(MOVES & EMX_FUSED_MOVES_ANY)) return 3;
+    bool stretch = false;
     // the blob count against the one compiled in.  (A blob-free launcher reads the field only of a descriptor that carries `args`,
-    // as the library's always does: a bare probe of the four fields above is answered from them alone.)
-    if ((NBLOBS > 0 || L->args) && L->nblobs != NBLOBS) return 4;
-    if (L->grid == 0) return 0;                       // the probe of emx_set_batch_target_fused
-    if (!L->args || L->grid < 0 || L->threads < 64 || L->threads > 1024 || L->threads % 64 != 0) return 3;
+    // as the library's always does: a bare probe of the four fields before it is answered from them alone.)
+    const int rc = fused_launch_checks(L, EMX_FUSED_ABI, sizeof(SmallRunArgs), NDIM, MOVES, 1024, &stretch, [](const emx_fused_launch* d) {
+        return (NBLOBS > 0 || d->args) && d->nblobs != NBLOBS ? 4 : FUSED_GO_ON;
+    });
+    if (rc != FUSED_GO_ON) return rc;
     SmallRunArgs a = *static_cast<const SmallRunArgs*>(L->args);
     if (a.D != NDIM) return 2;
     if (a.nblobs != NBLOBS || (NBLOBS > 0 && !a.blobs)) return 4;
     a.user = L->user;
-    hipError_t e = hipErrorInvalidValue;
-    if constexpr ((MOVES & EMX_FUSED_MOVES_STRETCH) != 0) {
-        if (stretch) e = launch_fused_move<USER, NDIM, MOVE_STRETCH, NBLOBS>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
-    }
-    if constexpr ((MOVES & EMX_FUSED_MOVES_ANY) != 0) {
-        if (!stretch || !(MOVES & EMX_FUSED_MOVES_STRETCH))      // the any-schedule kernel runs a single StretchMove to the same bits
-            e = launch_fused_move<USER, NDIM, SMALL_ANY_MOVE, NBLOBS>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
-    }
-    return e == hipSuccess ? 0 : 100 + (int)e;
+    return fused_launch_by_moves<MOVES>(stretch, [&](auto sel) {
+        return launch_fused_move<USER, NDIM, decltype(sel)::value, NBLOBS>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
+    });
 }
 
 }  // namespace emx

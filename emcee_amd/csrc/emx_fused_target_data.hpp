@@ -64,7 +64,7 @@ template <typename M>
 struct has_batch_data_term<M, std::void_t<decltype(std::declval<const M&>().term((const double*)nullptr, 0, 0, 0LL, (const void*)nullptr))>>
     : std::is_convertible<decltype(std::declval<const M&>().term((const double*)nullptr, 0, 0, 0LL, (const void*)nullptr)), double> {};
 
-// the launcher behind EMX_FUSED_BATCH_DATA_TARGET: fused_batch_launch's checks and answers against the data descriptor
+// the launcher behind EMX_FUSED_BATCH_DATA_TARGET: fused_launch_checks (emx_fused_target.hpp) against the data descriptor
 // (include/emx.h: emx_fused_batch_data_launch), then one launch of the batch
 template <typename USER, int NDIM, int MOVES>
 int fused_batch_data_launch(const emx_fused_batch_data_launch* L) {
@@ -76,29 +76,19 @@ int fused_batch_data_launch(const emx_fused_batch_data_launch* L) {
     static_assert(has_batch_data_term<USER>::value,
                   "EMX_FUSED_BATCH_DATA_TARGET: the model needs  __device__ double term(const double* x, int ndim, int member, long long k, "
                   "const void* user) const");
-    if (!L || L->abi != EMX_FUSED_BATCH_DATA_ABI || L->args_bytes != (uint32_t)sizeof(SmallRunArgs)) return 1;
-    if (L->ndim != NDIM) return 2;
-    const bool stretch = L->movesel == MOVE_STRETCH;
-    if (!stretch && L->movesel != SMALL_ANY_MOVE) return 3;
-    if (!stretch && !(MOVES & EMX_FUSED_MOVES_ANY)) return 3;
-    if (L->nblobs != 0) return 4;                     // a data target carries no blobs
-    if (L->grid == 0) return 0;                       // the probe of emx_set_batch_target_fused_data
-    if (!L->args || !L->ndata || L->grid < 0 || L->threads < 64 || L->threads > 1024 || L->threads % 64 != 0) return 3;
+    bool stretch = false;
+    // a data target carries no blobs (4); a launch (grid != 0) needs the members' counts: one of the shape check's faults (3)
+    const auto site = [](const emx_fused_batch_data_launch* d) { return d->nblobs != 0 ? 4 : d->grid != 0 && !d->ndata ? 3 : FUSED_GO_ON; };
+    const int rc = fused_launch_checks(L, EMX_FUSED_BATCH_DATA_ABI, sizeof(SmallRunArgs), NDIM, MOVES, 1024, &stretch, site);
+    if (rc != FUSED_GO_ON) return rc;
     SmallRunArgs a = *static_cast<const SmallRunArgs*>(L->args);
     if (a.D != NDIM) return 2;
     if (a.nblobs != 0) return 4;
     a.user = L->user;
     a.ndata = reinterpret_cast<const long long*>(L->ndata);
-    hipError_t e = hipErrorInvalidValue;
-    if constexpr (MODEL && (MOVES & EMX_FUSED_MOVES_STRETCH) != 0) {
-        if (stretch)
-            e = launch_fused_move<USER, NDIM, MOVE_STRETCH, 0, true>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
-    }
-    if constexpr (MODEL && (MOVES & EMX_FUSED_MOVES_ANY) != 0) {
-        if (!stretch || !(MOVES & EMX_FUSED_MOVES_STRETCH))      // the any-schedule kernel runs a single StretchMove to the same bits
-            e = launch_fused_move<USER, NDIM, SMALL_ANY_MOVE, 0, true>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
-    }
-    return e == hipSuccess ? 0 : 100 + (int)e;
+    return fused_launch_by_moves<MODEL ? MOVES : 0>(stretch, [&](auto sel) {
+        return launch_fused_move<USER, NDIM, decltype(sel)::value, 0, true>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
+    });
 }
 
 }  // namespace emx

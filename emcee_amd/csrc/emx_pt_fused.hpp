@@ -524,45 +524,29 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
 
 template <typename LIKE, typename PRIOR, int NDIM, int MOVESEL, bool DATA = false>
 hipError_t launch_pt_move(int grid, int threads, size_t lds, hipStream_t st, const PtRunArgs& a) {
-    constexpr int G = fused_g(NDIM), V = fused_v(NDIM), CH = fused_ch(NDIM);
-    auto kern = k_pt_run<G, V, CH, MOVESEL, LIKE, PRIOR, DATA>;
-    static size_t lds_granted[MAX_DEVICES] = {};      // as launch_small_move: function attributes are per device
-    int dev = 0;
-    if (lds > 48 * 1024 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MAX_DEVICES && lds > lds_granted[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_granted[dev] = lds;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, a);
-    return hipGetLastError();
+    static size_t lds_granted[MAX_DEVICES] = {};
+    return fused_launch_kernel(k_pt_run<fused_g(NDIM), fused_v(NDIM), fused_ch(NDIM), MOVESEL, LIKE, PRIOR, DATA>, lds_granted, grid, threads, lds,
+                               st, a);
 }
 
-// the launcher behind EMX_FUSED_PT_TARGET: fused_batch_launch's checks, then one launch of every object (include/emx.h:
-// emx_pt_fused_launch).  The probe (grid == 0) also reports whether a prior functor is compiled in.
+// the launcher behind EMX_FUSED_PT_TARGET: fused_launch_checks (emx_fused_target.hpp), then one launch of every object
+// (include/emx.h: emx_pt_fused_launch).  The probe (grid == 0) also reports whether a prior functor is compiled in.
 template <typename LIKE, typename PRIOR, int NDIM, int MOVES>
 int fused_pt_launch(emx_pt_fused_launch* L) {
     static_assert(NDIM >= 1 && NDIM <= 256, "a fused tempered target has 1 <= ndim <= 256");
     static_assert((MOVES & (EMX_FUSED_MOVES_STRETCH | EMX_FUSED_MOVES_ANY)) != 0, "no move selector compiled in");
-    if (!L || L->abi != EMX_FUSED_PT_ABI || L->args_bytes != (uint32_t)sizeof(PtRunArgs)) return 1;
-    if (L->ndim != NDIM) return 2;
-    const bool stretch = L->movesel == MOVE_STRETCH;
-    if (!stretch && L->movesel != SMALL_ANY_MOVE) return 3;
-    if (!stretch && !(MOVES & EMX_FUSED_MOVES_ANY)) return 3;
-    L->has_prior = std::is_same<PRIOR, NoFusedPrior>::value ? 0 : 1;
-    if (L->grid == 0) return 0;                       // the probe of emx_pt_set_target_fused
-    if (!L->args || L->grid < 0 || L->threads < 64 || L->threads > PT_RUN_MAX_THREADS || L->threads % 64 != 0) return 3;
+    bool stretch = false;
+    const int rc = fused_launch_checks(L, EMX_FUSED_PT_ABI, sizeof(PtRunArgs), NDIM, MOVES, PT_RUN_MAX_THREADS, &stretch, [](emx_pt_fused_launch* d) {
+        d->has_prior = std::is_same<PRIOR, NoFusedPrior>::value ? 0 : 1;      // the probe reports it
+        return FUSED_GO_ON;
+    });
+    if (rc != FUSED_GO_ON) return rc;
     PtRunArgs a = *static_cast<const PtRunArgs*>(L->args);
     if (a.D != NDIM) return 2;
     a.user = L->user;
-    hipError_t e = hipErrorInvalidValue;
-    if constexpr ((MOVES & EMX_FUSED_MOVES_STRETCH) != 0) {
-        if (stretch) e = launch_pt_move<LIKE, PRIOR, NDIM, MOVE_STRETCH>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
-    }
-    if constexpr ((MOVES & EMX_FUSED_MOVES_ANY) != 0) {
-        if (!stretch || !(MOVES & EMX_FUSED_MOVES_STRETCH))      // the any-schedule kernel runs a single StretchMove to the same bits
-            e = launch_pt_move<LIKE, PRIOR, NDIM, SMALL_ANY_MOVE>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
-    }
-    return e == hipSuccess ? 0 : 100 + (int)e;
+    return fused_launch_by_moves<MOVES>(stretch, [&](auto sel) {
+        return launch_pt_move<LIKE, PRIOR, NDIM, decltype(sel)::value>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
+    });
 }
 
 }  // namespace emx

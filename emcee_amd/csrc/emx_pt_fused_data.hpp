@@ -40,7 +40,7 @@
 
 namespace emx {
 
-// the launcher behind EMX_FUSED_PT_DATA_TARGET: fused_pt_launch's checks and answers against the data ABI, then one launch of every
+// the launcher behind EMX_FUSED_PT_DATA_TARGET: fused_launch_checks (emx_fused_target.hpp) against the data ABI, then one launch of every
 // object with a wave a row in the second pass (include/emx.h: emx_pt_fused_launch; PtRunArgs::ndata is the library's)
 template <typename MODEL, typename PRIOR, int NDIM, int MOVES>
 int fused_pt_data_launch(emx_pt_fused_launch* L) {
@@ -52,28 +52,19 @@ int fused_pt_data_launch(emx_pt_fused_launch* L) {
     static_assert(has_batch_data_term<MODEL>::value,
                   "EMX_FUSED_PT_DATA_TARGET: the model needs  __device__ double term(const double* x, int ndim, int member, long long k, "
                   "const void* user) const");
-    if (!L || L->abi != EMX_FUSED_PT_DATA_ABI || L->args_bytes != (uint32_t)sizeof(PtRunArgs)) return 1;
-    if (L->ndim != NDIM) return 2;
-    const bool stretch = L->movesel == MOVE_STRETCH;
-    if (!stretch && L->movesel != SMALL_ANY_MOVE) return 3;
-    if (!stretch && !(MOVES & EMX_FUSED_MOVES_ANY)) return 3;
-    L->has_prior = std::is_same<PRIOR, NoFusedPrior>::value ? 0 : 1;
-    if (L->grid == 0) return 0;                       // the probe of emx_pt_set_target_fused_data
-    if (!L->args || L->grid < 0 || L->threads < 64 || L->threads > PT_RUN_MAX_THREADS || L->threads % 64 != 0) return 3;
+    bool stretch = false;
+    const int rc = fused_launch_checks(L, EMX_FUSED_PT_DATA_ABI, sizeof(PtRunArgs), NDIM, MOVES, PT_RUN_MAX_THREADS, &stretch, [](emx_pt_fused_launch* d) {
+        d->has_prior = std::is_same<PRIOR, NoFusedPrior>::value ? 0 : 1;      // the probe reports it
+        return FUSED_GO_ON;
+    });
+    if (rc != FUSED_GO_ON) return rc;
     PtRunArgs a = *static_cast<const PtRunArgs*>(L->args);
     if (a.D != NDIM) return 2;
     if (!a.ndata) return 3;                           // the members' counts are the library's to fill
     a.user = L->user;
-    hipError_t e = hipErrorInvalidValue;
-    if constexpr (OK && (MOVES & EMX_FUSED_MOVES_STRETCH) != 0) {
-        if (stretch)
-            e = launch_pt_move<MODEL, PRIOR, NDIM, MOVE_STRETCH, true>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
-    }
-    if constexpr (OK && (MOVES & EMX_FUSED_MOVES_ANY) != 0) {
-        if (!stretch || !(MOVES & EMX_FUSED_MOVES_STRETCH))      // the any-schedule kernel runs a single StretchMove to the same bits
-            e = launch_pt_move<MODEL, PRIOR, NDIM, SMALL_ANY_MOVE, true>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
-    }
-    return e == hipSuccess ? 0 : 100 + (int)e;
+    return fused_launch_by_moves<OK ? MOVES : 0>(stretch, [&](auto sel) {
+        return launch_pt_move<MODEL, PRIOR, NDIM, decltype(sel)::value, true>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
+    });
 }
 
 }  // namespace emx

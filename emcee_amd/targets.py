@@ -160,7 +160,36 @@ class DeviceKernel(DeviceTarget):
             ens._cb_owner = self
 
 
-class DeviceFused(DeviceTarget):
+def _check_launcher(fn_ptr, message):
+    """a launcher or native callback: a ctypes function or a non-null address (an integer or a ``ctypes.c_void_p``), else TypeError(message)"""
+    if not isinstance(fn_ptr, ctypes._CFuncPtr):
+        addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
+        if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
+            raise TypeError(message)
+
+
+def _check_user(who, user, readers="the functor reads"):
+    """a fused target's ``user``: None, an integer, a ``ctypes.c_void_p`` or a torch CUDA tensor"""
+    if not (user is None or isinstance(user, (int, np.integer, ctypes.c_void_p)) or hasattr(user, "data_ptr")) or isinstance(user, bool):
+        raise TypeError("%s's user is a device pointer: None, an integer, a ctypes.c_void_p or a torch CUDA tensor" % who)
+    if hasattr(user, "data_ptr") and not getattr(user, "is_cuda", False):
+        raise TypeError("%s's user tensor must live on the GPU (%s it on the device)" % (who, readers))
+
+
+class _FusedUser(object):
+    """the ``user`` of the fused targets"""
+
+    def user_address(self):
+        """-> the device address handed to the functor (None: a null pointer)"""
+        u = self.user
+        if u is None:
+            return None
+        if hasattr(u, "data_ptr"):
+            return int(u.data_ptr())
+        return u.value if isinstance(u, ctypes.c_void_p) else int(u)
+
+
+class DeviceFused(_FusedUser, DeviceTarget):
     """The user's per-row ``__device__`` log-probability compiled INTO the half-step kernel of :class:`~emcee_amd.EnsembleSampler`:
     ``fn_ptr`` is the launcher that ``EMX_FUSED_ENSEMBLE_TARGET(name, Functor, ndim)`` of ``emx_fused_ensemble.hpp`` emits in the
     user's own translation unit (an ``emx_fused_ensemble_fn`` of ``include/emx.h``: a ctypes function or a non-null address),
@@ -205,20 +234,12 @@ class DeviceFused(DeviceTarget):
     kind = _lib.TARGET_FUSED_ENSEMBLE
 
     def __init__(self, fn_ptr, ndim, user=None, nblobs=0, small_fn=None, ndata=None):
-        if not isinstance(fn_ptr, ctypes._CFuncPtr):
-            addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
-            if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
-                raise TypeError("DeviceFused needs an emx_fused_ensemble_fn: a ctypes function or a non-null address")
+        _check_launcher(fn_ptr, "DeviceFused needs an emx_fused_ensemble_fn: a ctypes function or a non-null address")
         if isinstance(ndim, bool) or not isinstance(ndim, (int, np.integer)) or not 1 <= ndim <= 256:
             raise TypeError("DeviceFused needs the ndim its launcher was compiled for, an integer in [1, 256]; got %r" % (ndim,))
-        if not (user is None or isinstance(user, (int, np.integer, ctypes.c_void_p)) or hasattr(user, "data_ptr")) or isinstance(user, bool):
-            raise TypeError("DeviceFused's user is a device pointer: None, an integer, a ctypes.c_void_p or a torch CUDA tensor")
-        if hasattr(user, "data_ptr") and not getattr(user, "is_cuda", False):
-            raise TypeError("DeviceFused's user tensor must live on the GPU (the functor reads it on the device)")
-        if small_fn is not None and not isinstance(small_fn, ctypes._CFuncPtr):
-            addr = small_fn.value if isinstance(small_fn, ctypes.c_void_p) else small_fn
-            if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
-                raise TypeError("DeviceFused's small_fn is an EMX_FUSED_ENSEMBLE_SMALL_TARGET launcher: a ctypes function, a non-null address or None")
+        _check_user("DeviceFused", user)
+        if small_fn is not None:
+            _check_launcher(small_fn, "DeviceFused's small_fn is an EMX_FUSED_ENSEMBLE_SMALL_TARGET launcher: a ctypes function, a non-null address or None")
         self.fn_ptr, self.ndim, self.user, self.small_fn = fn_ptr, int(ndim), user, small_fn
         self.nblobs = _check_nblobs("DeviceFused", nblobs)
         self.ndata = _check_ndata("DeviceFused", ndata)
@@ -226,15 +247,6 @@ class DeviceFused(DeviceTarget):
             raise ValueError("DeviceFused: a target that sums over data (ndata) carries no blobs; nblobs=%d is refused" % self.nblobs)
         if self.ndata is not None and small_fn is not None:
             raise ValueError("DeviceFused: a target that sums over data (ndata) has no one-workgroup form; small_fn is refused")
-
-    def user_address(self):
-        """-> the device address handed to the functor (None: a null pointer)"""
-        u = self.user
-        if u is None:
-            return None
-        if hasattr(u, "data_ptr"):
-            return int(u.data_ptr())
-        return u.value if isinstance(u, ctypes.c_void_p) else int(u)
 
     def bind(self, ens):
         if ens.ndim != self.ndim:
@@ -262,6 +274,13 @@ def _check_ndata(who, ndata):
     if isinstance(ndata, bool) or not isinstance(ndata, (int, np.integer)) or not 0 <= ndata < 2 ** 31:
         raise ValueError("%s: ndata is an integer in [0, 2**31) (the data the target's term runs over), or None; got %r" % (who, ndata))
     return int(ndata)
+
+
+def _check_member_ndata(who, ndata):
+    """one count for every member (_check_ndata), or a sequence / array with one a member -> None, an int or a tuple of ints"""
+    if ndata is None or isinstance(ndata, (bool, int, float, np.generic)):
+        return _check_ndata(who, ndata)
+    return tuple(_check_ndata(who, n) for n in (ndata.tolist() if isinstance(ndata, np.ndarray) and ndata.dtype == object else list(ndata)))
 
 
 def fused_data_sum(terms):
@@ -331,14 +350,11 @@ class BatchKernel(BatchTarget):
     the function has the signature ``emx_batch_log_prob_blobs_fn`` and also writes a ``(nbatch, rows, K)`` block of blobs."""
 
     def __init__(self, fn_ptr, user_ptr=None, nblobs=0):
-        if not isinstance(fn_ptr, ctypes._CFuncPtr):
-            addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
-            if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
-                raise TypeError("BatchKernel needs an emx_batch_log_prob_fn: a ctypes function or a non-null address")
+        _check_launcher(fn_ptr, "BatchKernel needs an emx_batch_log_prob_fn: a ctypes function or a non-null address")
         self.fn_ptr, self.user_ptr, self.nblobs = fn_ptr, user_ptr, _check_nblobs("BatchKernel", nblobs)
 
 
-class BatchFused(BatchTarget):
+class BatchFused(_FusedUser, BatchTarget):
     """The user's per-row ``__device__`` log-probability compiled INTO the batch kernel: ``fn_ptr`` is the launcher that
     ``EMX_FUSED_BATCH_TARGET(name, Functor, ndim)`` of ``emx_fused_target.hpp`` emits in the user's own translation unit (an
     ``emx_fused_batch_fn`` of ``include/emx.h``: a ctypes function or a non-null address), ``ndim`` the dimension it was compiled
@@ -372,37 +388,17 @@ class BatchFused(BatchTarget):
     kind = _lib.TARGET_FUSED_USER
 
     def __init__(self, fn_ptr, ndim, user=None, nblobs=0, ndata=None):
-        if not isinstance(fn_ptr, ctypes._CFuncPtr):
-            addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
-            if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
-                raise TypeError("BatchFused needs an emx_fused_batch_fn: a ctypes function or a non-null address")
+        _check_launcher(fn_ptr, "BatchFused needs an emx_fused_batch_fn: a ctypes function or a non-null address")
         if isinstance(ndim, bool) or not isinstance(ndim, (int, np.integer)) or ndim < 1:
             raise TypeError("BatchFused needs the ndim its launcher was compiled for, an integer >= 1; got %r" % (ndim,))
-        if not (user is None or isinstance(user, (int, np.integer, ctypes.c_void_p)) or hasattr(user, "data_ptr")) or isinstance(user, bool):
-            raise TypeError("BatchFused's user is a device pointer: None, an integer, a ctypes.c_void_p or a torch CUDA tensor")
-        if hasattr(user, "data_ptr") and not getattr(user, "is_cuda", False):
-            raise TypeError("BatchFused's user tensor must live on the GPU (the functor reads it on the device)")
+        _check_user("BatchFused", user)
         self.fn_ptr, self.ndim, self.user = fn_ptr, int(ndim), user
         self.nblobs = _check_nblobs("BatchFused", nblobs)
-        if ndata is None or isinstance(ndata, (bool, int, float, np.generic)):
-            self.ndata = _check_ndata("BatchFused", ndata)
-        else:                             # one count a member: _check_ndata's rule for every entry
-            self.ndata = tuple(_check_ndata("BatchFused", n) for n in (ndata.tolist() if isinstance(ndata, np.ndarray) and ndata.dtype == object
-                                                                       else list(ndata)))
+        self.ndata = _check_member_ndata("BatchFused", ndata)
         if self.ndata is not None and self.nblobs > 0:
             raise ValueError("BatchFused: a target that sums over data (ndata) carries no blobs; nblobs=%d is refused" % self.nblobs)
 
-    def user_address(self):
-        """-> the device address handed to the functor (None: a null pointer)"""
-        u = self.user
-        if u is None:
-            return None
-        if hasattr(u, "data_ptr"):
-            return int(u.data_ptr())
-        return u.value if isinstance(u, ctypes.c_void_p) else int(u)
-
-
-class PTFused(BatchTarget):
+class PTFused(_FusedUser, BatchTarget):
     """The user's per-row ``__device__`` log-likelihood (and, optionally, log-prior) compiled INTO the tempered kernel of
     :class:`~emcee_amd.PTSampler`: ``fn_ptr`` is the launcher that ``EMX_FUSED_PT_TARGET(name, LikeFunctor, PriorFunctor, ndim)`` of
     ``emx_pt_fused.hpp`` emits in the user's own translation unit (an ``emx_pt_fused_fn`` of ``include/emx.h``), ``ndim`` the
@@ -429,25 +425,13 @@ class PTFused(BatchTarget):
     times at 4 096; 3.4 times SLOWER at 16 data, 12 to 15 % slower at 256); at 8 rungs of 64 x 16 only at 4 096 (1.5 times)."""
 
     def __init__(self, fn_ptr, ndim, user=None, has_prior=None, ndata=None):
-        if not isinstance(fn_ptr, ctypes._CFuncPtr):
-            addr = fn_ptr.value if isinstance(fn_ptr, ctypes.c_void_p) else fn_ptr
-            if isinstance(addr, bool) or not isinstance(addr, (int, np.integer)) or not addr:
-                raise TypeError("PTFused needs an emx_pt_fused_fn: a ctypes function or a non-null address")
+        _check_launcher(fn_ptr, "PTFused needs an emx_pt_fused_fn: a ctypes function or a non-null address")
         if isinstance(ndim, bool) or not isinstance(ndim, (int, np.integer)) or ndim < 1:
             raise TypeError("PTFused needs the ndim its launcher was compiled for, an integer >= 1; got %r" % (ndim,))
-        if not (user is None or isinstance(user, (int, np.integer, ctypes.c_void_p)) or hasattr(user, "data_ptr")) or isinstance(user, bool):
-            raise TypeError("PTFused's user is a device pointer: None, an integer, a ctypes.c_void_p or a torch CUDA tensor")
-        if hasattr(user, "data_ptr") and not getattr(user, "is_cuda", False):
-            raise TypeError("PTFused's user tensor must live on the GPU (the functors read it on the device)")
+        _check_user("PTFused", user, "the functors read")
         self.fn_ptr, self.ndim, self.user = fn_ptr, int(ndim), user
         self.has_prior = None if has_prior is None else bool(has_prior)
-        if ndata is None or isinstance(ndata, (bool, int, float, np.generic)):
-            self.ndata = _check_ndata("PTFused", ndata)
-        else:                             # one count an object: _check_ndata's rule for every entry
-            self.ndata = tuple(_check_ndata("PTFused", n) for n in (ndata.tolist() if isinstance(ndata, np.ndarray) and ndata.dtype == object
-                                                                    else list(ndata)))
-
-    user_address = BatchFused.user_address
+        self.ndata = _check_member_ndata("PTFused", ndata)
 
 
 def get_include():
@@ -457,25 +441,39 @@ def get_include():
     return [os.path.join(os.path.dirname(here), "include"), os.path.join(here, "csrc")]
 
 
-class BatchFusedLibrary(object):
-    """What :func:`compile_fused` built: ``path`` of the shared library, ``lib`` (its ``ctypes.CDLL``: the user's own ``extern
-    "C"`` setup functions of ``source`` are there), ``name`` of the launcher, ``ndim``, ``nblobs``, ``data`` (the launcher is an
-    ``EMX_FUSED_BATCH_DATA_TARGET`` one) and :meth:`target`."""
+class _FusedLibrary(object):
+    """Base of what the three compile functions build: ``path``, ``lib`` (the ``ctypes.CDLL``), ``name`` and ``launcher``, ``ndim``,
+    ``data``, and the refusals of :meth:`target`'s ``ndata`` in the words of the class (``_who``, ``_compiler``, ``_counts``)."""
 
-    def __init__(self, path, name, ndim, nblobs=0, data=False):
-        self.path, self.name, self.ndim, self.nblobs = path, name, int(ndim), int(nblobs)
-        self.data = bool(data)            # target() takes the members' data counts
+    def __init__(self, path, name, ndim, data):
+        self.path, self.name, self.ndim = path, name, int(ndim)
+        self.data = bool(data)            # the launcher is a data-target one: target() takes the data counts
         _lib.load()                       # one HIP runtime per process: the library's (torch's) first
         self.lib = ctypes.CDLL(path)
         self.launcher = getattr(self.lib, name)
 
+    def _check_target_ndata(self, ndata):
+        if self.data and ndata is None:
+            raise ValueError("%s.target: the library was built with data=True; give ndata, %s" % (self._who, self._counts))
+        if not self.data and ndata is not None:
+            raise ValueError("%s.target: ndata is for a library built with %s(..., data=True)" % (self._who, self._compiler))
+
+
+class BatchFusedLibrary(_FusedLibrary):
+    """What :func:`compile_fused` built: ``path`` of the shared library, ``lib`` (its ``ctypes.CDLL``: the user's own ``extern
+    "C"`` setup functions of ``source`` are there), ``name`` of the launcher, ``ndim``, ``nblobs``, ``data`` (the launcher is an
+    ``EMX_FUSED_BATCH_DATA_TARGET`` one) and :meth:`target`."""
+
+    _who, _compiler, _counts = "BatchFusedLibrary", "compile_fused", "the members' numbers of data"
+
+    def __init__(self, path, name, ndim, nblobs=0, data=False):
+        self.nblobs = int(nblobs)
+        _FusedLibrary.__init__(self, path, name, ndim, data)
+
     def target(self, user=None, ndata=None):
         """-> :class:`BatchFused` of the compiled functor with the device pointer ``user``; a library built with ``data=True``
         needs ``ndata`` -- the data every member's ``term`` runs over, an integer or ``nbatch`` of them -- and any other refuses it"""
-        if self.data and ndata is None:
-            raise ValueError("BatchFusedLibrary.target: the library was built with data=True; give ndata, the members' numbers of data")
-        if not self.data and ndata is not None:
-            raise ValueError("BatchFusedLibrary.target: ndata is for a library built with compile_fused(..., data=True)")
+        self._check_target_ndata(ndata)
         t = BatchFused(self.launcher, self.ndim, user, nblobs=self.nblobs, ndata=ndata)
         t._library = self                 # the launcher's code lives as long as the target
         return t
@@ -513,32 +511,58 @@ def _compile_cached(what, header, source, tail, key_parts, name, flags, cache_di
     return so
 
 
-class DeviceFusedLibrary(object):
+def _compile_ndim(who, ndim):
+    ndim = int(ndim)
+    if ndim < 1 or ndim > 256:
+        raise ValueError("%s: 1 <= ndim <= 256; got %d" % (who, ndim))
+    return ndim
+
+
+def _compile_nblobs(who, nblobs, data):
+    nblobs = _check_nblobs(who, nblobs)
+    if data and nblobs:
+        raise ValueError("%s: a data target (data=True) carries no blobs; nblobs=%d is refused" % (who, nblobs))
+    return nblobs
+
+
+def _compile_names(who, prefix, ndim, idents, name, flags):
+    """the identifier check of the functor types (``idents``: (what, identifier) pairs, the first one required) and of ``name``, the
+    default launcher name, the flags as strings -> (name, flags)"""
+    for what, ident in idents + (("name", name),):
+        if (ident is not None or what == idents[0][0]) and not (isinstance(ident, str) and re.match(r"^[A-Za-z_][A-Za-z0-9_:]*$", ident)):
+            raise ValueError("%s: %s must be a C++ identifier; got %r" % (who, what, ident))
+    return name or "%s_%s_%d" % (prefix, idents[0][1].replace(":", "_"), ndim), [str(f) for f in flags]
+
+
+def _compile_form(who, header, source, tail, data_tail, key, name, flags, cache_dir, data):
+    """the plain translation unit, or with ``data`` the data header's and its tail under the key + ("data target",) -> path of the
+    library.  (A plain build keeps the key, and with it the cached library, it always had.)"""
+    if data:
+        return _compile_cached(who, header.replace(".hpp", "_data.hpp"), source, data_tail, key + ("data target",), name, flags, cache_dir)
+    return _compile_cached(who, header, source, tail, key, name, flags, cache_dir)
+
+
+class DeviceFusedLibrary(_FusedLibrary):
     """What :func:`compile_fused_ensemble` built: ``path`` of the shared library, ``lib`` (its ``ctypes.CDLL``: the user's own
     ``extern "C"`` setup functions of ``source`` are there), ``name`` of the launcher, ``ndim``, ``nblobs``, ``small_name`` /
     ``small_launcher`` (the one-workgroup launcher, None when it was built with ``small=False``) and :meth:`target`."""
 
+    _who, _compiler, _counts = "DeviceFusedLibrary", "compile_fused_ensemble", "the number of data"
+
     def __init__(self, path, name, ndim, nblobs=0, small_name=None, data=False):
-        self.path, self.name, self.ndim, self.nblobs = path, name, int(ndim), _check_nblobs("DeviceFusedLibrary", nblobs)
-        self.data = bool(data)            # the launcher is an EMX_FUSED_ENSEMBLE_DATA_TARGET one: target() takes the data count
-        _lib.load()                       # one HIP runtime per process: the library's (torch's) first
-        self.lib = ctypes.CDLL(path)
-        self.launcher = getattr(self.lib, name)
+        self.nblobs = _check_nblobs("DeviceFusedLibrary", nblobs)
+        _FusedLibrary.__init__(self, path, name, ndim, data)
         self.small_name = small_name
         self.small_launcher = getattr(self.lib, small_name) if small_name else None
 
     def target(self, user=None, ndata=None):
         """-> :class:`DeviceFused` of the compiled functor with the device pointer ``user``; a library built with ``data=True``
         needs ``ndata``, the number of data its ``term`` runs over, and any other refuses it"""
-        if self.data and ndata is None:
-            raise ValueError("DeviceFusedLibrary.target: the library was built with data=True; give ndata, the number of data")
-        if not self.data and ndata is not None:
-            raise ValueError("DeviceFusedLibrary.target: ndata is for a library built with compile_fused_ensemble(..., data=True)")
+        self._check_target_ndata(ndata)
         if self.data:
             t = DeviceFused(self.launcher, self.ndim, user, ndata=ndata)
-            t._library = self
-            return t
-        t = DeviceFused(self.launcher, self.ndim, user, nblobs=self.nblobs, small_fn=self.small_launcher)
+        else:
+            t = DeviceFused(self.launcher, self.ndim, user, nblobs=self.nblobs, small_fn=self.small_launcher)
         t._library = self                 # the launcher's code lives as long as the target
         return t
 
@@ -564,54 +588,39 @@ def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir
     sums over data (:class:`DeviceFused`'s ``ndata``).  The translation unit is ``#include <emx_fused_ensemble_data.hpp>``,
     ``source`` and ``EMX_FUSED_ENSEMBLE_DATA_TARGET(name, functor, ndim)``; no one-workgroup launcher is emitted and ``nblobs``
     is refused.  ``data=False`` keeps the translation unit and the cache key it always had."""
-    nblobs = _check_nblobs("compile_fused_ensemble", nblobs)
-    if data and nblobs:
-        raise ValueError("compile_fused_ensemble: a data target (data=True) carries no blobs; nblobs=%d is refused" % nblobs)
-    ndim = int(ndim)
-    if ndim < 1 or ndim > 256:
-        raise ValueError("compile_fused_ensemble: 1 <= ndim <= 256; got %d" % ndim)
-    for what, ident in (("functor", functor), ("name", name)):
-        if (ident is not None or what == "functor") and not (isinstance(ident, str) and re.match(r"^[A-Za-z_][A-Za-z0-9_:]*$", ident)):
-            raise ValueError("compile_fused_ensemble: %s must be a C++ identifier; got %r" % (what, ident))
-    name = name or "emx_fused_ensemble_%s_%d" % (functor.replace(":", "_"), ndim)
-    flags = [str(f) for f in flags]
+    nblobs = _compile_nblobs("compile_fused_ensemble", nblobs, data)
+    ndim = _compile_ndim("compile_fused_ensemble", ndim)
+    name, flags = _compile_names("compile_fused_ensemble", "emx_fused_ensemble", ndim, (("functor", functor),), name, flags)
     tail = "EMX_FUSED_ENSEMBLE_TARGET(%s, %s, %d)" % (name, functor, ndim)
     key = ("ensemble", source, functor, ndim, name)
     if nblobs:                            # (a blob-free build keeps the key, and with it the cached library, it always had)
         tail = "EMX_FUSED_ENSEMBLE_TARGET_BLOBS(%s, %s, %d, %d)" % (name, functor, ndim, nblobs)
         key += ("nblobs", nblobs)
-    if data:
-        tail = "EMX_FUSED_ENSEMBLE_DATA_TARGET(%s, %s, %d)" % (name, functor, ndim)
-        so = _compile_cached("compile_fused_ensemble", "emx_fused_ensemble_data.hpp", source, tail, key + ("data target",), name, flags, cache_dir)
-        return DeviceFusedLibrary(so, name, ndim, 0, None, data=True)
-    small_name = name + "_small" if small else None
-    if not small:                         # (the default build keeps the form of key it always had; the headers are part of its hash)
-        key += ("half-step launcher only",)
-    else:
+    small_name = name + "_small" if small and not data else None
+    if small_name:
         tail += ("\nEMX_FUSED_ENSEMBLE_SMALL_TARGET_BLOBS(%s, %s, %d, %d)" % (small_name, functor, ndim, nblobs) if nblobs else
                  "\nEMX_FUSED_ENSEMBLE_SMALL_TARGET(%s, %s, %d)" % (small_name, functor, ndim))
-    so = _compile_cached("compile_fused_ensemble", "emx_fused_ensemble.hpp", source, tail, key, name, flags, cache_dir)
-    return DeviceFusedLibrary(so, name, ndim, nblobs, small_name)
+    elif not data:                        # (the default build keeps the form of key it always had; the headers are part of its hash)
+        key += ("half-step launcher only",)
+    so = _compile_form("compile_fused_ensemble", "emx_fused_ensemble.hpp", source, tail,
+                       "EMX_FUSED_ENSEMBLE_DATA_TARGET(%s, %s, %d)" % (name, functor, ndim), key, name, flags, cache_dir, data)
+    return DeviceFusedLibrary(so, name, ndim, nblobs, small_name, data=data)
 
 
-class PTFusedLibrary(object):
+class PTFusedLibrary(_FusedLibrary):
     """What :func:`compile_fused_pt` built: ``path``, ``lib`` (its ``ctypes.CDLL``), ``name`` of the launcher, ``ndim``,
     ``has_prior``, ``data`` (the launcher is an ``EMX_FUSED_PT_DATA_TARGET`` one) and :meth:`target`."""
 
+    _who, _compiler, _counts = "PTFusedLibrary", "compile_fused_pt", "the objects' numbers of data"
+
     def __init__(self, path, name, ndim, has_prior, data=False):
-        self.path, self.name, self.ndim, self.has_prior = path, name, int(ndim), bool(has_prior)
-        self.data = bool(data)            # target() takes the objects' data counts
-        _lib.load()                       # one HIP runtime per process: the library's (torch's) first
-        self.lib = ctypes.CDLL(path)
-        self.launcher = getattr(self.lib, name)
+        self.has_prior = bool(has_prior)
+        _FusedLibrary.__init__(self, path, name, ndim, data)
 
     def target(self, user=None, ndata=None):
         """-> :class:`PTFused` of the compiled functors with the device pointer ``user``; a library built with ``data=True``
         needs ``ndata`` -- the data every object's ``term`` runs over, an integer or ``nbatch`` of them -- and any other refuses it"""
-        if self.data and ndata is None:
-            raise ValueError("PTFusedLibrary.target: the library was built with data=True; give ndata, the objects' numbers of data")
-        if not self.data and ndata is not None:
-            raise ValueError("PTFusedLibrary.target: ndata is for a library built with compile_fused_pt(..., data=True)")
+        self._check_target_ndata(ndata)
         t = PTFused(self.launcher, self.ndim, user, has_prior=self.has_prior, ndata=ndata)
         t._library = self                 # the launcher's code lives as long as the target
         return t
@@ -630,22 +639,12 @@ def compile_fused_pt(source, likelihood, ndim, prior=None, name=None, flags=(), 
     log-likelihood sums over the object's data (:class:`PTFused`'s ``ndata``); ``prior`` is what it is above.  The translation unit
     is ``#include <emx_pt_fused_data.hpp>``, ``source`` and ``EMX_FUSED_PT_DATA_TARGET(name, likelihood, prior or emx::NoFusedPrior,
     ndim)``.  ``data=False`` keeps the translation unit and the cache key it always had."""
-    ndim = int(ndim)
-    if ndim < 1 or ndim > 256:
-        raise ValueError("compile_fused_pt: 1 <= ndim <= 256; got %d" % ndim)
-    for what, ident in (("likelihood", likelihood), ("prior", prior), ("name", name)):
-        if (ident is not None or what == "likelihood") and not (isinstance(ident, str) and re.match(r"^[A-Za-z_][A-Za-z0-9_:]*$", ident)):
-            raise ValueError("compile_fused_pt: %s must be a C++ identifier; got %r" % (what, ident))
-    name = name or "emx_pt_fused_%s_%d" % (likelihood.replace(":", "_"), ndim)
-    flags = [str(f) for f in flags]
-    key = ("pt", source, likelihood, prior, ndim, name)
-    if data:                              # (a plain build keeps the key, and with it the cached library, it always had)
-        tail = "EMX_FUSED_PT_DATA_TARGET(%s, %s, %s, %d)" % (name, likelihood, prior or "emx::NoFusedPrior", ndim)
-        so = _compile_cached("compile_fused_pt", "emx_pt_fused_data.hpp", source, tail, key + ("data target",), name, flags, cache_dir)
-        return PTFusedLibrary(so, name, ndim, prior is not None, data=True)
-    tail = "EMX_FUSED_PT_TARGET(%s, %s, %s, %d)" % (name, likelihood, prior or "emx::NoFusedPrior", ndim)
-    so = _compile_cached("compile_fused_pt", "emx_pt_fused.hpp", source, tail, key, name, flags, cache_dir)
-    return PTFusedLibrary(so, name, ndim, prior is not None)
+    ndim = _compile_ndim("compile_fused_pt", ndim)
+    name, flags = _compile_names("compile_fused_pt", "emx_pt_fused", ndim, (("likelihood", likelihood), ("prior", prior)), name, flags)
+    args = (name, likelihood, prior or "emx::NoFusedPrior", ndim)
+    so = _compile_form("compile_fused_pt", "emx_pt_fused.hpp", source, "EMX_FUSED_PT_TARGET(%s, %s, %s, %d)" % args,
+                       "EMX_FUSED_PT_DATA_TARGET(%s, %s, %s, %d)" % args, ("pt", source, likelihood, prior, ndim, name), name, flags, cache_dir, data)
+    return PTFusedLibrary(so, name, ndim, prior is not None, data=data)
 
 
 def compile_fused(source, functor, ndim, nblobs=0, name=None, flags=(), cache_dir=None, data=False):
@@ -667,24 +666,13 @@ def compile_fused(source, functor, ndim, nblobs=0, name=None, flags=(), cache_di
     log-probability sums over per-member data (:class:`BatchFused`'s ``ndata``).  The translation unit is ``#include
     <emx_fused_target_data.hpp>``, ``source`` and ``EMX_FUSED_BATCH_DATA_TARGET(name, functor, ndim)``; ``nblobs`` is refused.
     ``data=False`` keeps the translation unit and the cache key it always had."""
-    ndim = int(ndim)
-    if ndim < 1 or ndim > 256:
-        raise ValueError("compile_fused: 1 <= ndim <= 256; got %d" % ndim)
-    nblobs = _check_nblobs("compile_fused", nblobs)
-    if data and nblobs:
-        raise ValueError("compile_fused: a data target (data=True) carries no blobs; nblobs=%d is refused" % nblobs)
-    for what, ident in (("functor", functor), ("name", name)):
-        if ident is not None and not re.match(r"^[A-Za-z_][A-Za-z0-9_:]*$", ident):
-            raise ValueError("compile_fused: %s must be a C++ identifier; got %r" % (what, ident))
-    name = name or "emx_fused_%s_%d" % (functor.replace(":", "_"), ndim)
-    flags = [str(f) for f in flags]
+    ndim = _compile_ndim("compile_fused", ndim)
+    nblobs = _compile_nblobs("compile_fused", nblobs, data)
+    name, flags = _compile_names("compile_fused", "emx_fused", ndim, (("functor", functor),), name, flags)
     tail = ("EMX_FUSED_BATCH_TARGET_BLOBS(%s, %s, %d, %d)" % (name, functor, ndim, nblobs) if nblobs else
             "EMX_FUSED_BATCH_TARGET(%s, %s, %d)" % (name, functor, ndim))
     # (nblobs joins the key only when there are blobs: a blob-free build does not depend on how the count is spelt)
     key = ("batch", source, functor, ndim, name) + (("nblobs", nblobs) if nblobs else ())
-    if data:
-        tail = "EMX_FUSED_BATCH_DATA_TARGET(%s, %s, %d)" % (name, functor, ndim)
-        so = _compile_cached("compile_fused", "emx_fused_target_data.hpp", source, tail, key + ("data target",), name, flags, cache_dir)
-        return BatchFusedLibrary(so, name, ndim, 0, data=True)
-    so = _compile_cached("compile_fused", "emx_fused_target.hpp", source, tail, key, name, flags, cache_dir)
-    return BatchFusedLibrary(so, name, ndim, nblobs)
+    so = _compile_form("compile_fused", "emx_fused_target.hpp", source, tail, "EMX_FUSED_BATCH_DATA_TARGET(%s, %s, %d)" % (name, functor, ndim), key,
+                       name, flags, cache_dir, data)
+    return BatchFusedLibrary(so, name, ndim, nblobs, data=data)
