@@ -82,7 +82,7 @@ __global__ __launch_bounds__(CB_MAX_THREADS) void k_batch_cb(const BatchCbArgs A
                 const double lq = pinf ? -__builtin_inf() : lraw;             // the likelihood of a row outside the prior is ignored
                 const double lpn = pt_tempered(beta, lq, pq), lpo = lp[i];
                 if (gl == 0 && ((!pinf && lraw != lraw) || lpn != lpn)) raise_status(M.status(), ST_NAN_LOGP);
-                const double lnpdiff = A.fac[r] + lpn - lpo;
+                const double lnpdiff = A.fac[r] + lpn - lpo;                         // (small_update's accept rule, on the tempered lp)
                 const bool accept = lnpdiff > A.logu[r];
                 Row<G, V, CH> x;
                 if (accept || rows) load_row<G, V, CH>(x, accept ? A.q + r * D : X + (size_t)i * D, D, gl);
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(CB_MAX_THREADS) void k_batch_cb(const BatchCbArgs A
                 const int i = A.wi[r];
                 const double lpn = A.lpq[r], lpo = lp[i];
                 if (gl == 0 && lpn != lpn) raise_status(M.status(), ST_NAN_LOGP);      // ensemble.py:550-551
-                const double lnpdiff = A.fac[r] + lpn - lpo;                         // red_blue.py:99
+                const double lnpdiff = A.fac[r] + lpn - lpo;                         // red_blue.py:99 (small_update's accept rule)
                 const bool accept = lnpdiff > A.logu[r];                             // red_blue.py:100
                 Row<G, V, CH> x;
                 if (accept || stored) load_row<G, V, CH>(x, accept ? A.q + r * D : X + (size_t)i * D, D, gl);
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(CB_MAX_THREADS) void k_batch_cb(const BatchCbArgs A
             Row<G, V, CH> q;
             double factor = 0.0;
             bool badq = false;
-            if (kind == MOVE_GAUSS) {
+            if (kind == MOVE_GAUSS) {                                      // (the move ladder, SMALL_ANY_MOVE in emx_kernels.hpp, on kind alone)
                 double u;
                 native_gauss_slot(na, D, A.gmode[m], A.gcol, pos, i, j0, j1, j2, z, u);
                 lu = plan_log_uniform(u);

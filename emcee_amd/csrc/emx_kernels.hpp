@@ -1964,6 +1964,10 @@ static __global__ __launch_bounds__(512) void k_persist_gauss(const PersistGauss
 }
 
 constexpr int SMALL_ANY_MOVE = 7;      // MOVESEL: the kernel carries all three split-ensemble moves and picks per step
+// THE MOVE LADDER turns a step's move (MOVESEL, or the run-time kind under SMALL_ANY_MOVE) into the code compiled for it: Gaussian
+// (Philox plans only: never under PLANNED), else stretch, else DE, else snooker.  It is written out at every plan, proposal and
+// update site of the one-workgroup kernels (k_small_run here, k_pt_run, k_batch_cb); each site says so, and all of them must agree
+// arm for arm: a fifth move is an arm at each.
 
 // move of a native-mode step: one Philox draw against the cdf (the host's philox_move_choice)
 __host__ __device__ inline int native_move_choice(uint64_t seed, uint64_t step, const double* cdf, int n) {
@@ -2108,6 +2112,8 @@ __device__ __forceinline__ void small_update(const SmallRunArgs& A, const Member
     const double lp_new = eval_valu_target<G, V, CH>(q, mu, iv, M.tp0(), M.tp1(), A.target, M.tscale(), D, gl, lane);
     if (live && gl == 0 && (lp_new != lp_new)) raise_status(M.status(), ST_NAN_LOGP);
     const double lp_old = lps[i];
+    // THE ACCEPT RULE.  Its twins, which must agree with it: both pass 2 forms of k_small_run's fused target (below), k_batch_cb's
+    // two commits (emx_batch_cb.hip) and, on the tempered log-probability, both pass 2 forms of k_pt_run (emx_pt_fused.hpp)
     const double lnpdiff = factor + lp_new - lp_old;                  // red_blue.py:99
     const bool accept = live && !badq && (lnpdiff > logu);            // red_blue.py:100
     if (accept) {
@@ -2140,6 +2146,11 @@ __device__ __forceinline__ double fused_call_blobs(const double* x, int ndim, in
 // lane 0's value in every lane; the whole wave is active
 __device__ __forceinline__ double wave_first(double x) {
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
+}
+
+// the commit of an accepted row by a whole wave (the DATA forms of k_small_run and k_pt_run: lane 0 has decided, 64 lanes copy)
+__device__ __forceinline__ void wave_commit_row(double* dst, const double* src, int D, int lane) {
+    for (int d = lane; d < D; d += 64) dst[d] = src[d];
 }
 
 // a data target's value of one row, by a WHOLE wave (emx_fused_target_data.hpp, "THE VALUE"): lane 0 calls base, the 64 lanes
@@ -2371,6 +2382,7 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
             int i = 0, a0 = 0, a1 = 0, a2 = 0;
             double z = 0.0, lu = 0.0, fc = 0.0;
             const int S = A.nsplits[m];
+            // (the move ladder, SMALL_ANY_MOVE above; PLANNED has left this pass by now)
             if (MOVESEL == MOVE_GAUSS || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_GAUSS)) {
                 double u;
                 native_gauss_slot(na, D, A.gmode[m], A.step_col ? A.step_col[sb + b] : 0, pos, i, a0, a1, a2, z, u);
@@ -2417,6 +2429,7 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                         double factor = 0.0;
                         bool badq = false;
                         const int i = orders[pos], j0 = p0s[pos], j1 = p1s[pos], j2 = p2s[pos];
+                        // (the move ladder, SMALL_ANY_MOVE above: every copy agrees arm for arm)
                         if (!PLANNED && (MOVESEL == MOVE_GAUSS || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_GAUSS)))
                             small_propose<G, V, CH, MOVE_GAUSS>(M, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq, &gg);
                         else if (MOVESEL == MOVE_STRETCH || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_STRETCH))
@@ -2451,12 +2464,12 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                             int acc = 0;
                             if (lane == 0 && !bad) {
                                 if (lp_new != lp_new) raise_status(M.status(), ST_NAN_LOGP);
-                                const double lnpdiff = fac + lp_new - lps[i];            // red_blue.py:99
+                                const double lnpdiff = fac + lp_new - lps[i];            // red_blue.py:99 (small_update's accept rule)
                                 acc = lnpdiff > logus[pos] ? 1 : 0;                      // red_blue.py:100
                             }
                             const bool accept = __builtin_amdgcn_readfirstlane(acc) != 0;
                             if (accept) {
-                                for (int d = lane; d < D; d += 64) Xs[(size_t)i * D + d] = qrow[d];
+                                wave_commit_row(Xs + (size_t)i * D, qrow, D, lane);
                                 if (lane == 0) lps[i] = lp_new;
                             }
                             if (lane == 0) accs[i] = accept ? 1 : 0;
@@ -2480,7 +2493,7 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                                 lp_new = fused_call<USER>(qrow, D, (int)M.m(), A.user);
                             }
                             if (lp_new != lp_new) raise_status(M.status(), ST_NAN_LOGP);
-                            const double lnpdiff = fac + lp_new - lps[i];            // red_blue.py:99
+                            const double lnpdiff = fac + lp_new - lps[i];            // red_blue.py:99 (small_update's accept rule)
                             accept = lnpdiff > logus[pos];                           // red_blue.py:100
                             if (accept) {
                                 for (int d = 0; d < D; ++d) Xs[(size_t)i * D + d] = qrow[d];
@@ -2507,6 +2520,7 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                             double factor = 0.0;
                             bool badq = false;
                             const int i = orders[pos], j0 = p0s[pos], j1 = p1s[pos], j2 = p2s[pos];
+                            // (the move ladder, SMALL_ANY_MOVE above: every copy agrees arm for arm)
                             if (!PLANNED && (MOVESEL == MOVE_GAUSS || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_GAUSS)))
                                 small_propose<G, V, CH, MOVE_GAUSS>(M, Xs, live, i, j0, j1, j2, s0s[pos], facs[pos], gam, D, gl, sub, q, factor, badq, &gg);
                             else if (MOVESEL == MOVE_STRETCH || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_STRETCH))
@@ -2564,6 +2578,7 @@ static __global__ __launch_bounds__(1024) void k_small_run(const SmallRunArgs A)
                     const int pos = pos0 + (live ? t : 0);
                     const int i = orders[pos], j0 = p0s[pos], j1 = p1s[pos], j2 = p2s[pos];
                     const double s0 = s0s[pos], fac = facs[pos], logu = logus[pos];
+                    // (the move ladder, SMALL_ANY_MOVE above: every copy agrees arm for arm)
                     if (!PLANNED && (MOVESEL == MOVE_GAUSS || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_GAUSS)))
                         small_update<G, V, CH, MOVE_GAUSS>(A, M, Xs, lps, accs, live, i, j0, j1, j2, s0, fac, logu, gam, mu, iv, D, gl, sub, lane, &gg);
                     else if (MOVESEL == MOVE_STRETCH || (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_STRETCH))

@@ -128,6 +128,8 @@ struct PtMember {          // what small_propose needs of a rung
 };
 
 // prior, likelihood and tempered log-probability of one row: k_batch_cb<..., TEMPERED>'s and k_pt_init's rule.  -> the NaN status
+// (The prior -- functor, else box, else flat -- is written out here and in pt_row_eval_data; the rest of the rule here and in
+// pt_row_finish.  Each pair must agree.)
 template <typename LIKE, typename PRIOR>
 __device__ __forceinline__ bool pt_row_eval(const double* x, int D, int member, const void* user, double beta, const double* lo,
                                             const double* hi, bool box, double& pq, double& lq, double& lpn) {
@@ -282,6 +284,7 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
             int i = 0, a0 = 0, a1 = 0, a2 = 0;
             double z = 0.0, lu = 0.0, fc = 0.0;
             const int S = A.nsplits[m];
+            // (the move ladder, SMALL_ANY_MOVE in emx_kernels.hpp, for this kernel's two selectors: every copy agrees arm for arm)
             if (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_GAUSS) {
                 double u;
                 native_gauss_slot(na, D, A.gmode[m], A.step_col ? A.step_col[sb + b] : 0, pos, i, a0, a1, a2, z, u);
@@ -324,6 +327,9 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
                 for (int rb = wv * WPW; rb < TR; rb += nwave * WPW) {              // wave-uniform
                     const int r = rb + sub;
                     if (r >= TR) continue;                                          // row-uniform from here on
+                    // THE SLOT RULE (rung, slot, move, split sizes, plan entry): the same text stands in both forms of pass 2 below and
+                    // must agree with them to the bit, or a proposal is decided against another walker's plan entry.  Only the last
+                    // skip differs: this pass keeps a dead row (slot >= ns) in flight, both forms of pass 2 skip it.
                     const int t = r / R, slot = c0 + (r - t * R);
                     const int m = mvs[b * T + t];
                     const int kind = MOVESEL == SMALL_ANY_MOVE ? A.kind[m] : MOVESEL;
@@ -341,6 +347,7 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
                     double factor = 0.0;
                     bool badq = false;
                     const int i = orders[pos], j0 = p0s[pos], j1 = p1s[pos], j2 = p2s[pos];
+                    // (the move ladder, SMALL_ANY_MOVE in emx_kernels.hpp, for this kernel's two selectors: every copy agrees arm for arm)
                     if (MOVESEL == SMALL_ANY_MOVE && kind == MOVE_GAUSS) {
                         GaussGen gg;
                         gg.gseed = seedS[t];
@@ -371,6 +378,7 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
                     // pass 2, a wave a row -- the prior by lane 0, the model over the object's data by the wave, the tempered
                     // decision by lane 0, the commit by every lane; the values stored are the one-lane form's
                     for (int r = __builtin_amdgcn_readfirstlane(wv); r < TR; r += nwave) {      // wave-uniform, as every skip below
+                        // (pass 1's slot rule, a dead row skipped)
                         const int t = r / R, slot = c0 + (r - t * R);
                         const int m = mvs[b * T + t];
                         const int kind = MOVESEL == SMALL_ANY_MOVE ? A.kind[m] : MOVESEL;
@@ -390,12 +398,12 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
                         int acc = 0;
                         if (lane == 0 && !bad) {
                             if (pt_row_finish(pinf, pq, lraw, betaS[t], lq, lpn)) raise_status(A.status + (m0 + t) * SMALL_STATUS_WORDS, ST_NAN_LOGP);
-                            const double lnpdiff = fac + lpn - lps[w];
+                            const double lnpdiff = fac + lpn - lps[w];             // (small_update's accept rule, emx_kernels.hpp, on the tempered lp)
                             acc = lnpdiff > logus[pos] ? 1 : 0;
                         }
                         const bool accept = __builtin_amdgcn_readfirstlane(acc) != 0;
                         if (accept) {
-                            for (int d = lane; d < D; d += 64) Xs[(size_t)w * D + d] = qrow[d];
+                            wave_commit_row(Xs + (size_t)w * D, qrow, D, lane);
                             if (lane == 0) {
                                 lps[w] = lpn;
                                 Ls[w] = lq;
@@ -407,6 +415,7 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
                 } else
                 // pass 2: one lane a row -- prior, likelihood, the tempered decision, the commit
                 for (int r = tid; r < TR; r += NT) {
+                    // (pass 1's slot rule, a dead row skipped)
                     const int t = r / R, slot = c0 + (r - t * R);
                     const int m = mvs[b * T + t];
                     const int kind = MOVESEL == SMALL_ANY_MOVE ? A.kind[m] : MOVESEL;
@@ -424,7 +433,7 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
                         double pq, lq, lpn;
                         const bool nan = pt_row_eval<LIKE, PRIOR>(qrow, D, (int)(m0 + t), A.user, betaS[t], loS, hiS, box, pq, lq, lpn);
                         if (nan) raise_status(A.status + (m0 + t) * SMALL_STATUS_WORDS, ST_NAN_LOGP);
-                        const double lnpdiff = fac + lpn - lps[w];
+                        const double lnpdiff = fac + lpn - lps[w];                 // (small_update's accept rule, emx_kernels.hpp, on the tempered lp)
                         accept = lnpdiff > logus[pos];
                         if (accept) {
                             for (int d = 0; d < D; ++d) Xs[(size_t)w * D + d] = qrow[d];
