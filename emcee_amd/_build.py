@@ -6,6 +6,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, "csrc", f) for f in ("emx.hip", "emx_small.hip", "emx_aux.hip", "emx_hot.hip", "emx_wide.hip", "emx_mtdev.hip", "emx_slab.hip", "emx_pvalu.hip", "emx_pmix.hip", "emx_pslab.hip", "emx_podd.hip", "emx_walkkde.hip", "emx_batch.hip", "emx_batch_cb.hip", "emx_batch_acf.hip", "emx_pt.hip", "emx_batch_summary.hip")]     # translation units, built in parallel
 SRC = SRCS[0]
+# the chain-analysis units that came after the summaries (the summaries' tests count SRCS): built and linked like SRCS
+MORE_SRCS = [os.path.join(HERE, "csrc", f) for f in ("emx_rhat.hip",)]
 # EMX_BUILD_FLAVOUR=exp: the experiments flavour (-DEMX_EXPERIMENTS=1: the timing experiments' skip-phase switches, tuning "ablate",
 # tools/ablate.py) as libemx_exp.so beside the product library; load it with EMX_LIB=<path>.  The product is built without them.
 FLAVOUR = os.environ.get("EMX_BUILD_FLAVOUR", "")
@@ -13,7 +15,7 @@ LIB = os.path.join(HERE, "libemx_exp.so" if FLAVOUR == "exp" else "libemx.so")
 HOST_SRCS = [os.path.join(HERE, "csrc", f) for f in ("emx_mtpipe.cpp", "emx_mtjump.cpp")]       # plain host C++ (threads, SIMD clones): no device pass
 # every header of csrc/ (globbed: round 5's emx_planlog.hpp / emx_logtab.hpp were missing from a hand-kept list, so an edit of the
 # kernels' logarithm rebuilt nothing) + the C ABI
-DEPS = SRCS + HOST_SRCS + sorted(os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith((".hpp", ".h"))) + [
+DEPS = SRCS + MORE_SRCS + HOST_SRCS + sorted(os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith((".hpp", ".h"))) + [
     os.path.join(os.path.dirname(HERE), "include", "emx.h")]
 HOST_FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-pthread", "-fvisibility=hidden"]
 # -ffp-contract=off: the proposal arithmetic must round like NumPy's separate multiply/subtract.
@@ -69,7 +71,7 @@ def build(force=False, verbose=False):
         hostcxx = shutil.which("amdclang++") or shutil.which("clang++") or shutil.which("g++")
     os.makedirs(OBJCACHE, exist_ok=True)
     objs, procs = [], []
-    for src in SRCS + HOST_SRCS:
+    for src in SRCS + MORE_SRCS + HOST_SRCS:
         host = src in HOST_SRCS
         flags = HOST_FLAGS if host else FLAGS + EXTRA_FLAGS.get(os.path.basename(src), [])
         obj = os.path.join(OBJCACHE, "%s.%s.o" % (os.path.basename(src), _unit_hash(src, flags)))

@@ -264,6 +264,39 @@ class Backend(object):
         qs = np.quantile(x, q, axis=0) if len(q) else np.empty((0, x.shape[1]))
         return _summary.BatchSummary(n, x.mean(axis=0), c, qs, x[at].copy(), float(lp[at]))
 
+    def get_rhat(self, discard=0, thin=1, chains="walkers", log_prob=False):
+        """-> :class:`~emcee_amd.summary.RHat` ``(rhat, within, between, nchains, length)`` of the stored samples over the steps
+        of ``get_chain(discard=discard, thin=thin)``, each array ``(ndim,)`` -- ``(ndim + 1,)`` with ``log_prob=True``.
+
+        %s
+
+        One ensemble is one group: only ``chains="walkers"`` is accepted here (``ValueError`` otherwise).  A device-resident
+        chain is reduced where it lives (``emx_rhat``): ``within`` and ``between`` come from the device, ``rhat`` is formed from
+        them on the host, and only these numbers cross.  A chain on the host (user-written moves, Python blobs) goes through
+        :func:`emcee_amd.summary.split_rhat`, and so does a device chain whose call fails (no room for the scratch next to a
+        long chain)."""
+        _summary.check_chains(chains, ("walkers",))
+        if int(thin) != thin or thin < 1:
+            raise ValueError("thin must be an integer >= 1; got %r" % (thin,))
+        if int(discard) != discard or discard < 0:
+            raise ValueError("discard must be an integer >= 0; got %r" % (discard,))
+        thin, discard = int(thin), int(discard)
+        it = self.iteration if self.initialized else 0
+        if it <= 0:
+            raise AttributeError("you must run the sampler with 'store == True' before accessing the results")
+        start = min(discard + thin - 1, it)                 # reference backend.py:53
+        h = _summary.check_rhat_length(len(range(start, it, thin)))
+        if self._dev is not None:
+            try:
+                within, between, nc, hd = self._dev.rhat(start, it, thin, log_prob)
+            except EmxError as e:
+                autocorr.logger.debug("device R-hat unavailable (%s): NumPy on a copy of the chain", e)
+            else:
+                assert hd == h and nc == 2 * self.nwalkers
+                return _summary.RHat(_summary.rhat_of(within, between, h), within, between, nc, h)
+        lp = self.get_value("log_prob", discard=discard, thin=thin) if log_prob else None
+        return _summary.split_rhat(self.get_value("chain", discard=discard, thin=thin), log_prob=lp)
+
     def get_histograms(self, bins=64, range=None, discard=0, thin=1, pairs="all", pair_bins=None):
         """-> :class:`~emcee_amd.summary.Histograms`: the marginal histogram of every parameter and the 2-d histogram of every
         requested parameter pair (a corner plot's panels) over the steps of ``get_chain(discard=discard, thin=thin)`` and all
@@ -483,3 +516,6 @@ class Backend(object):
 
     def __exit__(self, exception_type, exception_value, traceback):
         pass
+
+
+Backend.get_rhat.__doc__ = Backend.get_rhat.__doc__ % _summary.RHAT_DEFINITION

@@ -264,8 +264,8 @@ class EnsembleBatch(object):
     def set_tuning(self, key, value):
         """``"batch_threads"`` / ``"batch_plan_steps"`` (include/emx.h): the launch shape; ``"batch_acf_series"``: series per
         FFT chunk of ``get_autocorr_time(on_device=True)``; ``"batch_summary_members"``: members per pass of
-        ``get_summary``; ``"batch_hist_members"`` / ``"batch_hist_rows"``: members and rows of a member per chunk of
-        ``get_histograms``.  No bit depends on them."""
+        ``get_summary``; ``"batch_rhat_members"``: members per pass of ``get_rhat``; ``"batch_hist_members"`` /
+        ``"batch_hist_rows"``: members and rows of a member per chunk of ``get_histograms``.  No bit depends on them."""
         self._tuning[key] = int(value)
         if self._h is not None:
             self._ck(self._lib().emx_batch_set_tuning(self._h, key.encode(), int(value)))
@@ -504,6 +504,40 @@ class EnsembleBatch(object):
                                                          ptr(order), ptr(mx), ptr(mlp), C.byref(ns)))
         assert ns.value == n
         return n, mean, c, order, mx, mlp
+
+    def get_rhat(self, discard=0, thin=1, chains="walkers", log_prob=False):
+        """-> :class:`~emcee_amd.summary.RHat` ``(rhat, within, between, nchains, length)`` over the selected steps
+        (``get_chain``'s ``discard`` / ``thin``), computed next to the chain (``emx_rhat_batch``); only these numbers cross to
+        the host.  ``chains="walkers"``: every member is its own group, arrays ``(B, ndim)`` -- row ``b`` is ``bt[b].get_rhat()``
+        bit for bit.  ``chains="members"``: the replicates are pooled, all ``B nwalkers`` walkers form one group, arrays
+        ``(ndim,)`` -- "do my B independent ensembles agree?".  ``log_prob=True`` makes the last axis ``ndim + 1``.
+
+        %s
+
+        :func:`emcee_amd.summary.split_rhat` is the same definition on ``get_chain()``'s array.  A device failure raises
+        :class:`emcee_amd._lib.EmxError` (no fallback).  Tuning ``"batch_rhat_members"`` (members per pass) changes no bit."""
+        _summary.check_chains(chains, ("walkers", "members"))
+        r = self._rhat(discard, thin, 0, self.nbatch, 1 if chains == "members" else 0, log_prob)
+        return r if chains == "walkers" else _summary.RHat(r.rhat[0], r.within[0], r.between[0], r.nchains, r.length)
+
+    def _rhat(self, discard, thin, lo, hi, pool, log_prob):
+        """-> RHat with arrays (groups, W): ``emx_rhat_batch`` on members [lo, hi); ``pool`` 0: a group a member, P > 0: members
+        with equal ``(m - lo) mod P`` pooled into P groups.  Arguments are checked before any device is touched."""
+        lo, hi, pool = int(lo), int(hi), int(pool)
+        if not 0 <= lo < hi <= self.nbatch:
+            raise ValueError("members [%d, %d) outside a batch of %d" % (lo, hi, self.nbatch))
+        if pool < 0 or (pool and (hi - lo) % pool):
+            raise ValueError("pool = %d: 0, or a divisor of the %d members" % (pool, hi - lo))
+        start, it, nt = self._summary_rows(discard, thin)
+        h = _summary.check_rhat_length(nt)
+        G, W = (pool if pool else hi - lo), self.ndim + (1 if log_prob else 0)
+        within, between = np.empty((G, W)), np.empty((G, W))
+        ptr = (lambda a: a.ctypes.data_as(C.c_void_p))
+        nc, hd = C.c_int64(0), C.c_int64(0)
+        self._ck(self._lib().emx_rhat_batch(self._h, lo, hi, pool, start, it, int(thin), int(bool(log_prob)), ptr(within), ptr(between),
+                                            C.byref(nc), C.byref(hd)))
+        assert hd.value == h
+        return _summary.RHat(_summary.rhat_of(within, between, h), within, between, nc.value, h)
 
     def get_histograms(self, bins=64, range=None, discard=0, thin=1, pairs="all", pair_bins=None):
         """-> :class:`~emcee_amd.summary.BatchHistograms`: for EVERY member the marginal histogram of every parameter and the 2-d
@@ -754,6 +788,13 @@ class _Member(object):
         x = self.get_chain(discard=discard, thin=thin)
         return thin * integrated_time(x, c=c, tol=tol, quiet=quiet)
 
+    def get_rhat(self, discard=0, thin=1, chains="walkers", log_prob=False):
+        """:meth:`EnsembleBatch.get_rhat` of this member alone, its walkers as chains, without the leading axis: what
+        ``EnsembleSampler.get_rhat`` returns.  One ensemble is one group: only ``chains="walkers"`` (``ValueError`` otherwise)."""
+        _summary.check_chains(chains, ("walkers",))
+        r = self._batch._rhat(discard, thin, self.index, self.index + 1, 0, log_prob)
+        return _summary.RHat(r.rhat[0], r.within[0], r.between[0], r.nchains, r.length)
+
     def get_summary(self, discard=0, thin=1, quantiles=(0.16, 0.5, 0.84), cov=True):
         """:meth:`EnsembleBatch.get_summary` of this member alone, without the leading axis."""
         r = self._batch._summary(discard, thin, quantiles, cov, self.index, self.index + 1)
@@ -776,3 +817,6 @@ class _Member(object):
     def get_last_sample(self):
         s = self._batch.get_last_sample()
         return State(s.coords[self.index], log_prob=s.log_prob[self.index], blobs=None if s.blobs is None else s.blobs[self.index])
+
+
+EnsembleBatch.get_rhat.__doc__ = EnsembleBatch.get_rhat.__doc__ % _summary.RHAT_DEFINITION

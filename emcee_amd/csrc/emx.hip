@@ -440,6 +440,7 @@ struct emx_ctx {
     double *chain = nullptr, *chain_lp = nullptr;
     int64_t cap = 0, stored = 0, proposals = 0;
     EnsSummary* summary = nullptr;        // emx_summary's scratch (emx_batch_summary.hip)
+    RhatScratch* rhat = nullptr;          // emx_rhat's scratch (emx_rhat.hip)
     int64_t tune_summary_compact = 1;     // emx_summary: passes 2 ... 7 of the selection on a compacted list: 0 never, 1 where a quarter or less is left, 2 always
     int64_t tune_hist_chunk_rows = 0;     // emx_histograms: selected rows a chunk of the code plane (0: about 256 MB of codes)
     // split-phase buffers
@@ -1230,6 +1231,7 @@ int emx_internal_chain_view(emx_ctx* c, EmxChainView* v) {
     v->summary_compact = c->tune_summary_compact;
     v->summary = &c->summary;
     v->hist_chunk_rows = c->tune_hist_chunk_rows;
+    v->rhat = &c->rhat;
     return 0;
 }
 
@@ -1422,6 +1424,7 @@ int emx_destroy(emx_ctx* c) {
     for (double* s : {c->blobs, c->evalblobs, c->blob_plane})
         if (s) hipFree(s);
     emx_internal_ens_summary_release(c->summary);
+    emx_internal_rhat_release(c->rhat);
 
     for (auto& s : c->ring) {
         if (s.order) hipFree(s.order);       // the slot's single block

@@ -94,6 +94,9 @@ struct emx_batch {
     int64_t tune_summary_members = 0;
     // emx_histograms_batch (emx_batch_summary.hip): tuning "batch_hist_members" / "batch_hist_rows" (0: auto); its scratch is summary's
     int64_t tune_hist_members = 0, tune_hist_rows = 0;
+    // emx_rhat_batch (emx_rhat.hip): its scratch; tuning "batch_rhat_members" (0: auto)
+    RhatScratch* rhat = nullptr;
+    int64_t tune_rhat_members = 0;
     // parallel tempering (emx_pt_set_tempering; pt_T 0: untempered): groups of pt_T members, member m at rung m % pt_T; each
     // member's beta, the box prior, L and P per walker, the L chain, the caller's prior, the swap cadence and counters
     int32_t pt_T = 0;
@@ -965,6 +968,8 @@ int emx_internal_batch_view(emx_batch* b, EmxBatchView* v) {
     v->nblobs = b->nblobs;
     v->hist_members = b->tune_hist_members;
     v->hist_rows = b->tune_hist_rows;
+    v->rhat_members = b->tune_rhat_members;
+    v->rhat = &b->rhat;
     return 0;
 }
 
@@ -1030,6 +1035,7 @@ int emx_batch_destroy(emx_batch* b) {
     if (b->stream) hipStreamSynchronize(b->stream);
     if (b->acf) emx_internal_batch_acf_release(b->acf);
     if (b->summary) emx_internal_batch_summary_release(b->summary);
+    emx_internal_rhat_release(b->rhat);
     for (void* p : {(void*)b->X, (void*)b->lp, (void*)b->acc, (void*)b->acc_count, (void*)b->seeds, (void*)b->tp0, (void*)b->tp1,
                     (void*)b->tscales, (void*)b->chain, (void*)b->chain_lp, (void*)b->fac_dev, (void*)b->col_dev, (void*)b->cb_q,
                     (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi, (void*)b->cb_nrows, (void*)b->pt_beta,
@@ -1065,6 +1071,9 @@ int emx_batch_set_tuning(emx_batch* b, const char* key, int64_t value) {
     } else if (!std::strcmp(key, "batch_hist_rows")) {
         BNEED(b, value >= 0, "batch_hist_rows: 0 (auto) or a positive number of rows");
         b->tune_hist_rows = value;
+    } else if (!std::strcmp(key, "batch_rhat_members")) {
+        BNEED(b, value >= 0, "batch_rhat_members: 0 (auto) or a positive number of members");
+        b->tune_rhat_members = value;
     } else {
         return fail(b, -1, "unknown batch tuning key '%s'", key);
     }

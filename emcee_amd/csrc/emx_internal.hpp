@@ -8,6 +8,8 @@
 #include "../../include/emx.h"
 
 struct EnsSummary;     // emx_summary's scratch (emx_batch_summary.hip), kept on the context between calls
+struct RhatScratch;    // emx_rhat's / emx_rhat_batch's scratch (emx_rhat.hip), kept on the context / the batch handle between calls
+void emx_internal_rhat_release(RhatScratch* s);      // implemented in emx_rhat.hip: frees it (emx_destroy, emx_batch_destroy)
 struct EmxChainView {
     double* chain;       // (stored, N, D) device-resident chain, or nullptr
     double* chain_lp;    // (stored, N)
@@ -22,6 +24,7 @@ struct EmxChainView {
     int64_t summary_compact;     // tuning "summary_compact"
     EnsSummary** summary;        // the context's slot (nullptr until the first call)
     int64_t hist_chunk_rows;     // tuning "hist_chunk_rows" (0: auto)
+    RhatScratch** rhat;          // the context's slot (nullptr until the first call)
 };
 
 // implemented in emx.hip
@@ -46,7 +49,7 @@ extern FftApi g_fft;
 constexpr int FFT_D2Z = 0x6a, FFT_Z2D = 0x6c;
 int fft_load(const char* path, std::string& err);      // 0, or -5 with the reason in err
 
-// ---- the batch handle seen from emx_batch_acf.hip and emx_batch_summary.hip (the handle itself lives in emx_batch.hip)
+// ---- the batch handle seen from emx_batch_acf.hip, emx_batch_summary.hip and emx_rhat.hip (the handle itself lives in emx_batch.hip)
 struct BatchAcf;     // emx_autocorr_batch's hipFFT plans and scratch, kept on the handle between calls
 struct BatchSummary;     // emx_summary_batch's scratch (emx_batch_summary.hip), kept on the handle between calls
 struct EmxBatchView {
@@ -64,6 +67,8 @@ struct EmxBatchView {
     int32_t nblobs;
     int64_t hist_members;    // tuning "batch_hist_members" (0: auto)
     int64_t hist_rows;       // tuning "batch_hist_rows" (0: auto)
+    int64_t rhat_members;    // tuning "batch_rhat_members" (0: auto)
+    RhatScratch** rhat;      // the handle's slot (nullptr until the first call)
 };
 // implemented in emx_batch.hip
 int emx_internal_batch_view(emx_batch* b, EmxBatchView* v);

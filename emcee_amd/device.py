@@ -449,6 +449,17 @@ class DeviceEnsemble:
                                       ptr(order), ptr(mx), ptr(mlp), C.byref(ns)))
         return ns.value, mean, c, order, mx, float(mlp[0])
 
+    def rhat(self, start, stop, stride=1, log_prob=False):
+        """-> (within (W), between (W), C, h): emx_rhat over the stored rows ``start, start + stride, ... < stop``, the walkers as
+        chains; W is ndim, plus one for the log-prob column with ``log_prob``"""
+        W = self.ndim + (1 if log_prob else 0)
+        within, between = np.empty(W), np.empty(W)
+        ptr = (lambda a: a.ctypes.data_as(C.c_void_p))
+        nc, h = C.c_int64(0), C.c_int64(0)
+        self._ck(self.lib.emx_rhat(self.ctx, int(start), int(stop), int(stride), int(bool(log_prob)), ptr(within), ptr(between),
+                                   C.byref(nc), C.byref(h)))
+        return within, between, nc.value, h.value
+
     def chain_minmax(self, start, stop, stride=1, plane=0):
         """-> (lo (W), hi (W), nonfinite (W) int64): emx_chain_minmax over the stored rows ``start, start + stride, ... < stop`` and
         every walker: per column the smallest and the largest finite value and the number of non-finite ones."""

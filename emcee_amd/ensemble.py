@@ -760,7 +760,11 @@ class EnsembleSampler(object):
     def get_blob_histograms(self, **kwargs):
         return self.backend.get_blob_histograms(**kwargs)
 
+    def get_rhat(self, **kwargs):
+        return self.backend.get_rhat(**kwargs)
+
     get_summary.__doc__ = Backend.get_summary.__doc__
+    get_rhat.__doc__ = Backend.get_rhat.__doc__
     get_histograms.__doc__ = Backend.get_histograms.__doc__
     get_blob_histograms.__doc__ = Backend.get_blob_histograms.__doc__
     get_blob_summary.__doc__ = Backend.get_blob_summary.__doc__

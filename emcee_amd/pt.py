@@ -52,6 +52,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import summary as _summary
 from .batch import EnsembleBatch, _trampoline
 from .ensemble import _refuse_extended_precision, walkers_independent
 from .state import State
@@ -453,6 +454,20 @@ class PTSampler(object):
         lead = (self.nbatch, self.ntemps)
         return type(r)(r.nsamples, *[None if a is None else a.reshape(lead + a.shape[1:]) for a in r[1:]])
 
+    def get_rhat(self, discard=0, thin=1, chains="walkers", log_prob=False):
+        """-> :class:`~emcee_amd.summary.RHat` of the rungs (:meth:`EnsembleBatch.get_rhat` on the underlying batch, the same
+        bits).  ``chains="walkers"``: every rung of every object is its own group, its walkers the chains, arrays ``(nbatch,
+        ntemps, ndim)``.  ``chains="members"``: each rung is pooled over the objects, ``nbatch nwalkers`` walkers a group, arrays
+        ``(ntemps, ndim)`` -- with an adaptive ladder the same rung of different objects settles at different temperatures, so
+        the pooled chains then sample different distributions and a large R-hat says only that.  ``log_prob=True`` adds the
+        stored tempered log-prob as a last column."""
+        _summary.check_chains(chains, ("walkers", "members"))
+        r = self._b._rhat(discard, thin, 0, self.nbatch * self.ntemps, self.ntemps if chains == "members" else 0, log_prob)
+        if chains == "members":
+            return r
+        lead = (self.nbatch, self.ntemps)
+        return type(r)(*[a.reshape(lead + a.shape[1:]) for a in r[:3]], r.nchains, r.length)
+
     def get_histograms(self, bins=64, range=None, discard=0, thin=1, pairs="all", pair_bins=None):
         """:meth:`EnsembleBatch.get_histograms` of every rung -> :class:`~emcee_amd.summary.BatchHistograms` with ``(nbatch, ntemps,
         ...)`` leading axes on every per-column and per-panel array.  ``range`` may additionally be ``(nbatch, ntemps, ndim, 2)``."""
@@ -499,3 +514,6 @@ class PTSampler(object):
         s = self._b.get_last_sample()
         return State(s.coords.reshape(self.nbatch, self.ntemps, self.nwalkers, self.ndim),
                      log_prob=s.log_prob.reshape(self.nbatch, self.ntemps, self.nwalkers))
+
+
+PTSampler.get_rhat.__doc__ += "\n\n        " + _summary.RHAT_DEFINITION

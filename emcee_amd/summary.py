@@ -10,7 +10,8 @@ from collections import namedtuple
 
 import numpy as np
 
-__all__ = ["BatchSummary", "Histograms", "BatchHistograms", "quantile_ranks", "lerp", "MAX_QUANTILES", "MAX_BINS", "MAX_PAIR_BINS"]
+__all__ = ["BatchSummary", "Histograms", "BatchHistograms", "RHat", "split_rhat", "quantile_ranks", "lerp", "MAX_QUANTILES", "MAX_BINS",
+           "MAX_PAIR_BINS"]
 
 MAX_QUANTILES = 16          # two ranks a quantile: the 32 ranks of one emx_summary_batch call
 
@@ -282,3 +283,93 @@ def host_histograms_batch(x, edges, pair_edges, pairs):
     counts = [np.stack([per[m][0][d] for m in range(M)]) for d in range(W)]
     pc = [np.stack([per[m][1][p] for m in range(M)]) for p in range(len(pairs))]
     return counts, pc
+
+
+# ---- split-R-hat: the definition, the host fallback of get_rhat, and what get_rhat does with the device's two arrays --------
+RHat = namedtuple("RHat", ["rhat", "within", "between", "nchains", "length"])
+RHat.__doc__ = """The result of ``get_rhat`` / :func:`split_rhat`: ``rhat``, ``within`` and ``between`` of one shape (the last axis the
+parameters, plus one for the log-prob column when asked for), ``nchains`` the number C of half-series in a group and ``length``
+their length h.  ``rhat`` is ``np.sqrt((length - 1) / length + between / within)`` bit for bit."""
+
+RHAT_DEFINITION = """The split-R-hat of Gelman and Rubin (BDA3 section 11.4, the Stan reference manual):
+
+    * Selection: the one ``get_chain(discard, thin)`` makes, ``nt`` stored steps.  ``h = nt // 2``: every series is split into its
+      first ``h`` selected samples and its last ``h``; the middle one is dropped when ``nt`` is odd.  ``nt < 4`` raises ``ValueError``.
+    * A series is one walker's values of one parameter; a group holds ``C = 2 x (walkers pooled)`` half-series ("chains") of
+      length ``h``.
+    * For every group and parameter, with ``mu_c`` the chain means and ``s_c^2`` the chain variances (``ddof = 1``):
+      ``within = mean_c s_c^2``, ``between = var_c(mu_c, ddof = 1)``, ``rhat = sqrt((h - 1) / h + between / within)``.
+      A constant group gives 0 / 0 = NaN and a non-finite sample NaN; neither raises.
+    * ``chains="walkers"``: every ensemble is its own group, its walkers the chains (the convention of the common emcee
+      converters).  ``chains="members"`` pools replicates.
+    * ``log_prob=True`` adds the same statistic of the stored log-prob series as one trailing column; a stored ``-inf`` gives NaN
+      there and nowhere else."""
+
+
+def rhat_of(within, between, length):
+    """``np.sqrt((h - 1) / h + between / within)``: the one expression every ``rhat`` comes from"""
+    h = int(length)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.sqrt((h - 1) / h + between / within)
+
+
+def check_chains(chains, allowed):
+    if chains not in allowed:
+        raise ValueError("chains must be %s; got %r" % (" or ".join(repr(a) for a in allowed), chains))
+    return chains
+
+
+def check_rhat_length(nt):
+    """-> h = nt // 2, or ValueError where fewer than 4 steps are selected"""
+    if nt < 4:
+        raise ValueError("the split R-hat needs at least 4 selected steps; got %d" % nt)
+    return nt // 2
+
+
+def split_rhat(x, log_prob=None, pool=False):
+    """-> :class:`RHat` of the array ``x``: ``(nsteps, nwalkers, ndim)``, one ensemble, result shape ``(ndim,)``; or ``(nsteps, B,
+    nwalkers, ndim)``, ``B`` ensembles -- each its own group, ``(B, ndim)``, or with ``pool=True`` all ``B nwalkers`` walkers one
+    group, ``(ndim,)``.  ``log_prob`` (``x``'s shape without the last axis) adds its column last.  This is the definition that
+    ``get_rhat`` computes next to the chain, and its fallback for chains kept on the host.
+
+    %s
+
+    The arithmetic is the device's, in NumPy's summation order, and holds far from the origin: a chain's variance is the
+    corrected two-pass form ``(G - r^2 / h) / (h - 1)`` about a centre within rounding of the chain's own mean (its first sample
+    plus the mean of the differences from it, so that a constant chain has variance 0 exactly), and ``between`` is the same form
+    over the residual chain means about one chain's centre.  Nothing is relative to ``|mean|``."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim not in (3, 4):
+        raise ValueError("x is (nsteps, nwalkers, ndim) or (nsteps, B, nwalkers, ndim); got shape %s" % (x.shape,))
+    if pool and x.ndim != 4:
+        raise ValueError("pool=True needs (nsteps, B, nwalkers, ndim); got shape %s" % (x.shape,))
+    if log_prob is not None:
+        lp = np.asarray(log_prob, dtype=np.float64)
+        if lp.shape != x.shape[:-1]:
+            raise ValueError("log_prob must have shape %s; got %s" % (x.shape[:-1], lp.shape))
+        x = np.concatenate([x, lp[..., None]], axis=-1)
+    nt, W = x.shape[0], x.shape[-1]
+    h = check_rhat_length(nt)
+    if x.ndim == 3 or pool:
+        y = x.reshape(nt, 1, -1, W)                     # member-major, then walker: the first chain is member 0's walker 0
+    else:
+        y = x
+    K = y.shape[2]
+    C = 2 * K
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        z = np.stack([y[:h], y[nt - h:]], axis=3)       # (h, G, K, 2, W)
+        x0 = z[0]
+        mu0 = x0 + (z - x0).sum(axis=0) / h
+        d = z - mu0
+        r = d.sum(axis=0)
+        var = ((d * d).sum(axis=0) - r * r / h) / (h - 1)
+        e = (mu0 - mu0[:, :1, :1, :]) + r / h
+        within = var.sum(axis=(1, 2)) / C
+        e1 = e.sum(axis=(1, 2))
+        between = ((e * e).sum(axis=(1, 2)) - e1 * e1 / C) / (C - 1)
+    if x.ndim == 3 or pool:
+        within, between = within[0], between[0]
+    return RHat(rhat_of(within, between, h), within, between, C, h)
+
+
+split_rhat.__doc__ = split_rhat.__doc__ % RHAT_DEFINITION

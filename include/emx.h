@@ -519,6 +519,14 @@ int emx_summary(emx_ctx* ctx, int32_t plane, int64_t start, int64_t stop, int64_
  * elements were read from the chain (histogram passes, times the dim tiles of each, and the compaction), *listed_out the
  * length of the compacted list (-1: none was made), *list_reads_out how many times that list was read.  Outputs may be NULL. */
 int emx_summary_info(emx_ctx* ctx, int64_t* selection_reads_out, int64_t* listed_out, int64_t* list_reads_out);
+/* Split-R-hat of the context's device-resident chain over emx_summary's selection of rows, its nwalkers walkers as chains:
+ * emx_rhat_batch's kernels (csrc/emx_rhat.hip, the definition is there) run with one member.  within_out, between_out: (W),
+ * W = ndim + (log_prob != 0), the last column being the stored log-prob series'; *nchains_out = 2 nwalkers, *length_out =
+ * h = nt / 2.  The caller forms rhat = sqrt((h - 1) / h + between / within).  The same fixed summation order, so the same bits
+ * as a batch member holding the same chain.  -1 for bad arguments (fewer than 4 selected rows among them), -2 for a device
+ * failure.  Scratch stays on the context. */
+int emx_rhat(emx_ctx* ctx, int64_t start, int64_t stop, int64_t stride, int32_t log_prob, double* within_out, double* between_out,
+             int64_t* nchains_out, int64_t* length_out);
 /* Histograms of the device-resident chain over the rows and walkers of emx_summary's selection (plane 0: coordinates, W = ndim;
  * 2: blobs, W = nblobs), counted next to the chain (csrc/emx_hist.hpp).  The bin edges are the caller's and are never recomputed on
  * the device; a value v falls in bin b iff e[b] <= v < e[b + 1], the last bin closed on the right (np.histogram's rule); NaN,
@@ -682,6 +690,8 @@ int64_t emx_host_pull_capacity(int64_t nwalkers, int32_t world, int32_t nsplits,
  *                                  scratch within ~3 GB); a chunk may begin and end inside a member
  *   "batch_summary_members" 0 (auto) emx_summary_batch: at most this many members per pass (auto: the scratch within ~512 MB);
  *                                  every member is reduced on its own in an order fixed by its shape, so no bit depends on it
+ *   "batch_rhat_members" 0 (auto)  emx_rhat_batch: at most this many members per pass (auto: the scratch within ~512 MB); every
+ *                                  sum runs in an order fixed by the shape and the pooling, so no bit depends on it
  *   "batch_hist_members" 0 (auto)  emx_histograms_batch: at most this many members per chunk (auto: the chunk's one-byte bin-code
  *                                  plane, edges and counters within ~256 MB); every count is a sum of integers, so none depends on it
  *   "batch_hist_rows"    0 (auto)  emx_histograms_batch: selected rows of a member per chunk of the code plane (auto: all of them,
@@ -880,6 +890,24 @@ int emx_histograms_batch(emx_batch* b, int32_t plane, int32_t member_lo, int32_t
                          int64_t npairs, const int32_t* pairs, const int64_t* pair_off, int64_t* pair_counts_out,
                          int64_t* nsamples_out);
 int emx_histograms_batch_info(emx_batch* b, int64_t* launches_out);
+/* Split-R-hat (Gelman-Rubin, BDA3 section 11.4) of members [member_lo, member_hi) over emx_summary_batch's selection of rows,
+ * computed next to the member-major chain (csrc/emx_rhat.hip, which states the definition): with nt selected rows and
+ * h = nt / 2 (integer), every series (one walker's values of one parameter) is split into its first h and its last h selected
+ * samples (the middle one is dropped when nt is odd): the "chains", each with its mean mu_c and ddof = 1 variance s_c^2.  A
+ * group of C chains gives  within = mean_c s_c^2  and  between = var_c(mu_c, ddof = 1);  the caller forms
+ * rhat = sqrt((h - 1) / h + between / within).
+ *   pool 0: every member is its own group (C = 2 nwalkers), groups = members;
+ *   pool P > 0: the members with equal (m - member_lo) mod P are pooled into P groups (C = 2 nwalkers members / P); the number
+ *   of members must be a multiple of P.  A batch of replicates passes 1, a tempered handle its ntemps (one group a rung).
+ * within_out, between_out: (groups, W), W = ndim + (log_prob != 0); with log_prob the last column holds the same statistic of
+ * the stored log-prob series.  *nchains_out = C, *length_out = h (either may be NULL).  A constant group gives 0 and 0, a
+ * non-finite sample NaN in its group and column.  -1 for bad arguments (nt < 4 among them), -2 for a device failure.  Scratch
+ * stays on the handle.  No floating-point atomics; every sum runs in an order fixed by (nt, nwalkers,
+ * ndim, pool): slices of a half in order, then the two halves of a walker, walkers in order, members in order.  No bit depends
+ * on the member range (pool 0), on "batch_rhat_members" (0: auto, at most this many members per pass) or on the launch shape.
+ * (Named like emx_summary_batch: the emx_batch_ prefix is the handle's own closed set.) */
+int emx_rhat_batch(emx_batch* b, int32_t member_lo, int32_t member_hi, int32_t pool, int64_t start, int64_t stop, int64_t stride,
+                   int32_t log_prob, double* within_out, double* between_out, int64_t* nchains_out, int64_t* length_out);
 /* host twin of the selection (no device): the ranks[r]-th smallest of x[0], x[stride], ..., n values, with the same key
  * transform and digit search as the kernels.  0, or -1 for bad arguments (n < 1, stride < 1, nranks outside [0, 32], a rank
  * outside [0, n)). */
