@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, "csrc", f) for f in ("emx.hip", "emx_small.hip", "emx_aux.hip", "emx_hot.hip", "emx_wide.hip", "emx_mtdev.hip", "emx_slab.hip", "emx_pvalu.hip", "emx_pmix.hip", "emx_pslab.hip", "emx_podd.hip", "emx_walkkde.hip", "emx_batch.hip", "emx_batch_cb.hip", "emx_batch_acf.hip", "emx_pt.hip", "emx_batch_summary.hip")]     # translation units, built in parallel
 SRC = SRCS[0]
 # the chain-analysis units that came after the summaries (the summaries' tests count SRCS): built and linked like SRCS
-MORE_SRCS = [os.path.join(HERE, "csrc", f) for f in ("emx_rhat.hip",)]
+MORE_SRCS = [os.path.join(HERE, "csrc", f) for f in ("emx_rhat.hip", "emx_pt_evidence.hip")]
 # EMX_BUILD_FLAVOUR=exp: the experiments flavour (-DEMX_EXPERIMENTS=1: the timing experiments' skip-phase switches, tuning "ablate",
 # tools/ablate.py) as libemx_exp.so beside the product library; load it with EMX_LIB=<path>.  The product is built without them.
 FLAVOUR = os.environ.get("EMX_BUILD_FLAVOUR", "")

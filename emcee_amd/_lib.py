@@ -272,6 +272,8 @@ SIGNATURES = {
     "emx_rhat_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P,
                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "emx_rhat": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "emx_pt_evidence": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P,
+                                  C.POINTER(C.c_int64)]),
 }
 
 

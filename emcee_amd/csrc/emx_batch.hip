@@ -97,6 +97,8 @@ struct emx_batch {
     // emx_rhat_batch (emx_rhat.hip): its scratch; tuning "batch_rhat_members" (0: auto)
     RhatScratch* rhat = nullptr;
     int64_t tune_rhat_members = 0;
+    // emx_pt_evidence (emx_pt_evidence.hip): its scratch
+    PtEvidenceScratch* pt_evidence = nullptr;
     // parallel tempering (emx_pt_set_tempering; pt_T 0: untempered): groups of pt_T members, member m at rung m % pt_T; each
     // member's beta, the box prior, L and P per walker, the L chain, the caller's prior, the swap cadence and counters
     int32_t pt_T = 0;
@@ -970,6 +972,10 @@ int emx_internal_batch_view(emx_batch* b, EmxBatchView* v) {
     v->hist_rows = b->tune_hist_rows;
     v->rhat_members = b->tune_rhat_members;
     v->rhat = &b->rhat;
+    v->pt_T = b->pt_T;
+    v->chain_L = b->chain_L;
+    v->chain_beta = b->chain_beta;
+    v->pt_evidence = &b->pt_evidence;
     return 0;
 }
 
@@ -1036,6 +1042,7 @@ int emx_batch_destroy(emx_batch* b) {
     if (b->acf) emx_internal_batch_acf_release(b->acf);
     if (b->summary) emx_internal_batch_summary_release(b->summary);
     emx_internal_rhat_release(b->rhat);
+    emx_internal_pt_evidence_release(b->pt_evidence);
     for (void* p : {(void*)b->X, (void*)b->lp, (void*)b->acc, (void*)b->acc_count, (void*)b->seeds, (void*)b->tp0, (void*)b->tp1,
                     (void*)b->tscales, (void*)b->chain, (void*)b->chain_lp, (void*)b->fac_dev, (void*)b->col_dev, (void*)b->cb_q,
                     (void*)b->cb_lp, (void*)b->cb_fac, (void*)b->cb_logu, (void*)b->cb_wi, (void*)b->cb_nrows, (void*)b->pt_beta,

@@ -10,6 +10,8 @@
 struct EnsSummary;     // emx_summary's scratch (emx_batch_summary.hip), kept on the context between calls
 struct RhatScratch;    // emx_rhat's / emx_rhat_batch's scratch (emx_rhat.hip), kept on the context / the batch handle between calls
 void emx_internal_rhat_release(RhatScratch* s);      // implemented in emx_rhat.hip: frees it (emx_destroy, emx_batch_destroy)
+struct PtEvidenceScratch;     // emx_pt_evidence's scratch (emx_pt_evidence.hip), kept on the batch handle between calls
+void emx_internal_pt_evidence_release(PtEvidenceScratch* s);      // implemented in emx_pt_evidence.hip: frees it (emx_batch_destroy)
 struct EmxChainView {
     double* chain;       // (stored, N, D) device-resident chain, or nullptr
     double* chain_lp;    // (stored, N)
@@ -49,7 +51,7 @@ extern FftApi g_fft;
 constexpr int FFT_D2Z = 0x6a, FFT_Z2D = 0x6c;
 int fft_load(const char* path, std::string& err);      // 0, or -5 with the reason in err
 
-// ---- the batch handle seen from emx_batch_acf.hip, emx_batch_summary.hip and emx_rhat.hip (the handle itself lives in emx_batch.hip)
+// ---- the batch handle seen from emx_batch_acf.hip, emx_batch_summary.hip, emx_rhat.hip and emx_pt_evidence.hip (the handle itself lives in emx_batch.hip)
 struct BatchAcf;     // emx_autocorr_batch's hipFFT plans and scratch, kept on the handle between calls
 struct BatchSummary;     // emx_summary_batch's scratch (emx_batch_summary.hip), kept on the handle between calls
 struct EmxBatchView {
@@ -69,6 +71,11 @@ struct EmxBatchView {
     int64_t hist_rows;       // tuning "batch_hist_rows" (0: auto)
     int64_t rhat_members;    // tuning "batch_rhat_members" (0: auto)
     RhatScratch** rhat;      // the handle's slot (nullptr until the first call)
+    // a tempered handle (emx_pt_evidence.hip): rungs an object (0: untempered), the L plane (B, cap, N) and the beta plane (B, cap)
+    int32_t pt_T;
+    const double* chain_L;
+    const double* chain_beta;
+    PtEvidenceScratch** pt_evidence;     // the handle's slot (nullptr until the first call)
 };
 // implemented in emx_batch.hip
 int emx_internal_batch_view(emx_batch* b, EmxBatchView* v);

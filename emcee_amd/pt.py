@@ -46,6 +46,9 @@ Evidence (:meth:`log_evidence_estimate`).  ``mean_logL[g, t]``, the mean of ``L`
 ``int(fburnin * iteration)`` and over all walkers, is computed on the device; thermodynamic integration over each object's
 ladder (:func:`thermodynamic_integration_log_evidence`) gives ``log Z`` and ptemcee's error estimate.  The ladder must be
 constant over those steps: freeze adaptation (``adaptive = False``) and discard the adaptive phase first.
+:meth:`get_evidence` reduces the stored ``L`` plane next to the chain into per-block sums (``emx_pt_evidence``) and returns the
+stepping-stone estimate (:func:`stepping_stone_log_evidence`, which states the definition) beside thermodynamic integration, each
+with a Monte-Carlo error from consecutive blocks of the chain.
 """
 import ctypes as C
 
@@ -58,7 +61,7 @@ from .ensemble import _refuse_extended_precision, walkers_independent
 from .state import State
 from .targets import BatchCallable, BatchFused, BatchKernel, BatchTarget, DeviceFused, DeviceTarget, PTFused
 
-__all__ = ["PTSampler", "default_betas", "thermodynamic_integration_log_evidence"]
+__all__ = ["PTSampler", "default_betas", "thermodynamic_integration_log_evidence", "stepping_stone_log_evidence"]
 
 _ADAPT_MAX_T = 256          # k_pt_swap keeps an adapting ladder in LDS (PT_ADAPT_MAX_T)
 
@@ -133,6 +136,106 @@ def thermodynamic_integration_log_evidence(betas, logls):
         if sel.any():
             logz[sel], dlogz[sel] = _ti(fb[sel], fl[sel])
     return logz.reshape(shape), dlogz.reshape(shape)
+
+
+EVIDENCE_DEFINITION = """The definition (``csrc/emx_pt_evidence.hip`` states the same):
+
+    * Selection: the rows ``get_chain(discard, thin)`` selects, ``nt`` of them.  ``K = nblocks``, ``bl = nt // K``: the LAST
+      ``K bl`` selected rows are used (the remainder is dropped at the early, burn-in end), cut into ``K`` consecutive blocks
+      aligned in time across all rungs of an object.  ``bl < 1`` raises ``ValueError``; ``K = 1`` gives NaN errors.
+    * Pair ``j`` (``0 ... T - 2``) covers rungs ``j`` and ``j + 1``: ``d = b[j] - b[j + 1]``; over the ``n = bl nwalkers`` values
+      ``L`` of rung ``j + 1``, the hotter one, in block ``k``: ``a = d L``, ``M = max a``, ``S = sum exp(a - M)``; the block's
+      log-ratio is ``M + log(S / n)``.  ``L = -inf`` contributes 0; a block of nothing else gives ``-inf``, never NaN; a NaN
+      sample makes the block NaN.
+    * The whole selection merges the blocks in block order: ``M* = max_k M``, ``S* = sum_k S_k exp(M_k - M*)``,
+      ``log_ratios[g, j] = M* + log(S* / (K n))``: the forward stepping-stone estimate of ``Z(b[j]) / Z(b[j + 1])`` (Xie et al.
+      2011), whose weights are bounded by the hotter rung's own maximum.
+    * ``mean_logl[g, t]``: the blocks' sums of ``L`` added in block order, over ``K n``.  ``tail[g] = b[T - 1] mean_logl[g, T - 1]``
+      when ``b[T - 1] > 0`` -- the extrapolation thermodynamic integration makes when it appends a rung at 0 -- else 0.
+    * ``logz_ss = sum_j log_ratios[:, j] + tail`` (``j`` ascending); ``block_logz_ss[:, k]`` the same from block ``k`` alone;
+      ``err_ss = std_k(block_logz_ss, ddof=1) / sqrt(K)``.  ``logz_ti, dlogz_ti =``
+      :func:`thermodynamic_integration_log_evidence` ``(b, mean_logl)``, ``block_logz_ti`` the same from each block's means,
+      ``err_ti`` formed like ``err_ss``.  With one rung there are no pairs: ``logz_ss = tail``."""
+
+
+def _check_nblocks(nblocks):
+    if isinstance(nblocks, (bool, np.bool_)) or int(nblocks) != nblocks or nblocks < 1:
+        raise ValueError("nblocks must be an integer >= 1; got %r" % (nblocks,))
+    return int(nblocks)
+
+
+def _block_length(nt, K):
+    if nt // K < 1:
+        raise ValueError("nblocks = %d blocks need at least as many selected steps; got %d" % (K, nt))
+    return nt // K
+
+
+def _std_error(blocks):
+    """std over the last axis (ddof = 1) / sqrt(K); NaN for K = 1"""
+    K = blocks.shape[-1]
+    if K < 2:
+        return np.full(blocks.shape[:-1], np.nan)
+    with np.errstate(invalid="ignore"):
+        return np.std(blocks, axis=-1, ddof=1) / np.sqrt(K)
+
+
+def _evidence_from_blocks(b, A, M, S, bl, n):
+    """the host's half of the definition: the ladders ``b`` (G, T), the blocks' sums of L ``A`` (G, T, K) and the pairs' ``M`` and
+    ``S`` (G, T - 1, K) of blocks of ``n`` samples -> :class:`~emcee_amd.summary.Evidence`"""
+    G, T, K = A.shape
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        block_lr = M + np.log(S / n)                                        # (G, T - 1, K)
+        Ms = np.fmax.reduce(M, axis=-1, initial=-np.inf)
+        w = np.where(M == -np.inf, S, S * np.exp(M - Ms[..., None]))        # a block without weight holds 0 (NaN for a NaN sample)
+        Ss, tot = np.zeros((G, T - 1)), np.zeros((G, T))
+        for k in range(K):
+            Ss = Ss + w[..., k]
+            tot = tot + A[..., k]
+        log_r = Ms + np.log(Ss / (K * n))
+        mean = tot / (K * n)
+        block_mean = A / n                                                  # (G, T, K)
+        ends_above = b[:, -1] > 0
+        tail = np.where(ends_above, b[:, -1] * np.where(ends_above, mean[:, -1], 0.0), 0.0)
+        block_tail = np.where(ends_above[:, None], b[:, -1:] * np.where(ends_above[:, None], block_mean[:, -1], 0.0), 0.0)
+        logz, block_logz = np.zeros(G), np.zeros((G, K))
+        for j in range(T - 1):
+            logz = logz + log_r[:, j]
+            block_logz = block_logz + block_lr[:, j]
+        logz, block_logz = logz + tail, block_logz + block_tail
+        ti, dti = thermodynamic_integration_log_evidence(b, mean)
+        block_ti = np.stack([thermodynamic_integration_log_evidence(b, block_mean[..., k])[0] for k in range(K)], axis=-1)
+    return _summary.Evidence(logz, _std_error(block_logz), ti, dti, _std_error(block_ti), log_r, mean, tail, block_logz, block_ti, b, K,
+                             int(bl))
+
+
+def stepping_stone_log_evidence(betas, logls, nblocks=8):
+    """-> :class:`~emcee_amd.summary.Evidence` from stored log-likelihoods: ``logls`` ``(..., T, nsteps, nwalkers)`` (e.g.
+    :meth:`PTSampler.get_log_likelihood`), ``betas`` ``(T,)`` or ``(..., T)``, decreasing.  :meth:`PTSampler.get_evidence` computes
+    the same next to the chain; this is its definition on arrays.  The leading axes ``...`` are flattened into ``G``.
+
+    %s"""
+    logls = np.asarray(logls, dtype=np.float64)
+    if logls.ndim < 3:
+        raise ValueError("logls is (..., T, nsteps, nwalkers); got shape %s" % (logls.shape,))
+    K = _check_nblocks(nblocks)
+    T, nt, N = logls.shape[-3:]
+    bl = _block_length(nt, K)
+    n = bl * N
+    betas = np.asarray(betas, dtype=np.float64)
+    if betas.shape[-1:] != (T,):
+        raise ValueError("betas holds %s values a ladder for %d rungs" % (betas.shape[-1:], T))
+    b = np.ascontiguousarray(np.broadcast_to(betas, logls.shape[:-2])).reshape(-1, T)
+    x = logls.reshape((-1, T, nt, N))[:, :, nt - K * bl:].reshape(-1, T, K, n)
+    with np.errstate(invalid="ignore", over="ignore"):
+        A = x.sum(axis=-1)
+        d = b[:, :-1] - b[:, 1:]
+        a = d[:, :, None, None] * x[:, 1:]
+        M = np.fmax.reduce(a, axis=-1, initial=-np.inf)                     # a NaN is passed over here and met in S
+        S = np.where(a == -np.inf, 0.0, np.exp(a - M[..., None])).sum(axis=-1)
+    return _evidence_from_blocks(b, A, M, S, bl, n)
+
+
+stepping_stone_log_evidence.__doc__ %= EVIDENCE_DEFINITION
 
 
 class PTSampler(object):
@@ -481,8 +584,69 @@ class PTSampler(object):
         split = (lambda arrays: [a.reshape(lead + a.shape[1:]) for a in arrays])
         return type(r)(r.nsamples, split(r.edges), split(r.counts), r.pairs, split(r.pair_edges), split(r.pair_counts))
 
+    def _has_normalised_prior(self):
+        return not (self._box is None and self._prior is None and not (self._fused is not None and self._fused.has_prior))
+
+    def _evidence_rows(self, discard, thin, nblocks, need_prior=False):
+        """-> (start, stop, nt, K, bl) after the argument checks (no device is touched)"""
+        if int(thin) != thin or thin < 1:
+            raise ValueError("thin must be an integer >= 1; got %r" % (thin,))
+        if int(discard) != discard or discard < 0:
+            raise ValueError("discard must be an integer >= 0; got %r" % (discard,))
+        K = _check_nblocks(nblocks)
+        if need_prior and not self._has_normalised_prior():
+            raise ValueError("the evidence needs a normalised prior: with log_prior=None the prior is flat and improper")
+        it = self.iteration
+        if it <= 0:
+            raise AttributeError("you must run the sampler with 'store == True' before accessing the results")
+        thin, discard = int(thin), int(discard)
+        start = min(discard + thin - 1, it)
+        nt = len(range(start, it, thin))
+        return start, it, nt, K, _block_length(nt, K)
+
+    def _evidence_blocks(self, discard=0, thin=1, nblocks=8, lo=0, hi=None):
+        """``emx_pt_evidence`` on objects [lo, hi) -> (sum_L (objects, T, K), amax (objects, T - 1, K), sexp (objects, T - 1, K),
+        betas (objects, T), ladder_changed (objects), block length): what the device makes of the L plane."""
+        hi = self.nbatch if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo < hi <= self.nbatch:
+            raise ValueError("objects [%d, %d) outside the %d of the sampler" % (lo, hi, self.nbatch))
+        start, it, _, K, bl = self._evidence_rows(discard, thin, nblocks)
+        G, T = hi - lo, self.ntemps
+        A, M, S = np.empty((G, T, K)), np.empty((G, T - 1, K)), np.empty((G, T - 1, K))
+        b, changed = np.empty((G, T)), np.zeros(G, dtype=np.int32)
+        ptr = (lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None)
+        rows = C.c_int64(0)
+        self._ck(self._b._lib().emx_pt_evidence(self._h, lo, hi, start, it, int(thin), K, ptr(A), ptr(M), ptr(S), ptr(b), ptr(changed),
+                                                C.byref(rows)))
+        assert rows.value == bl
+        return A, M, S, b, changed, bl
+
+    def get_evidence(self, discard=0, thin=1, nblocks=8):
+        """-> :class:`~emcee_amd.summary.Evidence`: every object's log-evidence by the stepping-stone estimator and by
+        thermodynamic integration, each with a Monte-Carlo error from ``nblocks`` consecutive blocks of the selected steps
+        (``get_chain``'s ``discard`` / ``thin``).  The stored log-likelihood plane is reduced next to the chain
+        (``emx_pt_evidence``); only ``nbatch ntemps nblocks`` sums cross to the host.  The stepping-stone estimate needs far fewer
+        rungs than thermodynamic integration, and stays finite where the likelihood is ``-inf`` on part of the prior (there the
+        hottest rung's mean ``L``, and with it ``logz_ti``, is ``-inf``).  Needs a normalised prior (a box, or a prior callable),
+        and a ladder that did not change over the used steps: freeze adaptation (``adaptive = False``) and discard the
+        adaptive phase first.  :func:`stepping_stone_log_evidence` is the same on :meth:`get_log_likelihood`'s array.  A device
+        failure raises :class:`emcee_amd._lib.EmxError` (no fallback).
+
+        %s"""
+        start, _, nt, K, bl = self._evidence_rows(discard, thin, nblocks, need_prior=True)
+        A, M, S, b, changed, bl = self._evidence_blocks(discard, thin, K)
+        if changed.any():
+            bad = np.flatnonzero(changed)
+            raise ValueError("object %d%s: the ladder changed within the %d used steps from stored step %d on: the evidence needs one "
+                             "ladder. Freeze adaptation (adaptive = False), run on, and discard the adaptive phase (discard)"
+                             % (bad[0], "" if len(bad) == 1 else " (and %d more)" % (len(bad) - 1), K * bl,
+                                start + (nt - K * bl) * int(thin)))
+        return _evidence_from_blocks(b, A, M, S, bl, bl * self.nwalkers)
+
     def mean_log_likelihood(self, discard=0):
-        """``(nbatch, ntemps)``: the mean of ``L`` over the stored steps from ``discard`` on and every walker, on the device."""
+        """``(nbatch, ntemps)``: the mean of ``L`` over the stored steps from ``discard`` on and every walker, on the device
+        (:meth:`get_evidence` gives the same per block, with ``thin``, and the evidence estimates made from it)."""
         it = self.iteration
         if it <= 0:
             raise AttributeError("you must run the sampler with 'store == True' before accessing the results")
@@ -496,7 +660,8 @@ class PTSampler(object):
     def log_evidence_estimate(self, fburnin=0.1):
         """-> ``(logZ, dlogZ)``, each ``(nbatch,)``: thermodynamic integration over each object's ladder of the mean ``L`` of the
         stored steps after ``int(fburnin * iteration)``.  Needs a normalised prior (a box, or a prior callable), and a ladder
-        that did not change over those steps."""
+        that did not change over those steps.  :meth:`get_evidence` adds the stepping-stone estimate, which needs far fewer
+        rungs, and the Monte-Carlo error of both."""
         if self._box is None and self._prior is None and not (self._fused is not None and self._fused.has_prior):
             raise ValueError("the evidence needs a normalised prior: with log_prior=None the prior is flat and improper")
         discard = int(fburnin * self.iteration)
@@ -517,3 +682,4 @@ class PTSampler(object):
 
 
 PTSampler.get_rhat.__doc__ += "\n\n        " + _summary.RHAT_DEFINITION
+PTSampler.get_evidence.__doc__ %= EVIDENCE_DEFINITION.replace("\n", "\n    ")

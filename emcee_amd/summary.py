@@ -10,8 +10,8 @@ from collections import namedtuple
 
 import numpy as np
 
-__all__ = ["BatchSummary", "Histograms", "BatchHistograms", "RHat", "split_rhat", "quantile_ranks", "lerp", "MAX_QUANTILES", "MAX_BINS",
-           "MAX_PAIR_BINS"]
+__all__ = ["BatchSummary", "Histograms", "BatchHistograms", "RHat", "Evidence", "split_rhat", "quantile_ranks", "lerp", "MAX_QUANTILES",
+           "MAX_BINS", "MAX_PAIR_BINS"]
 
 MAX_QUANTILES = 16          # two ranks a quantile: the 32 ranks of one emx_summary_batch call
 
@@ -290,6 +290,16 @@ RHat = namedtuple("RHat", ["rhat", "within", "between", "nchains", "length"])
 RHat.__doc__ = """The result of ``get_rhat`` / :func:`split_rhat`: ``rhat``, ``within`` and ``between`` of one shape (the last axis the
 parameters, plus one for the log-prob column when asked for), ``nchains`` the number C of half-series in a group and ``length``
 their length h.  ``rhat`` is ``np.sqrt((length - 1) / length + between / within)`` bit for bit."""
+
+Evidence = namedtuple("Evidence", ["logz_ss", "err_ss", "logz_ti", "dlogz_ti", "err_ti", "log_ratios", "mean_logl", "tail", "block_logz_ss",
+                                   "block_logz_ti", "betas", "nblocks", "block_length"])
+Evidence.__doc__ = """The result of ``PTSampler.get_evidence`` / :func:`emcee_amd.pt.stepping_stone_log_evidence`, for ``G`` objects,
+``T`` rungs and ``K = nblocks`` blocks of ``block_length`` selected steps: ``logz_ss`` ``(G,)`` the stepping-stone log-evidence and
+``err_ss`` its Monte-Carlo error (the standard error of the ``K`` single-block estimates ``block_logz_ss`` ``(G, K)``; NaN for
+``K = 1``); ``logz_ti`` / ``dlogz_ti`` thermodynamic integration and ptemcee's discretisation estimate, ``err_ti`` its Monte-Carlo
+error from ``block_logz_ti`` ``(G, K)``; ``log_ratios`` ``(G, T - 1)`` the estimates of ``log Z(b[j]) / Z(b[j + 1])``;
+``mean_logl`` ``(G, T)`` the mean log-likelihood of every rung; ``tail`` ``(G,)`` the part of ``logz_ss`` extrapolated from the
+hottest rung to ``beta = 0`` (0 when the ladder ends there); ``betas`` ``(G, T)`` the ladder used."""
 
 RHAT_DEFINITION = """The split-R-hat of Gelman and Rubin (BDA3 section 11.4, the Stan reference manual):
 

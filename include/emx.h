@@ -950,6 +950,19 @@ int emx_pt_swap(emx_batch* b);
 int emx_pt_swap_counts(emx_batch* b, uint64_t* attempts, uint64_t* accepts);
 /* out (B): the mean of each member's L chain over rows start, start + stride, ... < stop and every walker, on the device */
 int emx_pt_mean_loglike(emx_batch* b, int64_t start, int64_t stop, int64_t stride, double* out);
+/* The per-block sums behind PTSampler.get_evidence (csrc/emx_pt_evidence.hip, which states the definition) of objects
+ * [g_lo, g_hi) over the stored rows start, start + stride, ... < stop (nt of them): with K = nblocks and bl = nt / K, the last K bl
+ * selected rows are cut into K consecutive blocks of n = bl nwalkers samples a rung.  sum_L (objects, T, K): the sum of L over
+ * block k of rung t.  amax / sexp (objects, T - 1, K): for pair j of rungs j and j + 1, with d = b[j] - b[j + 1] and a = d L over
+ * the samples of rung j + 1, M = max a and S = sum exp(a - M) (L = -inf: no weight; a block of nothing else: M = -inf, S = 0; a NaN
+ * sample: S NaN).  betas (objects, T): the stored ladder of the first used row; ladder_changed (objects): 1 where some used row's
+ * ladder differs from it in any bit.  *block_rows = bl (may be NULL).  The caller merges the blocks (the stepping-stone and the
+ * thermodynamic-integration evidence and their Monte-Carlo errors).  The L plane is read once; no floating-point atomics; every
+ * sum and every (M, S) merge runs in an order fixed by (nt, nblocks, nwalkers, stride): no bit depends on the object range or the
+ * launch shape.  -1 for bad arguments (an untempered handle, no stored chain, rows outside the stored ones, nblocks outside
+ * [1, nt]), -2 for a device failure. */
+int emx_pt_evidence(emx_batch* b, int64_t g_lo, int64_t g_hi, int64_t start, int64_t stop, int64_t stride, int32_t nblocks,
+                    double* sum_L, double* amax, double* sexp, double* betas, int32_t* ladder_changed, int64_t* block_rows);
 /* the tempered state: coords (B, nwalkers, ndim), L and P (B, nwalkers); set computes lp with the formula above and each member's
  * current beta */
 int emx_pt_set_state(emx_batch* b, const double* coords, const double* loglike, const double* logprior);
