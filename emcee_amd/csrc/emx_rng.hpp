@@ -4,7 +4,10 @@
 //
 // The native mode replaces the reference's serial MT19937 consumer
 // (red_blue.py:80 shuffle, stretch.py:30-32, red_blue.py:100) with draws that are a pure
-// function of (seed, step, walker): same distributions, different stream.
+// function of (seed, step, walker): a different stream with the same distributions of the draws -- except the split, which is a
+// bijection from a small keyed family with the reference's exact set sizes, NOT a uniform shuffle below a few thousand walkers
+// (valid all the same: it does not depend on the state).  Measured in profiles/philox_split_statistics.md; the stream's
+// definition in words and in NumPy is tests/philox_ref.py.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -139,9 +142,12 @@ EMX_HD uint64_t bounded64(uint32_t a, uint32_t b, uint64_t n) {
 // ---------------------------------------------------------------------------------------
 // Keyed bijection on [0, n): the per-step random split.  Walker w belongs to
 // sub-ensemble  perm(w) % nsplits  and is member number  perm(w) / nsplits  of it, which
-// gives exactly the set sizes of `arange(n) % nsplits` shuffled (red_blue.py:78-80).
-// Built from invertible k-bit mixers (xorshift / odd multiply-add), cycle-walked for
-// non-power-of-two n.
+// gives exactly the set sizes of `arange(n) % nsplits` shuffled (red_blue.py:78-80) -- the sizes, not the shuffle: the
+// bijection comes from a small keyed family (three odd multiply-adds with multipliers 5 mod 8, i.e. the identity mod 4,
+// and xorshifts on k bits), and for n below a few thousand some pairs of walkers share a set far more or less often
+// than under a uniform shuffle (profiles/philox_split_statistics.md; 0.36 against 0.49 at n = 64).  Any split that
+// does not depend on the state keeps detailed balance, and every ordered pair of walkers still meets
+// (tests/test_philox_ref_cpu.py).  Cycle-walked for non-power-of-two n.
 // ---------------------------------------------------------------------------------------
 struct PermKey {
     uint64_t n;

@@ -58,7 +58,10 @@ def test_plans_differ_between_steps_and_seeds():
 
 
 def test_split_pair_statistics_over_steps():
-    """Two fixed walkers share a sub-ensemble ~(n/2-1)/(n-1) of the time, like a uniform shuffle."""
+    """THIS pair of walkers, (3, 17) of 64, shares a sub-ensemble about (n/2-1)/(n-1) of the time and walker 0 is in set 0 about
+    half of it, as under a uniform shuffle.  That is not so of every pair: the split is a keyed bijection from a small family, not
+    a uniform shuffle (at this size pairs range from 0.36 to 0.53 against 0.49; profiles/philox_split_statistics.md,
+    tests/test_philox_ref_cpu.py, which measures all pairs and asserts what the sampler needs: that every ordered pair meets)."""
     N = 64
     same = 0
     first = 0
