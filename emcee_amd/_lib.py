@@ -272,6 +272,9 @@ SIGNATURES = {
     "emx_rhat_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P,
                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "emx_rhat": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "emx_pt_set_target_fused_blobs": (C.c_int, [_P, PT_FUSED_FN, C.c_int32, _P, C.c_int32]),
+    "emx_pt_fused_check_blobs": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(MoveDesc), C.c_int32, C.c_char_p, C.c_int32]),
+    "emx_pt_get_blobs": (C.c_int, [_P, _dp]),
     "emx_pt_evidence": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P,
                                   C.POINTER(C.c_int64)]),
 }

@@ -92,9 +92,9 @@ class EnsembleBatch(object):
         msg = C.create_string_buffer(256)
         arr = (_lib.MoveDesc * len(self._descs))(*self._descs)
         self.nblobs = int(getattr(self._targets[0], "nblobs", 0)) if isinstance(self._targets[0], BatchTarget) else 0
-        if self.nblobs and self._tempered:
-            raise TypeError("a tempered batch records no blobs (nblobs = %d)" % self.nblobs)
-        if lib.emx_check_batch_blobs(self.nwalkers, self.ndim, self._targets[0].kind, len(self._descs), arr, self.nblobs, msg, 256) != 0:
+        # (a PTFused's blobs live in the tempered kernel's LDS map, whose bound depends on ntemps: PTSampler checks them)
+        check_blobs = 0 if isinstance(self._targets[0], PTFused) else self.nblobs
+        if lib.emx_check_batch_blobs(self.nwalkers, self.ndim, self._targets[0].kind, len(self._descs), arr, check_blobs, msg, 256) != 0:
             raise ValueError("EnsembleBatch: %s" % msg.value.decode())
         if seeds is None:
             seeds = np.random.randint(0, 2 ** 32, size=self.nbatch, dtype=np.uint64)
@@ -222,16 +222,20 @@ class EnsembleBatch(object):
         ptr = (lambda a: None if a is None else a.ctypes.data_as(C.c_void_p))
         self._ck(self._lib().emx_batch_set_target(h, kind, ptr(p0), ptr(p1), ptr(scales), int(self._per_member)))
 
-    def _bind_callback(self, h):
+    def _bind_callback(self, h, tempered=False):
+        """the handle's callback.  A tempered handle takes a callback with blobs once it is tempered (emx_pt_set_tempering refuses a
+        handle that already has blobs), so PTSampler's handle is first bound as if the target had none -- that binding is never
+        called -- and PTSampler binds again with ``tempered=True`` after emx_pt_set_tempering."""
         t = self._targets[0]
-        ftype = _lib.BATCH_LOG_PROB_BLOBS_FN if self.nblobs else _lib.BATCH_LOG_PROB_FN
+        nblobs = self.nblobs if tempered or not self._tempered else 0
+        ftype = _lib.BATCH_LOG_PROB_BLOBS_FN if nblobs else _lib.BATCH_LOG_PROB_FN
         if isinstance(t, BatchKernel):
             fn = t.fn_ptr if isinstance(t.fn_ptr, ftype) else C.cast(t.fn_ptr, ftype)
             user = t.user_ptr if isinstance(t.user_ptr, C.c_void_p) else C.c_void_p(t.user_ptr)
         else:
-            fn, user = ftype(_trampoline(t.fn, self.device, self._cb_box, self.nblobs)), None
+            fn, user = ftype(_trampoline(t.fn, self.device, self._cb_box, nblobs)), None
         self._cb_keep = fn                # the library holds the pointer: keep the object alive
-        if self.nblobs:
+        if nblobs:
             self._ck(self._lib().emx_set_batch_target_callback_blobs(h, fn, user, self.nblobs))
         else:
             self._ck(self._lib().emx_set_batch_target_callback(h, fn, user))
@@ -258,6 +262,8 @@ class EnsembleBatch(object):
         t, lib = self._targets[0], self._lib()
         if t.ndata is not None:           # a data target: one count an object, every rung of an object its object's
             self._bind_fused_target(h, _lib.PT_FUSED_FN, lib.emx_pt_set_target_fused_data, counts=t.ndata, repeat=self._pt_ntemps)
+        elif self.nblobs:
+            self._bind_fused_target(h, _lib.PT_FUSED_FN, lib.emx_pt_set_target_fused_blobs, self.nblobs)
         else:
             self._bind_fused_target(h, _lib.PT_FUSED_FN, lib.emx_pt_set_target_fused)
 

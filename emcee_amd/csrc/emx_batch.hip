@@ -165,9 +165,9 @@ const char* shape_refusal(int64_t N, int32_t D, int32_t target, int32_t nmoves, 
         snprintf(buf, n, "a batch target carries 1 ... %d blobs a sample; got %d", BATCH_MAX_BLOBS, nblobs);
         return buf;
     }
-    if (nblobs > 0 && target != EMX_TARGET_DEVICE_CALLBACK && target != EMX_TARGET_FUSED_USER)
-        return "blobs come from a batched callback (emx_set_batch_target_callback_blobs) or a fused user target "
-               "(emx_set_batch_target_fused_blobs): the built-in and the tempered targets have none";
+    if (nblobs > 0 && target != EMX_TARGET_DEVICE_CALLBACK && target != EMX_TARGET_FUSED_USER && target != EMX_TARGET_FUSED_PT)
+        return "blobs come from a batched callback (emx_set_batch_target_callback_blobs), a fused user target "
+               "(emx_set_batch_target_fused_blobs) or a fused tempered target (emx_pt_set_target_fused_blobs): the built-in targets have none";
     if (N > 4096 || D > 256) {
         snprintf(buf, n, "nwalkers x ndim = %lld x %d is outside the one-workgroup kernel (nwalkers <= 4096, ndim <= 256)", (long long)N, D);
         return buf;
@@ -447,21 +447,23 @@ int launch(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t st
 // ---- fused tempered targets (EMX_TARGET_FUSED_PT; emx_pt_fused.hpp) ----
 
 // staging rows a rung: the largest split, halved until the object fits with one plan step (k_pt_run then runs a half-step in chunks)
-int64_t pt_stage_rows(int32_t T, int64_t N, int32_t D, int32_t nmoves, const emx_move_desc* moves) {
+int64_t pt_stage_rows(int32_t T, int64_t N, int32_t D, int32_t nmoves, const emx_move_desc* moves, int32_t nblobs = 0) {
     int64_t R = fused_stage_rows(N, nmoves, moves);
-    while (R > 1 && pt_lds_layout(T, N, D, 1, R).total > SMALL_LDS_MAX) R = (R + 1) / 2;
+    while (R > 1 && pt_lds_layout(T, N, D, 1, R, nblobs).total > SMALL_LDS_MAX) R = (R + 1) / 2;
     return R;
 }
 
 // one workgroup's LDS for an object of T rungs with `plan_steps` plan steps; the staging rows a rung: the largest split
-size_t pt_fused_lds(int32_t T, int64_t N, int32_t D, int32_t nmoves, const emx_move_desc* moves, int plan_steps) {
-    return pt_lds_layout(T, N, D, plan_steps, pt_stage_rows(T, N, D, nmoves, moves)).total;
+size_t pt_fused_lds(int32_t T, int64_t N, int32_t D, int32_t nmoves, const emx_move_desc* moves, int plan_steps, int32_t nblobs = 0) {
+    return pt_lds_layout(T, N, D, plan_steps, pt_stage_rows(T, N, D, nmoves, moves, nblobs), nblobs).total;
 }
 
 // nullptr when one workgroup holds the object with at least one plan step, else why not (the bytes needed)
-const char* pt_fused_refusal(int32_t T, int64_t N, int32_t D, int32_t nmoves, const emx_move_desc* moves, char* buf, size_t n) {
+// (nblobs > 0: a shape that fits only without the blobs is refused in words of its own)
+const char* pt_fused_refusal(int32_t T, int64_t N, int32_t D, int32_t nmoves, const emx_move_desc* moves, char* buf, size_t n,
+                             int32_t nblobs = 0) {
     if (T < 1) return "ntemps must be >= 1";
-    if (const char* why = shape_refusal(N, D, EMX_TARGET_FUSED_PT, nmoves, moves, buf, n)) return why;
+    if (const char* why = shape_refusal(N, D, EMX_TARGET_FUSED_PT, nmoves, moves, buf, n, nblobs)) return why;
     // (the coordinates alone bound T N D: the products below stay far inside 64 bits)
     const double coords = (double)T * (double)N * (double)D * 8.0;
     const size_t need = coords > 1e12 ? (size_t)1 << 40 : pt_fused_lds(T, N, D, nmoves, moves, 1);
@@ -471,12 +473,24 @@ const char* pt_fused_refusal(int32_t T, int64_t N, int32_t D, int32_t nmoves, co
                  T, (long long)N, D, need, SMALL_LDS_MAX);
         return buf;
     }
+    if (nblobs > 0) {
+        const size_t with = pt_fused_lds(T, N, D, nmoves, moves, 1, nblobs);
+        if (with > SMALL_LDS_MAX) {
+            snprintf(buf, n, "ntemps x nwalkers x ndim = %d x %lld x %d with a fused tempered target and %d blobs a walker does not fit one "
+                             "workgroup's LDS (%zu bytes > %zu; %zu without the blobs): run it on the callback path (targets.BatchKernel)",
+                     T, (long long)N, D, nblobs, with, SMALL_LDS_MAX, need);
+            return buf;
+        }
+    }
     return nullptr;
 }
 
 // what a fused tempered target's launcher answered, as the handle's error; 0: it launched (or probed)
-int pt_fused_launcher_refusal(emx_batch* b, int rc, int movesel, bool data = false) {
+int pt_fused_launcher_refusal(emx_batch* b, int rc, int movesel, bool data = false, int nblobs = 0) {
     if (rc == 0) return 0;
+    if (rc == 4)
+        return fail(b, -1, "the fused tempered target's launcher was compiled for another number of blobs than the %d asked for "
+                           "(EMX_FUSED_PT_TARGET_BLOBS's nblobs; EMX_FUSED_PT_TARGET and the data form have none)", nblobs);
     if (rc == 1 && data)
         return fail(b, -8, "the fused tempered data target's launcher was built against another version of emx_pt_fused_data.hpp, or is "
                            "not an EMX_FUSED_PT_DATA_TARGET launcher (the library has EMX_FUSED_PT_DATA_ABI 0x%x and %zu bytes of kernel "
@@ -560,6 +574,15 @@ int launch_pt(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t
     a.adapt_t0 = (long long)b->pt_updates;
     a.user = b->ptf_user;
     a.ndata = b->ptf_data ? reinterpret_cast<const long long*>(b->ptf_ndata) : nullptr;
+    const int32_t K = b->nblobs;
+    if (K > 0) {
+        BNEED(b, !b->ptf_data && b->blobs != nullptr, "fused tempered target with blobs without their storage (emx_pt_set_target_fused_blobs)");
+        BNEED(b, !a.store || b->chain_blobs != nullptr, "no blob plane (emx_batch_chain_config)");
+        a.nblobs = K;
+        a.blobs = b->blobs;
+        a.chain_blobs = b->chain_blobs;
+        a.stage_rows = (int32_t)pt_stage_rows(T, b->N, b->D, nm, b->moves.data(), K);
+    }
     if (any_gauss && nsteps > 0) {
         // the step-size factors and the sequential column: launch's host arithmetic
         std::vector<double> facs((size_t)b->B * nsteps, 1.0);
@@ -596,16 +619,17 @@ int launch_pt(emx_batch* b, int64_t i0, int64_t nsteps, int32_t thin_by, int32_t
     int plan_steps = (int)std::max<int64_t>(1, std::min<int64_t>(64, threads / ((int64_t)T * b->N)));
     if (b->tune_threads > 0) threads = (int)b->tune_threads;
     if (b->tune_plan_steps > 0) plan_steps = (int)b->tune_plan_steps;
-    while (plan_steps > 1 && pt_fused_lds(T, b->N, b->D, nm, b->moves.data(), plan_steps) > SMALL_LDS_MAX) plan_steps = (plan_steps + 1) / 2;
+    while (plan_steps > 1 && pt_fused_lds(T, b->N, b->D, nm, b->moves.data(), plan_steps, K) > SMALL_LDS_MAX) plan_steps = (plan_steps + 1) / 2;
     a.plan_steps = plan_steps;
-    const size_t lds = pt_fused_lds(T, b->N, b->D, nm, b->moves.data(), plan_steps);
+    const size_t lds = pt_fused_lds(T, b->N, b->D, nm, b->moves.data(), plan_steps, K);
     BNEED(b, threads <= PT_RUN_MAX_THREADS, "batch_threads: at most %d with a fused tempered target", PT_RUN_MAX_THREADS);
     BNEED(b, lds <= SMALL_LDS_MAX && threads >= 64 && threads % 64 == 0,
           "fused tempered launch shape: %d threads and %d plan steps need %zu bytes of LDS", threads, plan_steps, lds);
     const int movesel = (nm == 1 && b->moves[0].kind == EMX_MOVE_STRETCH) ? (int)EMX_MOVE_STRETCH : SMALL_ANY_MOVE;
     auto fl = fused_desc<emx_pt_fused_launch>(b, b->ptf_data ? EMX_FUSED_PT_DATA_ABI : EMX_FUSED_PT_ABI, sizeof(PtRunArgs), movesel, &a, b->B / T, threads,
                                               lds, b->ptf_user);
-    if (int rc = pt_fused_launcher_refusal(b, b->ptf_fn(&fl), movesel, b->ptf_data)) return rc;
+    fl.nblobs = K;
+    if (int rc = pt_fused_launcher_refusal(b, b->ptf_fn(&fl), movesel, b->ptf_data, K)) return rc;
     b->last_threads = threads;
     b->last_plan_steps = plan_steps;
     ++b->launches;
@@ -679,6 +703,12 @@ int swap_pass(emx_batch* b, uint64_t step, int64_t row, bool swap) {
     s.lag = b->pt_lag;
     s.time = b->pt_time;
     s.adapt_t = (long long)b->pt_updates;
+    if (b->nblobs > 0) {
+        BNEED(b, b->blobs != nullptr && (row < 0 || b->chain_blobs != nullptr), "no blob plane (emx_batch_chain_config)");
+        s.blobs = b->blobs;
+        s.chain_blobs = b->chain_blobs;
+        s.nblobs = b->nblobs;
+    }
     BHIP(b, pt_swap_launch(b->B / b->pt_T, b->stream, s));
     ++b->launches;
     if (s.adapt) ++b->pt_updates;
@@ -694,9 +724,9 @@ int eval_callback(emx_batch* b) {
         } else {
             BHIP(b, hipMemsetAsync(b->pt_P, 0, (size_t)b->B * b->N * 8, b->stream));
         }
-        if (int rc = call_back(b, b->X, b->N, b->pt_L)) return rc;
+        if (int rc = call_back(b, b->X, b->N, b->pt_L, b->blobs)) return rc;      // the state's blobs by the same call
         BHIP(b, pt_init_launch(b->X, b->lp, b->pt_L, b->pt_P, b->pt_beta, b->pr_fn ? nullptr : b->pt_lo, b->pt_hi, b->status, b->B,
-                               (int32_t)b->N, b->D, b->stream));
+                               (int32_t)b->N, b->D, b->stream, b->blobs, b->nblobs));
         ++b->launches;
         return 0;
     }
@@ -876,7 +906,6 @@ int run_callback(emx_batch* b, int64_t total, int32_t thin_by, int32_t store) {
 // block is dropped (its width changes); nothing may be stored yet when K > 0 (the plane would miss those rows)
 int set_blobs(emx_batch* b, int32_t K) {
     BNEED(b, K >= 0 && K <= BATCH_MAX_BLOBS, "a batch target carries 1 ... %d blobs a sample; got %d", BATCH_MAX_BLOBS, K);
-    BNEED(b, K == 0 || b->pt_T == 0, "a tempered batch does not take blobs");
     BNEED(b, K == 0 || b->stored == 0, "a target with blobs is set before the first stored step");
     if (K == b->nblobs && (K == 0 || b->blobs)) return 0;
     BHIP(b, hipStreamSynchronize(b->stream));
@@ -998,7 +1027,11 @@ int emx_batch_check(int64_t nwalkers, int32_t ndim, int32_t target, int32_t nmov
 int emx_check_batch_blobs(int64_t nwalkers, int32_t ndim, int32_t target, int32_t nmoves, const emx_move_desc* moves, int32_t nblobs,
                           char* msg, int32_t msglen) {
     char buf[320];
-    const char* why = (nmoves > 0 && !moves) ? "no moves" : shape_refusal(nwalkers, ndim, target, nmoves, moves, buf, sizeof buf, nblobs);
+    // (a fused tempered target's blobs live in k_pt_run's LDS map, whose bound depends on ntemps: emx_pt_fused_check_blobs)
+    const char* why = (nmoves > 0 && !moves) ? "no moves"
+                      : (target == EMX_TARGET_FUSED_PT && nblobs > 0)
+                          ? "the blobs of a fused tempered target are checked with its ntemps (emx_pt_fused_check_blobs), not as a batch member's"
+                          : shape_refusal(nwalkers, ndim, target, nmoves, moves, buf, sizeof buf, nblobs);
     if (!why) return 0;
     if (msg && msglen > 0) snprintf(msg, (size_t)msglen, "%s", why);
     return -1;
@@ -1141,7 +1174,8 @@ int emx_batch_set_target(emx_batch* b, int32_t kind, const double* p0, const dou
 int emx_set_batch_target_callback_blobs(emx_batch* b, emx_batch_log_prob_blobs_fn fn, void* user, int32_t nblobs) {
     BNEED(b, fn != nullptr, "emx_set_batch_target_callback_blobs: no function");
     BNEED(b, nblobs >= 1 && nblobs <= BATCH_MAX_BLOBS, "emx_set_batch_target_callback_blobs: 1 <= nblobs <= %d; got %d", BATCH_MAX_BLOBS, nblobs);
-    BNEED(b, b->pt_T == 0, "a tempered batch does not take blobs");
+    BNEED(b, b->pt_T == 0 || b->target == EMX_TARGET_DEVICE_CALLBACK, "a fused tempered handle has the blobs of its launcher "
+                                                                      "(emx_pt_set_target_fused_blobs), not a callback's");
     if (int rc = settle_target(b, nblobs)) return rc;
     b->cb_fn = nullptr;
     b->cbb_fn = fn;
@@ -1208,12 +1242,13 @@ int emx_set_batch_target_fused_data(emx_batch* b, emx_fused_batch_data_fn fn, in
 // emx_pt_set_target_fused and emx_pt_set_target_fused_data (`ndata_host` non-null: the data ABI, a plain EMX_FUSED_PT_TARGET launcher
 // answers 1)
 static int pt_set_target_fused(emx_batch* b, const char* who, emx_pt_fused_fn fn, int32_t ndim_compiled, const void* user_dev, bool data,
-                               const int64_t* ndata_host) {
-    if (int rc = fused_bind_checks(b, who, EMX_TARGET_FUSED_PT, fn != nullptr, ndim_compiled, data, ndata_host)) return rc;
-    // the probe: abi, args_bytes and ndim against what the launcher was compiled with; nothing is launched
+                               const int64_t* ndata_host, int32_t nblobs = 0) {
+    if (int rc = fused_bind_checks(b, who, EMX_TARGET_FUSED_PT, fn != nullptr, ndim_compiled, data, ndata_host, nblobs)) return rc;
+    // the probe: abi, args_bytes, ndim and nblobs against what the launcher was compiled with; nothing is launched
     auto fl = fused_desc<emx_pt_fused_launch>(b, data ? EMX_FUSED_PT_DATA_ABI : EMX_FUSED_PT_ABI, sizeof(PtRunArgs), MOVE_STRETCH, nullptr);
-    if (int rc = pt_fused_launcher_refusal(b, fn(&fl), fl.movesel, data)) return rc;
-    if (int rc = settle_target(b, 0)) return rc;
+    fl.nblobs = nblobs;
+    if (int rc = pt_fused_launcher_refusal(b, fn(&fl), fl.movesel, data, nblobs)) return rc;
+    if (int rc = settle_target(b, nblobs)) return rc;
     if (data)
         if (int rc = upload_counts(b, &b->ptf_ndata, ndata_host)) return rc;
     b->ptf_fn = fn;
@@ -1229,14 +1264,23 @@ int emx_pt_set_target_fused(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compi
     return pt_set_target_fused(b, "emx_pt_set_target_fused", fn, ndim_compiled, user_dev, false, nullptr);
 }
 
+int emx_pt_set_target_fused_blobs(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compiled, const void* user_dev, int32_t nblobs) {
+    return pt_set_target_fused(b, "emx_pt_set_target_fused", fn, ndim_compiled, user_dev, false, nullptr, nblobs);
+}
+
 int emx_pt_set_target_fused_data(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compiled, const void* user_dev, const int64_t* ndata_host) {
     return pt_set_target_fused(b, "emx_pt_set_target_fused_data", fn, ndim_compiled, user_dev, true, ndata_host);
 }
 
 int emx_pt_fused_check(int32_t ntemps, int64_t nwalkers, int32_t ndim, int32_t nmoves, const emx_move_desc* moves, char* msg,
                        int32_t msglen) {
-    char buf[320];
-    const char* why = (nmoves < 1 || !moves) ? "no moves" : pt_fused_refusal(ntemps, nwalkers, ndim, nmoves, moves, buf, sizeof buf);
+    return emx_pt_fused_check_blobs(ntemps, nwalkers, ndim, nmoves, moves, 0, msg, msglen);
+}
+
+int emx_pt_fused_check_blobs(int32_t ntemps, int64_t nwalkers, int32_t ndim, int32_t nmoves, const emx_move_desc* moves, int32_t nblobs,
+                             char* msg, int32_t msglen) {
+    char buf[400];
+    const char* why = (nmoves < 1 || !moves) ? "no moves" : pt_fused_refusal(ntemps, nwalkers, ndim, nmoves, moves, buf, sizeof buf, nblobs);
     if (!why) return 0;
     if (msg && msglen > 0) snprintf(msg, (size_t)msglen, "%s", why);
     return -1;
@@ -1457,13 +1501,14 @@ int emx_pt_set_tempering(emx_batch* b, int32_t ntemps, const double* betas, cons
                                                  "commit and the swap pass belong to the batched callback path (emx_set_batch_target_callback)");
     BNEED(b, b->target == EMX_TARGET_DEVICE_CALLBACK || b->target == EMX_TARGET_FUSED_PT,
           "tempering needs a batched callback target (emx_set_batch_target_callback)");
-    BNEED(b, b->nblobs == 0, "tempering does not run a target with blobs (emx_set_batch_target_callback_blobs): the tempered commit "
-                             "and the swap pass carry none");
+    // (a callback handle takes its blobs once it is tempered; a fused tempered target brings them with its launcher)
+    BNEED(b, b->nblobs == 0 || b->target == EMX_TARGET_FUSED_PT,
+          "tempering does not take over a batch's target with blobs: emx_set_batch_target_callback_blobs comes after emx_pt_set_tempering");
     if (b->target == EMX_TARGET_FUSED_PT) {
         BNEED(b, !(b->ptf_has_prior && box_lo), "the fused tempered target's launcher carries a prior functor: a box prior on top is refused");
         if (!b->moves.empty()) {
-            char buf[320];
-            const char* why = pt_fused_refusal(ntemps, b->N, b->D, (int32_t)b->moves.size(), b->moves.data(), buf, sizeof buf);
+            char buf[400];
+            const char* why = pt_fused_refusal(ntemps, b->N, b->D, (int32_t)b->moves.size(), b->moves.data(), buf, sizeof buf, b->nblobs);
             BNEED(b, !why, "%s", why);
         }
     }
@@ -1587,6 +1632,8 @@ int emx_pt_set_state(emx_batch* b, const double* coords, const double* loglike, 
     BHIP(b, hipMemcpyAsync(b->pt_L, loglike, BN * 8, hipMemcpyHostToDevice, b->stream));
     BHIP(b, hipMemcpyAsync(b->pt_P, logprior, BN * 8, hipMemcpyHostToDevice, b->stream));
     BHIP(b, hipMemcpyAsync(b->lp, lp.data(), BN * 8, hipMemcpyHostToDevice, b->stream));
+    // the state bypassed the likelihood: the blobs of a handle that has them are NaN (every byte 0xff is a quiet NaN)
+    if (b->nblobs > 0 && b->blobs) BHIP(b, hipMemsetAsync(b->blobs, 0xff, BN * b->nblobs * 8, b->stream));
     BHIP(b, hipStreamSynchronize(b->stream));
     return 0;
 }
@@ -1641,6 +1688,15 @@ int emx_pt_get_state(emx_batch* b, double* loglike, double* logprior) {
     const size_t BN = (size_t)b->B * b->N;
     if (loglike) BHIP(b, hipMemcpyAsync(loglike, b->pt_L, BN * 8, hipMemcpyDeviceToHost, b->stream));
     if (logprior) BHIP(b, hipMemcpyAsync(logprior, b->pt_P, BN * 8, hipMemcpyDeviceToHost, b->stream));
+    BHIP(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int emx_pt_get_blobs(emx_batch* b, double* out) {
+    BNEED(b, b->pt_T > 0, "no tempering set (emx_pt_set_tempering)");
+    BNEED(b, b->nblobs > 0 && b->blobs, "the handle's likelihood has no blobs");
+    BNEED(b, out != nullptr, "no output buffer");
+    BHIP(b, hipMemcpyAsync(out, b->blobs, (size_t)b->B * b->N * b->nblobs * 8, hipMemcpyDeviceToHost, b->stream));
     BHIP(b, hipStreamSynchronize(b->stream));
     return 0;
 }

@@ -42,7 +42,8 @@ __device__ __forceinline__ double box_prior(const double* q, const double* lo, c
 }
 
 // TEMPERED: the commit of parallel tempering (BatchCbArgs' tempering fields); the untempered instantiation is the kernel as it
-// was, bit for bit and instruction for instruction.  BLOBS (untempered only): the commit carries the caller's blobs with the row
+// was, bit for bit and instruction for instruction.  BLOBS: the commit carries the caller's blobs with the row; with TEMPERED the
+// tempered decision stands as it is and the blob commit comes behind it (a row outside the prior has NaN blobs, as its L is -inf)
 template <int G, int V, int CH, bool TEMPERED, bool BLOBS = false>
 __global__ __launch_bounds__(CB_MAX_THREADS) void k_batch_cb(const BatchCbArgs A) {
     constexpr int WPW = 64 / G;
@@ -88,6 +89,16 @@ __global__ __launch_bounds__(CB_MAX_THREADS) void k_batch_cb(const BatchCbArgs A
                 if (accept || rows) load_row<G, V, CH>(x, accept ? A.q + r * D : X + (size_t)i * D, D, gl);
                 if (accept) store_row<G, V, CH>(x, X + (size_t)i * D, D, gl);
                 if (rows) store_row_stream<G, V, CH>(x, cr + (size_t)i * D, D, gl);
+                if constexpr (BLOBS) {                                               // the blobs follow the accepted row; the plane's row only
+                    const int K = A.nblobs;                                          // where this commit writes the stored rows
+                    double* bw = A.blobs + (b * (size_t)N + i) * K;
+                    double* bc = rows ? A.chain_blobs + (((size_t)b * A.cap + A.chain_row) * (size_t)N + i) * K : nullptr;
+                    for (int k = gl; k < K; k += G) {
+                        const double v = accept ? (pinf ? __builtin_nan("") : A.bq[r * K + k]) : bw[k];
+                        if (accept) bw[k] = v;
+                        if (rows) bc[k] = v;
+                    }
+                }
                 if (gl == 0) {
                     const double lo = Lm[i];
                     if (accept) {
@@ -226,8 +237,8 @@ __global__ __launch_bounds__(64) void k_batch_lp_check(const double* lp, uint32_
 
 template <int G, int V, int CH>
 hipError_t launch_cb(int grid, int threads, hipStream_t st, const BatchCbArgs& a) {
-    if (a.nblobs > 0 && a.beta) return hipErrorInvalidValue;      // tempered handles carry no blobs
-    auto kern = a.beta ? k_batch_cb<G, V, CH, true> : a.nblobs > 0 ? k_batch_cb<G, V, CH, false, true> : k_batch_cb<G, V, CH, false>;
+    auto kern = a.beta ? (a.nblobs > 0 ? k_batch_cb<G, V, CH, true, true> : k_batch_cb<G, V, CH, true>)
+                       : a.nblobs > 0 ? k_batch_cb<G, V, CH, false, true> : k_batch_cb<G, V, CH, false>;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, st, a);
     return hipGetLastError();
 }

@@ -55,8 +55,9 @@ struct BatchCbArgs {
     double* chain_L;           // (B, cap, N)
     int32_t rows_in_commit;    // the commit writes the stored step's rows (0: the swap pass writes them after the step)
     double* chain_beta;        // (B, cap): the stored step's beta of each member, written with its rows
-    // blobs (emx_set_batch_target_callback_blobs; nblobs 0: none, the kernel above bit for bit; untempered only): the caller's
-    // blobs of q, row for row with lpq; an accepted row's replace the walker's, and a stored step writes the walker's to the plane
+    // blobs (emx_set_batch_target_callback_blobs; nblobs 0: none, the kernel above bit for bit): the caller's blobs of q, row for
+    // row with lpq; an accepted row's replace the walker's, and a stored step writes the walker's to the plane (tempered with
+    // rows_in_commit 0: the swap pass writes the plane's rows, the commit only the walker's blobs)
     const double* bq;          // (B, R, nblobs)
     double* blobs;             // (B, N, nblobs)
     double* chain_blobs;       // (B, cap, N, nblobs)

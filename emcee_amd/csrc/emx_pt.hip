@@ -11,7 +11,11 @@
 //   group's new ladder (pt_adapt_ladder, rung order) and writes beta[1 ... T - 2], then, after vmcnt(0) and the barrier, the
 //   lanes recompute lp of every walker of the moved rungs, and after a second wait and barrier the stored rows are written.
 //   With adaptation off the pass is the loop above alone.
-// k_pt_init: the tempered initial state (box prior, -inf likelihood outside the prior, tempered lp, NaN check).
+//   Blobs (PtSwapArgs::nblobs > 0): a blob belongs to the point, so the lane that exchanges x exchanges the K doubles of the two rows
+//   too (the pair's vmcnt(0) and barrier cover those stores), and a stored step writes every rung's rows of the blob plane.  The
+//   ladder update does not touch them.  nblobs == 0 launches the blob-free instantiation: the pass above.
+// k_pt_init: the tempered initial state (box prior, -inf likelihood outside the prior, tempered lp, NaN check; NaN blobs where the
+//   prior is -inf).
 // k_pt_mean_loglike: one workgroup a member, the mean of its L chain rows over the walkers (thermodynamic integration's input).
 // k_pt_relp: lp from L, P and each member's beta (emx_pt_set_ladder).
 // emx_host_pt_swap_draws / emx_host_pt_adapt_ladder: the host twins of the swap draws and of the ladder update.
@@ -27,6 +31,8 @@ namespace {
 
 constexpr int PT_THREADS = 256;
 
+// BLOBS: the handle's target has blobs (PtSwapArgs::nblobs > 0); the blob-free instantiation is the pass as it was, instruction for instruction
+template <bool BLOBS>
 __global__ __launch_bounds__(PT_THREADS) void k_pt_swap(const PtSwapArgs A) {
     __shared__ unsigned int nacc;
     __shared__ unsigned int pacc[PT_ADAPT_MAX_T];     // adaptation: each pair's accepts of this pass, pair i at i - 1
@@ -57,6 +63,15 @@ __global__ __launch_bounds__(PT_THREADS) void k_pt_swap(const PtSwapArgs A) {
                         const double v = xh[d];
                         xh[d] = xc[d];
                         xc[d] = v;
+                    }
+                    if constexpr (BLOBS) {                         // a blob belongs to the point: it changes places with x
+                        double* bh2 = A.blobs + rh * A.nblobs;
+                        double* bc2 = A.blobs + rc * A.nblobs;
+                        for (int q = 0; q < A.nblobs; ++q) {
+                            const double v = bh2[q];
+                            bh2[q] = bc2[q];
+                            bc2[q] = v;
+                        }
                     }
                     A.L[rh] = Lc;
                     A.P[rh] = Pc;
@@ -107,6 +122,12 @@ __global__ __launch_bounds__(PT_THREADS) void k_pt_swap(const PtSwapArgs A) {
             A.chain_lp[crow * N + e] = A.lp[m * N + e];
             A.chain_L[crow * N + e] = A.L[m * N + e];
         }
+        if constexpr (BLOBS) {
+            const size_t NK = (size_t)N * A.nblobs;
+            const double* bw = A.blobs + m * NK;
+            double* cb = A.chain_blobs + crow * NK;
+            for (size_t e = tid; e < NK; e += nt) cb[e] = bw[e];
+        }
     }
 }
 
@@ -117,7 +138,8 @@ __global__ __launch_bounds__(PT_THREADS) void k_pt_relp(double* lp, const double
 }
 
 __global__ __launch_bounds__(64) void k_pt_init(const double* X, double* lp, double* L, double* P, const double* beta,
-                                                const double* box_lo, const double* box_hi, uint32_t* status, int N, int D) {
+                                                const double* box_lo, const double* box_hi, uint32_t* status, int N, int D,
+                                                double* blobs, int K) {
     const size_t b = blockIdx.x;
     bool nan = false;
     for (int w = threadIdx.x; w < N; w += 64) {
@@ -138,6 +160,8 @@ __global__ __launch_bounds__(64) void k_pt_init(const double* X, double* lp, dou
         const double v = pt_tempered(beta[b], l, p);
         L[r] = l;
         lp[r] = v;
+        if (pinf)                                              // the row's blobs are ignored like its L
+            for (int q = 0; q < K; ++q) blobs[r * K + q] = __builtin_nan("");
         nan |= (!pinf && lraw != lraw) || v != v;
     }
     if (__ballot(nan) != 0ull && threadIdx.x == 0) raise_status(status + b * SMALL_STATUS_WORDS, ST_NAN_LOGP);
@@ -167,13 +191,17 @@ __global__ __launch_bounds__(PT_THREADS) void k_pt_mean_loglike(const double* ch
 }  // namespace
 
 hipError_t pt_swap_launch(int groups, hipStream_t st, const PtSwapArgs& a) {
-    hipLaunchKernelGGL(k_pt_swap, dim3(groups), dim3(PT_THREADS), 0, st, a);
+    if (a.nblobs > 0)
+        hipLaunchKernelGGL(k_pt_swap<true>, dim3(groups), dim3(PT_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL(k_pt_swap<false>, dim3(groups), dim3(PT_THREADS), 0, st, a);
     return hipGetLastError();
 }
 
 hipError_t pt_init_launch(const double* X, double* lp, double* L, double* P, const double* beta, const double* box_lo,
-                          const double* box_hi, uint32_t* status, int32_t B, int32_t N, int32_t D, hipStream_t st) {
-    hipLaunchKernelGGL(k_pt_init, dim3(B), dim3(64), 0, st, X, lp, L, P, beta, box_lo, box_hi, status, N, D);
+                          const double* box_hi, uint32_t* status, int32_t B, int32_t N, int32_t D, hipStream_t st, double* blobs,
+                          int32_t nblobs) {
+    hipLaunchKernelGGL(k_pt_init, dim3(B), dim3(64), 0, st, X, lp, L, P, beta, box_lo, box_hi, status, N, D, blobs, blobs ? nblobs : 0);
     return hipGetLastError();
 }
 

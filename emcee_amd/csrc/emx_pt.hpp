@@ -113,14 +113,20 @@ struct PtSwapArgs {
     int32_t adapt;
     double lag, time;
     long long adapt_t;         // the update counter t before this pass
+    // blobs of a target that has them (nblobs 0: none, the pass as without them): a blob belongs to the point, so an accepted pair
+    // exchanges the K doubles of its two rows with x, and a stored step writes every rung's rows of the plane
+    double* blobs;             // (B, N, nblobs)
+    double* chain_blobs;       // (B, cap, N, nblobs)
+    int32_t nblobs;
 };
 
 // one swap pass (and / or the stored rows) of every group: one workgroup a group
 hipError_t pt_swap_launch(int groups, hipStream_t st, const PtSwapArgs& a);
 // the initial state of a tempered batch: L := -inf where P is -inf (the box evaluated here when box_lo), lp := pt_tempered, and
-// ST_NAN_LOGP where L is NaN with P > -inf or lp is NaN
+// ST_NAN_LOGP where L is NaN with P > -inf or lp is NaN; blobs (B, N, nblobs; nullptr / 0: none) := NaN where P is -inf
 hipError_t pt_init_launch(const double* X, double* lp, double* L, double* P, const double* beta, const double* box_lo,
-                          const double* box_hi, uint32_t* status, int32_t B, int32_t N, int32_t D, hipStream_t st);
+                          const double* box_hi, uint32_t* status, int32_t B, int32_t N, int32_t D, hipStream_t st,
+                          double* blobs = nullptr, int32_t nblobs = 0);
 // lp := pt_tempered(beta[m], L, P) of every walker of every member (emx_pt_set_ladder)
 hipError_t pt_relp_launch(double* lp, const double* L, const double* P, const double* beta, int32_t B, int32_t N, hipStream_t st);
 // out[m] = mean of chain_L rows start, start + stride, ... < stop of member m over every walker

@@ -12,6 +12,17 @@
 // own, no barrier, no cross-lane operation.  member = object * ntemps + rung.  The likelihood is untempered; where the prior is
 // -inf it is not called.  -inf is legal; a NaN likelihood where the prior is finite raises the reference's error naming (object, rung).
 //
+// Blobs -- derived quantities recorded with every sample (PTSampler.get_blobs) -- come from the likelihood's five-argument form,
+// emx_fused_target.hpp's contract:
+//
+//     struct MyLike { __device__ double operator()(const double* x, int ndim, int member, const void* user, double* blobs) const; };
+//     EMX_FUSED_PT_TARGET_BLOBS(my_model, MyLike, MyPrior, /*ndim=*/5, /*nblobs=*/2)
+//
+// The call writes blobs[0 ... nblobs) (lane-private, zero on entry; 1 <= nblobs <= 32, any value is legal) and returns the untempered
+// likelihood as before; the prior produces none.  A walker's blobs are replaced exactly when its proposal is accepted, an accepted
+// swap exchanges them with x, L and P, and where the prior is -inf (an initial-state walker) they are NaN.  Everything else of the run
+// is bit for bit that of the same functor without blobs.
+//
 // k_pt_run: workgroup g runs object g -- all its ntemps rungs -- for a whole launch.  No workgroup waits for another.  LDS map
 // (pt_lds_layout; T rungs, N walkers, D dims, B plan steps, R staging rows a rung, DS = D | 1):
 //   doubles  X (T, N, D) | lp, L, P (T, N) each | plan s0, logu, fac (B, T, N) each | beta (T) | swap log-uniforms (T - 1, N) |
@@ -19,6 +30,7 @@
 //   64-bit   seeds (T) | swap accepts of the launch (T - 1)
 //   32-bit   plan order, p0, p1, p2 (B, T, N) each | swap partners (T - 1, N) | moves (B, T) | accept counts (T, N) | pair accepts (T)
 //   bytes    accept flags (T, N)
+//   doubles  (only with K blobs, behind everything above so that K = 0 moves no offset) the walkers' blobs (T, N, K) | staging blobs (T, R, K)
 // A half-step is two passes over the rows of all rungs (T R rows) with a barrier between them: pass 1 (G lanes a row) makes every
 // proposal with small_propose into its staging row; pass 2 (one lane a row) is prior, likelihood, k_batch_cb<..., TEMPERED>'s
 // decision and the commit.  The swap pass is k_pt_swap's on LDS, its draws made by every lane before the step's half-steps (they do
@@ -39,7 +51,7 @@
 
 // bumped with ANY change of PtRunArgs or of k_pt_run's LDS layout: a launcher and a library of different values refuse each other
 #ifndef EMX_FUSED_PT_ABI
-#define EMX_FUSED_PT_ABI 2u
+#define EMX_FUSED_PT_ABI 3u
 #endif
 
 namespace emx {
@@ -78,15 +90,19 @@ struct PtRunArgs {
     long long adapt_t0;                          // the update counter t before this launch's first pass
     const void* user;
     const long long* ndata;                      // DATA form: the data count of every member (B); nullptr for a plain target
+    // blobs (EMX_FUSED_PT_TARGET_BLOBS; nblobs 0: none): the walkers' current ones (B, N, nblobs) and the plane (B, cap, N, nblobs)
+    double *blobs, *chain_blobs;
+    int32_t nblobs;
 };
 
 // the LDS map of one object, in bytes from the start of dynamic LDS (host and device: one definition)
 struct PtLds {
     size_t total;          // > SMALL_LDS_MAX on the host: refused; the offsets below are then meaningless
     uint32_t X, lp, L, P, s0, logu, fac, beta, swlu, stage, sfac, box, seeds, swacc, order, p0, p1, p2, swj, mvs, acnt, pacc, accs;
+    uint32_t wbl, sbl;     // K > 0 only: the walkers' blobs and the staging blobs
 };
 
-__host__ __device__ inline PtLds pt_lds_layout(int64_t T, int64_t N, int64_t D, int64_t B, int64_t R) {
+__host__ __device__ inline PtLds pt_lds_layout(int64_t T, int64_t N, int64_t D, int64_t B, int64_t R, int64_t K = 0) {
     PtLds o;
     const size_t TN = (size_t)(T * N), plan = (size_t)B * TN, pairs = (size_t)(T > 1 ? (T - 1) * N : 0), DS = (size_t)(D | 1);
     size_t at = 0;
@@ -118,6 +134,12 @@ __host__ __device__ inline PtLds pt_lds_layout(int64_t T, int64_t N, int64_t D, 
     o.acnt = take(TN * 4);
     o.pacc = take((size_t)T * 4);
     o.accs = take(TN);
+    o.wbl = o.sbl = 0;
+    if (K > 0) {           // behind every region a blob-free object has: K = 0 moves no offset and takes no byte
+        at = (at + 7) & ~(size_t)7;
+        o.wbl = take(TN * (size_t)K * 8);
+        o.sbl = take((size_t)(T * R) * (size_t)K * 8);
+    }
     o.total = (at + 15) & ~(size_t)15;
     return o;
 }
@@ -130,9 +152,10 @@ struct PtMember {          // what small_propose needs of a rung
 // prior, likelihood and tempered log-probability of one row: k_batch_cb<..., TEMPERED>'s and k_pt_init's rule.  -> the NaN status
 // (The prior -- functor, else box, else flat -- is written out here and in pt_row_eval_data; the rest of the rule here and in
 // pt_row_finish.  Each pair must agree.)
-template <typename LIKE, typename PRIOR>
+// NBLOBS > 0: the likelihood's five-argument form writes the row's blobs (zeroed here first; NaN where the prior is -inf)
+template <typename LIKE, typename PRIOR, int NBLOBS = 0>
 __device__ __forceinline__ bool pt_row_eval(const double* x, int D, int member, const void* user, double beta, const double* lo,
-                                            const double* hi, bool box, double& pq, double& lq, double& lpn) {
+                                            const double* hi, bool box, double& pq, double& lq, double& lpn, double* blobs = nullptr) {
     if constexpr (!std::is_same<PRIOR, NoFusedPrior>::value) {
         pq = PRIOR{}(x, D, member, user);
     } else {
@@ -143,7 +166,13 @@ __device__ __forceinline__ bool pt_row_eval(const double* x, int D, int member, 
     }
     const bool pinf = pq == -__builtin_inf();
     double lraw = -__builtin_inf();
-    if (!pinf) lraw = LIKE{}(x, D, member, user);      // the likelihood of a row outside the prior is ignored: not called
+    if constexpr (NBLOBS > 0) {
+#pragma unroll
+        for (int k = 0; k < NBLOBS; ++k) blobs[k] = pinf ? __builtin_nan("") : 0.0;
+        if (!pinf) lraw = LIKE{}(x, D, member, user, blobs);
+    } else {
+        if (!pinf) lraw = LIKE{}(x, D, member, user);      // the likelihood of a row outside the prior is ignored: not called
+    }
     lq = pinf ? -__builtin_inf() : lraw;
     lpn = pt_tempered(beta, lq, pq);
     return (!pinf && lraw != lraw) || lpn != lpn;
@@ -180,7 +209,7 @@ __device__ __forceinline__ bool pt_row_finish(bool pinf, double pq, double lraw,
     return (!pinf && lraw != lraw) || lpn != lpn;
 }
 
-template <int G, int V, int CH, int MOVESEL, typename LIKE, typename PRIOR, bool DATA = false>
+template <int G, int V, int CH, int MOVESEL, typename LIKE, typename PRIOR, bool DATA = false, int NBLOBS = 0>
 static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRunArgs A) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int WPW = 64 / G;
@@ -188,7 +217,8 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
     const int lane = tid & 63, wv = tid >> 6, nwave = NT >> 6, sub = lane / G, gl = lane % G;
     const int TN = T * N, TR = T * R, DS = D | 1, ND = N * D;
     const size_t m0 = (size_t)blockIdx.x * (size_t)T;
-    const PtLds O = pt_lds_layout(T, N, D, B, R);
+    static_assert(!(DATA && NBLOBS > 0), "the DATA form carries no blobs");
+    const PtLds O = pt_lds_layout(T, N, D, B, R, NBLOBS);
     char* lds = reinterpret_cast<char*>(smem);
     double* Xs = reinterpret_cast<double*>(lds + O.X);
     double* lps = reinterpret_cast<double*>(lds + O.lp);
@@ -214,6 +244,8 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
     uint32_t* acnt = reinterpret_cast<uint32_t*>(lds + O.acnt);
     unsigned int* pacc = reinterpret_cast<unsigned int*>(lds + O.pacc);
     uint8_t* accs = reinterpret_cast<uint8_t*>(lds + O.accs);
+    [[maybe_unused]] double* wbl = reinterpret_cast<double*>(lds + O.wbl);      // NBLOBS > 0: the walkers' blobs (T, N, NBLOBS)
+    [[maybe_unused]] double* sbl = reinterpret_cast<double*>(lds + O.sbl);      // ... and the staging rows' (T, R, NBLOBS)
     const bool box = A.box_lo != nullptr;
 
     // ---- the object's rungs are consecutive members: one contiguous block of every member-strided array ----
@@ -236,6 +268,8 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
             loS[d] = A.box_lo[d];
             hiS[d] = A.box_hi[d];
         }
+    if constexpr (NBLOBS > 0)
+        for (int e = tid; e < TN * NBLOBS; e += NT) wbl[e] = A.blobs[m0 * (size_t)N * NBLOBS + e];
     __syncthreads();
     if (A.eval0) {
         // the initial state (k_pt_init's rule), every walker's own row through the functors
@@ -257,7 +291,12 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
         for (int r = tid; r < TN; r += NT) {
             const int t = r / N;
             double pq, lq, lpn;
-            const bool nan = pt_row_eval<LIKE, PRIOR>(Xs + (size_t)r * D, D, (int)(m0 + t), A.user, betaS[t], loS, hiS, box, pq, lq, lpn);
+            bool nan;
+            if constexpr (NBLOBS > 0)       // the walker's own blobs, NaN where P is -inf
+                nan = pt_row_eval<LIKE, PRIOR, NBLOBS>(Xs + (size_t)r * D, D, (int)(m0 + t), A.user, betaS[t], loS, hiS, box, pq, lq, lpn,
+                                                       wbl + (size_t)r * NBLOBS);
+            else
+                nan = pt_row_eval<LIKE, PRIOR>(Xs + (size_t)r * D, D, (int)(m0 + t), A.user, betaS[t], loS, hiS, box, pq, lq, lpn);
             if (nan) raise_status(A.status + (m0 + t) * SMALL_STATUS_WORDS, ST_NAN_LOGP);
             Ps[r] = pq;
             Ls[r] = lq;
@@ -431,12 +470,21 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
                     bool accept = false;
                     if (fac != -__builtin_inf()) {                                 // (-inf: a non-finite proposal, rejected without reaching a functor)
                         double pq, lq, lpn;
-                        const bool nan = pt_row_eval<LIKE, PRIOR>(qrow, D, (int)(m0 + t), A.user, betaS[t], loS, hiS, box, pq, lq, lpn);
+                        bool nan;
+                        if constexpr (NBLOBS > 0)       // the lane writes its row's staging blobs
+                            nan = pt_row_eval<LIKE, PRIOR, NBLOBS>(qrow, D, (int)(m0 + t), A.user, betaS[t], loS, hiS, box, pq, lq, lpn,
+                                                                   sbl + (size_t)r * NBLOBS);
+                        else
+                            nan = pt_row_eval<LIKE, PRIOR>(qrow, D, (int)(m0 + t), A.user, betaS[t], loS, hiS, box, pq, lq, lpn);
                         if (nan) raise_status(A.status + (m0 + t) * SMALL_STATUS_WORDS, ST_NAN_LOGP);
                         const double lnpdiff = fac + lpn - lps[w];                 // (small_update's accept rule, emx_kernels.hpp, on the tempered lp)
                         accept = lnpdiff > logus[pos];
                         if (accept) {
                             for (int d = 0; d < D; ++d) Xs[(size_t)w * D + d] = qrow[d];
+                            if constexpr (NBLOBS > 0) {
+#pragma unroll
+                                for (int q = 0; q < NBLOBS; ++q) wbl[(size_t)w * NBLOBS + q] = sbl[(size_t)r * NBLOBS + q];
+                            }
                             lps[w] = lpn;
                             Ls[w] = lq;
                             Ps[w] = pq;
@@ -466,6 +514,14 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
                                     const double v = xh[d];
                                     xh[d] = xc[d];
                                     xc[d] = v;
+                                }
+                                if constexpr (NBLOBS > 0) {       // a blob belongs to the point: it changes places with x
+#pragma unroll
+                                    for (int q = 0; q < NBLOBS; ++q) {
+                                        const double v = wbl[(size_t)rh * NBLOBS + q];
+                                        wbl[(size_t)rh * NBLOBS + q] = wbl[(size_t)rc * NBLOBS + q];
+                                        wbl[(size_t)rc * NBLOBS + q] = v;
+                                    }
                                 }
                                 Ls[rh] = Lc;
                                 Ps[rh] = Pc;
@@ -507,6 +563,11 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
                     A.chain_L[o] = Ls[e];
                     acnt[e] += accs[e];
                 }
+                if constexpr (NBLOBS > 0)
+                    for (int e = tid; e < TN * NBLOBS; e += NT) {
+                        const int t = e / (N * NBLOBS);
+                        A.chain_blobs[((m0 + t) * (size_t)A.cap + crow) * (size_t)(N * NBLOBS) + (e - t * N * NBLOBS)] = wbl[e];
+                    }
                 for (int t = tid; t < T; t += NT) A.chain_beta[(m0 + t) * (size_t)A.cap + crow] = betaS[t];
                 ++row;
                 __syncthreads();                     // the next half-step overwrites what was just copied
@@ -523,6 +584,8 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
         A.acc_count[m0 * (size_t)N + e] += acnt[e];
     }
     for (int t = tid; t < T; t += NT) A.beta[m0 + t] = betaS[t];
+    if constexpr (NBLOBS > 0)
+        for (int e = tid; e < TN * NBLOBS; e += NT) A.blobs[m0 * (size_t)N * NBLOBS + e] = wbl[e];
     if (T > 1 && npass > 0)
         for (int t = tid; t < T - 1; t += NT) {
             const size_t c = (size_t)blockIdx.x * (size_t)(T - 1) + t;
@@ -531,30 +594,33 @@ static __global__ __launch_bounds__(PT_RUN_MAX_THREADS) void k_pt_run(const PtRu
         }
 }
 
-template <typename LIKE, typename PRIOR, int NDIM, int MOVESEL, bool DATA = false>
+template <typename LIKE, typename PRIOR, int NDIM, int MOVESEL, bool DATA = false, int NBLOBS = 0>
 hipError_t launch_pt_move(int grid, int threads, size_t lds, hipStream_t st, const PtRunArgs& a) {
     static size_t lds_granted[MAX_DEVICES] = {};
-    return fused_launch_kernel(k_pt_run<fused_g(NDIM), fused_v(NDIM), fused_ch(NDIM), MOVESEL, LIKE, PRIOR, DATA>, lds_granted, grid, threads, lds,
-                               st, a);
+    return fused_launch_kernel(k_pt_run<fused_g(NDIM), fused_v(NDIM), fused_ch(NDIM), MOVESEL, LIKE, PRIOR, DATA, NBLOBS>, lds_granted, grid,
+                               threads, lds, st, a);
 }
 
 // the launcher behind EMX_FUSED_PT_TARGET: fused_launch_checks (emx_fused_target.hpp), then one launch of every object
-// (include/emx.h: emx_pt_fused_launch).  The probe (grid == 0) also reports whether a prior functor is compiled in.
-template <typename LIKE, typename PRIOR, int NDIM, int MOVES>
+// (include/emx.h: emx_pt_fused_launch).  The probe (grid == 0) also reports whether a prior functor is compiled in.  A descriptor
+// whose blob count is not the NBLOBS compiled in is answered 4, as fused_batch_launch answers it.
+template <typename LIKE, typename PRIOR, int NDIM, int MOVES, int NBLOBS = 0>
 int fused_pt_launch(emx_pt_fused_launch* L) {
     static_assert(NDIM >= 1 && NDIM <= 256, "a fused tempered target has 1 <= ndim <= 256");
+    static_assert(NBLOBS >= 0 && NBLOBS <= 32, "a fused tempered target has 0 <= nblobs <= 32");
     static_assert((MOVES & (EMX_FUSED_MOVES_STRETCH | EMX_FUSED_MOVES_ANY)) != 0, "no move selector compiled in");
     bool stretch = false;
     const int rc = fused_launch_checks(L, EMX_FUSED_PT_ABI, sizeof(PtRunArgs), NDIM, MOVES, PT_RUN_MAX_THREADS, &stretch, [](emx_pt_fused_launch* d) {
         d->has_prior = std::is_same<PRIOR, NoFusedPrior>::value ? 0 : 1;      // the probe reports it
-        return FUSED_GO_ON;
+        return d->nblobs != NBLOBS ? 4 : FUSED_GO_ON;
     });
     if (rc != FUSED_GO_ON) return rc;
     PtRunArgs a = *static_cast<const PtRunArgs*>(L->args);
     if (a.D != NDIM) return 2;
+    if (a.nblobs != NBLOBS || (NBLOBS > 0 && !a.blobs)) return 4;
     a.user = L->user;
     return fused_launch_by_moves<MOVES>(stretch, [&](auto sel) {
-        return launch_pt_move<LIKE, PRIOR, NDIM, decltype(sel)::value>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
+        return launch_pt_move<LIKE, PRIOR, NDIM, decltype(sel)::value, false, NBLOBS>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);
     });
 }
 
@@ -566,3 +632,9 @@ int fused_pt_launch(emx_pt_fused_launch* L) {
     }
 #define EMX_FUSED_PT_TARGET(name, LikeFunctor, PriorFunctor, ndim) \
     EMX_FUSED_PT_TARGET_MOVES(name, LikeFunctor, PriorFunctor, ndim, EMX_FUSED_MOVES_STRETCH | EMX_FUSED_MOVES_ANY)
+// the likelihood's five-argument form (..., double* blobs) with `nblobs` doubles a sample; both move selectors
+#define EMX_FUSED_PT_TARGET_BLOBS(name, LikeFunctor, PriorFunctor, ndim, nblobs)                                                           \
+    extern "C" __attribute__((visibility("default"))) int name(emx_pt_fused_launch* launch) {                                              \
+        static_assert((nblobs) >= 1, "EMX_FUSED_PT_TARGET_BLOBS: 1 <= nblobs <= 32 (none: EMX_FUSED_PT_TARGET)");                          \
+        return emx::fused_pt_launch<LikeFunctor, PriorFunctor, (ndim), EMX_FUSED_MOVES_STRETCH | EMX_FUSED_MOVES_ANY, (nblobs)>(launch);   \
+    }

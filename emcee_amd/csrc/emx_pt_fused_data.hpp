@@ -35,7 +35,7 @@
 // bumped with ANY change of PtRunArgs, of k_pt_run's LDS layout or of the DATA form's launch rules.  A value of its own: a data
 // launcher handed EMX_FUSED_PT_ABI, and an EMX_FUSED_PT_TARGET launcher handed this one, answer 1
 #ifndef EMX_FUSED_PT_DATA_ABI
-#define EMX_FUSED_PT_DATA_ABI 0x50544402u
+#define EMX_FUSED_PT_DATA_ABI 0x50544403u
 #endif
 
 namespace emx {
@@ -61,6 +61,7 @@ int fused_pt_data_launch(emx_pt_fused_launch* L) {
     PtRunArgs a = *static_cast<const PtRunArgs*>(L->args);
     if (a.D != NDIM) return 2;
     if (!a.ndata) return 3;                           // the members' counts are the library's to fill
+    if (a.nblobs != 0) return 4;                      // the DATA form carries no blobs
     a.user = L->user;
     return fused_launch_by_moves<OK ? MOVES : 0>(stretch, [&](auto sel) {
         return launch_pt_move<MODEL, PRIOR, NDIM, decltype(sel)::value, true>(L->grid, L->threads, (size_t)L->lds_bytes, (hipStream_t)L->hip_stream, a);

@@ -25,8 +25,21 @@ swap exchanges ``x``, ``L`` and ``P`` and recomputes ``lp`` at both destinations
 before it.  ``pi_i`` and ``u`` are keyed by group g's rung-0 Philox seed and the step just taken
 (``emx_host_pt_swap_draws`` in ``include/emx.h`` rebuilds them on the host).
 
-Stored rows are the state after the step's swap pass: coordinates, tempered ``lp`` (:meth:`get_log_prob`) and ``L``
-(:meth:`get_log_likelihood`).  Accept counts are per member; swap attempts and accepts per (group, pair).
+Blobs (``PTSampler(..., blobs=True)``).  A likelihood with ``nblobs = K`` (1 ... 32: a ``BatchCallable`` / ``BatchKernel`` /
+``PTFused`` with ``nblobs``) produces K float64 values with every untempered ``L``; the prior produces none (a ``log_prior`` target
+with blobs is a ``TypeError``).  Recording is asked for: without ``blobs=True`` a likelihood with blobs is refused with a
+``TypeError``, as it always was, so that nobody pays for a plane they did not ask for.  A
+walker's blobs are replaced exactly when its proposal is accepted by the tempered commit.  An accepted swap exchanges the blobs
+together with ``x``, ``L`` and ``P``: a blob belongs to the point, not to the rung, so a blob that records ``member`` names the rung
+where the point was last evaluated.  Where ``P == -inf`` the row's ``L`` is already ignored and kept as ``-inf``; its blobs are
+likewise ignored and stored as NaN (the fused form never calls the likelihood there, the callback path calls it and discards the
+result, and this rule makes the two equal); such a row can only be an initial-state walker.  The ladder update does not touch
+blobs.  Coordinates, ``lp``, ``L``, ``P``, accept counts, swap counts, ladders and the Philox step of a run with blobs are bit for
+bit those of the same function without blobs.  :meth:`get_blobs`, :meth:`get_blob_summary` and :meth:`get_blob_histograms` read the
+blob plane next to the chain; ``get_last_sample().blobs`` the current state's.
+
+Stored rows are the state after the step's swap pass: coordinates, tempered ``lp`` (:meth:`get_log_prob`), ``L``
+(:meth:`get_log_likelihood`) and the blobs.  Accept counts are per member; swap attempts and accepts per (group, pair).
 
 Seeds.  ``seeds`` holds ``nbatch`` integers.  Member (g, t) draws as the :class:`~emcee_amd.EnsembleBatch` member seeded with
 ``s[g, t] = np.random.RandomState(seeds[g]).randint(0, 2**32, size=ntemps, dtype=np.uint64)[t]``, i.e. its Philox seed is
@@ -250,10 +263,12 @@ class PTSampler(object):
     ``betas``: strictly decreasing from 1 to >= 0, else :func:`default_betas` ``(ntemps, ndim, Tmax)``; every object starts on
     it.  ``moves``: the schedule forms of :class:`~emcee_amd.EnsembleBatch`'s callback path.  ``adaptive``: adapt each object's
     ladder after every swap pass (module docstring; ptemcee's ``adaptation_lag`` and ``adaptation_time``, both > 0).
-    ``adaptive`` and ``swap_every`` may be changed between runs."""
+    ``adaptive`` and ``swap_every`` may be changed between runs.  ``blobs=True``: record the blobs of a likelihood with ``nblobs >
+    0`` (module docstring, "Blobs"); without it such a likelihood is refused."""
 
     def __init__(self, ntemps, nwalkers, ndim, log_likelihood, log_prior=None, betas=None, Tmax=None, nbatch=1, moves=None,
-                 seeds=None, swap_every=1, device=None, rng="philox", adaptive=False, adaptation_lag=10000, adaptation_time=100):
+                 seeds=None, swap_every=1, device=None, rng="philox", adaptive=False, adaptation_lag=10000, adaptation_time=100,
+                 blobs=False):
         if rng != "philox":
             raise ValueError("PTSampler runs rng='philox' only (the MT19937 stream is made by one host generator a sampler; use "
                              "EnsembleSampler for rng=%r)" % (rng,))
@@ -266,9 +281,13 @@ class PTSampler(object):
         if isinstance(log_likelihood, DeviceFused):
             raise TypeError("PTSampler's log_likelihood is a targets.BatchCallable, targets.BatchKernel or targets.PTFused; a DeviceFused "
                             "is not: its launcher carries the single sampler's half-step kernel (compile the model as a PTFused)")
-        if isinstance(log_likelihood, BatchTarget) and getattr(log_likelihood, "nblobs", 0) > 0:
-            raise TypeError("PTSampler does not record blobs: its log_likelihood is a target with nblobs = 0 (the tempered commit and "
-                            "the swap pass carry none; got nblobs = %d)" % log_likelihood.nblobs)
+        if isinstance(log_likelihood, BatchTarget):
+            nb = int(getattr(log_likelihood, "nblobs", 0))
+            if nb > 0 and not blobs:
+                raise TypeError("PTSampler records blobs only when asked to: pass blobs=True to keep the %d blobs a sample of this "
+                                "log_likelihood next to the chain (nblobs = %d), or give a target with nblobs = 0" % (nb, nb))
+            if blobs and nb == 0:
+                raise ValueError("blobs=True needs a log_likelihood that produces blobs (a target with nblobs > 0); got nblobs = 0")
         if not isinstance(log_likelihood, BatchTarget):
             kind = "fused device target" if isinstance(log_likelihood, DeviceTarget) else type(log_likelihood).__name__
             raise TypeError("PTSampler's log_likelihood is a targets.BatchCallable or targets.BatchKernel; a %s is not (wrap the "
@@ -288,6 +307,9 @@ class PTSampler(object):
             if fused and isinstance(log_prior, BatchTarget):
                 raise TypeError("with a PTFused likelihood log_prior is None or (lo, hi): a BatchCallable / BatchKernel prior would need "
                                 "the callback path (compile the prior into the launcher: compile_fused_pt(..., prior=...))")
+            if isinstance(log_prior, BatchTarget) and getattr(log_prior, "nblobs", 0) > 0:
+                raise TypeError("log_prior is a target with nblobs = 0: the prior produces no blobs, the likelihood does (got nblobs = %d)"
+                                % log_prior.nblobs)
             if isinstance(log_prior, BatchTarget):
                 self._prior = log_prior
             elif isinstance(log_prior, DeviceTarget) or callable(log_prior):
@@ -320,11 +342,12 @@ class PTSampler(object):
         self._b = EnsembleBatch(self.nbatch * self.ntemps, self.nwalkers, self.ndim, self._wrap(log_likelihood), moves=moves,
                                 seeds=self.member_seeds.reshape(-1), device=device, _tempered=True, _ntemps=self.ntemps)
         self._fused = log_likelihood if fused else None
+        self.nblobs = self._b.nblobs        # blobs a sample of the likelihood (0: none)
         if fused:           # an object must fit one workgroup's LDS: refused here, before any device is touched
             msg = C.create_string_buffer(512)
             d = self._b._descs
             arr = (_lib.MoveDesc * len(d))(*d)
-            if _lib.load().emx_pt_fused_check(self.ntemps, self.nwalkers, self.ndim, len(d), arr, msg, 512) != 0:
+            if _lib.load().emx_pt_fused_check_blobs(self.ntemps, self.nwalkers, self.ndim, len(d), arr, self.nblobs, msg, 512) != 0:
                 raise ValueError("PTSampler: %s" % msg.value.decode())
         self.device = self._b.device
         self._h = None
@@ -337,11 +360,25 @@ class PTSampler(object):
             raise ValueError("an adaptive ladder needs betas[0 ... ntemps - 2] > 0")
 
     def _wrap(self, t):
-        """a BatchCallable's fn sees (nbatch, ntemps, R, ndim); a BatchKernel the handle's members as they are"""
+        """a BatchCallable's fn sees (nbatch, ntemps, R, ndim) -- and, with nblobs = K, returns (lp, blobs) of shapes (nbatch, ntemps,
+        R) and (nbatch, ntemps, R, K); a BatchKernel the handle's members as they are"""
         if isinstance(t, (BatchKernel, PTFused)):
             return t
-        fn, G, T, D = t.fn, self.nbatch, self.ntemps, self.ndim
-        return BatchCallable(lambda q: fn(q.view(G, T, q.shape[1], D)))
+        fn, G, T, D, K = t.fn, self.nbatch, self.ntemps, self.ndim, t.nblobs
+        if not K:
+            return BatchCallable(lambda q: fn(q.view(G, T, q.shape[1], D)))
+
+        def with_blobs(q):
+            R = q.shape[1]
+            res = fn(q.view(G, T, R, D))
+            if not (isinstance(res, (tuple, list)) and len(res) == 2):
+                raise ValueError("with nblobs = %d the likelihood returns (log_likelihood, blobs); got %s" % (K, type(res).__name__))
+            lp, bl = res
+            got = tuple(bl.shape) if hasattr(bl, "shape") else np.shape(bl)
+            if got != (G, T, R, K):
+                raise ValueError("the likelihood returned blobs of shape %s; expected (nbatch, ntemps, rows, nblobs) = %s" % (got, (G, T, R, K)))
+            return lp, bl.reshape(G * T, R, K)
+        return BatchCallable(with_blobs, nblobs=K)
 
     # ------------------------------------------------------------------ device plumbing
     def _ck(self, rc):
@@ -366,6 +403,8 @@ class PTSampler(object):
                     fn, user = _lib.BATCH_LOG_PROB_FN(_trampoline(p.fn, self.device, self._b._cb_box)), None
                 self._prior_keep = fn
                 self._ck(lib.emx_set_batch_prior_callback(h, fn, user))
+            if self.nblobs and self._fused is None:      # a callback with blobs is bound to the handle once it is tempered
+                self._b._bind_callback(h, tempered=True)
             self._h = h
         self._ck(lib.emx_pt_set_swap_every(self._h, self.swap_every))
         if self.adaptive:
@@ -467,8 +506,17 @@ class PTSampler(object):
         self._ck(_lib.load().emx_pt_get_state(self._handle(), L, P))
         return L, P
 
+    def _pt_blobs(self):
+        """-> the current state's blobs (nbatch, ntemps, nwalkers, nblobs) (emx_pt_get_blobs), None without blobs"""
+        if not self.nblobs:
+            return None
+        out = np.empty((self.nbatch, self.ntemps, self.nwalkers, self.nblobs))
+        self._ck(_lib.load().emx_pt_get_blobs(self._handle(), out))
+        return out
+
     def _set_pt_state(self, coords, L, P):
-        """set (coords, L, P) and lp from them (emx_pt_set_state; tests)"""
+        """set (coords, L, P) and lp from them (emx_pt_set_state; tests).  The blobs of a likelihood that has them become NaN: the
+        state bypasses the likelihood."""
         f = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
         self._ck(_lib.load().emx_pt_set_state(self._handle(), f(coords), f(L), f(P)))
 
@@ -493,6 +541,13 @@ class PTSampler(object):
     def get_log_likelihood(self, discard=0, thin=1, flat=False):
         """the untempered log-likelihoods, ``(nbatch, ntemps, nsteps, nwalkers)``."""
         return self._read(2, discard, thin, flat)
+
+    def get_blobs(self, discard=0, thin=1, flat=False):
+        """the blobs stored with every sample, ``(nbatch, ntemps, nsteps, nwalkers, nblobs)``; ``flat`` -> ``(nbatch, ntemps, nsteps *
+        nwalkers, nblobs)``.  None when the likelihood has no blobs."""
+        if not self.nblobs:
+            return None
+        return self._read(4, discard, thin, flat)
 
     def get_betas(self, discard=0, thin=1):
         """the ladder of every stored step, ``(nbatch, nsteps, ntemps)`` (each row as stored: after the step's swap pass and
@@ -557,6 +612,13 @@ class PTSampler(object):
         lead = (self.nbatch, self.ntemps)
         return type(r)(r.nsamples, *[None if a is None else a.reshape(lead + a.shape[1:]) for a in r[1:]])
 
+    def get_blob_summary(self, discard=0, thin=1, quantiles=(0.16, 0.5, 0.84), cov=True):
+        """:meth:`EnsembleBatch.get_blob_summary` of every rung, with ``(nbatch, ntemps, ...)`` leading axes: :meth:`get_summary` over
+        the blob plane, ``nblobs`` in ``ndim``'s place.  ``ValueError`` when the likelihood has no blobs."""
+        r = self._b.get_blob_summary(discard=discard, thin=thin, quantiles=quantiles, cov=cov)
+        lead = (self.nbatch, self.ntemps)
+        return type(r)(r.nsamples, *[None if a is None else a.reshape(lead + a.shape[1:]) for a in r[1:]])
+
     def get_rhat(self, discard=0, thin=1, chains="walkers", log_prob=False):
         """-> :class:`~emcee_amd.summary.RHat` of the rungs (:meth:`EnsembleBatch.get_rhat` on the underlying batch, the same
         bits).  ``chains="walkers"``: every rung of every object is its own group, its walkers the chains, arrays ``(nbatch,
@@ -574,12 +636,20 @@ class PTSampler(object):
     def get_histograms(self, bins=64, range=None, discard=0, thin=1, pairs="all", pair_bins=None):
         """:meth:`EnsembleBatch.get_histograms` of every rung -> :class:`~emcee_amd.summary.BatchHistograms` with ``(nbatch, ntemps,
         ...)`` leading axes on every per-column and per-panel array.  ``range`` may additionally be ``(nbatch, ntemps, ndim, 2)``."""
+        return self._histograms(self._b.get_histograms, self.ndim, bins, range, discard, thin, pairs, pair_bins)
+
+    def get_blob_histograms(self, bins=64, range=None, discard=0, thin=1, pairs="all", pair_bins=None):
+        """:meth:`EnsembleBatch.get_blob_histograms` of every rung, reshaped as :meth:`get_histograms` is, ``nblobs`` in ``ndim``'s
+        place.  ``ValueError`` when the likelihood has no blobs."""
+        return self._histograms(self._b.get_blob_histograms, self.nblobs, bins, range, discard, thin, pairs, pair_bins)
+
+    def _histograms(self, get, W, bins, range, discard, thin, pairs, pair_bins):
         if range is not None and np.ndim(range) == 4:
             range = np.asarray(range, dtype=np.float64)
             if range.shape[:2] != (self.nbatch, self.ntemps):
-                raise ValueError("range: (nbatch, ntemps, ndim, 2) = (%d, %d, %d, 2); got %s" % (self.nbatch, self.ntemps, self.ndim, range.shape))
+                raise ValueError("range: (nbatch, ntemps, ndim, 2) = (%d, %d, %d, 2); got %s" % (self.nbatch, self.ntemps, W, range.shape))
             range = range.reshape((self.nbatch * self.ntemps,) + range.shape[2:])
-        r = self._b.get_histograms(bins=bins, range=range, discard=discard, thin=thin, pairs=pairs, pair_bins=pair_bins)
+        r = get(bins=bins, range=range, discard=discard, thin=thin, pairs=pairs, pair_bins=pair_bins)
         lead = (self.nbatch, self.ntemps)
         split = (lambda arrays: [a.reshape(lead + a.shape[1:]) for a in arrays])
         return type(r)(r.nsamples, split(r.edges), split(r.counts), r.pairs, split(r.pair_edges), split(r.pair_counts))
@@ -674,11 +744,12 @@ class PTSampler(object):
         return thermodynamic_integration_log_evidence(lad[:, 0], means)
 
     def get_last_sample(self):
-        """:class:`State` with ``(nbatch, ntemps, nwalkers, ndim)`` coordinates and tempered ``(nbatch, ntemps, nwalkers)``
-        log-probs."""
+        """:class:`State` with ``(nbatch, ntemps, nwalkers, ndim)`` coordinates, tempered ``(nbatch, ntemps, nwalkers)``
+        log-probs and, for a likelihood with blobs, ``(nbatch, ntemps, nwalkers, nblobs)`` blobs (else None)."""
         s = self._b.get_last_sample()
-        return State(s.coords.reshape(self.nbatch, self.ntemps, self.nwalkers, self.ndim),
-                     log_prob=s.log_prob.reshape(self.nbatch, self.ntemps, self.nwalkers))
+        lead = (self.nbatch, self.ntemps, self.nwalkers)
+        return State(s.coords.reshape(lead + (self.ndim,)), log_prob=s.log_prob.reshape(lead),
+                     blobs=None if s.blobs is None else s.blobs.reshape(lead + (self.nblobs,)))
 
 
 PTSampler.get_rhat.__doc__ += "\n\n        " + _summary.RHAT_DEFINITION

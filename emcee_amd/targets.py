@@ -422,9 +422,14 @@ class PTFused(_FusedUser, BatchTarget):
     computes the same value.  A length other than ``nbatch`` is refused when the sampler takes the target.  Nothing chooses between
     the two forms for the user.  Where it pays, measured on a straight-line fit against the one-lane, one-accumulator functor
     (``profiles/pt_fused_data.md``): at 8 rungs of 32 x 5 from about 1 024 data an object (2.0 times the speed there, 2.6 to 2.8
-    times at 4 096; 3.4 times SLOWER at 16 data, 12 to 15 % slower at 256); at 8 rungs of 64 x 16 only at 4 096 (1.5 times)."""
+    times at 4 096; 3.4 times SLOWER at 16 data, 12 to 15 % slower at 256); at 8 rungs of 64 x 16 only at 4 096 (1.5 times).
 
-    def __init__(self, fn_ptr, ndim, user=None, has_prior=None, ndata=None):
+    ``nblobs = K > 0``: the launcher was emitted by ``EMX_FUSED_PT_TARGET_BLOBS(name, LikeFunctor, PriorFunctor, ndim, K)`` around the
+    likelihood's five-argument form ``(x, ndim, member, user, double* blobs)``, which writes K float64 derived quantities a row
+    (``PTSampler.get_blobs``; the semantics are in the ``pt`` module's docstring).  A launcher compiled for another count is refused
+    when the target is bound.  No blobs with ``ndata`` (``ValueError``)."""
+
+    def __init__(self, fn_ptr, ndim, user=None, nblobs=0, has_prior=None, ndata=None):
         _check_launcher(fn_ptr, "PTFused needs an emx_pt_fused_fn: a ctypes function or a non-null address")
         if isinstance(ndim, bool) or not isinstance(ndim, (int, np.integer)) or ndim < 1:
             raise TypeError("PTFused needs the ndim its launcher was compiled for, an integer >= 1; got %r" % (ndim,))
@@ -432,6 +437,9 @@ class PTFused(_FusedUser, BatchTarget):
         self.fn_ptr, self.ndim, self.user = fn_ptr, int(ndim), user
         self.has_prior = None if has_prior is None else bool(has_prior)
         self.ndata = _check_member_ndata("PTFused", ndata)
+        self.nblobs = _check_nblobs("PTFused", nblobs)
+        if self.ndata is not None and self.nblobs > 0:
+            raise ValueError("PTFused: a target that sums over data (ndata) carries no blobs; nblobs=%d is refused" % self.nblobs)
 
 
 def get_include():
@@ -609,24 +617,27 @@ def compile_fused_ensemble(source, functor, ndim, name=None, flags=(), cache_dir
 
 class PTFusedLibrary(_FusedLibrary):
     """What :func:`compile_fused_pt` built: ``path``, ``lib`` (its ``ctypes.CDLL``), ``name`` of the launcher, ``ndim``,
-    ``has_prior``, ``data`` (the launcher is an ``EMX_FUSED_PT_DATA_TARGET`` one) and :meth:`target`."""
+    ``has_prior``, ``data`` (the launcher is an ``EMX_FUSED_PT_DATA_TARGET`` one), ``nblobs`` and :meth:`target`."""
 
     _who, _compiler, _counts = "PTFusedLibrary", "compile_fused_pt", "the objects' numbers of data"
+    nblobs = 0                            # (an instance attribute only of a library built with blobs)
 
-    def __init__(self, path, name, ndim, has_prior, data=False):
+    def __init__(self, path, name, ndim, has_prior, data=False, nblobs=0):
         self.has_prior = bool(has_prior)
+        if _compile_nblobs("PTFusedLibrary", nblobs, data):
+            self.nblobs = int(nblobs)
         _FusedLibrary.__init__(self, path, name, ndim, data)
 
     def target(self, user=None, ndata=None):
         """-> :class:`PTFused` of the compiled functors with the device pointer ``user``; a library built with ``data=True``
         needs ``ndata`` -- the data every object's ``term`` runs over, an integer or ``nbatch`` of them -- and any other refuses it"""
         self._check_target_ndata(ndata)
-        t = PTFused(self.launcher, self.ndim, user, has_prior=self.has_prior, ndata=ndata)
+        t = PTFused(self.launcher, self.ndim, user, nblobs=self.nblobs, has_prior=self.has_prior, ndata=ndata)
         t._library = self                 # the launcher's code lives as long as the target
         return t
 
 
-def compile_fused_pt(source, likelihood, ndim, prior=None, name=None, flags=(), cache_dir=None, data=False):
+def compile_fused_pt(source, likelihood, ndim, prior=None, name=None, flags=(), cache_dir=None, data=False, nblobs=0):
     """Compile the user's model into the tempered kernel -> :class:`PTFusedLibrary`.
 
     ``source``: HIP C++ that defines the functor type ``likelihood`` and, unless ``prior`` is None, the functor type ``prior`` (both
@@ -638,13 +649,22 @@ def compile_fused_pt(source, likelihood, ndim, prior=None, name=None, flags=(), 
     ``data=True``: ``likelihood`` is a model with ``base(x, ndim, member, user)`` and ``term(x, ndim, member, k, user)`` members whose
     log-likelihood sums over the object's data (:class:`PTFused`'s ``ndata``); ``prior`` is what it is above.  The translation unit
     is ``#include <emx_pt_fused_data.hpp>``, ``source`` and ``EMX_FUSED_PT_DATA_TARGET(name, likelihood, prior or emx::NoFusedPrior,
-    ndim)``.  ``data=False`` keeps the translation unit and the cache key it always had."""
+    ndim)``.  ``data=False`` keeps the translation unit and the cache key it always had.
+
+    ``nblobs = K > 0``: ``likelihood`` has the five-argument form ``(x, ndim, member, user, double* blobs)`` (the prior keeps four) and
+    the translation unit ends in ``EMX_FUSED_PT_TARGET_BLOBS(name, likelihood, prior or emx::NoFusedPrior, ndim, K)``; K joins the
+    cache key only then, so a blob-free build keeps the key and the cached library it always had.  Refused with ``data=True``: the
+    data form carries no blobs."""
+    nblobs = _compile_nblobs("compile_fused_pt", nblobs, data)
     ndim = _compile_ndim("compile_fused_pt", ndim)
     name, flags = _compile_names("compile_fused_pt", "emx_pt_fused", ndim, (("likelihood", likelihood), ("prior", prior)), name, flags)
     args = (name, likelihood, prior or "emx::NoFusedPrior", ndim)
-    so = _compile_form("compile_fused_pt", "emx_pt_fused.hpp", source, "EMX_FUSED_PT_TARGET(%s, %s, %s, %d)" % args,
-                       "EMX_FUSED_PT_DATA_TARGET(%s, %s, %s, %d)" % args, ("pt", source, likelihood, prior, ndim, name), name, flags, cache_dir, data)
-    return PTFusedLibrary(so, name, ndim, prior is not None, data=data)
+    tail, key = "EMX_FUSED_PT_TARGET(%s, %s, %s, %d)" % args, ("pt", source, likelihood, prior, ndim, name)
+    if nblobs:
+        tail, key = "EMX_FUSED_PT_TARGET_BLOBS(%s, %s, %s, %d, %d)" % (args + (nblobs,)), key + ("nblobs", nblobs)
+    so = _compile_form("compile_fused_pt", "emx_pt_fused.hpp", source, tail, "EMX_FUSED_PT_DATA_TARGET(%s, %s, %s, %d)" % args, key, name, flags,
+                       cache_dir, data)
+    return PTFusedLibrary(so, name, ndim, prior is not None, data=data, nblobs=nblobs)
 
 
 def compile_fused(source, functor, ndim, nblobs=0, name=None, flags=(), cache_dir=None, data=False):

@@ -758,8 +758,9 @@ int emx_set_batch_target_fused(emx_batch* b, emx_fused_batch_fn fn, int32_t ndim
  * without reaching the target (a non-finite coordinate, a -inf factor), keep the previous ones.  Values are not validated (NaN is
  * legal).  emx_batch_eval_state_log_prob fills the blobs of the state, emx_batch_chain_read reads the plane (what 4) and
  * emx_summary_batch_plane summarises it.  Coordinates, log-probs and accept counts are bit for bit those of the same function
- * without blobs.  Untempered handles only (emx_pt_set_tempering refuses a handle with blobs); the built-in targets have none.
- * Set before the first stored step.
+ * without blobs.  The built-in targets have none.  Set before the first stored step.  A tempered handle carries them too (a
+ * callback handle takes emx_set_batch_target_callback_blobs once it is tempered; emx_pt_set_tempering refuses a callback handle
+ * that already has blobs): see "blobs of a tempered handle" below.
  *
  * emx_set_batch_target_fused_blobs: emx_set_batch_target_fused for a launcher emitted by EMX_FUSED_BATCH_TARGET_BLOBS(name,
  * Functor, ndim, nblobs) -- the functor's five-argument form (..., double* blobs).  The walkers' blobs live in LDS behind the
@@ -967,6 +968,22 @@ int emx_pt_evidence(emx_batch* b, int64_t g_lo, int64_t g_hi, int64_t start, int
  * current beta */
 int emx_pt_set_state(emx_batch* b, const double* coords, const double* loglike, const double* logprior);
 int emx_pt_get_state(emx_batch* b, double* loglike, double* logprior);
+/* ---- blobs of a tempered handle (emcee_amd.PTSampler.get_blobs) ----
+ * A likelihood with nblobs = K (emx_set_batch_target_callback_blobs AFTER emx_pt_set_tempering, in place of the callback the handle
+ * was tempered with; or emx_pt_set_target_fused_blobs, which like emx_pt_set_target_fused comes before it) produces K doubles with
+ * every untempered L; the prior produces none.  A walker's blobs are replaced exactly when its proposal is accepted by the tempered
+ * commit.  An accepted swap exchanges them together with x, L and P: a blob belongs to the point, not to the rung (a blob that
+ * records `member` names the rung where the point was last evaluated).  Where P is -inf the row's L is ignored and kept as -inf; its
+ * blobs are likewise ignored and stored as NaN (the fused form never calls the likelihood there, the callback path calls it and
+ * discards the result); such a row can only be an initial-state walker.  Stored rows are the blobs after the step's swap pass; the
+ * ladder update does not touch them.  Coordinates, lp, L, P, accept and swap counts, ladders and the Philox step are bit for bit
+ * those of the same function without blobs.  The plane is emx_batch_chain_read's what 4 and plane 4 of emx_summary_batch_plane,
+ * emx_histograms_batch and emx_chain_minmax_batch, as on an untempered handle (L stays what 2); emx_get_blobs_batch reads the
+ * current state's.
+ * emx_pt_get_blobs: the current state's blobs -> out (B, nwalkers, nblobs), next to emx_pt_get_state; -1 for an untempered handle
+ * or one without blobs.  emx_pt_set_state keeps its signature and sets the blobs of a handle that has them to NaN: it bypasses the
+ * likelihood, so there is nothing they could hold. */
+int emx_pt_get_blobs(emx_batch* b, double* out);
 /* the swap draws of every pair after Philox step `step` under `seed`: perm_out / logu_out (ntemps - 1, nwalkers), row i - 1 for
  * pair i: pi_i(k) and log u_{i,k}.  0, or -1 for bad arguments. */
 int emx_host_pt_swap_draws(uint64_t seed, uint64_t step, int64_t nwalkers, int32_t ntemps, int32_t* perm_out, double* logu_out);
@@ -1014,9 +1031,16 @@ typedef struct emx_pt_fused_launch {
     const void* args;        /* PtRunArgs */
     const void* user;        /* user_dev */
     int32_t has_prior;       /* out: 1 when the launcher carries a prior functor */
+    int32_t nblobs;          /* blobs a sample of the handle's likelihood (0: none); the launcher answers 4 when it was compiled for another count */
 } emx_pt_fused_launch;
 typedef int (*emx_pt_fused_fn)(emx_pt_fused_launch*);     /* 0, or non-zero and nothing launched */
 int emx_pt_set_target_fused(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compiled, const void* user_dev);
+/* The same for a launcher emitted by EMX_FUSED_PT_TARGET_BLOBS(name, LikeFunctor, PriorFunctor, ndim, nblobs) around the likelihood's
+ * five-argument form (..., double* blobs): nblobs (1 ... 32) doubles a sample, kept in LDS with the walkers (ntemps nwalkers nblobs
+ * doubles) and the staging rows (ntemps rows nblobs), behind everything a blob-free object holds: emx_pt_fused_check_blobs.  The
+ * probe hands the count to the launcher in the descriptor's `nblobs`, which answers 4 when it was compiled for another one (-1 and
+ * "another number of blobs" at bind time).  nblobs 0 is emx_pt_set_target_fused.  The DATA form carries no blobs. */
+int emx_pt_set_target_fused_blobs(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_compiled, const void* user_dev, int32_t nblobs);
 /* ... whose log-likelihood SUMS OVER AN OBJECT'S DATA (emcee_amd.targets.PTFused(..., ndata=) / compile_fused_pt(..., data=True)):
  * log L(x) = base(x) + sum_k term(x; datum k).  The caller's translation unit includes emcee_amd/csrc/emx_pt_fused_data.hpp and emits
  * the launcher with EMX_FUSED_PT_DATA_TARGET(name, Model, PriorFunctor, ndim) around a model with base(x, ndim, member, user) and
@@ -1037,6 +1061,10 @@ int emx_pt_set_target_fused_data(emx_batch* b, emx_pt_fused_fn fn, int32_t ndim_
  * schedule with at least one plan step, else -1 and the reason (with the bytes needed) in msg */
 int emx_pt_fused_check(int32_t ntemps, int64_t nwalkers, int32_t ndim, int32_t nmoves, const emx_move_desc* moves, char* msg,
                        int32_t msglen);
+/* emx_pt_fused_check for a likelihood with nblobs blobs a sample (nblobs 0: emx_pt_fused_check itself, the same answers and the
+ * same text).  A shape that fits only without the blobs is refused with a message that names LDS and the "<nblobs> blobs". */
+int emx_pt_fused_check_blobs(int32_t ntemps, int64_t nwalkers, int32_t ndim, int32_t nmoves, const emx_move_desc* moves, int32_t nblobs,
+                             char* msg, int32_t msglen);
 
 #ifdef __cplusplus
 }
