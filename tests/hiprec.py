@@ -116,6 +116,11 @@ def dsum(x, axis=0):
     return h[0], l[0]
 
 
+def rowdot(x, y):
+    """row-wise dot product of two double-double arrays (n, D) -> (n,) double-double"""
+    return dsum(mul(x, y), axis=1)
+
+
 def to_float(x):
     return x[0] + x[1]
 

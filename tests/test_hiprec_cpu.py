@@ -101,6 +101,22 @@ def test_sqrt_and_sum_against_mpmath():
     assert abs(ddF(s) - want) <= REL * sum(abs(F(u)) for u in t)
 
 
+def test_rowdot_against_fractions():
+    """ordinary rows, rows that cancel almost completely, and an odd number of columns"""
+    rs = np.random.RandomState(5)
+    n, D = 12, 37
+    a = rs.randn(n, D) * 2.0 ** rs.randint(-20, 20, (n, D))
+    b = rs.randn(n, D) * 2.0 ** rs.randint(-20, 20, (n, D))
+    a[:4, 18:36], b[:4, 18:36] = a[:4, :18], -b[:4, :18] * (1 + rs.randn(4, 18) * 2.0 ** -45)
+    x = hp.fast_two_sum(a, a * rs.uniform(-1, 1, (n, D)) * 2.0 ** -54)
+    y = hp.fast_two_sum(b, b * rs.uniform(-1, 1, (n, D)) * 2.0 ** -54)
+    r = hp.rowdot(x, y)
+    assert r[0].shape == (n,)
+    for i in range(n):
+        terms = [ddF(x, (i, d)) * ddF(y, (i, d)) for d in range(D)]
+        assert abs(ddF(r, i) - sum(terms)) <= REL * sum(abs(t) for t in terms), i
+
+
 def test_walk_weights_sum_to_zero_and_proposal_exact():
     rs = np.random.RandomState(4)
     ns, s, D = 5, 7, 3
