@@ -394,10 +394,23 @@ struct emx_ctx {
     int64_t tune_mt_regen_min = 16384;   // exact mode, host pipeline with device finish: from this many walkers on a stretch step's fixed-length draws are made again
                                          // on the device from the generator's state (k_plan_regen) instead of crossing PCIe; 0: never
     int64_t pipe_regen_steps = 0;
+    int64_t tune_persist_carry = 1;      // device-wide stretch launches without stored rows over arranged plans take k_persist's CARRY instantiation (0: never)
+    int64_t persist_carry_launches = 0;
+    bool plan_tail_ok = false;           // the last step native_prepare_batch planned was a stretch step of two splits: step plan_tail_step under plan_tail_seed
+    uint64_t plan_tail_step = 0, plan_tail_seed = 0;
+    // (Safety does not rest on these: an arranged step is a valid listing of its split whatever ran before, and k_persist trusts a keep
+    // mask only at a boundary INSIDE a launch, whose steps are consecutive by construction -- run_persist takes them one after another
+    // from c->prepared, step numbers ascending, all of the launch's move.)
+    int32_t* arr_scr[2] = {nullptr, nullptr};     // native_prepare_batch: the arrangement lists of the batch being planned | of the batch expected next
+    int arr_cur = 0;
+    bool pre_valid = false;                       // arr_scr[arr_cur] holds the lists of pre_nb steps from pre_first under pre_seed
+    uint64_t pre_first = 0, pre_seed = 0;
+    int pre_nb = 0;
     int64_t tune_persist_odd = 1;        // 0: dense targets of odd ndim never take k_persist (emx_podd.hip)
     int64_t tune_persist_slab_skew = 1;  // k_persist_slab: the second wave of a SIMD starts its row loads when its sibling's have arrived (0: at once; 2 ... 4: earlier)
     int64_t tune_persist_slab_local_max = 4096;      // largest ensemble that takes the one-XCD form of k_persist_slab (beyond: the device-wide form; measured, profiles/r06/pslab.txt)
     int64_t call_steps = 1;              // steps of the emx_run call being served (1: emx_step_begin on its own)
+    bool call_store = false;             // ... and whether that call stores chain rows (its launches then never take k_persist's CARRY form)
     int64_t tune_persist_exact = 1;      // 0: exact (MT19937) mode never takes the persistent kernels
     int64_t tune_persist_valu = 1;       // 0: never the persistent kernel of the element-wise targets (emx_pvalu.hip)
     int64_t tune_persist_local_max = 8192;    // largest ensemble that takes it
@@ -416,6 +429,7 @@ struct emx_ctx {
     struct Prepared {   // native plans already evaluated on the device, in step order
         int move, S, slot;
         bool lean;          // only the columns the fused half-step reads were written
+        bool arranged;      // split 0 is listed in plan_arrange_host's slot order after the step before (keep masks in the head of p1)
         int gcol;           // Gaussian sequential mode: the coordinate this step moves
         uint64_t step;
         NativeArgs nat;
@@ -430,6 +444,7 @@ struct emx_ctx {
         int move = 0, S = 2, slot = 0;
         bool store = false;
         bool native = false;
+        bool arranged = false; // Prepared::arranged
         bool lean = false;     // native plan without the columns nothing on the fused path reads (emx_plan_get completes it)
         bool devplan = false;  // exact-mode plan written by the device producer: there is no host copy of it
         int gcol = 0;
@@ -580,6 +595,7 @@ static void drop_prepared(emx_ctx* c) {
     for (auto it = c->prepared.rbegin(); it != c->prepared.rend(); ++it)
         if (it->move < (int)c->moves.size() && c->moves[it->move].kind == EMX_MOVE_GAUSS) c->moves[it->move].gammas = it->cursor_before;
     c->prepared.clear();
+    c->plan_tail_ok = false;          // (the next batch starts a sequence of its own: its first step is in position order)
 }
 
 #define FAIL(ctx, code, ...)                         \
@@ -1461,6 +1477,8 @@ int emx_destroy(emx_ctx* c) {
     if (c->persist_bar) hipFree(c->persist_bar);
     if (c->persist_started) hipHostFree(c->persist_started);
     if (c->persist_ver) hipFree(c->persist_ver);
+    for (int q = 0; q < 2; ++q)
+        if (c->arr_scr[q]) hipFree(c->arr_scr[q]);
     if (c->d_desc) hipFree(c->d_desc);
     if (c->d_ctr) hipFree(c->d_ctr);
     if (c->h_ctr) hipHostFree(c->h_ctr);
@@ -1673,6 +1691,11 @@ int emx_set_tuning(emx_ctx* c, const char* key, int64_t v) {
     if (!strcmp(key, "mt_regen_min_walkers")) {      // 0: never k_plan_regen (takes effect when a pipeline starts)
         PIPE_STOP(c);
         c->tune_mt_regen_min = v < 0 ? 0 : v;
+        return 0;
+    }
+    if (!strcmp(key, "persist_carry")) {     // 0: never k_persist's CARRY instantiation (and the plans made from then on are not arranged for it)
+        NEED(c, v == 0 || v == 1, "tuning persist_carry: 0 or 1");
+        c->tune_persist_carry = v;
         return 0;
     }
     if (!strcmp(key, "persist_rows_late")) {
@@ -2936,6 +2959,7 @@ int emx_step_begin_with(emx_ctx* c, int32_t store, int32_t move_index, int32_t* 
 // to c->prepared in step order.  (Measured and dropped, rounds 2 and 3: the NEXT batch on a second, low-priority stream next to
 // this batch's half-steps, with and without raised wave priority for the half-step kernel -- the co-resident plan waves slow
 // every half-step launch by 0.8 us: C2 23.69 -> 24.40 us/step, C3 38.65 -> 39.5; profiles/r03/ab_side_stream.txt.)
+static bool persist_carry_plans(const emx_ctx* c);
 static int native_prepare_batch(emx_ctx* c, uint64_t first_step, int nb, int forced_move, hipStream_t st) {
     const int nm = (int)c->moves.size();
     NativeBatchArgs B{};
@@ -2986,11 +3010,45 @@ static int native_prepare_batch(emx_ctx* c, uint64_t first_step, int nb, int for
         B.move[b] = m.kind;
         B.S[b] = m.nsplits;
     }
-    if (only_stretch && B.lean && !B.ablate && !B.desc)       // (the same arithmetic without the other moves' branches: 32 VGPRs against 80)
-        hipLaunchKernelGGL(k_native_plan_batch_stretch, dim3((unsigned)((c->N + 255) / 256), (unsigned)nb), dim3(256), 0, st, B);
-    else
+    if (only_stretch && B.lean && !B.ablate && !B.desc) {     // (the same arithmetic without the other moves' branches: 32 VGPRs against 80)
+        // where k_persist's CARRY form can run these steps, split 0 of every step is listed after the step before (plan_arrange_host):
+        // the steps of a batch after each other, its first step after the step in front of it -- a stretch step of two splits too, since
+        // the schedule has no other move -- unless it is the run's first
+        bool all_two = true;
+        for (int b = 0; b < nb; ++b) all_two = all_two && B.S[b] == 2;
+        const int64_t n0 = c->N / 2;
+        unsigned extra = 0;
+        if (nb > 1 && all_two && persist_carry_plans(c) && st == c->stream && (n0 + 255) / 256 <= PLAN_ARRANGE_MAX_BLOCKS) {
+            B.arrange = 1;
+            B.arr0 = (c->plan_tail_ok && c->plan_tail_seed == c->ph_seed && c->plan_tail_step + 1 == first_step) ? 1 : 0;
+            if (B.arr0) B.kprev0 = make_perm_key((uint64_t)c->N, c->ph_seed, first_step - 1);
+            for (int b = 0; b < nb; ++b) c->prepared[c->prepared.size() - (size_t)nb + (size_t)b].arranged = b > 0 || B.arr0;
+            // The arrangement lists are a function of the keys alone.  Two buffers: the plan kernel of a batch reads one and, as extra
+            // workgroups, fills the other for the batch expected next (the steps that follow, as many, the same seed); a batch that
+            // was not foreseen -- the first, one after another seed or step -- has them made by a launch of its own first.
+            const size_t words = (size_t)plan_arrange_words(c->N) * NATIVE_BATCH_MAX;
+            for (int q = 0; q < 2; ++q)
+                if (!c->arr_scr[q]) HIPOK(c, hipMalloc((void**)&c->arr_scr[q], words * sizeof(int32_t)));
+            B.arr_scr = c->arr_scr[c->arr_cur];
+            const bool foreseen = B.arr0 && c->pre_valid && c->pre_first == first_step && c->pre_seed == c->ph_seed && c->pre_nb == nb;
+            if (!foreseen) hipLaunchKernelGGL(k_plan_arrange, dim3((unsigned)((n0 + 255) / 256), (unsigned)nb), dim3(256), 0, st, B);
+            B.pre_scr = c->arr_scr[c->arr_cur ^ 1];
+            for (int k = 0; k <= nb; ++k) B.set_pre_key(k, make_perm_key((uint64_t)c->N, c->ph_seed, first_step + (uint64_t)nb - 1 + (uint64_t)k));
+            c->pre_valid = true;
+            c->pre_first = first_step + (uint64_t)nb;
+            c->pre_seed = c->ph_seed;
+            c->pre_nb = nb;
+            c->arr_cur ^= 1;          // (the next arranged batch reads what this launch's extra workgroups write)
+            extra = (unsigned)((n0 + 255) / 256);
+        }
+        hipLaunchKernelGGL(k_native_plan_batch_stretch, dim3((unsigned)((c->N + 255) / 256) + extra, (unsigned)nb), dim3(256), 0, st, B);
+    } else
         hipLaunchKernelGGL(k_native_plan_batch, dim3((unsigned)((c->N + 255) / 256), (unsigned)nb), dim3(256), 0, st, B);
     HIPOK(c, hipGetLastError());
+    // the step the next batch's first step may be arranged after: planned here, a stretch step of two splits
+    c->plan_tail_ok = nb > 0 && B.move[nb - 1] == EMX_MOVE_STRETCH && B.S[nb - 1] == 2;
+    c->plan_tail_step = first_step + (uint64_t)nb - 1;
+    c->plan_tail_seed = c->ph_seed;
     return 0;
 }
 
@@ -3001,6 +3059,7 @@ static int step_begin_impl(emx_ctx* c, int32_t store, int32_t forced_move, int32
     auto& cur = c->cur;
     cur.store = store != 0;
     cur.native = false;
+    cur.arranged = false;
     cur.devplan = false;
     const int nm = (int)c->moves.size();
     const bool devp = forced_move < 0 && mtdev_eligible(c);
@@ -3078,6 +3137,7 @@ static int step_begin_impl(emx_ctx* c, int32_t store, int32_t forced_move, int32
         cur.S = pr.S;
         cur.native = true;
         cur.lean = pr.lean;
+        cur.arranged = pr.arranged;
         cur.gcol = pr.gcol;
         cur.nat = pr.nat;
         cur.slot = pr.slot;
@@ -3135,6 +3195,7 @@ static int complete_lean_plan(emx_ctx* c) {
     hipLaunchKernelGGL(k_native_plan_batch, dim3((unsigned)((c->N + 255) / 256), 1u), dim3(256), 0, c->stream, B);
     HIPOK(c, hipGetLastError());
     cur.lean = false;
+    cur.arranged = false;       // (the slot now lists split 0 in position order, and p1 holds partners, not keep masks)
     return 0;
 }
 
@@ -3995,6 +4056,16 @@ static bool persist_wanted(const emx_ctx* c) {
     return sh.G == 8 && sh.V == 2 && sh.CH == (dpb == 1 ? 1 : dpb == 2 ? 2 : 4);
 }
 
+// Can a launch of k_persist's CARRY form run this context's stretch steps?  (Then native_prepare_batch arranges their plans: the
+// even-ndim dense kernel up to ndim 64 at a device-wide grid; which launches take the form is run_persist's decision.)  Not for a
+// call that stores chain rows, whose launches keep ROWS_LATE: arranging costs the plan kernel 8.7 us a batch of sixteen steps at
+// 65 536 walkers (profiles/r07/carry.md), which such a run would pay for nothing.
+static bool persist_carry_plans(const emx_ctx* c) {
+    if (!c->tune_persist_carry || c->call_store) return false;
+    if (c->rng_mode != EMX_RNG_PHILOX || (c->N & 1) || (c->D & 1) || c->Dp > 64 || !persist_wanted(c)) return false;
+    return persist_shape(c, 2) != 0;
+}
+
 // The element-wise targets (csrc/emx_pvalu.hip): the one-XCD form only -- ensembles of up to 8 192 walkers, rows of 4 or 8 lanes per walker
 // (ndim <= 64 even, <= 32 odd), Philox plans, one replica, every move of the schedule one the kernel knows at a shape it can take.
 static bool persist_valu_wanted(const emx_ctx* c) {
@@ -4165,6 +4236,7 @@ static int run_persist(emx_ctx* c, int64_t i0, int64_t total, int32_t thin_by, i
     int launch_S = 2;
     bool launch_local = false;           // the one-XCD form: an eight times larger grid of which every eighth workgroup works
     bool launch_mix = false;             // DE and snooker steps of a mixture in this launch (k_persist_mix)
+    bool carry_ok = true;                // no step after the launch's first whose plan is not arranged after the step before
     double launch_gammas = 0.0;
     // Philox plans live in a ring of TWO batches of sixteen steps (PLAN_RING): a launch may read the plans of at most two batches --
     // a third would be written into the half of the ring whose slots this very launch still reads (round 6, when a launch grew from
@@ -4213,6 +4285,8 @@ static int run_persist(emx_ctx* c, int64_t i0, int64_t total, int32_t thin_by, i
         int mvi, S;
         int rc = emx_step_begin(c, st, &mvi, &S);
         if (rc) return rc;
+        // k_persist's CARRY form: every step boundary inside the launch joins a step to one whose split 0 is arranged after it
+        if (steps > 0 && !(c->cur.native && c->cur.arranged)) carry_ok = false;
         if (launch_move < 0) {
             launch_move = c->moves[mvi].kind;
             launch_gammas = c->moves[mvi].gammas;
@@ -4351,7 +4425,11 @@ static int run_persist(emx_ctx* c, int64_t i0, int64_t total, int32_t thin_by, i
         } else if (c->D & 1) {
             e = launch_persist_dense_odd(c->Dp / 16, launch_move, launch_local ? 1 : 0, grid, block, lds, c->stream, P);
         } else {
-            e = launch_hot_persist_dense(c->Dp / 16, launch_move, launch_local ? 1 : 0, rows_late ? 1 : 0, grid, block, lds, c->stream, P);
+            // launches that store none, device-wide, stretch steps of two splits over arranged Philox plans: own rows carried over the
+            // step boundary in registers (k_persist's CARRY; profiles/r07/carry.md) -- tuning persist_carry 0: never
+            const bool carry = c->tune_persist_carry && carry_ok && !mtmode && !store && !launch_local && launch_move == EMX_MOVE_STRETCH && launch_S == 2;
+            if (carry) c->persist_carry_launches++;
+            e = launch_hot_persist_dense(c->Dp / 16, launch_move, launch_local ? 1 : 0, carry ? 2 : rows_late ? 1 : 0, grid, block, lds, c->stream, P);
         }
         if (launch_local) c->persist_local_launches++;
         if (e != hipSuccess) FAIL(c, -2, "persistent half-step launch failed: %s", hipGetErrorString(e));
@@ -4571,12 +4649,50 @@ int emx_persist_local_launches(emx_ctx* c, int64_t* n) {
     return 0;
 }
 
+int emx_persist_carry_launches(emx_ctx* c, int64_t* n) {
+    *n = c->persist_carry_launches;
+    return 0;
+}
+
+// the host's form of an arranged lean stretch plan (plan_arrange_host, csrc/emx_kernels.hpp): what k_plan_arrange and
+// k_native_plan_batch_stretch write for `step`, the logarithms apart
+int emx_plan_arrange(uint64_t seed, uint64_t step, int32_t has_prev, int64_t nwalkers, double a, int32_t* order, int32_t* p0, double* s0,
+                     double* uacc, int32_t* keep_mask) {
+    if (nwalkers < 2 || (nwalkers & 1) || nwalkers > (1ll << 30) || !order || !p0 || !s0 || !uacc || !keep_mask) return -1;
+    if (has_prev && step == 0) return -1;
+    const int64_t N = nwalkers, n0 = N / 2;
+    NativeArgs na{};
+    na.seed = seed;
+    na.step = step;
+    na.pk = make_perm_key((uint64_t)N, seed, step);
+    std::vector<int32_t> pos_of((size_t)n0);
+    if (has_prev) {
+        plan_arrange_host(N, make_perm_key((uint64_t)N, seed, step - 1), na.pk, pos_of.data(), keep_mask);
+    } else {
+        for (int64_t s = 0; s < n0; ++s) pos_of[(size_t)s] = (int32_t)s;
+        for (int64_t tl = 0; tl < (n0 + 15) / 16; ++tl) keep_mask[tl] = 0;
+    }
+    for (int64_t pos = 0; pos < N; ++pos) {
+        const int split = pos < n0 ? 0 : 1;
+        const int t = split ? (int)(pos - n0) : pos_of[(size_t)pos];
+        int i, a0, a1, a2;
+        double z, u;
+        native_slot<MOVE_STRETCH>(na, (int)N, 2, split, t, a, 0.0, 0.0, i, a0, a1, a2, z, u);
+        order[pos] = i;
+        p0[pos] = a0;
+        s0[pos] = z;
+        uacc[pos] = u;
+    }
+    return 0;
+}
+
 int emx_run(emx_ctx* c, int64_t nsteps, int32_t thin_by, int32_t store) {
     HIPOK(c, hipSetDevice(c->device));
     NEED(c, thin_by >= 1, "Invalid thinning argument");
     NEED(c, !c->cur.active, "emx_run: a step begun with emx_step_begin is still open");
     const int64_t total = nsteps * thin_by;
     c->call_steps = total;
+    c->call_store = store != 0;
     // exact mode, general path: the plans of the whole call come from the host pipeline (generator / tokenizer /
     // finisher threads) instead of being made inline, one step at a time, by this thread
     const bool devp = mtdev_eligible(c);
@@ -5691,6 +5807,11 @@ int emx_device_ptr(emx_ctx* c, int32_t which, void** ptr, int64_t* nbytes) {
         case 6: *ptr = c->disp; *nbytes = c->disp ? c->N * c->D * 8 : 0; return 0;
         case 7: *ptr = c->dbg; *nbytes = c->dbg ? c->dbg_blocks * 16 * 8 : 0; return 0;
         case 8: *ptr = c->my_flags; *nbytes = c->my_flags ? EMX_MAX_PEERS * 8 : 0; return 0;
+    }
+    if (which >= 16 && which < 16 + PLAN_RING) {        // slot which - 16 of the plan ring: one block, PersistCols' layout (the tests of the arranged plans)
+        *ptr = c->ring[which - 16].order;
+        *nbytes = c->ring[which - 16].order ? c->N * 48 : 0;
+        return 0;
     }
     FAIL(c, -1, "unknown device pointer id %d", which);
 }

@@ -1490,9 +1490,14 @@ __device__ __forceinline__ bool persist_handshake(const PersistArgs& P) {
     return ok_s != 0;
 }
 
-template <int G, int V, int CH, int DPB, int MOVE = MOVE_STRETCH, bool LOCAL = false, bool ROWS_LATE = false>
+// CARRY (round 7; the device-wide stretch form of launches whose every step boundary joins two steps of one arranged sequence of plans,
+// plan_arrange_host, and that store no chain rows): at a step boundary a wave keeps the rows and log-probs it holds of the walkers that
+// stay in its slots (the keep mask of its tile, loaded with the next half-step's plan entries) and prefetches the others, which nobody
+// writes meanwhile -- no stamp loads, no reloads, no wait behind the barrier (profiles/r07/carry.md).
+template <int G, int V, int CH, int DPB, int MOVE = MOVE_STRETCH, bool LOCAL = false, bool ROWS_LATE = false, bool CARRY = false>
 static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
     static_assert(MOVE == MOVE_STRETCH || MOVE == MOVE_DE || MOVE == MOVE_SNOOKER, "the red / blue moves");
+    static_assert(!CARRY || (MOVE == MOVE_STRETCH && !LOCAL && !ROWS_LATE), "CARRY: the device-wide stretch form without stored rows");
     // LOCAL: the one-XCD form for small ensembles.  The dispatcher deals workgroups to the eight XCDs in turn (workgroup i -> XCD
     // i mod 8: tools/exp/cu_mask_probe.hip), so of an eight times larger grid only every eighth workgroup works -- all of them on one
     // XCD, whose L2 then keeps the walker state coherent without agent-scope accesses (3.0 + 2.5 us of partner round trip and barrier
@@ -1537,6 +1542,7 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
     // half-step -- ticks summed over the launch's half-steps: partner rows arrive | proposals + tile | MFMA + reductions |
     // decisions + commit issued | stores acknowledged | barrier
     unsigned long long pst[6] = {0, 0, 0, 0, 0, 0}, pt = 0;
+    unsigned long long pstb[2] = {0, 0};        // "partner rows arrive" again: of the half-steps behind a step boundary | of the others (not the launch's first)
     const bool prof = EMX_OPT_STAMPS && A.dbg && wib == EMX_STAMP_WAVE;
     if (prof) {
         pt = __builtin_readcyclecounter();
@@ -1619,10 +1625,20 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
             my_i_n = J.order[pbase + myrow];
             my_logu_n = J.logu[pbase + myrow];
         }
+        // CARRY: the keep mask of this wave's tile in the next half-step, where that one is the first of a step (0: every row is loaded).
+        // (Every wave of the grid has a tile: persist_shape_of takes grids of tiles / waves-per-workgroup workgroups only where that
+        // divides -- 2 080 walkers are 65 workgroups of one wave -- so `wave` is below the split's N / 32 tiles, each with a mask.)
+        unsigned keep_n = 0u;
+        if constexpr (CARRY) {
+            if (more && !pre) keep_n = (unsigned)J.p1[wave];
+        }
         // (the scheduler puts these loads BEHIND the wait for the partner rows.  Forced in front of it -- a scheduling barrier here -- the
         // step is 2.4 % slower, 20.17 -> 20.65 us: ten more requests in front of the rows; profiles/r06/stagger/entries_early_ab.txt)
         // -------- proposals -> the wave's LDS tile (R = Q - mu), kept in registers for the commit --------
-        if (prof) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+        if (prof) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (n > 0) pstb[I.split == 0 ? 0 : 1] += __builtin_readcyclecounter() - pt;
+        }
         EMX_PSTAMP(0);       // partner rows (and the next half-step's plan entries) have arrived
         Row<G, V, CH> qk[PF];
 #pragma unroll
@@ -1672,10 +1688,16 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
         // half-step before (65 536 x 64 with the chain stored every step: 27.6-27.9 -> 26.3-26.4 us/step; without stored rows the same
         // move costs 4 %: 20.25 -> 21.1, hence a template parameter; profiles/r06/stagger/ownrows_late_ab*.txt)
         double my_lpo_n = 0.0;
-        if (!ROWS_LATE && more) {
+        if (!ROWS_LATE && !CARRY && more) {
 #pragma unroll
             for (int k = 0; k < PF; ++k) load_row_agent<G, V, CH, CPOL>(xi[k], Xr, wi_n[k], D, gl);
             my_lpo_n = load_agent(A.lp + my_i_n);
+        }
+        if (CARRY && more) {      // the keep slots' registers are left alone: they hold the walker's row of this half-step
+#pragma unroll
+            for (int k = 0; k < PF; ++k)
+                if (!((keep_n >> (k * WPW + sub)) & 1u)) load_row_agent<G, V, CH, CPOL>(xi[k], Xr, wi_n[k], D, gl);
+            if (!((keep_n >> myrow) & 1u)) my_lpo_n = load_agent(A.lp + my_i_n);
         }
         EMX_WAVE_SYNC();
         EMX_PSTAMP(1);       // proposals made, tile written, chain rows and next own rows issued
@@ -1710,11 +1732,13 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
         EMX_PSTAMP(2);       // MFMA chain + reductions
         // -------- decisions (red_blue.py:99-100) and commit (move.py:33-34) --------
         bool acc = false;
+        double lp_kept = my_lpo;            // CARRY: the log-prob of this decision lane's walker after this half-step
         if (mine) {
             const double lpn = -0.5 * my_qf;
             if (lpn != lpn) raise_status(A.status, ST_NAN_LOGP);
             const double lnpdiff = facS[myrow] + lpn - my_lpo;
             acc = lnpdiff > my_logu;
+            if (CARRY && acc) lp_kept = lpn;
             store_scope<LOCAL>(A.acc + my_i, (uint8_t)(acc ? 1 : 0));       // (a walker's mark is written by another XCD every step: write-through)
             if (acc) {
                 store_scope<LOCAL>(A.lp + my_i, lpn);
@@ -1776,7 +1800,15 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
         my_i = my_i_n;
         my_logu = my_logu_n;
         my_lpo = my_lpo_n;
-        if (!pre) {      // first split of a new step: the walkers that moved in the half-step before are loaded again
+        if constexpr (CARRY) {      // a kept walker: what this wave made of it (keep_n is 0 inside a step)
+#pragma unroll
+            for (int k = 0; k < PF; ++k) {
+                const int row = k * WPW + sub;
+                if (((keep_n >> row) & 1u) && ((am64 >> ((row & 3) * 16 + (row >> 2))) & 1ull)) xi[k] = qk[k];
+            }
+            if ((keep_n >> myrow) & 1u) my_lpo = lp_kept;
+        }
+        if (!CARRY && !pre) {      // first split of a new step: the walkers that moved in the half-step before are loaded again
             unsigned vk[PF];
 #pragma unroll
             for (int k = 0; k < PF; ++k) vk[k] = load_agent(P.ver + wi[k]);
@@ -1797,6 +1829,8 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) o[k] = pst[k];
         o[6] = (unsigned long long)P.niter;
+        o[7] = pstb[0];
+        o[8] = pstb[1];
         o[12] = wall_clock64();
     }
 #undef EMX_PSTAMP
@@ -3005,12 +3039,173 @@ struct NativeBatchArgs {
     int32_t lean;           // 1: only the columns the fused half-step kernel of the step's move reads are written (below)
     int32_t ablate;         // timing experiments only (tuning "ablate" bits 8..): 1 no logs, 2 no stores, 4 return at once; 0 in production
     const StepDesc* desc;   // graph replay: per-step NativeArgs from device memory instead of nat[]
+    // the lean stretch batch (k_native_plan_batch_stretch) for k_persist's CARRY form: split 0 of a step is listed in the slot order
+    // plan_arrange_host defines, after the step before (step b - 1 of the batch; for step 0 the key `kprev0`, where `arr0` says it has one)
+    int32_t arrange, arr0;
+    PermKey kprev0;
+    int32_t* arr_scr;       // this batch's arrangement lists (plan_arrange_block), plan_arrange_words(N) words a step
+    int32_t* pre_scr;       // ... and where this launch's extra workgroups make those of the batch after (nullptr: they do not)
+    // the keys of that batch's steps from the host, the step in front of it first: what differs from nat[0].pk (deriving them costs
+    // a thread about 600 instructions, six times the arrangement proper: profiles/r07/carry.md)
+    struct KeyWords {
+        uint32_t m1, c1, m2, c2, m3, c3, m1inv, m2inv, m3inv;
+    } pre_keys[NATIVE_BATCH_MAX + 1];
+    __host__ __device__ PermKey pre_key(int k) const {
+        PermKey K = nat[0].pk;          // (n, bits, mask and the shifts depend on the ensemble's size alone)
+        const KeyWords& w = pre_keys[k];
+        K.m1 = w.m1; K.c1 = w.c1; K.m2 = w.m2; K.c2 = w.c2; K.m3 = w.m3; K.c3 = w.c3;
+        K.m1inv = w.m1inv; K.m2inv = w.m2inv; K.m3inv = w.m3inv;
+        return K;
+    }
+    void set_pre_key(int k, const PermKey& K) { pre_keys[k] = KeyWords{K.m1, K.c1, K.m2, K.c2, K.m3, K.c3, K.m1inv, K.m2inv, K.m3inv}; }
 };
+static_assert(sizeof(NativeBatchArgs) <= 4096, "kernel arguments of the plan kernels");
+
+// ---- split 0 of a stretch step (S = 2, even N) arranged after the step before: k_persist's CARRY form ----
+// With the keys Kp (step before) and K: a(s) = perm_inv(2 s + 1, Kp) is the walker of the step before's split-1 slot s.  Where it belongs
+// to split 0 of this step (perm_fwd(a(s), K) even) slot s of split 0 lists it -- a KEEP slot: the wave that ran it still holds its row --
+// and the other slots, ascending, take the walkers b(p) = perm_inv(2 p, K) that were in split 0 of the step before (perm_fwd(b(p), Kp)
+// even), p ascending: nobody writes those during the step before's second half, so they can be prefetched.  There are as many of the
+// one as of the other.  Every slot's entry is native_slot's of the walker's position perm_fwd(c(s), K) / 2: the draws belong to the
+// walker, the listing of a split is free.  One 16-bit keep mask per tile of 16 slots (bit s & 15).
+// The host's form, the definition (emx_plan_arrange; tests/test_plan_carry_cpu.py): -> pos_of[s], the position whose entry slot s holds
+inline void plan_arrange_host(int64_t N, const PermKey& Kp, const PermKey& K, int32_t* pos_of, int32_t* keep_mask) {
+    const int64_t n0 = N / 2;
+    for (int64_t tl = 0; tl < (n0 + 15) / 16; ++tl) keep_mask[tl] = 0;
+    int64_t p = 0;
+    for (int64_t s = 0; s < n0; ++s) {
+        const uint32_t a = perm_inv((uint32_t)(2 * s + 1), Kp), pa = perm_fwd(a, K);
+        if (!(pa & 1u)) {
+            pos_of[s] = (int32_t)(pa >> 1);
+            keep_mask[s >> 4] |= 1 << (s & 15);
+        } else {
+            while (perm_fwd(perm_inv((uint32_t)(2 * p), K), Kp) & 1u) ++p;
+            pos_of[s] = (int32_t)p++;
+        }
+    }
+}
+
+// The device's form, in two parts, through a scratch list of the context's own (plan_arrange_words(N) words a step).  This part: every
+// 256 slots' keep flags, the hole slots' ranks and the fillers, block by block, with the blocks' counts:
+// [n0] a keep slot's position, or -1 - (rank of the hole in its block) | [n0] block k's fillers' positions from word 256 k |
+// [2 nblk] holes, fillers of block k | [ntiles] keep masks
+// It reads nothing but the two keys, so it need not wait for anything on the device: the plan kernel of a batch runs it for the batch
+// AFTER as extra workgroups (native_plan_batch_body), and only a batch nobody foresaw takes the launch of its own (k_plan_arrange).
+__host__ __device__ inline int64_t plan_arrange_words(int64_t N) {
+    const int64_t n0 = N / 2;
+    return 2 * n0 + 2 * ((n0 + 255) / 256) + (n0 + 15) / 16;
+}
+static __device__ __forceinline__ void plan_arrange_block(int N, const PermKey& Kp, const PermKey& K, int32_t* scr, int bx) {
+    const int n0 = N / 2, nblk = (n0 + 255) / 256;
+    const int s = bx * 256 + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    bool keep = false, fill = false;
+    uint32_t pa = 0;
+    if (s < n0) {
+        pa = perm_fwd(perm_inv((uint32_t)(2 * s + 1), Kp), K);
+        keep = !(pa & 1u);
+        fill = !(perm_fwd(perm_inv((uint32_t)(2 * s), K), Kp) & 1u);
+    }
+    const bool hole = s < n0 && !keep;
+    const unsigned long long mh = __ballot(hole), mf = __ballot(fill), mk = __ballot(keep);
+    __shared__ int wh[4], wf[4];
+    if (lane == 0) {
+        wh[wv] = __popcll(mh);
+        wf[wv] = __popcll(mf);
+    }
+    __syncthreads();
+    int hb = 0, fb = 0;
+    for (int w = 0; w < wv; ++w) {
+        hb += wh[w];
+        fb += wf[w];
+    }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (s < n0) scr[s] = keep ? (int32_t)(pa >> 1) : -1 - (hb + __popcll(mh & below));
+    if (fill) scr[n0 + bx * 256 + fb + __popcll(mf & below)] = s;
+    if (threadIdx.x == 0) {
+        scr[2 * n0 + 2 * bx] = wh[0] + wh[1] + wh[2] + wh[3];
+        scr[2 * n0 + 2 * bx + 1] = wf[0] + wf[1] + wf[2] + wf[3];
+    }
+    if ((lane & 15) == 0 && s < n0) scr[2 * n0 + 2 * nblk + (s >> 4)] = (int32_t)((mk >> lane) & 0xffffull);
+}
+static __global__ __launch_bounds__(256) void k_plan_arrange(const NativeBatchArgs B) {
+    const int b = blockIdx.y;
+    if (b == 0 && !B.arr0) return;
+    const PermKey K = B.nat[b].pk, Kp = b ? B.nat[b - 1].pk : B.kprev0;
+    plan_arrange_block(B.N, Kp, K, B.arr_scr + (size_t)b * plan_arrange_words(B.N), blockIdx.x);
+}
+constexpr int PLAN_ARRANGE_MAX_BLOCKS = 1024;      // 256-slot blocks of a split k_plan_arrange's reader sums in LDS: ensembles of up to 524 288 walkers
+
+// ... and the plan kernel's part: the position whose entry split-0 slot `pos` holds.  Called by every thread of a block.
+static __device__ __forceinline__ int plan_arranged_pos(const NativeBatchArgs& B, int b, int pos) {
+    __shared__ int hpre[PLAN_ARRANGE_MAX_BLOCKS], fpre[PLAN_ARRANGE_MAX_BLOCKS], wth[4], wtf[4];
+    const int n0 = B.N / 2, nblk = (n0 + 255) / 256, E = (nblk + 255) / 256;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int32_t* scr = B.arr_scr + (size_t)b * plan_arrange_words(B.N);
+    int hs = 0, fs = 0;
+    for (int e = 0; e < E; ++e) {
+        const int k = tid * E + e;
+        if (k < nblk) {
+            hs += scr[2 * n0 + 2 * k];
+            fs += scr[2 * n0 + 2 * k + 1];
+        }
+    }
+    int hi = hs, fi = fs;           // inclusive sums over the wave
+    for (int d = 1; d < 64; d <<= 1) {
+        const int h2 = __shfl_up(hi, d), f2 = __shfl_up(fi, d);
+        if (lane >= d) {
+            hi += h2;
+            fi += f2;
+        }
+    }
+    if (lane == 63) {
+        wth[wv] = hi;
+        wtf[wv] = fi;
+    }
+    __syncthreads();
+    int hx = hi - hs, fx = fi - fs;        // exclusive, over the block
+    for (int w = 0; w < wv; ++w) {
+        hx += wth[w];
+        fx += wtf[w];
+    }
+    for (int e = 0; e < E; ++e) {
+        const int k = tid * E + e;
+        if (k < nblk) {
+            hpre[k] = hx;
+            fpre[k] = fx;
+            hx += scr[2 * n0 + 2 * k];
+            fx += scr[2 * n0 + 2 * k + 1];
+        }
+    }
+    __syncthreads();
+    if (pos >= n0) return -1;
+    if ((pos & 15) == 0) B.p1[b][pos >> 4] = scr[2 * n0 + 2 * nblk + (pos >> 4)];      // the tile's keep mask: into the head of the lean plan's unwritten p1 column
+    int w = scr[pos];
+    if (w < 0) {                    // a hole: filler number hpre[block] + its rank, in the last block whose fillers start at or below it
+        const int r = hpre[blockIdx.x] + (-1 - w);
+        int lo = 0, hi2 = nblk - 1;
+        while (lo < hi2) {
+            const int mid = (lo + hi2 + 1) >> 1;
+            if (fpre[mid] <= r) lo = mid; else hi2 = mid - 1;
+        }
+        w = scr[n0 + min(max(lo * 256 + (r - fpre[lo]), 0), n0 - 1)];       // (inside the list whatever the words say)
+    }
+    return w;
+}
 
 template <bool ONLY_STRETCH>
 static __device__ __forceinline__ void native_plan_batch_body(const NativeBatchArgs& B) {
     const int b = blockIdx.y;
     const int pos = blockIdx.x * blockDim.x + threadIdx.x;
+    int t_arr = -1;
+    if constexpr (ONLY_STRETCH) {
+        const int nplan = (B.N + 255) / 256;
+        if ((int)blockIdx.x >= nplan) {     // extra workgroups: the arrangement lists of step b of the batch after, for that batch's launch
+            if (B.pre_scr) plan_arrange_block(B.N, B.pre_key(b), B.pre_key(b + 1), B.pre_scr + (size_t)b * plan_arrange_words(B.N), (int)blockIdx.x - nplan);
+            return;
+        }
+        // (uniform over the block: the blocks that hold slots of an arranged split 0)
+        if (B.arrange && (b > 0 || B.arr0) && (int)(blockIdx.x * blockDim.x) < B.N / 2) t_arr = plan_arranged_pos(B, b, pos);
+    }
     if (pos >= B.N || (EMX_EXPERIMENTS && !ONLY_STRETCH && (B.ablate & 4))) return;
     const int N = B.N, S = B.S[b];
     int split = 0, t = pos;
@@ -3020,6 +3215,7 @@ static __device__ __forceinline__ void native_plan_batch_body(const NativeBatchA
         if (t < n) { split = s; break; }
         t -= n;
     }
+    if (ONLY_STRETCH && t_arr >= 0) t = t_arr;      // (a slot of an arranged split 0: the entry of another position of the split)
     int i, a0, a1, a2;
     double z, u;
     const int mv = ONLY_STRETCH ? MOVE_STRETCH : B.move[b];

@@ -127,6 +127,8 @@ int emx_status(emx_ctx* ctx, uint32_t* bits);
  *   "persist_rows_late"        1         launches that store chain rows (stretch move, even ndim <= 64) ask for the next half-step's own rows behind the
  *                                        MFMA phase instead of in front of it (k_persist<..., ROWS_LATE>): 1 the one-XCD form and device-wide launches
  *                                        with eight tiles a CU and half-step (65 536 walkers), 2 always, 0 never
+ *   "persist_carry"            1         device-wide stretch launches that store no rows, over Philox plans arranged after the step before, keep own rows
+ *                                        over the step boundary in registers (k_persist<..., CARRY>, emx_persist_carry_launches); 0: never.  0 or 1, else an error
  *   "persist_stagger"          -1        how * 256 + n: some waves of a k_persist / k_persist_mix workgroup ask for their partner rows n x 64 clocks
  *                                        after the others (how 0: waves 4-7, 1: odd waves, 2: the waves of SIMDs 2 and 3, 4: SIMD k waits k n); -1: 516
  *                                        for device-wide stretch launches without stored rows, 528 for the DE move and DE + snooker mixtures (k_persist_mix), else 0
@@ -380,7 +382,8 @@ int emx_set_shard_buffers(emx_ctx* ctx, void* sendbuf, void* gathered, int64_t r
 /* raw device pointers for zero-copy wrapping (torch.distributed all-gather buffers):
  * which: 0 coords (N,D), 1 log_prob (N), 2 sendbuf (rows/rank, D+2), 3 gathered (world*rows/rank, D+2),
  *        4 chain (stored, N, D), 5 chain log_prob (stored, N), 6 Gaussian-move displacements (N, D),
- *        8 direct-exchange barrier flags (one uint64 per rank) */
+ *        8 direct-exchange barrier flags (one uint64 per rank),
+ *        16 + r: slot r of the plan ring, one block of 48 N bytes: [order|p0] int32, [s0|uacc] f64, [p1|p2] int32, [logu|fac] f64 */
 int emx_device_ptr(emx_ctx* ctx, int32_t which, void** ptr, int64_t* nbytes);
 int emx_shard_slots(emx_ctx* ctx, int32_t split, int64_t* t_lo, int64_t* t_hi, int64_t* ns);
 /* after the all-gather of `sendbuf`s into `gathered`: write the other ranks' rows into X */
@@ -631,6 +634,18 @@ int emx_persist_info(emx_ctx* ctx, int64_t out[4]);
  * been enqueued since the launch that gave up and are still unsettled, another pipeline has been started since, or a step begun
  * with emx_step_begin is open when the failure is noticed. */
 int emx_persist_local_launches(emx_ctx* ctx, int64_t* n);
+/* ... and how many took the CARRY form (tuning "persist_carry"): device-wide launches of stretch steps (two splits, even ndim <= 64, no
+ * rows stored) over Philox plans whose split 0 is listed in the slot order emx_plan_arrange defines, so that a wave finds the walkers
+ * it updated in the second half of a step in the same slots of the next step's first half and keeps their rows in registers */
+int emx_persist_carry_launches(emx_ctx* ctx, int64_t* n);
+/* host only: the lean stretch plan of `step` (two splits, even `nwalkers`) as the plan kernels write it for k_persist's CARRY form --
+ * order, p0, s0, uacc: (nwalkers) entries, split 0 then split 1; keep_mask: one word per 16 slots of split 0, bit s & 15.  has_prev != 0:
+ * split 0 is arranged after step - 1: slot s lists the walker of that step's split-1 slot s where it belongs to this step's split 0
+ * (keep bit set), the other slots in ascending order list the walkers of this step's split 0 that were in split 0 before, in ascending
+ * position.  has_prev == 0: position order, empty masks.  Split 1 is always in position order.  Every entry is the walker's own:
+ * a listing order changes no draw.  -> 0, or -1 on a bad argument (odd or < 2 walkers, has_prev at step 0, a null pointer) */
+int emx_plan_arrange(uint64_t seed, uint64_t step, int32_t has_prev, int64_t nwalkers, double a, int32_t* order, int32_t* p0, double* s0,
+                     double* uacc, int32_t* keep_mask);
 /* host only: the grid the persistent kernel takes for `nwalkers` walkers updated in `nsplits` half-steps on a device of `num_cu`
  * CUs -- waves per workgroup (8 / 4 / 2 / 1; 0: no persistent grid, the per-half-step launches run) and workgroups */
 int emx_host_persist_shape(int64_t nwalkers, int32_t nsplits, int32_t num_cu, int32_t* waves_per_group, int32_t* groups);

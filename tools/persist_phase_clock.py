@@ -22,6 +22,21 @@ NAMES = ["partner rows + next plan entries arrive (sc1 round trip)", "proposals,
          "device-wide barrier (arrive, poll)"]
 
 
+BAR_WORD0 = 4096          # first word of the barrier's wall-clock pairs in the stamp buffer
+MAX_ITERS = 40            # PERSIST_MAX_ITERS
+
+
+def info_groups(ens):
+    """workgroups of the device-wide grid k_persist takes for this ensemble (include/emx.h emx_host_persist_shape)"""
+    import ctypes as C
+    import torch
+    from emcee_amd import _lib
+    w, g = C.c_int32(0), C.c_int32(0)
+    cu = torch.cuda.get_device_properties(0).multi_processor_count
+    assert _lib.load().emx_host_persist_shape(ens.nwalkers, 2, cu, C.byref(w), C.byref(g)) == 0 and g.value > 0
+    return g.value
+
+
 def main(N=65536, D=64, store=0):
     import torch
     from emcee_amd.parallel import _DevView
@@ -43,7 +58,12 @@ def main(N=65536, D=64, store=0):
         ptr, nbytes = ens.device_ptr(7)
         t = torch.as_tensor(_DevView(ptr, nbytes // 8), device=torch.device("cuda", 0))
         raw = t.view(torch.int64).cpu().numpy().reshape(-1, 16)
-        rows.append(raw[raw[:, 6] != 0].copy())
+        # workgroup g writes row g; the barrier's wall-clock pairs start at word BAR_WORD0 (persist_barrier's `wall`, csrc/emx_kernels.hpp),
+        # so only the rows in front of it are workgroups' -- of them, those this launch's grid wrote: word 6 is its half-steps
+        wg = raw[:BAR_WORD0 // 16]
+        assert info_groups(ens) <= len(wg), "the grid has more workgroups than rows in front of the barrier's words"
+        wg = wg[:info_groups(ens)]
+        rows.append(wg[(wg[:, 6] > 0) & (wg[:, 6] <= MAX_ITERS)].copy())
     info = ens.persist_info()
     ens.set_tuning("phase_clock", 0)
     ens.close()
@@ -65,6 +85,13 @@ def main(N=65536, D=64, store=0):
               % (name, np.median(per[:, k]), np.percentile(per[:, k], 10), np.percentile(per[:, k], 90),
                  100 * np.median(per[:, k]) / np.median(per.sum(axis=1))))
     print("  sum of medians %.2f us per half-step" % np.median(per, axis=0).sum())
+    # the first phase again, by the kind of half-step (words 7 and 8; the launch's first half-step is in neither): a launch of
+    # niter half-steps has niter / 2 - 1 behind a step boundary and niter / 2 second halves of a step
+    ok = niter >= 4
+    for k, name, cnt in ((7, "behind a step boundary (first split of a step)", niter / 2 - 1), (8, "inside a step (second split)", niter / 2)):
+        v = raw[ok, k] / cnt[ok] * ns_per_tick / 1e3
+        print("  partner rows arrive, half-steps %-46s median %6.2f us   p10 %6.2f   p90 %6.2f"
+              % (name, np.median(v), np.percentile(v, 10), np.percentile(v, 90)))
 
 
 if __name__ == "__main__":
