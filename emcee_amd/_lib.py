@@ -192,6 +192,8 @@ SIGNATURES = {
     "emx_persist_carry_launches": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "emx_plan_arrange": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    "emx_persist_pprefetch_launches": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "emx_plan_partner_stable": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_double, C.c_void_p]),
     "emx_host_mt_jump": (C.c_int, [_u32p, C.c_uint64, C.c_int32, _u32p]),
     "emx_host_persist_shape": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "emx_timer_start": (C.c_int, [_P]),

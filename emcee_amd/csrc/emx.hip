@@ -396,6 +396,8 @@ struct emx_ctx {
     int64_t pipe_regen_steps = 0;
     int64_t tune_persist_carry = 1;      // device-wide stretch launches without stored rows over arranged plans take k_persist's CARRY instantiation (0: never)
     int64_t persist_carry_launches = 0;
+    int64_t tune_persist_partner_prefetch = 1;      // ... and ask for a step boundary's partner-stable rows a half-step early (plan_partner_stable_host; 0: the CARRY form without)
+    int64_t persist_pprefetch_launches = 0;
     bool plan_tail_ok = false;           // the last step native_prepare_batch planned was a stretch step of two splits: step plan_tail_step under plan_tail_seed
     uint64_t plan_tail_step = 0, plan_tail_seed = 0;
     // (Safety does not rest on these: an arranged step is a valid listing of its split whatever ran before, and k_persist trusts a keep
@@ -1696,6 +1698,11 @@ int emx_set_tuning(emx_ctx* c, const char* key, int64_t v) {
     if (!strcmp(key, "persist_carry")) {     // 0: never k_persist's CARRY instantiation (and the plans made from then on are not arranged for it)
         NEED(c, v == 0 || v == 1, "tuning persist_carry: 0 or 1");
         c->tune_persist_carry = v;
+        return 0;
+    }
+    if (!strcmp(key, "persist_partner_prefetch")) {     // 0: k_persist's CARRY form loads every partner row behind the barrier (the masks are written all the same)
+        NEED(c, v == 0 || v == 1, "tuning persist_partner_prefetch: 0 or 1");
+        c->tune_persist_partner_prefetch = v;
         return 0;
     }
     if (!strcmp(key, "persist_rows_late")) {
@@ -4428,7 +4435,13 @@ static int run_persist(emx_ctx* c, int64_t i0, int64_t total, int32_t thin_by, i
             // launches that store none, device-wide, stretch steps of two splits over arranged Philox plans: own rows carried over the
             // step boundary in registers (k_persist's CARRY; profiles/r07/carry.md) -- tuning persist_carry 0: never
             const bool carry = c->tune_persist_carry && carry_ok && !mtmode && !store && !launch_local && launch_move == EMX_MOVE_STRETCH && launch_S == 2;
-            if (carry) c->persist_carry_launches++;
+            if (carry) {
+                // (k_persist<..., CARRY> has no code for stored rows: `store` is the call's, this is every half-step's)
+                for (int k = 0; k < n; ++k) NEED(c, !P.it[k].chain && !P.it[k].chain_lp, "persistent half-steps: the CARRY form was given a half-step that stores rows");
+                c->persist_carry_launches++;
+                P.pprefetch = c->tune_persist_partner_prefetch ? 1 : 0;
+                if (P.pprefetch) c->persist_pprefetch_launches++;
+            }
             e = launch_hot_persist_dense(c->Dp / 16, launch_move, launch_local ? 1 : 0, carry ? 2 : rows_late ? 1 : 0, grid, block, lds, c->stream, P);
         }
         if (launch_local) c->persist_local_launches++;
@@ -4654,6 +4667,11 @@ int emx_persist_carry_launches(emx_ctx* c, int64_t* n) {
     return 0;
 }
 
+int emx_persist_pprefetch_launches(emx_ctx* c, int64_t* n) {
+    *n = c->persist_pprefetch_launches;
+    return 0;
+}
+
 // the host's form of an arranged lean stretch plan (plan_arrange_host, csrc/emx_kernels.hpp): what k_plan_arrange and
 // k_native_plan_batch_stretch write for `step`, the logarithms apart
 int emx_plan_arrange(uint64_t seed, uint64_t step, int32_t has_prev, int64_t nwalkers, double a, int32_t* order, int32_t* p0, double* s0,
@@ -4683,6 +4701,17 @@ int emx_plan_arrange(uint64_t seed, uint64_t step, int32_t has_prev, int64_t nwa
         s0[pos] = z;
         uacc[pos] = u;
     }
+    return 0;
+}
+
+// ... and of the partner-stable masks behind its keep masks (plan_partner_stable_host): of the plan of `step` arranged after step - 1
+int emx_plan_partner_stable(uint64_t seed, uint64_t step, int64_t nwalkers, double a, int32_t* stable_mask) {
+    if (nwalkers < 2 || (nwalkers & 1) || nwalkers > (1ll << 30) || !stable_mask || step == 0) return -1;
+    const size_t N = (size_t)nwalkers;
+    std::vector<int32_t> order(N), p0(N), keep((N / 2 + 15) / 16);
+    std::vector<double> s0(N), uacc(N);
+    if (emx_plan_arrange(seed, step, 1, nwalkers, a, order.data(), p0.data(), s0.data(), uacc.data(), keep.data())) return -1;
+    plan_partner_stable_host(nwalkers, make_perm_key((uint64_t)nwalkers, seed, step - 1), p0.data(), stable_mask);
     return 0;
 }
 

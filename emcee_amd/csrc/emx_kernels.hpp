@@ -1323,6 +1323,7 @@ struct PersistArgs {
     unsigned seq;                  // number of this launch (left in the barrier block's fourth `go` word once its grid is known co-resident)
     unsigned* started_host;        // pinned host word (or null): `seq` again, for the host -- launch k + 1 has started, so launch k is over
     int32_t stagger;               // > 0: some waves issue their partner loads later than the others (persist_stagger_wait)
+    int32_t pprefetch;             // k_persist's CARRY form: 1: a step's first half-step finds its partner-stable rows prefetched (tuning persist_partner_prefetch)
 };
 static_assert(sizeof(PersistArgs) <= 4096, "kernel arguments of the persistent kernels");
 
@@ -1490,6 +1491,15 @@ __device__ __forceinline__ bool persist_handshake(const PersistArgs& P) {
     return ok_s != 0;
 }
 
+// the first array where FIRST, else the second: one name for an array that lives at another scope in one instantiation of a kernel
+template <bool FIRST, class T, int NA, int NB>
+__device__ __forceinline__ auto& pick_array(T (&a)[NA], T (&b)[NB]) {
+    if constexpr (FIRST)
+        return a;
+    else
+        return b;
+}
+
 // CARRY (round 7; the device-wide stretch form of launches whose every step boundary joins two steps of one arranged sequence of plans,
 // plan_arrange_host, and that store no chain rows): at a step boundary a wave keeps the rows and log-probs it holds of the walkers that
 // stay in its slots (the keep mask of its tile, loaded with the next half-step's plan entries) and prefetches the others, which nobody
@@ -1583,23 +1593,38 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
         my_lpo = load_agent(A.lp + my_i);
     }
     // stored steps: the rows (and log-probs) of a half-step leave one half-step later
-    Row<G, V, CH> crow[DEFER ? PF : 1];
+    // (CARRY has none of this: the launcher takes that instantiation only for launches that store no rows -- run_persist checks that no
+    // half-step of such a launch has chain pointers -- and what it would hold for them, 32 registers of rows at DPB 4, is what the
+    // prefetched partner rows live in across the barrier)
+    constexpr bool STORED = !CARRY;
+    Row<G, V, CH> crow[(DEFER && STORED) ? PF : 1];
     int cwi[PF], cmy_i = 0;
     double clp = 0.0;
     double *cchain = nullptr, *cchain_lp = nullptr;
+    if constexpr (STORED) {
 #pragma unroll
-    for (int k = 0; k < PF; ++k) {
-        if (DEFER || k == 0) crow[DEFER ? k : 0] = xi[k];
-        cwi[k] = 0;
+        for (int k = 0; k < PF; ++k) {
+            if (DEFER || k == 0) crow[DEFER ? k : 0] = xi[k];
+            cwi[k] = 0;
+        }
     }
+    // CARRY: the partner rows live across the barrier in front of a step's first half-step -- those nobody writes during the half-step
+    // before (the tile's partner-stable mask, written by the plan kernel behind the keep masks) are asked for under its MFMA phase
+    Row<G, V, CH> xa_c[CARRY ? PF : 1];
+    unsigned stable = 0u;           // of THIS half-step: the slots whose partner row is already in xa_c
     for (int n = 0; n < P.niter; ++n) {
         const PersistCols I(P.it[n], (size_t)P.base.N);
         // -------- partner rows: the walkers the previous half-step updated --------
-        Row<G, V, CH> xa[PF], xb[DE ? PF : 1], xc[SN ? PF : 1];
+        Row<G, V, CH> xa_l[CARRY ? 1 : PF], xb[DE ? PF : 1], xc[SN ? PF : 1];
+        Row<G, V, CH>(&xa)[PF] = pick_array<CARRY>(xa_c, xa_l);
         persist_stagger_wait(P.stagger, wib);
 #pragma unroll
         for (int k = 0; k < PF; ++k) {
-            load_row_agent<G, V, CH, CPOL>(xa[k], Xr, ja[k], D, gl);
+            if constexpr (CARRY) {
+                if (!((stable >> (k * WPW + sub)) & 1u)) load_row_agent<G, V, CH, CPOL>(xa[k], Xr, ja[k], D, gl);
+            } else {
+                load_row_agent<G, V, CH, CPOL>(xa[k], Xr, ja[k], D, gl);
+            }
             if constexpr (DE) load_row_agent<G, V, CH, CPOL>(xb[k], Xr, jb[k], D, gl);
             if constexpr (SN) load_row_agent<G, V, CH, CPOL>(xc[k], Xr, jc[k], D, gl);
         }
@@ -1628,9 +1653,14 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
         // CARRY: the keep mask of this wave's tile in the next half-step, where that one is the first of a step (0: every row is loaded).
         // (Every wave of the grid has a tile: persist_shape_of takes grids of tiles / waves-per-workgroup workgroups only where that
         // divides -- 2 080 walkers are 65 workgroups of one wave -- so `wave` is below the split's N / 32 tiles, each with a mask.)
-        unsigned keep_n = 0u;
+        // ... and its partner-stable mask (tuning persist_partner_prefetch; plan_partner_stable_host): the slots whose partner was in
+        // split 0 of THIS step, so that nobody writes its row during this half-step -- 0 inside a step and with the key off
+        unsigned keep_n = 0u, stable_n = 0u;
         if constexpr (CARRY) {
-            if (more && !pre) keep_n = (unsigned)J.p1[wave];
+            if (more && !pre) {
+                keep_n = (unsigned)J.p1[wave];
+                if (P.pprefetch) stable_n = (unsigned)J.p1[((P.base.N / 2 + 15) >> 4) + wave];
+            }
         }
         // (the scheduler puts these loads BEHIND the wait for the partner rows.  Forced in front of it -- a scheduling barrier here -- the
         // step is 2.4 % slower, 20.17 -> 20.65 us: ten more requests in front of the rows; profiles/r06/stagger/entries_early_ab.txt)
@@ -1667,13 +1697,13 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
         }
         // -------- stored steps: the rows of the half-step BEFORE go out now, next to the MFMA phase -- issued before its barrier
         //          their 17 MB would sit between the commits and the arrival (every store is acknowledged in order) --------
-        if (DEFER && cchain) {
+        if (STORED && DEFER && cchain) {
 #pragma unroll
             for (int k = 0; k < PF; ++k) store_row_stream<G, V, CH>(crow[k], cchain + (size_t)cwi[k] * D, D, gl);
             if (mine) cchain_lp[cmy_i] = clp;
             cchain = nullptr;
         }
-        if (I.chain) {
+        if (STORED && I.chain) {
 #pragma unroll
             for (int k = 0; k < PF; ++k) {
                 if constexpr (DEFER)
@@ -1698,6 +1728,10 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
             for (int k = 0; k < PF; ++k)
                 if (!((keep_n >> (k * WPW + sub)) & 1u)) load_row_agent<G, V, CH, CPOL>(xi[k], Xr, wi_n[k], D, gl);
             if (!((keep_n >> myrow) & 1u)) my_lpo_n = load_agent(A.lp + my_i_n);
+            // the next half-step's stable partner rows: xa is dead behind the proposals, and nobody writes these rows in this half-step
+#pragma unroll
+            for (int k = 0; k < PF; ++k)
+                if ((stable_n >> (k * WPW + sub)) & 1u) load_row_agent<G, V, CH, CPOL>(xa[k], Xr, ja_n[k], D, gl);
         }
         EMX_WAVE_SYNC();
         EMX_PSTAMP(1);       // proposals made, tile written, chain rows and next own rows issued
@@ -1744,7 +1778,7 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
                 store_scope<LOCAL>(A.lp + my_i, lpn);
                 store_scope<LOCAL>(P.ver + my_i, stamp);
             }
-            if (I.chain_lp) {
+            if (STORED && I.chain_lp) {
                 if constexpr (DEFER)
                     clp = acc ? lpn : my_lpo;
                 else
@@ -1759,7 +1793,7 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
             const bool ac = (am64 >> ((row & 3) * 16 + (row >> 2))) & 1ull;
             if (ac) {
                 store_row_agent<G, V, CH, CPOL_ST>(qk[pp], Xr, wi[pp], D, gl);
-                if (I.chain) {
+                if (STORED && I.chain) {
                     if constexpr (DEFER)
                         crow[pp] = qk[pp];
                     else
@@ -1767,7 +1801,7 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
                 }
             }
         }
-        if (DEFER && I.chain) {
+        if (STORED && DEFER && I.chain) {
             cchain = I.chain;
             cchain_lp = I.chain_lp;
             cmy_i = my_i;
@@ -1800,6 +1834,7 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
         my_i = my_i_n;
         my_logu = my_logu_n;
         my_lpo = my_lpo_n;
+        stable = stable_n;
         if constexpr (CARRY) {      // a kept walker: what this wave made of it (keep_n is 0 inside a step)
 #pragma unroll
             for (int k = 0; k < PF; ++k) {
@@ -1819,7 +1854,7 @@ static __global__ __launch_bounds__(512) void k_persist(const PersistArgs P) {
             if (vm == stamp) my_lpo = load_agent(A.lp + my_i);
         }
     }
-    if (DEFER && cchain) {      // the last half-step's rows
+    if (STORED && DEFER && cchain) {      // the last half-step's rows
 #pragma unroll
         for (int k = 0; k < PF; ++k) store_row_stream<G, V, CH>(crow[k], cchain + (size_t)cwi[k] * D, D, gl);
         if (mine) cchain_lp[cmy_i] = clp;
@@ -3085,6 +3120,17 @@ inline void plan_arrange_host(int64_t N, const PermKey& Kp, const PermKey& K, in
     }
 }
 
+// ... and which of an arranged split 0's partners were in split 0 of the step before (key Kp): nobody writes those rows during that
+// step's second half either, so k_persist's CARRY form asks for them under its MFMA phase (tuning persist_partner_prefetch).  p0: the
+// arranged plan's partners.  One 16-bit word per tile of 16 slots (bit s & 15), as the keep masks.  The definition
+// (emx_plan_partner_stable; tests/test_plan_partner_stable_cpu.py); the device's form is the plan kernel's own (native_plan_batch_body).
+inline void plan_partner_stable_host(int64_t N, const PermKey& Kp, const int32_t* p0, int32_t* stable_mask) {
+    const int64_t n0 = N / 2;
+    for (int64_t tl = 0; tl < (n0 + 15) / 16; ++tl) stable_mask[tl] = 0;
+    for (int64_t s = 0; s < n0; ++s)
+        if (!(perm_fwd((uint32_t)p0[s], Kp) & 1u)) stable_mask[s >> 4] |= 1 << (s & 15);
+}
+
 // The device's form, in two parts, through a scratch list of the context's own (plan_arrange_words(N) words a step).  This part: every
 // 256 slots' keep flags, the hole slots' ranks and the fillers, block by block, with the blocks' counts:
 // [n0] a keep slot's position, or -1 - (rank of the hole in its block) | [n0] block k's fillers' positions from word 256 k |
@@ -3249,6 +3295,16 @@ static __device__ __forceinline__ void native_plan_batch_body(const NativeBatchA
         B.logu[b][pos] = u;
         B.fac[b][pos] = z;
         return;
+    }
+    if constexpr (ONLY_STRETCH) {
+        // an arranged split 0: which slots' partners were in split 0 of the step before (plan_partner_stable_host) -- one word a tile,
+        // behind the keep masks in the unwritten p1 column (uniform over the block, as above)
+        const int n0 = N / 2;
+        if (B.arrange && (b > 0 || B.arr0) && (int)(blockIdx.x * blockDim.x) < n0) {
+            const bool st = pos < n0 && !(perm_fwd((uint32_t)a0, b ? B.nat[b - 1].pk : B.kprev0) & 1u);
+            const unsigned long long ms = __ballot(st);
+            if ((pos & 15) == 0 && pos < n0) B.p1[b][((n0 + 15) >> 4) + (pos >> 4)] = (int32_t)((ms >> (threadIdx.x & 63)) & 0xffffull);
+        }
     }
     B.order[b][pos] = i;
     B.p0[b][pos] = a0;

@@ -742,8 +742,10 @@ class DeviceEnsemble:
         self._ck(self.lib.emx_persist_local_launches(self.ctx, C.byref(loc)))
         car = C.c_int64(0)
         self._ck(self.lib.emx_persist_carry_launches(self.ctx, C.byref(car)))
+        ppf = C.c_int64(0)
+        self._ck(self.lib.emx_persist_pprefetch_launches(self.ctx, C.byref(ppf)))
         return {"qualifies": bool(out[0]), "launches": int(out[1]), "halfsteps": int(out[2]), "recovered": int(out[3]),
-                "local_launches": int(loc.value), "carry_launches": int(car.value)}
+                "local_launches": int(loc.value), "carry_launches": int(car.value), "pprefetch_launches": int(ppf.value)}
 
     def small_info(self):
         """the one-workgroup kernel (include/emx.h emx_small_info): launches since creation and the steps run in them"""

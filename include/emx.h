@@ -129,6 +129,9 @@ int emx_status(emx_ctx* ctx, uint32_t* bits);
  *                                        with eight tiles a CU and half-step (65 536 walkers), 2 always, 0 never
  *   "persist_carry"            1         device-wide stretch launches that store no rows, over Philox plans arranged after the step before, keep own rows
  *                                        over the step boundary in registers (k_persist<..., CARRY>, emx_persist_carry_launches); 0: never.  0 or 1, else an error
+ *   "persist_partner_prefetch" 1         the CARRY form asks for the partner rows of a step's first half-step that nobody writes during the half-step
+ *                                        before (the partner was in split 0 of the step before: emx_plan_partner_stable) under that half-step's MFMA
+ *                                        phase, not behind the barrier (emx_persist_pprefetch_launches); 0: every partner row behind the barrier.  0 or 1, else an error
  *   "persist_stagger"          -1        how * 256 + n: some waves of a k_persist / k_persist_mix workgroup ask for their partner rows n x 64 clocks
  *                                        after the others (how 0: waves 4-7, 1: odd waves, 2: the waves of SIMDs 2 and 3, 4: SIMD k waits k n); -1: 516
  *                                        for device-wide stretch launches without stored rows, 528 for the DE move and DE + snooker mixtures (k_persist_mix), else 0
@@ -646,6 +649,12 @@ int emx_persist_carry_launches(emx_ctx* ctx, int64_t* n);
  * a listing order changes no draw.  -> 0, or -1 on a bad argument (odd or < 2 walkers, has_prev at step 0, a null pointer) */
 int emx_plan_arrange(uint64_t seed, uint64_t step, int32_t has_prev, int64_t nwalkers, double a, int32_t* order, int32_t* p0, double* s0,
                      double* uacc, int32_t* keep_mask);
+/* ... and how many of the CARRY launches found the partner-stable rows of their step boundaries prefetched (tuning "persist_partner_prefetch") */
+int emx_persist_pprefetch_launches(emx_ctx* ctx, int64_t* n);
+/* host only: the partner-stable masks of the plan emx_plan_arrange(seed, step, 1, ...) gives, as the plan kernels write them behind its
+ * keep masks: one word per 16 slots of split 0, bit s & 15 set when slot s's partner p0[s] was in split 0 of step - 1 -- a row nobody
+ * writes during that step's second half.  -> 0, or -1 on a bad argument (odd or < 2 walkers, step 0, a null pointer) */
+int emx_plan_partner_stable(uint64_t seed, uint64_t step, int64_t nwalkers, double a, int32_t* stable_mask);
 /* host only: the grid the persistent kernel takes for `nwalkers` walkers updated in `nsplits` half-steps on a device of `num_cu`
  * CUs -- waves per workgroup (8 / 4 / 2 / 1; 0: no persistent grid, the per-half-step launches run) and workgroups */
 int emx_host_persist_shape(int64_t nwalkers, int32_t nsplits, int32_t num_cu, int32_t* waves_per_group, int32_t* groups);
